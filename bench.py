@@ -12,22 +12,23 @@ rank processes its own pairs; the only collective is an RCCL all_gather of per-p
 `python bench.py --gpus N` launches the N ranks itself (torch.distributed.run, one process per GPU, 127.0.0.1 rendezvous) when it
 is not already running under a launcher; under a launcher WORLD_SIZE must equal --gpus.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize and reduced with MAX over ranks;
-blocks are repeated until >= --min-time seconds have been measured and the MEDIAN block is reported (`ms_per_step` = median block / K).
+Timing: W warm-up steps, then ONE block of EXACTLY K = --steps steps, bracketed by barrier + synchronize and reduced with MAX over ranks
+(`ms_per_step` = block / K).  --min-time S repeats the block until >= S seconds have been measured and reports the MEDIAN block (the default
+under --full is 2 s).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the stream it runs on), `cpu_baseline` (the
-oracle - the only CPU implementation of this algorithm that exists - timed on the host cores) and, at N=1, the two other regimes of
-the north star: `host_streamed` (pinned host memory -> hipMemcpyAsync -> kernels, PCIe-inclusive) and `frame_latency_us` (one
-stereo pair through the reference-shaped synchronous C++ API).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs DIR if given, and ONE JSON line (rank 0).
+--full adds everything else: parity of every unique pair against the oracle, `roofline` (dominant kernel, HIP-event timed on the stream it
+runs on), `cpu_baseline` (the oracle - the only CPU implementation of this algorithm that exists - timed on the host cores), the N > 1
+self-check, and, at N=1, the two other regimes of the north star: `host_streamed` (pinned host memory -> hipMemcpyAsync -> kernels,
+PCIe-inclusive) and `frame_latency_us` (one stereo pair through the reference-shaped synchronous C++ API), plus the other configurations and
+input families (--no-cpu-baseline / --no-extras / --profile-steps trim a --full run).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's pairs) as .npy files in float32 / float64: see dump_outputs().  The
+inputs are seeded synthetic pairs, identical from run to run for the same arguments.
 """
 import argparse
 import json
 import os
-
-# libjsorb's own default (jsorb_api.hip, jsorb_runtime_defaults), set here as well because torch initialises the HIP runtime before the
-# library is loaded: 16 hardware queues, so that the library's lane / upload / main streams do not share a queue (INTEGRATION.md).  The
-# value in effect is reported in the JSON line ("env").
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import socket
 import subprocess
 import sys
@@ -169,7 +170,56 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child process, not exec: the device queries above may already have brought up the HIP runtime in this one
+    sys.exit(subprocess.call(cmd))
+
+
+def synth_pairs(seeds, H, W, world=1):
+    """synth_stereo_pair(seed, H, W) for every seed, in order.  The generator is Python + numpy (~20 ms per 752x480 pair), so a large set is
+    made by a pool of fresh worker processes - at most 16 over all ranks of the node; the pairs are the same either way."""
+    from jetson_slam_amd.synth import synth_stereo_pair
+    n_workers = min(len(seeds) // 16, max(1, min(16, usable_cores()) // world))
+    if n_workers < 2:
+        return [synth_stereo_pair(s, H, W) for s in seeds]
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(n_workers, mp_context=multiprocessing.get_context("spawn")) as pool:
+        return list(pool.map(synth_stereo_pair, seeds, [H] * len(seeds), [W] * len(seeds), chunksize=8))
+
+
+def dump_outputs(orb, groups, per, P, out_dir, limit_bytes=48 << 20):
+    """--dump-outputs: what a caller of the timed path receives for the pairs of the last step (this rank's), as .npy files in out_dir:
+      counts.npy        float64 [P, 3]  keypoints left, keypoints right, stereo matches (n_final) of every pair of the step
+      sample_pairs.npy  float64 [S]     a fixed sample of the step's pairs (seeded; S depends only on the configuration and P)
+      left_keypoints.npy / right_keypoints.npy      float64 [sum N, 6]   per keypoint the 6 int32 words of jsorb_copy_keypoints
+                                                                         (x, y, score, angle as f32 bits, octave, size)
+      left_descriptors.npy / right_descriptors.npy  float32 [sum N, 32]  the 32 descriptor bytes per keypoint
+      u_right.npy / depth.npy                       float32 [sum N_left] (jsorb_copy_stereo)
+    The per-keypoint arrays concatenate the sampled pairs in sample order (a pair's rows: its counts).  S is as many pairs as fit in
+    limit_bytes at the keypoint cap of every image, so the files stay below 64 MB whatever the images hold."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = groups[0][0].T                                     # keypoint cap per image
+    worst = 2 * cap * (6 * 8 + 32 * 4) + cap * 2 * 4         # bytes of one pair at the cap
+    n_sample = max(1, min(P, 32, limit_bytes // worst))
+    pick = np.sort(np.random.default_rng(0).choice(P, n_sample, replace=False))
+    counts = np.zeros((P, 3), np.float64)
+    parts = {k: [] for k in ("left_keypoints", "left_descriptors", "right_keypoints", "right_descriptors", "u_right", "depth")}
+    for i in range(P):
+        a, b = groups[i // per]
+        j = i % per
+        u, d, st = orb.stereo_result(a, j)
+        counts[i] = (a.n_keypoints(j), b.n_keypoints(j), st["n_final"])
+        if i in pick:
+            parts["left_keypoints"].append(a.keypoints(j).reshape(6, -1).T.astype(np.float64))
+            parts["left_descriptors"].append(a.descriptors(j).astype(np.float32))
+            parts["right_keypoints"].append(b.keypoints(j).reshape(6, -1).T.astype(np.float64))
+            parts["right_descriptors"].append(b.descriptors(j).astype(np.float32))
+            parts["u_right"].append(u.astype(np.float32))
+            parts["depth"].append(d.astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), counts)
+    np.save(os.path.join(out_dir, "sample_pairs.npy"), pick.astype(np.float64))
+    for k, v in parts.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.concatenate(v))
 
 
 def median(v):
@@ -185,21 +235,32 @@ def main():
     ap.add_argument("--pairs", type=int, default=128, help="stereo pairs per GPU per step (weak scaling)")
     ap.add_argument("--pairs-total", type=int, default=0, help="strong scaling: this many pairs per step over ALL GPUs (64 on c2 = BASELINE C4)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--min-time", type=float, default=2.0, help="repeat the block of --steps steps until this many seconds are measured; the median block is reported")
+    ap.add_argument("--min-time", type=float, default=None, help="repeat the block of --steps steps until this many seconds are measured; the median block is reported "
+                    "(default: 0 = one block of exactly --steps steps; 2.0 under --full)")
     ap.add_argument("--tile", type=int, default=0, help="override the configuration's tile size (default: the yaml-faithful one)")
     ap.add_argument("--seed-base", type=int, default=1, help="seed of the first synthetic pair (parity soaks over other pairs: tools/micro/soak_bench.sh)")
     ap.add_argument("--unique", type=int, default=0, help="unique synthetic pairs per rank and input set (default: one per pair of the step, at most 128)")
     ap.add_argument("--input-sets", type=int, default=0, help="input sets rotated through the steps (default: 4 = 370 MB of level-0 data per GPU at the default c2 step - more than "
                     "the 256 MiB Infinity Cache, so that no step re-reads its images from the cache; 1 for the other configurations)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-streamed / frame-latency / C4 side measurements")
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra steps with per-kernel hipEvent timing")
+    ap.add_argument("--full", action="store_true", help="besides the headline: oracle parity of every unique pair, the per-kernel / roofline pass, the CPU "
+                    "baseline, the N > 1 self-check and the side measurements (host-streamed, frame latency, C4, other configurations and inputs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the host-streamed / frame-latency / C4 / other-configuration side measurements")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: extra steps with per-kernel hipEvent timing")
     ap.add_argument("--single-stream", action="store_true", help="profiling aid: one lane, all handles on ONE HIP stream (clean per-kernel durations under rocprofv3)")
     ap.add_argument("--dry-multi", action="store_true", help="N > 1 self-check only: a short run (no CPU baseline, no side measurements) whose line carries multi_gpu_diag.self_check - "
                     "distinct devices / PCI addresses, NUMA binding, all_gather < 100 us, no rank > 5 %% slower than the fastest; the ranks exit with 3 if a check fails (a launcher reports that as a failed worker)")
     ap.add_argument("--groups", type=int, default=1, help="split the step's pairs over this many independent left/right handle pairs on their own "
                     "HIP streams (round-1 schedule; the library now does the equivalent split internally, so the default is ONE handle pair)")
     args = ap.parse_args()
+    if args.dry_multi:
+        args.full = True                          # the self-check is part of the --full line
+    if args.min_time is None:
+        args.min_time = 2.0 if args.full else 0.0
+    if not args.full:
+        args.no_cpu_baseline = args.no_extras = True
+        args.profile_steps = 0
     if args.dry_multi:
         args.no_cpu_baseline = args.no_extras = True
         args.min_time = min(args.min_time, 0.5)
@@ -216,8 +277,7 @@ def main():
                          "`python bench.py --gpus N`, which starts the ranks itself)" % (args.gpus, world))
 
     import torch
-    from jetson_slam_amd import orb
-    from jetson_slam_amd.synth import synth_stereo_pair
+    from jetson_slam_amd import orb       # before torch's first device call: orb.py sets the library's runtime defaults (GPU_MAX_HW_QUEUES)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -296,12 +356,14 @@ def main():
     # images in the 256 MiB Infinity Cache
     n_sets = args.input_sets if args.input_sets > 0 else (4 if (args.config == "c2" and args.tile <= 0 and not args.single_stream and not strong and P >= 64) else 1)
     sets_u, sets_d = [], []
+    all_pairs = synth_pairs([args.seed_base + si * P * world + p_first + i for si in range(n_sets) for i in range(n_unique)], H, W, world)
     for si in range(n_sets):
-        host_pairs = [synth_stereo_pair(args.seed_base + si * P * world + p_first + i, H, W) for i in range(n_unique)]
+        host_pairs = all_pairs[si * n_unique:(si + 1) * n_unique]
         lu, ru = np.stack([p[0] for p in host_pairs]), np.stack([p[1] for p in host_pairs])
         idx = np.arange(P) % n_unique
         sets_u.append((lu, ru))
         sets_d.append((torch.from_numpy(lu[idx]).to(dev), torch.from_numpy(ru[idx]).to(dev)))
+    del all_pairs, host_pairs
     left_u, right_u = sets_u[0]
     left_d, right_d = sets_d[0]
     cur_set = [0]
@@ -413,48 +475,53 @@ def main():
     dt = median(blocks)
     pairs_per_s = args.steps * P * world / dt
 
-    # ---- parity of EVERY unique pair of this rank against the oracle: counts + a checksum of kp | desc | kp | desc | uRight | depth ----
-    from oracle import pyoracle as po
-    okw = dict(height=H, width=W, n_levels=L, tile_h=tile, tile_w=tile, th_fast_max=th)
-    cores = usable_cores()
-    bound = bool(placement_info[0] and placement_info[0].get("bound"))      # a bound rank's affinity mask already is its share of the host
-    n_bad = 0
-    for si in range(n_sets):                 # every input set once more (untimed), every unique pair of it against the oracle; the last set stays in the handles
-        step(si)
-        fence()
-        o_digest, o_counts = po.pairs_digest(sets_u[si][0], sets_u[si][1], mb, bf, max(1, cores if bound else cores // world), **okw)
-        for i in range(n_unique):
-            a, b = groups[i // per]
-            j = i % per
-            u, d, st = orb.stereo_result(a, j)
-            got = po.digest_arrays([a.keypoints(j), a.descriptors(j), b.keypoints(j), b.descriptors(j), u, d])
-            if got != int(o_digest[i]) or [a.n_keypoints(j), b.n_keypoints(j), st["n_final"]] != o_counts[i].tolist():
-                n_bad += 1
-    parity_local = n_bad == 0
-    counts_ok = True
-    if world > 1:
-        # EVERY rank checks EVERY row of the table the last step's all_gather delivered to it: the expected table is the oracle's counts of
-        # all P * world pairs in global pair order (each rank's oracle computes its own block from the seeds; the blocks are exchanged with a
-        # second, untimed all_gather)
-        torch.cuda.synchronize(dev)
-        exp_local = torch.from_numpy(np.ascontiguousarray(o_counts[np.arange(P) % n_unique], dtype=np.int32)).reshape(-1)
-        if gloo:
-            exp_parts = [torch.zeros_like(exp_local) for _ in range(world)]
-            dist.all_gather(exp_parts, exp_local)
+    if args.dump_outputs and rank == 0:              # the handles still hold what the last timed step computed
+        dump_outputs(orb, groups, per, P, args.dump_outputs)
+
+    parity = counts_ok = o_counts = None
+    if args.full:
+        # ---- parity of EVERY unique pair of this rank against the oracle: counts + a checksum of kp | desc | kp | desc | uRight | depth ----
+        from oracle import pyoracle as po
+        okw = dict(height=H, width=W, n_levels=L, tile_h=tile, tile_w=tile, th_fast_max=th)
+        cores = usable_cores()
+        bound = bool(placement_info[0] and placement_info[0].get("bound"))      # a bound rank's affinity mask already is its share of the host
+        n_bad = 0
+        for si in range(n_sets):                 # every input set once more (untimed), every unique pair of it against the oracle; the last set stays in the handles
+            step(si)
+            fence()
+            o_digest, o_counts = po.pairs_digest(sets_u[si][0], sets_u[si][1], mb, bf, max(1, cores if bound else cores // world), **okw)
+            for i in range(n_unique):
+                a, b = groups[i // per]
+                j = i % per
+                u, d, st = orb.stereo_result(a, j)
+                got = po.digest_arrays([a.keypoints(j), a.descriptors(j), b.keypoints(j), b.descriptors(j), u, d])
+                if got != int(o_digest[i]) or [a.n_keypoints(j), b.n_keypoints(j), st["n_final"]] != o_counts[i].tolist():
+                    n_bad += 1
+        parity_local = n_bad == 0
+        counts_ok = True
+        if world > 1:
+            # EVERY rank checks EVERY row of the table the last step's all_gather delivered to it: the expected table is the oracle's counts of
+            # all P * world pairs in global pair order (each rank's oracle computes its own block from the seeds; the blocks are exchanged with a
+            # second, untimed all_gather)
+            torch.cuda.synchronize(dev)
+            exp_local = torch.from_numpy(np.ascontiguousarray(o_counts[np.arange(P) % n_unique], dtype=np.int32)).reshape(-1)
+            if gloo:
+                exp_parts = [torch.zeros_like(exp_local) for _ in range(world)]
+                dist.all_gather(exp_parts, exp_local)
+            else:
+                exp_dev = exp_local.to(dev)
+                exp_parts = [torch.zeros_like(exp_dev) for _ in range(world)]
+                dist.all_gather(exp_parts, exp_dev)
+            counts_ok = all(bool(torch.equal(gathered[r_].cpu(), exp_parts[r_].cpu())) for r_ in range(world))
+            flag = torch.tensor([1 if (parity_local and counts_ok) else 0], dtype=torch.int32, device="cpu" if gloo else dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            parity = bool(flag.item())
         else:
-            exp_dev = exp_local.to(dev)
-            exp_parts = [torch.zeros_like(exp_dev) for _ in range(world)]
-            dist.all_gather(exp_parts, exp_dev)
-        counts_ok = all(bool(torch.equal(gathered[r_].cpu(), exp_parts[r_].cpu())) for r_ in range(world))
-        flag = torch.tensor([1 if (parity_local and counts_ok) else 0], dtype=torch.int32, device="cpu" if gloo else dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        parity = bool(flag.item())
-    else:
-        parity = parity_local
+            parity = parity_local
 
     # ---- what makes the first real multi-GPU run diagnosable: every rank's own median block time, and the time of the all_gather itself ----
     multi_diag = None
-    if world > 1:
+    if world > 1 and args.full:
         ag_probe[0] = []
         for _ in range(12):
             step()
@@ -515,13 +582,15 @@ def main():
     # ---- per-kernel hipEvent timing pass (serialises launches and forces one lane, so it is separate from the timed region) ----
     # all handles on ONE stream here, so that a kernel's event-to-event time is its own duration and not the overlap with the other
     # handle's kernels (the timed region above overlaps left and right on different streams)
-    shared_stream = torch.cuda.Stream(dev)
-    for e in handles:
-        e.set_stream(shared_stream.cuda_stream)
-        e.enable_kernel_timing(True)
-    kt = timed_steps(handles, step, fence, args.profile_steps)
-    for e in handles:
-        e.enable_kernel_timing(False)
+    kt = {}
+    if args.full:
+        shared_stream = torch.cuda.Stream(dev)
+        for e in handles:
+            e.set_stream(shared_stream.cuda_stream)
+            e.enable_kernel_timing(True)
+        kt = timed_steps(handles, step, fence, args.profile_steps)
+        for e in handles:
+            e.enable_kernel_timing(False)
 
     # ---- north-star regime (i) at N > 1: every rank streams its own pairs from its own pinned host buffers at the same time (per-GPU PCIe
     # links; no inter-GPU traffic); rank 0 reports the sum and the per-GPU rates ----
@@ -542,76 +611,78 @@ def main():
         dist.all_gather_object(placements, placement_info[0])
     if rank == 0:
         ab, Ppx, T = algo_bytes_per_pair(exl)
-        per_step_ms = {k: v[2] for k, v in kt.items()}
-        if args.profile_steps <= 0 or not any(v[1] for v in kt.values()):
-            kt = {"k_detect": [1.0, 1]}                 # no profiling pass requested: the roofline block is a placeholder
-            per_step_ms = {"k_detect": 0.0}
-        dom = max(per_step_ms, key=per_step_ms.get)
-        avg_ms = kt[dom][0] / max(1, kt[dom][1])
-        # one launch of an extract-side kernel covers `per` images = per/2 stereo pairs; a stereo-side launch covers `per` pairs
-        units = per if dom in ("k_stereo", "k_median") else per / 2.0
-        achieved = ab * units / (avg_ms * 1e-3) / 1e9
-        traffic, traffic_source, step_traffic = None, None, None
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tpath):
+        roof, dom = None, None                          # the roofline needs the per-kernel pass of a --full run
+        if args.full:
+            per_step_ms = {k: v[2] for k, v in kt.items()}
+            if args.profile_steps <= 0 or not any(v[1] for v in kt.values()):
+                kt = {"k_detect": [1.0, 1]}                 # no profiling pass requested: the roofline block is a placeholder
+                per_step_ms = {"k_detect": 0.0}
+            dom = max(per_step_ms, key=per_step_ms.get)
+            avg_ms = kt[dom][0] / max(1, kt[dom][1])
+            # one launch of an extract-side kernel covers `per` images = per/2 stereo pairs; a stereo-side launch covers `per` pairs
+            units = per if dom in ("k_stereo", "k_median") else per / 2.0
+            achieved = ab * units / (avg_ms * 1e-3) / 1e9
+            traffic, traffic_source, step_traffic = None, None, None
+            tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    per_kernel_traffic = tj.get(args.config if args.tile <= 0 else "", {})
+                    traffic = per_kernel_traffic.get(dom)
+                    traffic_source = tj.get("_source", "profiles/hbm_traffic.json") + " (builder-measured rocprofv3 PMC pass, NOT measured in this run)"
+                    # HBM bytes of one step: every extract-side kernel runs twice (left and right images), the stereo-side ones once
+                    if per_kernel_traffic and per == {"c2": 128}.get(args.config, 64):      # (the profile passes ran 128 images per launch at c2, 64 at c3 / c5: tools/profile_round.sh)
+                        step_traffic = sum((1 if k in ("k_stereo", "k_median") else 2) * v for k, v in per_kernel_traffic.items() if k.startswith("k_") and isinstance(v, (int, float)))
+                except Exception:
+                    traffic = None
+            roof = {"bound": "hbm", "bound_note": "the contract's roofline is HBM bandwidth; what binds this integer / bitwise path is vector-instruction issue (bound_actual, valu_issue_frac).  "
+                                                   "frac is ALGORITHMIC bytes of the whole pipeline over the dominant kernel's launch time (the contract's convention): it moves with k_detect's duration only - "
+                                                   "0.158 / 0.192 / 0.223 / 0.202 in rounds 1-4 (round 4 fell because k_detect's LDS request was raised on purpose, to leave room for a k_describe "
+                                                   "workgroup per CU), ~0.26 with the compact k_detect of round 5.  kernel_own_hbm_frac is what that kernel itself moves over HBM", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "avg_launch_ms": round(avg_ms, 4), "algo_bytes_per_pair": ab, "pairs_per_launch": units,
+                    "pipeline_achieved": round(ab * pairs_per_s / world / 1e9, 1),
+                    "pipeline_frac": round(ab * pairs_per_s / world / 1e9 / HBM_PEAK_GBS, 4),
+                    "kernel_ms_per_step": {k: round(v, 4) for k, v in per_step_ms.items()}}
+            # SURVEY 8(d) left the data-dependent bytes out of ALGO_BYTES as "< 6 %": outputs 56 N per image and, for the matcher, 64 N + 12 C + 462 M (N left
+            # keypoints, C candidate pairs, M window searches).  On the benchmark images they are a THIRD of the figure (round-5 review) - reported here as a
+            # second figure from the counts of the step's first pair; `frac` keeps the input-independent convention.
             try:
-                tj = json.load(open(tpath))
-                per_kernel_traffic = tj.get(args.config if args.tile <= 0 else "", {})
-                traffic = per_kernel_traffic.get(dom)
-                traffic_source = tj.get("_source", "profiles/hbm_traffic.json") + " (builder-measured rocprofv3 PMC pass, NOT measured in this run)"
-                # HBM bytes of one step: every extract-side kernel runs twice (left and right images), the stereo-side ones once
-                if per_kernel_traffic and per == {"c2": 128}.get(args.config, 64):      # (the profile passes ran 128 images per launch at c2, 64 at c3 / c5: tools/profile_round.sh)
-                    step_traffic = sum((1 if k in ("k_stereo", "k_median") else 2) * v for k, v in per_kernel_traffic.items() if k.startswith("k_") and isinstance(v, (int, float)))
-            except Exception:
-                traffic = None
-        roof = {"bound": "hbm", "bound_note": "the contract's roofline is HBM bandwidth; what binds this integer / bitwise path is vector-instruction issue (bound_actual, valu_issue_frac).  "
-                                               "frac is ALGORITHMIC bytes of the whole pipeline over the dominant kernel's launch time (the contract's convention): it moves with k_detect's duration only - "
-                                               "0.158 / 0.192 / 0.223 / 0.202 in rounds 1-4 (round 4 fell because k_detect's LDS request was raised on purpose, to leave room for a k_describe "
-                                               "workgroup per CU), ~0.26 with the compact k_detect of round 5.  kernel_own_hbm_frac is what that kernel itself moves over HBM", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "avg_launch_ms": round(avg_ms, 4), "algo_bytes_per_pair": ab, "pairs_per_launch": units,
-                "pipeline_achieved": round(ab * pairs_per_s / world / 1e9, 1),
-                "pipeline_frac": round(ab * pairs_per_s / world / 1e9 / HBM_PEAK_GBS, 4),
-                "kernel_ms_per_step": {k: round(v, 4) for k, v in per_step_ms.items()}}
-        # SURVEY 8(d) left the data-dependent bytes out of ALGO_BYTES as "< 6 %": outputs 56 N per image and, for the matcher, 64 N + 12 C + 462 M (N left
-        # keypoints, C candidate pairs, M window searches).  On the benchmark images they are a THIRD of the figure (round-5 review) - reported here as a
-        # second figure from the counts of the step's first pair; `frac` keeps the input-independent convention.
-        try:
-            _u0, _d0, st0 = orb.stereo_result(exl, 0)
-            nl0, nr0 = exl.n_keypoints(0), exr.n_keypoints(0)
-            extra = 56 * (nl0 + nr0) + 64 * nl0 + 12 * int(st0["n_candidate_pairs"]) + 462 * int(st0["n_corr_match"])
-            roof["algo_bytes_per_pair_incl_outputs_and_stereo"] = int(ab + extra)
-            roof["data_dependent_share"] = round(extra / float(ab + extra), 3)
-        except Exception:
-            pass
-        if traffic:
-            roof["kernel_own_hbm_frac"] = round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)      # the dominant kernel's own PMC bytes / its duration / peak
-        if step_traffic:
-            roof["step_traffic_bytes"] = int(step_traffic)
-            roof["step_traffic_over_algorithmic"] = round(step_traffic / (ab * P), 3)
-            roof["step_traffic_frac"] = round(step_traffic / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)      # all HBM bytes of a step / step time / peak
-        props = torch.cuda.get_device_properties(dev)
-        vv = valu_view(args.config if args.tile <= 0 else "", pairs_per_s / world, props.multi_processor_count, props.clock_rate * 1e3 if getattr(props, "clock_rate", 0) else 2.4e9)
-        if vv:
-            roof.update(vv)
-            # the two clocks side by side (round-5 review): `avg_launch_ms` above is this run's hipEvent time of the dominant kernel on its own stream (the
-            # --profile-steps pass), this one the builder's rocprofv3 --kernel-trace average of the same launch shape (profiles/valu_counters.json, digest-checked)
-            try:
-                tj_ = json.load(open(os.path.join(ROOT, "profiles", "valu_counters.json")))
-                us_ = tj_[args.config]["avg_us"].get("k_compact_flat" if dom == "k_compact" else dom) if args.tile <= 0 and per == int(tj_[args.config]["_pairs_per_launch"]) else None
-                if us_:
-                    roof["avg_launch_ms_rocprofv3"] = round(us_ / 1e3, 4)
-                    roof["frac_with_rocprofv3_duration"] = round(ab * units / (us_ * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+                _u0, _d0, st0 = orb.stereo_result(exl, 0)
+                nl0, nr0 = exl.n_keypoints(0), exr.n_keypoints(0)
+                extra = 56 * (nl0 + nr0) + 64 * nl0 + 12 * int(st0["n_candidate_pairs"]) + 462 * int(st0["n_corr_match"])
+                roof["algo_bytes_per_pair_incl_outputs_and_stereo"] = int(ab + extra)
+                roof["data_dependent_share"] = round(extra / float(ab + extra), 3)
             except Exception:
                 pass
-        if not args.no_extras:
-            pm = measure_copy_peak(torch, dev)
-            roof["peak_measured"] = pm
-            roof["peak_measured_what"] = "1 GiB device-to-device copy, read + write bytes, best of 6 (MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy)"
-            roof["frac_of_measured_peak"] = round(achieved / pm, 4)
-            roof["pipeline_frac_of_measured_peak"] = round(ab * pairs_per_s / world / 1e9 / pm, 4)
+            if traffic:
+                roof["kernel_own_hbm_frac"] = round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)      # the dominant kernel's own PMC bytes / its duration / peak
             if step_traffic:
-                roof["step_traffic_frac_of_measured_peak"] = round(step_traffic / (dt / args.steps) / 1e9 / pm, 4)
+                roof["step_traffic_bytes"] = int(step_traffic)
+                roof["step_traffic_over_algorithmic"] = round(step_traffic / (ab * P), 3)
+                roof["step_traffic_frac"] = round(step_traffic / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)      # all HBM bytes of a step / step time / peak
+            props = torch.cuda.get_device_properties(dev)
+            vv = valu_view(args.config if args.tile <= 0 else "", pairs_per_s / world, props.multi_processor_count, props.clock_rate * 1e3 if getattr(props, "clock_rate", 0) else 2.4e9)
+            if vv:
+                roof.update(vv)
+                # the two clocks side by side (round-5 review): `avg_launch_ms` above is this run's hipEvent time of the dominant kernel on its own stream (the
+                # --profile-steps pass), this one the builder's rocprofv3 --kernel-trace average of the same launch shape (profiles/valu_counters.json, digest-checked)
+                try:
+                    tj_ = json.load(open(os.path.join(ROOT, "profiles", "valu_counters.json")))
+                    us_ = tj_[args.config]["avg_us"].get("k_compact_flat" if dom == "k_compact" else dom) if args.tile <= 0 and per == int(tj_[args.config]["_pairs_per_launch"]) else None
+                    if us_:
+                        roof["avg_launch_ms_rocprofv3"] = round(us_ / 1e3, 4)
+                        roof["frac_with_rocprofv3_duration"] = round(ab * units / (us_ * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+                except Exception:
+                    pass
+            if not args.no_extras:
+                pm = measure_copy_peak(torch, dev)
+                roof["peak_measured"] = pm
+                roof["peak_measured_what"] = "1 GiB device-to-device copy, read + write bytes, best of 6 (MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy)"
+                roof["frac_of_measured_peak"] = round(achieved / pm, 4)
+                roof["pipeline_frac_of_measured_peak"] = round(ab * pairs_per_s / world / 1e9 / pm, 4)
+                if step_traffic:
+                    roof["step_traffic_frac_of_measured_peak"] = round(step_traffic / (dt / args.steps) / 1e9 / pm, 4)
         cpu = None
         host_streamed = hs_multi
         frame_latency = None
@@ -663,7 +734,7 @@ def main():
                         other_inputs[fam]["frac_of_headline"] = round(other_inputs[fam]["value"] / pairs_per_s, 3)
                     except Exception as e:
                         other_inputs[fam] = {"error": str(e)[:200]}
-        n0 = int(o_counts[0][0])
+        n0 = None if o_counts is None else int(o_counts[0][0])
         out = {
             "metric": "stereo pairs/s (FAST+ORB extract L+R + stereo match)", "value": round(pairs_per_s, 1), "unit": "stereo pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -678,7 +749,7 @@ def main():
                        "parallelism": "independent pairs sharded over %d GPU(s); RCCL all_gather of counts only" % world},
             "timing": {"blocks": len(blocks), "block_steps": args.steps, "measured_s": round(sum(blocks), 3), "statistic": "median block, max over ranks",
                        "block_ms_min": round(min(blocks) * 1e3, 3), "block_ms_max": round(max(blocks) * 1e3, 3)},
-            "parity_vs_oracle": parity, "parity_pairs_checked": n_unique * n_sets * world, "gathered_counts_ok": counts_ok if world > 1 else None,
+            "parity_vs_oracle": parity, "parity_pairs_checked": n_unique * n_sets * world if args.full else 0, "gathered_counts_ok": counts_ok if world > 1 else None,
             "roofline": roof, "cpu_baseline": cpu, "host_streamed": host_streamed, "frame_latency_us": frame_latency, "c4_batch64": c4, "multi_gpu_diag": multi_diag,
             "other_configs": other, "other_inputs": other_inputs, "rccl_init_s": None if rccl_init_s is None else round(rccl_init_s, 3),
             "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
@@ -689,9 +760,9 @@ def main():
             for k_ in ks:
                 d = d.get(k_) if isinstance(d, dict) else None
             return d
-        out["summary"] = {"pairs_per_s": out["value"], "ms_per_step": out["ms_per_step"], "parity_vs_oracle": parity, "roofline_frac": roof.get("frac"),
-                          "dominant_kernel": dom, "dominant_kernel_ms": roof.get("avg_launch_ms"), "kernel_own_hbm_frac": roof.get("kernel_own_hbm_frac"),
-                          "step_traffic_frac_of_measured_peak": roof.get("step_traffic_frac_of_measured_peak"), "valu_issue_frac": roof.get("valu_issue_frac"),
+        out["summary"] = {"pairs_per_s": out["value"], "ms_per_step": out["ms_per_step"], "parity_vs_oracle": parity, "roofline_frac": (roof or {}).get("frac"),
+                          "dominant_kernel": dom, "dominant_kernel_ms": (roof or {}).get("avg_launch_ms"), "kernel_own_hbm_frac": (roof or {}).get("kernel_own_hbm_frac"),
+                          "step_traffic_frac_of_measured_peak": (roof or {}).get("step_traffic_frac_of_measured_peak"), "valu_issue_frac": (roof or {}).get("valu_issue_frac"),
                           "cpu_baseline_pairs_per_s": _v(cpu, "value"), "host_streamed_pairs_per_s": _v(host_streamed, "value"),
                           "frame_latency_us_median": _v(frame_latency, "total_us_median"), "frame_latency_us_p90": _v(frame_latency, "total_us_p90"),
                           "frame_latency_us_median_persistent_threads": _v(frame_latency, "total_us_median_persistent_threads"),

@@ -5,6 +5,6 @@ fmt='import json,sys; d=json.loads(sys.stdin.readline()); print("  %s device-res
 for i in 1 2 3; do
   for q in "" 8; do
     export GPU_MAX_HW_QUEUES=$q; [ -z "$q" ] && unset GPU_MAX_HW_QUEUES
-    python bench.py --no-cpu-baseline --no-extras --min-time 1.5 2>/dev/null | python -c "$fmt" "queues=${q:-default}"
+    python bench.py --full --no-cpu-baseline --no-extras --min-time 1.5 2>/dev/null | python -c "$fmt" "queues=${q:-default}"
   done
 done

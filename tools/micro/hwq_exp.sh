@@ -9,7 +9,7 @@ fmt='import json,sys; d=json.loads(sys.stdin.readline()); print("  device-reside
 for q in "" 8; do
   echo "GPU_MAX_HW_QUEUES=$q"
   export GPU_MAX_HW_QUEUES=$q; [ -z "$q" ] && unset GPU_MAX_HW_QUEUES
-  python bench.py --no-cpu-baseline --no-extras --min-time 1.5 2>/dev/null | python -c "$fmt"
+  python bench.py --full --no-cpu-baseline --no-extras --min-time 1.5 2>/dev/null | python -c "$fmt"
   for l in 2 4; do echo "  host lanes $l:"; JSORB_HOST_LANES=$l python tools/micro/host_stream_sweep.py 2>&1 | tail -4 | sed 's/^/    /'; done
   tools/micro/frame_latency 480 752 8 30 20 435.2 47.906 /tmp/l.raw /tmp/r.raw 400 2>&1 | tail -1 | sed 's/^/  /'
 done

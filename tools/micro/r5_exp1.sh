@@ -2,7 +2,7 @@
 # round 5, experiment 1: what are more resident k_detect workgroups worth at the SAME band height?  (timing-only knock-out builds: wrong results)
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/../..}
 V=jetson_slam_amd/csrc/_build/variants
-B="python bench.py --no-cpu-baseline --no-extras --min-time 1.5"
+B="python bench.py --full --no-cpu-baseline --no-extras --min-time 1.5"
 fmt='import json,sys; d=json.loads(sys.stdin.readline()); k=d["roofline"]["kernel_ms_per_step"]; print("%-34s %8.1f pairs/s  %.4f ms/step  parity=%s  " % (sys.argv[1], d["value"], d["ms_per_step"], d["parity_vs_oracle"]) + " ".join("%s=%.4f" % (a[2:], b) for a, b in k.items() if b))'
 run() { name=$1; shift; env "$@" $B $EXTRA 2>/dev/null | tail -1 | python -c "$fmt" "$name"; }
 for i in 1 2; do

@@ -6,7 +6,7 @@ fmt='import json,sys; d=json.loads(sys.stdin.readline()); k=d["roofline"]["kerne
 BASE=$PWD/jetson_slam_amd/csrc/_build/variants/base/libjsorb.so
 for i in $(seq $N); do
   for cfg in "--config c2" "--config c3 --pairs 64" "--config c5 --pairs 64"; do
-    B="python bench.py --no-cpu-baseline --no-extras --min-time 1.0 $cfg"
+    B="python bench.py --full --no-cpu-baseline --no-extras --min-time 1.0 $cfg"
     JSORB_LIBRARY=$BASE $B 2>/dev/null | tail -1 | python -c "$fmt" "base ${cfg#--config }"
     $B 2>/dev/null | tail -1 | python -c "$fmt" "new  ${cfg#--config }"
   done

@@ -7,7 +7,7 @@ fmt='import json,sys; d=json.loads(sys.stdin.readline()); k=d["roofline"]["kerne
 P=$PWD/jetson_slam_amd/csrc/_build/variants/prev/libjsorb.so
 for cfg in "$@"; do
 for i in $(seq $N); do
-  B="python bench.py --no-cpu-baseline --no-extras --min-time 1.0 $cfg"
+  B="python bench.py --full --no-cpu-baseline --no-extras --min-time 1.0 $cfg"
   JSORB_LIBRARY=$P $B 2>/dev/null | tail -1 | python -c "$fmt" "prev ${cfg#--config }"
   $B 2>/dev/null | tail -1 | python -c "$fmt" "new  ${cfg#--config }"
 done

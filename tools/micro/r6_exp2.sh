@@ -2,7 +2,7 @@
 # round 6, experiment 2: what clock does the chip actually run the 4-lane pipeline at?  (the VALU-issue ceiling is priced at the nominal 2.4 GHz)
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/../..}
 O=gpurun_out
-( python bench.py --no-cpu-baseline --no-extras --min-time 8 > $O/r6_exp2_bench.json 2>$O/r6_exp2_err.txt ) &
+( python bench.py --full --no-cpu-baseline --no-extras --min-time 8 > $O/r6_exp2_bench.json 2>$O/r6_exp2_err.txt ) &
 BP=$!
 sleep 1
 : > $O/r6_exp2_clocks.txt

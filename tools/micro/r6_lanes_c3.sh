@@ -3,7 +3,7 @@ fmt='import json,sys; d=json.loads(sys.stdin.readline()); k=d["roofline"]["kerne
 for cfg in "--config c3 --pairs 64" "--config c3 --pairs 128"; do
 for i in 1 2; do
   for L in 4 6 8; do
-    JSORB_MAX_LANES=$L JSORB_LANE_MIN_MPX=2 python bench.py --no-cpu-baseline --no-extras --min-time 1.0 $cfg 2>/dev/null | tail -1 | python -c "$fmt" "lanes $L $cfg"
+    JSORB_MAX_LANES=$L JSORB_LANE_MIN_MPX=2 python bench.py --full --no-cpu-baseline --no-extras --min-time 1.0 $cfg 2>/dev/null | tail -1 | python -c "$fmt" "lanes $L $cfg"
   done
 done
 done
