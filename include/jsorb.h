@@ -62,7 +62,7 @@ typedef struct jsorb_stereo_stats {
 } jsorb_stereo_stats;
 
 /* kernel ids for jsorb_kernel_time */
-enum { JSORB_K_PYRAMID = 0, JSORB_K_DETECT, JSORB_K_COMPACT, JSORB_K_BLUR, JSORB_K_DESCRIBE, JSORB_K_STEREO, JSORB_K_MEDIAN, JSORB_K_NMS_MS, JSORB_K_COUNT };
+enum { JSORB_K_PYRAMID = 0, JSORB_K_DETECT, JSORB_K_COMPACT, JSORB_K_BLUR, JSORB_K_DESCRIBE, JSORB_K_STEREO, JSORB_K_MEDIAN, JSORB_K_NMS_MS, JSORB_K_RECTIFY, JSORB_K_COUNT };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -109,6 +109,27 @@ int jsorb_extract_batch_device_async(jsorb_extractor *e, const uint8_t *dev_imag
 int jsorb_extract_batch_host_async(jsorb_extractor *e, const uint8_t *host_images, size_t image_stride, int step, int n_images);
 /* Wait for everything enqueued on this handle and refresh the host-side counts. */
 int jsorb_sync(jsorb_extractor *e);
+
+/* ---- rectification of raw images (Examples/Stereo/stereo_euroc.cpp:106-107 build the maps with cv::initUndistortRectifyMap, :145-146 run
+ * cv::remap(INTER_LINEAR) on the host for both images of every frame before TrackStereo) ----
+ * Once a handle has maps, every extract entry point above reads the caller's RAW image and level 0 is the remapped image: OpenCV's
+ * remap(src, dst, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, 0) on 8-bit gray in its fixed-point form (INTER_BITS = 5, taps outside the
+ * source count as 0), computed on the device (k_rectify).  Everything downstream - pyramid, detection, descriptors, stereo, the mask (in
+ * rectified coordinates), jsorb_level_image_device / jsorb_copy_level_image at level 0 - sees the rectified image.  Maps are per handle (left and
+ * right differ) and have the handle's image size (source size == rectified size).  Setting or clearing maps waits for the handle's work in
+ * flight, converts and uploads once: it is a set-up call, not meant to be made per frame.  A handle without maps behaves as before. */
+/* Float maps (CV_32FC1, as stereo_euroc.cpp:106-107 builds them): map_step_floats floats between rows.  JSORB_ERR_INVALID unless width x height is
+ * the handle's image size. */
+int jsorb_set_rectify_maps(jsorb_extractor *e, const float *mapx, const float *mapy, int width, int height, int map_step_floats);
+/* Maps already in the fixed-point form of cv::convertMaps: xy = CV_16SC2 (ix, iy), a = CV_16UC1 (fy << 5 | fx, masked to 10 bits); steps in
+ * elements (xy_step in int16 pairs, a_step in uint16). */
+int jsorb_set_rectify_maps_fixed(jsorb_extractor *e, const int16_t *xy, const uint16_t *a, int width, int height, int xy_step, int a_step);
+int jsorb_clear_rectify_maps(jsorb_extractor *e);
+int jsorb_rectify_enabled(const jsorb_extractor *e);   /* 1: maps set, 0: none, negative: bad handle */
+/* Host-only, touches no device (like jsorb_plan_launch): the float -> fixed-point conversion jsorb_set_rectify_maps applies, for n map entries.
+ * X = round-half-even(mapx * 32); NaN, inf or an X outside the int range -> X = INT_MIN (a pixel outside the source); xy[2i] = saturate_int16(X >> 5),
+ * xy[2i+1] likewise from mapy, a[i] = (Y & 31) << 5 | (X & 31). */
+int jsorb_rectify_convert_maps(const float *mapx, const float *mapy, int n, int16_t *xy, uint16_t *a);
 
 /* ---- results (valid after a synchronous call or jsorb_sync, until the next extract on the handle) ---- */
 int jsorb_n_images(const jsorb_extractor *e);

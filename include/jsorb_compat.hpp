@@ -22,6 +22,7 @@
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -606,6 +607,41 @@ inline void AssignFeaturesToGrid(ORBExtractor &ex, float mnMinX, float mnMinY, f
             mGrid[i][j].assign(items.begin() + start[c], items.begin() + start[c + 1]);
         }
 }
+
+// Rectification on the device instead of the host cv::remap of the reference's stereo driver (Examples/Stereo/stereo_euroc.cpp:106-107 build
+// M1l/M2l, M1r/M2r with cv::initUndistortRectifyMap; :145-146 remap both images of every frame with INTER_LINEAR): set the maps ONCE per
+// extractor, then hand every extract() the raw camera image.  Maps of the extractor's image size, rows dense (width floats apart).
+inline void SetRectifyMaps(ORBExtractor &ex, const float *mapx, const float *mapy)
+{
+    int h = 0, w = 0;
+    if (jsorb_level_dims(ex.handle(), 0, &h, &w, nullptr) != JSORB_OK || jsorb_set_rectify_maps(ex.handle(), mapx, mapy, w, h, w) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_set_rectify_maps: ") + jsorb_last_error(ex.handle()));
+}
+inline void ClearRectifyMaps(ORBExtractor &ex)
+{
+    if (jsorb_clear_rectify_maps(ex.handle()) != JSORB_OK) throw std::runtime_error(std::string("jsorb_clear_rectify_maps: ") + jsorb_last_error(ex.handle()));
+}
+#ifdef JSORB_WITH_OPENCV
+// The two maps exactly as stereo_euroc.cpp:106-107 produces them: CV_32FC1 + CV_32FC1, or (after cv::convertMaps) CV_16SC2 + CV_16UC1.
+// (A template over cv::Mat only: its body is checked where it is used, so that headers that declare a reduced cv::Mat still compile.)
+template <typename MatT, typename = typename std::enable_if<std::is_same<MatT, cv::Mat>::value>::type>
+inline void SetRectifyMaps(ORBExtractor &ex, const MatT &M1, const MatT &M2)
+{
+    const int k32FC1 = 5, k16SC2 = 11, k16UC1 = 2;      // CV_32FC1, CV_16SC2, CV_16UC1
+    const size_t s1 = M1.step[0], s2 = M2.step[0];
+    int rc;
+    if (M1.rows != M2.rows || M1.cols != M2.cols) throw std::runtime_error("SetRectifyMaps: the two maps differ in size");
+    if (M1.type() == k32FC1 && M2.type() == k32FC1 && s1 == s2 && s1 % sizeof(float) == 0)
+        rc = jsorb_set_rectify_maps(ex.handle(), reinterpret_cast<const float *>(M1.data), reinterpret_cast<const float *>(M2.data), M1.cols, M1.rows,
+                                    (int)(s1 / sizeof(float)));
+    else if (M1.type() == k16SC2 && M2.type() == k16UC1 && s1 % 4 == 0 && s2 % 2 == 0)
+        rc = jsorb_set_rectify_maps_fixed(ex.handle(), reinterpret_cast<const int16_t *>(M1.data), reinterpret_cast<const uint16_t *>(M2.data), M1.cols,
+                                          M1.rows, (int)(s1 / 4), (int)(s2 / 2));
+    else
+        throw std::runtime_error("SetRectifyMaps: expects CV_32FC1 + CV_32FC1 (same step) or CV_16SC2 + CV_16UC1 maps");
+    if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_set_rectify_maps: ") + jsorb_last_error(ex.handle()));
+}
+#endif
 
 } // namespace Jetson_SLAM
 

@@ -33,7 +33,7 @@ using namespace jsorb;
 
 namespace {
 
-const char *k_names[JSORB_K_COUNT] = {"k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms"};
+const char *k_names[JSORB_K_COUNT] = {"k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms", "k_rectify"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; };
 
@@ -152,7 +152,7 @@ struct jsorb_extractor {
     hipGraphNode_t fg_describe_node = nullptr;      // its k_describe node: carries the caller-owned destinations of jsorb_extract_into
     int32_t *fg_dst_kp = nullptr;                   // ... as currently set in the executable graph
     uint8_t *fg_dst_desc = nullptr;
-    const void *fg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // l0 source, its pitch, main stream, (unused x 2), upload node
+    const void *fg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // l0 source, its pitch, main stream, rectification map, (unused), upload node
     // single frame from pageable host memory: the calling thread copies the image into this pinned buffer and the first kernel of the
     // frame pulls it over PCIe (JSORB_KERNEL_UPLOAD=0: hipMemcpyAsync instead).  hipMemcpyAsync from pageable memory goes through a
     // staging buffer of the runtime that the two extractor threads of a stereo frame take turns on: the right image started ~20 us late.
@@ -178,6 +178,12 @@ struct jsorb_extractor {
     int *sp_stats = nullptr, *h_sp_stats = nullptr, *sp_l1 = nullptr;   // sp_l1 / sp_aux: scratch of the speculative match (one pair)
     unsigned *sp_aux = nullptr;
     ImageSrc src{};            // where level 0 of the last extract lives
+    // rectification map (jsorb_set_rectify_maps): the entry points point `src` at the RAW input, run_pipeline remaps it into level 0 of the slab
+    // (k_rectify, first kernel of each lane) and points `src` there
+    bool rect_on = false;
+    RectMap rmap{};
+    void *rect_buf = nullptr;          // the map's xy, a and tile table in one device allocation (kept until destroy)
+    uint8_t *rect_raw = nullptr;       // strided host input with maps: the raw images land here, dense (B x H x W), allocated on first use
     bool extracted = false, stereo_done = false;
     int stereo_pairs = 0;
     bool timing = false;
@@ -639,7 +645,13 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         uint8_t *slab = e->slab + (size_t)f * g.slab_bytes, *blur = e->blur + (size_t)f * g.slab_bytes;
         unsigned long long *tile_out = e->tile_out + f * T, *kp = e->kp + f * T;
         int *counts = e->counts + f * CW;
-        if (e->copy_kind == 1) {
+        const ImageSrc raw = src;                   // with maps: the raw input k_rectify reads; level 0 is then its output in the slab
+        if (e->rect_on) { src.l0 = slab; src.l0_stride = g.slab_bytes; src.l0_pitch = g.lv[0].pitch; }
+        if (e->copy_kind == 1 && e->rect_on) {
+            for (int i = f; i < f + m; i++)
+                HIPCHK(e, hipMemcpy2DAsync(e->rect_raw + (size_t)i * raw.l0_stride, raw.l0_pitch, e->copy_src + (size_t)i * e->copy_stride, e->copy_step,
+                                           g.lv[0].W, g.lv[0].H, hipMemcpyHostToDevice, st));
+        } else if (e->copy_kind == 1) {
             for (int i = f; i < f + m; i++)
                 HIPCHK(e, hipMemcpy2DAsync(e->slab + (size_t)i * g.slab_bytes, g.lv[0].pitch, e->copy_src + (size_t)i * e->copy_stride, e->copy_step,
                                            g.lv[0].W, g.lv[0].H, hipMemcpyHostToDevice, st));
@@ -655,7 +667,7 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
             // The caller-owned destinations (jsorb_extract_into) are NOT part of the key: the reference's Frame builds fresh SyncedMem members
             // every frame, so they change from frame to frame - the k_describe node of the instantiated graph gets them patched in
             // (frame_graph_set_destinations) instead of the graph being captured again.
-            const void *key[6] = {e->src.l0, (const void *)(uintptr_t)e->src.l0_pitch, st, nullptr, nullptr, e->upload_pending ? e->h_upload : nullptr};
+            const void *key[6] = {e->src.l0, (const void *)(uintptr_t)e->src.l0_pitch, st, e->rect_on ? e->rect_buf : nullptr, nullptr, e->upload_pending ? e->h_upload : nullptr};
             if (e->frame_graph && memcmp(key, e->fg_key, sizeof key) == 0) {
                 e->fg_recaptures = 0;
                 if (!frame_graph_set_destinations(e)) { /* fall through to a fresh capture */ }
@@ -682,6 +694,8 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         const int skip_mask = experiment_env("JSORB_SKIP_KERNELS") ? atoi(experiment_env("JSORB_SKIP_KERNELS")) : 0;      // (read per call: the driver warms up with every kernel, then sets it)
 #define JSORB_STAGE(id, launch_stmt) do { if (!((skip_mask >> (id)) & 1)) TIMED(e, id, launch_stmt); } while (0)
         if (e->upload_pending) launch_upload_level0(e->h_upload, e->stage[0], (size_t)g.lv[0].H * g.lv[0].W, st);
+        if (e->rect_on)
+            JSORB_STAGE(JSORB_K_RECTIFY, launch_rectify(e->rmap, raw.l0, raw.l0_stride, raw.l0_pitch, slab, g.slab_bytes, g.lv[0].pitch, g.lv[0].W, g.lv[0].H, m, st));
         JSORB_STAGE(JSORB_K_PYRAMID, launch_pyramid(g, src, slab, e->lut_bits, m, e->pyr_lds, st));
         // single image: k_detect and k_blur (independent of each other) as ONE launch - a frame is a chain of small launches whose latencies add up
         static const bool fuse_env = !env_is(experiment_env("JSORB_FUSED_DETECT_BLUR"), 0);
@@ -748,6 +762,7 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         if (e->upload_pending && !e->sync_single) { HIPCHK(e, hipEventRecord(e->ev_upload_read, st)); e->upload_inflight = true; }      // (recorded behind the frame: an event record inside the captured graph is not an option on this runtime)
     }
     e->copy_kind = 0;
+    if (e->rect_on) { e->src.l0 = e->slab; e->src.l0_stride = g.slab_bytes; e->src.l0_pitch = g.lv[0].pitch; }
     e->upload_pending = false;
     e->mirror_pending = direct;
     e->deliver_kp_dev = nullptr;
@@ -1141,7 +1156,7 @@ void jsorb_destroy(jsorb_extractor *e)
         if (e->lane_used[j]) (void)hipStreamSynchronize(e->lane_used[j]);
     for (auto &t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     void *bufs[] = {e->stage[0], e->stage[1], e->slab, e->blur, e->mask, e->lut_bits, e->tile_out, e->kp, e->counts, e->row_tab, e->angles, e->desc,
-                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items};
+                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items, e->rect_buf, e->rect_raw};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     arena_release(e->det_spill);      // (every kernel of this handle has finished: the lanes were synchronised above)
@@ -1313,8 +1328,13 @@ static int extract_batch_host_enqueue(jsorb_extractor *e, const uint8_t *host_im
         return JSORB_OK;
     }
     // strided input: one 2-D copy per image into the pitched slab, enqueued by run_pipeline on the stream of the lane that owns the image
+    // (with maps: into the dense raw buffer that k_rectify reads)
     e->copy_src = host_images; e->copy_stride = image_stride; e->copy_step = step; e->copy_kind = 1;
     e->src.l0 = e->slab; e->src.l0_stride = e->g.slab_bytes; e->src.l0_pitch = l0.pitch;
+    if (e->rect_on) {
+        if (!e->rect_raw) HIPCHK(e, hipMalloc(&e->rect_raw, (size_t)e->B * img_bytes + 256));
+        e->src.l0 = e->rect_raw; e->src.l0_stride = img_bytes; e->src.l0_pitch = l0.W;
+    }
     e->last_stage = -1;
     return run_pipeline(e, n_images);
 }
@@ -1346,7 +1366,7 @@ static int extract_batch_device_enqueue(jsorb_extractor *e, const uint8_t *dev_i
     // (k_describe, k_stereo: rows at least 5 above the last).  JSORB_COPY_UNALIGNED=1 restores the copy.
     static const bool copy_unaligned = experiment_env("JSORB_COPY_UNALIGNED") && atoi(experiment_env("JSORB_COPY_UNALIGNED")) != 0;
     const bool aligned16 = (step % 16 == 0) && (((uintptr_t)dev_images) % 16 == 0) && (image_stride % 16 == 0);
-    const bool in_place = aligned16 || !copy_unaligned;
+    const bool in_place = aligned16 || !copy_unaligned || e->rect_on;      // (k_rectify reads any alignment)
     if (in_place) {   // no copy of the grayscale plane
         e->src.l0 = dev_images; e->src.l0_stride = image_stride; e->src.l0_pitch = step;
     } else {
@@ -1440,6 +1460,82 @@ int jsorb_extract_device(jsorb_extractor *e, const uint8_t *dev_image, int step,
     if (rc) return rc;
     return finish_single_frame(e, n_keypoints);
 }
+
+// ---- rectification maps (Examples/Stereo/stereo_euroc.cpp:106-107, 145-146) ----
+int jsorb_rectify_convert_maps(const float *mapx, const float *mapy, int n, int16_t *xy, uint16_t *a)
+{
+    if (!mapx || !mapy || !xy || !a || n < 0) return JSORB_ERR_INVALID;
+    rectify_convert_maps(mapx, mapy, (size_t)n, xy, a);
+    return JSORB_OK;
+}
+
+// The map's entries at pitch round_up(W, 4) (one 16-byte + one 8-byte load per lane of k_rectify), entries beyond W point outside the source, then
+// the per-tile source boxes.  The handle's work in flight is waited for first: its k_rectify launches read the buffer that is overwritten.
+static int rectify_upload(jsorb_extractor *e, const int16_t *xy, const uint16_t *a, int xy_step, int a_step)
+{
+    const int W = e->g.lv[0].W, H = e->g.lv[0].H, MP = round_up(W, 4);
+    const int ntx = (W + RECT_TW - 1) / RECT_TW, nty = (H + RECT_TH - 1) / RECT_TH;
+    std::vector<int16_t> hxy((size_t)2 * MP * H, (int16_t)-32768);
+    std::vector<uint16_t> ha((size_t)MP * H, 0);
+    for (int y = 0; y < H; y++) {
+        memcpy(&hxy[(size_t)2 * MP * y], xy + (size_t)2 * xy_step * y, (size_t)4 * W);
+        for (int x = 0; x < W; x++) ha[(size_t)MP * y + x] = a[(size_t)a_step * y + x] & 1023;
+    }
+    std::vector<int32_t> tiles((size_t)4 * ntx * nty);
+    rectify_tile_table(hxy.data(), ha.data(), W, H, MP, ntx, nty, tiles.data());
+    const size_t xy_bytes = (size_t)4 * MP * H, a_bytes = ((size_t)2 * MP * H + 255) & ~(size_t)255, t_bytes = tiles.size() * 4;
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = jsorb_sync(e);
+    if (rc) return rc;
+    if (!e->rect_buf) HIPCHK(e, hipMalloc(&e->rect_buf, xy_bytes + a_bytes + t_bytes));
+    uint8_t *base = static_cast<uint8_t *>(e->rect_buf);
+    HIPCHK(e, hipMemcpy(base, hxy.data(), xy_bytes, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(base + xy_bytes, ha.data(), (size_t)2 * MP * H, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(base + xy_bytes + a_bytes, tiles.data(), t_bytes, hipMemcpyHostToDevice));
+    e->rmap = RectMap{reinterpret_cast<const int *>(base), reinterpret_cast<const uint16_t *>(base + xy_bytes), reinterpret_cast<const int4 *>(base + xy_bytes + a_bytes),
+                      MP, ntx, nty};
+    e->rect_on = true;
+    frame_graph_drop(e);        // the single-frame graph starts with k_rectify now: captured again on the next frame
+    return JSORB_OK;
+}
+
+int jsorb_set_rectify_maps_fixed(jsorb_extractor *e, const int16_t *xy, const uint16_t *a, int width, int height, int xy_step, int a_step)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!xy || !a || width != e->g.lv[0].W || height != e->g.lv[0].H || xy_step < width || a_step < width) {
+        e->err = "rectification maps must have the handle's image size (and steps >= width)";
+        return JSORB_ERR_INVALID;
+    }
+    return rectify_upload(e, xy, a, xy_step, a_step);
+}
+
+int jsorb_set_rectify_maps(jsorb_extractor *e, const float *mapx, const float *mapy, int width, int height, int map_step_floats)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!mapx || !mapy || width != e->g.lv[0].W || height != e->g.lv[0].H || map_step_floats < width) {
+        e->err = "rectification maps must have the handle's image size (and a step >= width)";
+        return JSORB_ERR_INVALID;
+    }
+    std::vector<int16_t> xy((size_t)2 * width * height);
+    std::vector<uint16_t> a((size_t)width * height);
+    for (int y = 0; y < height; y++)
+        rectify_convert_maps(mapx + (size_t)map_step_floats * y, mapy + (size_t)map_step_floats * y, (size_t)width, &xy[(size_t)2 * width * y], &a[(size_t)width * y]);
+    return rectify_upload(e, xy.data(), a.data(), width, width);
+}
+
+int jsorb_clear_rectify_maps(jsorb_extractor *e)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!e->rect_on) return JSORB_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = jsorb_sync(e);
+    if (rc) return rc;
+    e->rect_on = false;
+    frame_graph_drop(e);
+    return JSORB_OK;
+}
+
+int jsorb_rectify_enabled(const jsorb_extractor *e) { return e ? (e->rect_on ? 1 : 0) : JSORB_ERR_INVALID; }
 
 int jsorb_n_images(const jsorb_extractor *e) { return e ? e->n_images : 0; }
 int jsorb_n_keypoints(const jsorb_extractor *e, int image)

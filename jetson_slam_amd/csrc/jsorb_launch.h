@@ -27,6 +27,23 @@ int detect_swar6_threshold(int threshold);   // k_detect: threshold of the 6-bit
 void fill_pyramid_layout(Geometry &g);     // rows per k_pyramid tile (pyr_th), sparse windows, workgroup table offsets (host side, once per handle)
 void launch_upload_level0(const uint8_t *host_pinned, uint8_t *dst, size_t bytes, hipStream_t s);      // bytes: a multiple of 16
 void launch_copy_level0(const uint8_t *src, size_t image_stride, int step, uint8_t *slab, size_t slab_bytes, int pitch, int W, int H, int n_images, hipStream_t s);
+// k_rectify (k_rectify.hip): a handle's rectification map in the fixed-point form, on the device
+#define RECT_TW 64                         // output tile of a workgroup: 64 columns (16 lanes x 4 pixels) x 32 rows (16 lane rows x RECT_RPL)
+#define RECT_TH 32
+#define RECT_RPL 2
+#define RECT_LDS_W 128                     // largest source box (bytes x rows) a workgroup stages in LDS; larger footprints take global taps
+#define RECT_LDS_H 64
+struct RectMap {
+    const int *xy;                         // per output pixel: (ix, iy) as two int16 (CV_16SC2), rows `pitch` entries apart
+    const uint16_t *a;                     // per output pixel: fy << 5 | fx (CV_16UC1 masked to 10 bits)
+    const int4 *tiles;                     // per output tile: source box x0, y0, rows, staged (rectify_tile_table)
+    int pitch;                             // entries per map row (a multiple of 4)
+    int ntx, nty;                          // output tiles per row / column
+};
+void launch_rectify(const RectMap &m, const uint8_t *src, size_t src_stride, int src_step, uint8_t *dst, size_t dst_stride, int dst_pitch, int W, int H,
+                    int n_images, hipStream_t s);
+void rectify_convert_maps(const float *mapx, const float *mapy, size_t n, int16_t *xy, uint16_t *a);      // host only
+void rectify_tile_table(const int16_t *xy, const uint16_t *a, int W, int H, int map_pitch, int ntx, int nty, int32_t *tiles);      // host only
 void launch_pyramid(const Geometry &g, const ImageSrc &src, uint8_t *slab, const uint32_t *ctab, int n_images, size_t lds_bytes, hipStream_t s);
 int detect_ring_bit_of_pixel(int k);       // bit of ring pixel k in the index of the arc LUT as k_detect forms it (the host stores the LUT in that order)
 // images with up to this many tiles: k_compact as a launch of its own runs its re-reading form with 256-thread workgroups on batch handles (k_compact.hip), and a

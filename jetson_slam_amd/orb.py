@@ -23,6 +23,8 @@ MAX_LEVELS = 16
 TH_HIGH, TH_LOW = 100, 50   # ORBmatcher::TH_HIGH / TH_LOW, src/ORBmatcher.cpp:24-25
 
 KERNELS = ["k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms"]
+# kernel ids beyond KERNELS (jsorb_kernel_time; KERNELS stays the list of the eight pipeline stages)
+K_RECTIFY = 8
 
 EXPORTS = [
     "jsorb_create", "jsorb_destroy", "jsorb_last_error", "jsorb_version", "jsorb_plan_launch", "jsorb_extract", "jsorb_extract_into", "jsorb_extract_device",
@@ -38,6 +40,7 @@ EXPORTS = [
     "jsorb_mem_free_device", "jsorb_mem_stream_create", "jsorb_mem_stream_destroy", "jsorb_mem_stream_sync", "jsorb_mem_device_sync", "jsorb_mem_buffer_sync", "jsorb_mem_h2d", "jsorb_mem_d2h",
     "jsorb_mem_d2d", "jsorb_mem_h2d_async", "jsorb_mem_d2h_async", "jsorb_mem_d2d_async", "jsorb_mem_set_zero", "jsorb_mem_set_zero_async",
     "jsorb_mem_last_error", "jsorb_read_mask_image", "jsorb_mask_image_last_error", "jsorb_create_masked",
+    "jsorb_set_rectify_maps", "jsorb_set_rectify_maps_fixed", "jsorb_clear_rectify_maps", "jsorb_rectify_enabled", "jsorb_rectify_convert_maps",
 ]
 
 
@@ -138,6 +141,11 @@ def load_library(path=None):
         "jsorb_is_in_frustum": (I, [P, I] + [P] * 12 + [F] * 4 + [I] * 5 + [F] * 2 + [P] * 6),
         "jsorb_unpack_frame": (I, [P, I, P, P]),
         "jsorb_assign_features_to_grid": (I, [P, I] + [F] * 4 + [I] * 2 + [P] * 2),
+        "jsorb_set_rectify_maps": (I, [P, P, P, I, I, I]),
+        "jsorb_set_rectify_maps_fixed": (I, [P, P, P, I, I, I, I]),
+        "jsorb_clear_rectify_maps": (I, [P]),
+        "jsorb_rectify_enabled": (I, [P]),
+        "jsorb_rectify_convert_maps": (I, [P, P, I, P, P]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -163,6 +171,21 @@ def read_mask_image(path):
     if rc != 0:
         raise JsorbError("jsorb_read_mask_image rc=%d: %s" % (rc, lib.jsorb_mask_image_last_error().decode()))
     return out
+
+
+def convert_maps(mapx, mapy):
+    """jsorb_rectify_convert_maps (host only, no GPU): float maps (CV_32FC1) -> OpenCV's fixed-point form, what cv::convertMaps(..., CV_16SC2)
+    returns: (xy int16[H, W, 2], a uint16[H, W] = fy << 5 | fx)."""
+    lib = load_library()
+    mapx = np.ascontiguousarray(mapx, np.float32)
+    mapy = np.ascontiguousarray(mapy, np.float32)
+    assert mapx.shape == mapy.shape
+    xy = np.zeros(mapx.shape + (2,), np.int16)
+    a = np.zeros(mapx.shape, np.uint16)
+    rc = lib.jsorb_rectify_convert_maps(mapx.ctypes.data, mapy.ctypes.data, mapx.size, xy.ctypes.data, a.ctypes.data)
+    if rc != 0:
+        raise JsorbError("jsorb_rectify_convert_maps rc=%d" % rc)
+    return xy, a
 
 
 def plan_launch(im_height, im_width, scale_factor, n_levels, tile_h=30, tile_w=30, fixed_multi_scale_tile_size=False, max_batch=1,
@@ -380,6 +403,31 @@ class ORBExtractor:
         self._chk(self._lib.jsorb_copy_tile_candidates(self._h, image, x.ctypes.data, y.ctypes.data, s.ctypes.data))
         return x, y, s
 
+    # ---- rectification of raw input (Examples/Stereo/stereo_euroc.cpp:106-107, 145-146) ----
+    def set_rectify_maps(self, mapx, mapy):
+        """From now on every extract reads RAW images and level 0 is cv::remap(raw, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT 0) computed on the
+        device.  float32 (H, W) maps of the handle's image size.  A set-up call (waits for the handle's work), not a per-frame one."""
+        mapx = np.ascontiguousarray(mapx, np.float32)
+        mapy = np.ascontiguousarray(mapy, np.float32)
+        assert mapx.shape == mapy.shape and mapx.ndim == 2
+        self._chk(self._lib.jsorb_set_rectify_maps(self._h, mapx.ctypes.data, mapy.ctypes.data, mapx.shape[1], mapx.shape[0], mapx.shape[1]))
+
+    def set_rectify_maps_fixed(self, xy, a):
+        """The same from maps in cv::convertMaps' fixed-point form: xy int16 (H, W, 2), a uint16 (H, W)."""
+        xy = np.ascontiguousarray(xy, np.int16)
+        a = np.ascontiguousarray(a, np.uint16)
+        assert xy.ndim == 3 and xy.shape[2] == 2 and a.shape == xy.shape[:2]
+        self._chk(self._lib.jsorb_set_rectify_maps_fixed(self._h, xy.ctypes.data, a.ctypes.data, a.shape[1], a.shape[0], a.shape[1], a.shape[1]))
+
+    def clear_rectify_maps(self):
+        self._chk(self._lib.jsorb_clear_rectify_maps(self._h))
+
+    def rectify_enabled(self):
+        rc = self._lib.jsorb_rectify_enabled(self._h)
+        if rc < 0:
+            self._chk(rc)
+        return bool(rc)
+
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
         self._chk(self._lib.jsorb_set_stream(self._h, stream_ptr))
@@ -402,6 +450,12 @@ class ORBExtractor:
             self._chk(self._lib.jsorb_kernel_time(self._h, i, C.byref(ms), C.byref(n)))
             res[name] = (ms.value, n.value)
         return res
+
+    def rectify_kernel_time(self):
+        """(total_ms, launches) of k_rectify (kernel id K_RECTIFY), measured like kernel_times()."""
+        ms, n = C.c_double(), C.c_long()
+        self._chk(self._lib.jsorb_kernel_time(self._h, K_RECTIFY, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
 
 def compute_stereo_matches(left, right, mb, mbf, th_high=TH_HIGH, th_low=TH_LOW):
