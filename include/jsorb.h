@@ -63,6 +63,8 @@ typedef struct jsorb_stereo_stats {
 
 /* kernel ids for jsorb_kernel_time */
 enum { JSORB_K_PYRAMID = 0, JSORB_K_DETECT, JSORB_K_COMPACT, JSORB_K_BLUR, JSORB_K_DESCRIBE, JSORB_K_STEREO, JSORB_K_MEDIAN, JSORB_K_NMS_MS, JSORB_K_RECTIFY, JSORB_K_COUNT };
+/* kernels of the mono / RGB-D Frame steps (jsorb_set_camera, jsorb_rgbd_depth*): ids after the pipeline's; JSORB_K_COUNT_ALL ids in all */
+enum { JSORB_K_UNDISTORT = JSORB_K_COUNT, JSORB_K_RGBD, JSORB_K_COUNT_ALL };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -130,6 +132,53 @@ int jsorb_rectify_enabled(const jsorb_extractor *e);   /* 1: maps set, 0: none, 
  * X = round-half-even(mapx * 32); NaN, inf or an X outside the int range -> X = INT_MIN (a pixel outside the source); xy[2i] = saturate_int16(X >> 5),
  * xy[2i+1] likewise from mapy, a[i] = (Y & 31) << 5 | (X & 31). */
 int jsorb_rectify_convert_maps(const float *mapx, const float *mapy, int n, int16_t *xy, uint16_t *a);
+
+/* ---- camera: keypoint undistortion of the mono / RGB-D Frame (Frame::UndistortKeyPoints, src/Frame.cpp:718-748; ComputeImageBounds :750-778) ----
+ * The camera is Tracking's mK (fx, fy, cx, cy; CV_32F, zero skew) and mDistCoef (k1, k2, p1, p2[, k3]; CV_32F, k3 = 0 in the 4-coefficient form),
+ * src/Tracking.cpp:80-91.  Undistortion is ACTIVE only when k1 != 0: the reference tests mDistCoef.at<float>(0) == 0.0 - k1 alone - and then takes
+ * mvKeysUn = mvKeys and the bounds 0, cols, 0, rows even if p1, p2 or k3 are nonzero.
+ * Arithmetic: OpenCV 4's undistortPoints(src, dst, K, D, noArray(), K) with the default criteria (5 iterations, no epsilon test), all in double:
+ *   fx, fy, cx, cy, k* = (double) of the floats; ifx = 1./fx; ify = 1./fy; u, v = (double) keypoint x, y
+ *   x = (u - cx)*ifx; y = (v - cy)*ify; x0 = x; y0 = y
+ *   5 times: r2 = x*x + y*y; icdist = 1/(1 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *            if icdist < 0: x = (u - cx)*ifx; y = (v - cy)*ify; stop
+ *            deltaX = 2*p1*x*y + p2*(r2 + 2*x*x); deltaY = p1*(r2 + 2*y*y) + 2*p2*x*y   (left to right)
+ *            x = (x0 - deltaX)*icdist; y = (y0 - deltaY)*icdist
+ *   x_un = (float)(fx*x + cx); y_un = (float)(fy*y + cy)
+ * With an active camera every extract entry point also runs k_undistort behind the extraction (inside the single-frame graph, on every lane of a
+ * batch) and jsorb_assign_features_to_grid bins (x_un, y_un).  Setting or clearing the camera waits for the handle's work in flight; results of an
+ * extract made before the call are undistorted with the new camera right away.  A handle that never sets a camera allocates and launches nothing. */
+typedef struct jsorb_camera { float fx, fy, cx, cy, k1, k2, p1, p2, k3; } jsorb_camera;
+int jsorb_set_camera(jsorb_extractor *e, const jsorb_camera *camera);        /* NULL clears */
+int jsorb_camera_enabled(const jsorb_extractor *e);                          /* 1: undistortion active (k1 != 0), 0: not, negative: bad handle */
+/* Host-only, touches no device (like jsorb_plan_launch): Frame::ComputeImageBounds (Frame.cpp:750-778) - the corners (0,0), (W,0), (0,H), (W,H)
+ * undistorted as above; out = {minX = min(c0.x, c2.x), maxX = max(c1.x, c3.x), minY = min(c0.y, c1.y), maxY = max(c2.y, c3.y)}, or {0, W, 0, H}
+ * when k1 == 0. */
+int jsorb_image_bounds(const jsorb_camera *camera, int width, int height, float out[4]);
+/* mvKeysUn of one image of the last batch: x_un[N] then y_un[N] (device: at image * 2T floats; NULL without an active camera).  The copy without
+ * an active camera returns the keypoint coordinates as floats (mvKeysUn = mvKeys). */
+const float *jsorb_keypoints_un_device(const jsorb_extractor *e, int image);
+int jsorb_copy_keypoints_un(const jsorb_extractor *e, int image, float *xy /* 2N: x[N] then y[N] */);
+
+/* ---- RGB-D: Frame::ComputeStereoFromRGBD (src/Frame.cpp:996-1017) with Tracking's depth conversion (src/Tracking.cpp:333-334) ----
+ * Per keypoint i: d = depth at the DISTORTED keypoint (row y, column x), converted like imDepth.convertTo(CV_32F, factor) would convert it:
+ *   JSORB_DEPTH_U16: d = (float)raw * factor (one rounding);  JSORB_DEPTH_F32: d = raw * factor if |factor - 1| > 1e-5, else d = raw.
+ * factor is Tracking's mDepthMapFactor (already inverted, Tracking.cpp:230-234).  If d > 0 (NaN never passes): depth = d, uRight = x_un - mbf/d
+ * (float, correctly rounded; x_un = kpU.pt.x, the keypoint's own x without an active camera), else both are -1.  Only the sampled pixels are read. */
+#define JSORB_DEPTH_F32 0
+#define JSORB_DEPTH_U16 1
+/* Synchronous, image 0 of the last extract; host depth image (step_bytes between rows); u_right / depth: N host floats each (either may be NULL). */
+int jsorb_rgbd_depth(jsorb_extractor *e, const void *host_depth, int format, size_t step_bytes, float factor, float mbf, float *u_right, float *depth);
+/* Batch: image i of the last batch against the depth image at dev_depths + i * image_stride (device memory, valid until jsorb_sync); enqueues only.
+ * n_images must be the last batch's; image_stride >= height * step_bytes.  Ordered after the work enqueued so far on the handle's main stream
+ * (jsorb_set_stream), and work enqueued there afterwards runs after it. */
+int jsorb_rgbd_depth_batch_device_async(jsorb_extractor *e, const void *dev_depths, size_t image_stride, size_t step_bytes, int format, float factor,
+                                        float mbf, int n_images);
+/* N floats of image `image` from the last RGB-D call since the last extract; NULL (copy: JSORB_ERR_STATE) for images it did not cover - the
+ * synchronous call covers image 0 only. */
+const float *jsorb_rgbd_uright_device(const jsorb_extractor *e, int image);
+const float *jsorb_rgbd_depth_device(const jsorb_extractor *e, int image);
+int jsorb_copy_rgbd(const jsorb_extractor *e, int image, float *u_right, float *depth);
 
 /* ---- results (valid after a synchronous call or jsorb_sync, until the next extract on the handle) ---- */
 int jsorb_n_images(const jsorb_extractor *e);
@@ -216,10 +265,15 @@ typedef struct jsorb_keypoint { float x, y, size, angle, response; int32_t octav
  * A device kernel interleaves the SoA; both arrays then come back with two asynchronous copies and ONE synchronisation (the
  * reference: four blocking SyncedMem::to_cpu() per stereo frame, then a host loop).  Either destination may be NULL. */
 int jsorb_unpack_frame(jsorb_extractor *e, int image, jsorb_keypoint *keypoints, uint8_t *descriptors);
+/* jsorb_unpack_frame plus mvKeysUn as cv::KeyPoint records (mvKeys with pt replaced, Frame.cpp:741-747) when the handle has an
+ * active camera (jsorb_set_camera), mvKeys again otherwise.  Any destination may be NULL;
+ * one synchronisation (none after a synchronous single-frame extract: the kernels wrote pinned host mirrors). */
+int jsorb_unpack_frame_un(jsorb_extractor *e, int image, jsorb_keypoint *keys, jsorb_keypoint *keys_un, uint8_t *descriptors);
 /* Frame::AssignFeaturesToGrid + Frame::PosInGrid (Frame.cpp:463-479, 696-706) on the device, as CSR over cols x rows cells:
  * cell (i, j) has index i*rows + j (mGrid[i][j]); cell_start has cols*rows + 1 entries; cell_items lists keypoint indices,
- * ascending inside a cell (the reference's push_back order).  Uses the extracted keypoint coordinates (mvKeysUn == mvKeys for
- * rectified stereo).  Host destinations; cols*rows <= 16384. */
+ * ascending inside a cell (the reference's push_back order).  Bins mvKeysUn: the undistorted coordinates when the handle has an active
+ * camera (jsorb_set_camera), else the extracted keypoint coordinates (mvKeysUn == mvKeys: rectified stereo, k1 == 0).  Host destinations;
+ * cols*rows <= 16384. */
 int jsorb_assign_features_to_grid(jsorb_extractor *e, int image, float min_x, float min_y, float grid_element_width_inv,
                                   float grid_element_height_inv, int cols, int rows, int32_t *cell_start, int32_t *cell_items);
 

@@ -589,7 +589,8 @@ inline void UnpackFrame(ORBExtractor &ex, std::vector<cv::KeyPoint> &mvKeys, cv:
 }
 #endif
 
-// Body of Frame::AssignFeaturesToGrid (Frame.cpp:463-479) for the extracted keypoints (mvKeysUn == mvKeys, rectified stereo):
+// Body of Frame::AssignFeaturesToGrid (Frame.cpp:463-479) over mvKeysUn: the undistorted keypoints when the extractor has an active camera
+// (SetCamera below: mono / RGB-D with lens distortion), the extracted ones otherwise (mvKeysUn == mvKeys: rectified stereo, k1 == 0).
 // mGrid is the reference's std::vector<std::size_t> mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS] (Frame.h:191).
 template <std::size_t COLS, std::size_t ROWS>
 inline void AssignFeaturesToGrid(ORBExtractor &ex, float mnMinX, float mnMinY, float mfGridElementWidthInv, float mfGridElementHeightInv,
@@ -640,6 +641,104 @@ inline void SetRectifyMaps(ORBExtractor &ex, const MatT &M1, const MatT &M2)
     else
         throw std::runtime_error("SetRectifyMaps: expects CV_32FC1 + CV_32FC1 (same step) or CV_16SC2 + CV_16UC1 maps");
     if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_set_rectify_maps: ") + jsorb_last_error(ex.handle()));
+}
+#endif
+
+// ---- mono / RGB-D Frame (Frame.cpp:251-354, 357-462): the camera, mvKeysUn, the image bounds and the RGB-D depth on the device ----
+// Set Tracking's camera ONCE per extractor (Tracking.cpp:80-91); every extract() then also undistorts its keypoints (k_undistort) when k1 != 0.
+inline void SetCamera(ORBExtractor &ex, const jsorb_camera &camera)
+{
+    if (jsorb_set_camera(ex.handle(), &camera) != JSORB_OK) throw std::runtime_error(std::string("jsorb_set_camera: ") + jsorb_last_error(ex.handle()));
+}
+inline void ClearCamera(ORBExtractor &ex)
+{
+    if (jsorb_set_camera(ex.handle(), nullptr) != JSORB_OK) throw std::runtime_error(std::string("jsorb_set_camera: ") + jsorb_last_error(ex.handle()));
+}
+
+// Frame.cpp:119-196 + UndistortKeyPoints (:718-748): mvKeys, mvKeysUn and the descriptor rows with one synchronisation.
+inline void UnpackFrame(ORBExtractor &ex, std::vector<jsorb_keypoint> &mvKeys, std::vector<jsorb_keypoint> &mvKeysUn, std::vector<unsigned char> &descriptors)
+{
+    const int n = jsorb_n_keypoints(ex.handle(), 0);
+    if (n < 0) throw std::runtime_error("UnpackFrame before extract");
+    mvKeys.resize(n);
+    mvKeysUn.resize(n);
+    descriptors.resize((size_t)32 * n);
+    if (n && jsorb_unpack_frame_un(ex.handle(), 0, mvKeys.data(), mvKeysUn.data(), descriptors.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_unpack_frame_un: ") + jsorb_last_error(ex.handle()));
+}
+
+// Frame::ComputeStereoFromRGBD (Frame.cpp:996-1017) on a raw depth plane - JSORB_DEPTH_U16 (the PNG as read, never converted as a whole) or
+// JSORB_DEPTH_F32 - with Tracking's mDepthMapFactor (already inverted, Tracking.cpp:230-234) applied to the sampled pixels only.
+inline void ComputeStereoFromRGBD(ORBExtractor &ex, const void *depth, int format, size_t step_bytes, float mDepthMapFactor, float mbf,
+                                  std::vector<float> &mvuRight, std::vector<float> &mvDepth)
+{
+    const int n = jsorb_n_keypoints(ex.handle(), 0);
+    if (n < 0) throw std::runtime_error("ComputeStereoFromRGBD before extract");
+    mvuRight.assign(n, -1.0f);
+    mvDepth.assign(n, -1.0f);
+    if (n && jsorb_rgbd_depth(ex.handle(), depth, format, step_bytes, mDepthMapFactor, mbf, mvuRight.data(), mvDepth.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_rgbd_depth: ") + jsorb_last_error(ex.handle()));
+}
+
+// Frame::ComputeImageBounds (Frame.cpp:750-778), host only.
+inline void ComputeImageBounds(const jsorb_camera &camera, int cols, int rows, float &mnMinX, float &mnMaxX, float &mnMinY, float &mnMaxY)
+{
+    float b[4];
+    if (jsorb_image_bounds(&camera, cols, rows, b) != JSORB_OK) throw std::runtime_error("jsorb_image_bounds: bad camera or image size");
+    mnMinX = b[0]; mnMaxX = b[1]; mnMinY = b[2]; mnMaxY = b[3];
+}
+
+#ifdef JSORB_WITH_OPENCV
+// mvKeys / mvKeysUn as std::vector<cv::KeyPoint> (the memory layout of jsorb_keypoint) and mDescriptors as N x 32 CV_8UC1.
+inline void UnpackFrame(ORBExtractor &ex, std::vector<cv::KeyPoint> &mvKeys, std::vector<cv::KeyPoint> &mvKeysUn, cv::Mat &mDescriptors)
+{
+    static_assert(sizeof(cv::KeyPoint) == sizeof(jsorb_keypoint), "jsorb_keypoint mirrors cv::KeyPoint");
+    const int n = jsorb_n_keypoints(ex.handle(), 0);
+    if (n < 0) throw std::runtime_error("UnpackFrame before extract");
+    mvKeys.resize(n);
+    mvKeysUn.resize(n);
+    mDescriptors = cv::Mat(n, 32, CV_8UC1);
+    if (n && jsorb_unpack_frame_un(ex.handle(), 0, reinterpret_cast<jsorb_keypoint *>(mvKeys.data()), reinterpret_cast<jsorb_keypoint *>(mvKeysUn.data()),
+                                   mDescriptors.data) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_unpack_frame_un: ") + jsorb_last_error(ex.handle()));
+}
+
+// (Templates over cv::Mat only, like SetRectifyMaps: their bodies are checked where they are used, so that headers that declare a reduced
+// cv::Mat still compile.)
+// Tracking's mK (3x3 CV_32F) and mDistCoef (4x1 or 5x1 CV_32F), Tracking.cpp:80-91.
+template <typename MatT, typename = typename std::enable_if<std::is_same<MatT, cv::Mat>::value>::type>
+inline jsorb_camera CameraFromMats(const MatT &mK, const MatT &mDistCoef)
+{
+    const int k32F = 5;      // CV_32F
+    if (mK.type() != k32F || mK.rows != 3 || mK.cols != 3 || mDistCoef.type() != k32F || (mDistCoef.total() != 4 && mDistCoef.total() != 5))
+        throw std::runtime_error("camera: expects mK 3x3 CV_32F and mDistCoef with 4 or 5 CV_32F coefficients");
+    jsorb_camera c;
+    c.fx = mK.template at<float>(0, 0); c.fy = mK.template at<float>(1, 1); c.cx = mK.template at<float>(0, 2); c.cy = mK.template at<float>(1, 2);
+    c.k1 = mDistCoef.template at<float>(0); c.k2 = mDistCoef.template at<float>(1);
+    c.p1 = mDistCoef.template at<float>(2); c.p2 = mDistCoef.template at<float>(3);
+    c.k3 = mDistCoef.total() == 5 ? mDistCoef.template at<float>(4) : 0.0f;
+    return c;
+}
+template <typename MatT, typename = typename std::enable_if<std::is_same<MatT, cv::Mat>::value>::type>
+inline void SetCamera(ORBExtractor &ex, const MatT &mK, const MatT &mDistCoef)
+{
+    SetCamera(ex, CameraFromMats(mK, mDistCoef));
+}
+template <typename MatT, typename = typename std::enable_if<std::is_same<MatT, cv::Mat>::value>::type>
+inline void ComputeImageBounds(const MatT &mK, const MatT &mDistCoef, int cols, int rows, float &mnMinX, float &mnMaxX, float &mnMinY, float &mnMaxY)
+{
+    ComputeImageBounds(CameraFromMats(mK, mDistCoef), cols, rows, mnMinX, mnMaxX, mnMinY, mnMaxY);
+}
+// imDepth as Tracking::GrabImageRGBD receives it (CV_16UC1 from the PNG, or CV_32FC1), BEFORE Tracking.cpp:333-334's convertTo: the factor is
+// applied to the sampled pixels only.
+template <typename MatT, typename = typename std::enable_if<std::is_same<MatT, cv::Mat>::value>::type>
+inline void ComputeStereoFromRGBD(ORBExtractor &ex, const MatT &imDepth, float mDepthMapFactor, float mbf, std::vector<float> &mvuRight,
+                                  std::vector<float> &mvDepth)
+{
+    const int k16UC1 = 2, k32FC1 = 5;
+    const int format = imDepth.type() == k16UC1 ? JSORB_DEPTH_U16 : imDepth.type() == k32FC1 ? JSORB_DEPTH_F32 : -1;
+    if (format < 0) throw std::runtime_error("ComputeStereoFromRGBD: expects a CV_16UC1 or CV_32FC1 depth image");
+    ComputeStereoFromRGBD(ex, imDepth.data, format, (size_t)imDepth.step[0], mDepthMapFactor, mbf, mvuRight, mvDepth);
 }
 #endif
 

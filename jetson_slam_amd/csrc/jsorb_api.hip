@@ -33,7 +33,8 @@ using namespace jsorb;
 
 namespace {
 
-const char *k_names[JSORB_K_COUNT] = {"k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms", "k_rectify"};
+const char *k_names[JSORB_K_COUNT_ALL] = {"k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms", "k_rectify",
+                                          "k_undistort", "k_rgbd"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; };
 
@@ -152,7 +153,7 @@ struct jsorb_extractor {
     hipGraphNode_t fg_describe_node = nullptr;      // its k_describe node: carries the caller-owned destinations of jsorb_extract_into
     int32_t *fg_dst_kp = nullptr;                   // ... as currently set in the executable graph
     uint8_t *fg_dst_desc = nullptr;
-    const void *fg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // l0 source, its pitch, main stream, rectification map, (unused), upload node
+    const void *fg_key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // l0 source, its pitch, main stream, rectification map, camera, upload node
     // single frame from pageable host memory: the calling thread copies the image into this pinned buffer and the first kernel of the
     // frame pulls it over PCIe (JSORB_KERNEL_UPLOAD=0: hipMemcpyAsync instead).  hipMemcpyAsync from pageable memory goes through a
     // staging buffer of the runtime that the two extractor threads of a stereo frame take turns on: the right image started ~20 us late.
@@ -184,12 +185,25 @@ struct jsorb_extractor {
     RectMap rmap{};
     void *rect_buf = nullptr;          // the map's xy, a and tile table in one device allocation (kept until destroy)
     uint8_t *rect_raw = nullptr;       // strided host input with maps: the raw images land here, dense (B x H x W), allocated on first use
+    // camera (jsorb_set_camera): with k1 != 0 run_pipeline appends k_undistort to every lane; buffers allocated on the first set, then kept
+    bool cam_on = false;
+    UndistortCam cam{};
+    float *un = nullptr;               // B x 2T floats: x_un[N] y_un[N] per image
+    float *h_un = nullptr;             // pinned mirror of image 0, written by k_undistort on the single-frame path
+    bool un_valid = false;             // `un` holds the last batch undistorted with the current camera
+    bool un_mirror = false;            // h_un was written by the last (single-image) pipeline: valid together with mirror_valid
+    // RGB-D (jsorb_rgbd_depth*): allocated on the first call, then kept
+    float *rg = nullptr;               // B x T uRight, then B x T depth
+    float *h_rg = nullptr;             // pinned: T uRight, T depth of image 0 (synchronous call)
+    uint8_t *h_depth = nullptr;        // pinned staging of one host depth image (dense rows), read in place by k_rgbd
+    bool rgbd_mirror = false;
+    int rgbd_images = 0;               // images of the last batch the last RGB-D call covered (0: none; the synchronous call covers image 0 only)
     bool extracted = false, stereo_done = false;
     int stereo_pairs = 0;
     bool timing = false;
     std::vector<TimedLaunch> timed;
-    double k_ms[JSORB_K_COUNT] = {0};
-    long k_n[JSORB_K_COUNT] = {0};
+    double k_ms[JSORB_K_COUNT_ALL] = {0};
+    long k_n[JSORB_K_COUNT_ALL] = {0};
     std::string err;
     // JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy
     bool trace_host = false;
@@ -667,7 +681,8 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
             // The caller-owned destinations (jsorb_extract_into) are NOT part of the key: the reference's Frame builds fresh SyncedMem members
             // every frame, so they change from frame to frame - the k_describe node of the instantiated graph gets them patched in
             // (frame_graph_set_destinations) instead of the graph being captured again.
-            const void *key[6] = {e->src.l0, (const void *)(uintptr_t)e->src.l0_pitch, st, e->rect_on ? e->rect_buf : nullptr, nullptr, e->upload_pending ? e->h_upload : nullptr};
+            const void *key[6] = {e->src.l0, (const void *)(uintptr_t)e->src.l0_pitch, st, e->rect_on ? e->rect_buf : nullptr, e->cam_on ? e->un : nullptr,
+                                  e->upload_pending ? e->h_upload : nullptr};      // (jsorb_set_camera drops the graph: the camera is a kernel argument)
             if (e->frame_graph && memcmp(key, e->fg_key, sizeof key) == 0) {
                 e->fg_recaptures = 0;
                 if (!frame_graph_set_destinations(e)) { /* fall through to a fresh capture */ }
@@ -735,6 +750,8 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         JSORB_STAGE(JSORB_K_DESCRIBE, launch_describe(g, src, slab, blur, kp, counts, e->angles + f * T, e->desc + f * T * 32, e->out_kp + f * T * 6, m, st,
                                                       direct ? Deliver{e->deliver_kp_dev, e->deliver_desc_dev, e->h_kp, e->h_desc, nullptr}
                                                              : Deliver{nullptr, nullptr, nullptr, nullptr, nullptr}));
+        if (e->cam_on)      // Frame::UndistortKeyPoints (Frame.cpp:718-748) behind the extraction, on the device counts
+            JSORB_STAGE(JSORB_K_UNDISTORT, launch_undistort(e->cam, e->out_kp + f * T * 6, counts, (int)T, e->un + f * T * 2, direct ? e->h_un : nullptr, m, st));
 #undef JSORB_STAGE
         if (capturing) {
             // Whatever happened between Begin and End (a launch error included), the stream must leave capture mode; on any failure the
@@ -762,6 +779,10 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         if (e->upload_pending && !e->sync_single) { HIPCHK(e, hipEventRecord(e->ev_upload_read, st)); e->upload_inflight = true; }      // (recorded behind the frame: an event record inside the captured graph is not an option on this runtime)
     }
     e->copy_kind = 0;
+    e->un_valid = e->cam_on;
+    e->un_mirror = direct && e->cam_on;
+    e->rgbd_images = 0;
+    e->rgbd_mirror = false;
     if (e->rect_on) { e->src.l0 = e->slab; e->src.l0_stride = g.slab_bytes; e->src.l0_pitch = g.lv[0].pitch; }
     e->upload_pending = false;
     e->mirror_pending = direct;
@@ -898,7 +919,7 @@ extern "C" {
 
 const char *jsorb_version(void) { return "jsorb 0.1 (gfx950)"; }
 
-const char *jsorb_kernel_name(int id) { return (id >= 0 && id < JSORB_K_COUNT) ? k_names[id] : ""; }
+const char *jsorb_kernel_name(int id) { return (id >= 0 && id < JSORB_K_COUNT_ALL) ? k_names[id] : ""; }
 
 const char *jsorb_last_error(const jsorb_extractor *e) { return e ? e->err.c_str() : "null handle"; }
 
@@ -1156,12 +1177,12 @@ void jsorb_destroy(jsorb_extractor *e)
         if (e->lane_used[j]) (void)hipStreamSynchronize(e->lane_used[j]);
     for (auto &t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     void *bufs[] = {e->stage[0], e->stage[1], e->slab, e->blur, e->mask, e->lut_bits, e->tile_out, e->kp, e->counts, e->row_tab, e->angles, e->desc,
-                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items, e->rect_buf, e->rect_raw};
+                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items, e->rect_buf, e->rect_raw, e->un, e->rg};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     arena_release(e->det_spill);      // (every kernel of this handle has finished: the lanes were synchronised above)
     if (e->h_counts) (void)hipHostFree(e->h_counts);
-    for (void *hp : {(void *)e->h_kp, (void *)e->h_desc, (void *)e->h_u, (void *)e->h_d, (void *)e->h_sp_u, (void *)e->h_sp_d, (void *)e->h_sp_stats, (void *)e->h_upload})
+    for (void *hp : {(void *)e->h_kp, (void *)e->h_desc, (void *)e->h_u, (void *)e->h_d, (void *)e->h_sp_u, (void *)e->h_sp_d, (void *)e->h_sp_stats, (void *)e->h_upload, (void *)e->h_un, (void *)e->h_rg, (void *)e->h_depth})
         if (hp) (void)hipHostFree(hp);
     if (e->h_stats) (void)hipHostFree(e->h_stats);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -1537,6 +1558,231 @@ int jsorb_clear_rectify_maps(jsorb_extractor *e)
 
 int jsorb_rectify_enabled(const jsorb_extractor *e) { return e ? (e->rect_on ? 1 : 0) : JSORB_ERR_INVALID; }
 
+// ---- camera: Frame::UndistortKeyPoints / ComputeImageBounds (Frame.cpp:718-778) ----
+static UndistortCam to_cam(const jsorb_camera &c) { return UndistortCam{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3}; }
+
+int jsorb_image_bounds(const jsorb_camera *camera, int width, int height, float out[4])
+{
+    if (!camera || !out || width < 1 || height < 1) return JSORB_ERR_INVALID;
+    const UndistortCam c = to_cam(*camera);
+    if (!camera_active(c)) {
+        out[0] = 0.0f; out[1] = (float)width; out[2] = 0.0f; out[3] = (float)height;
+        return JSORB_OK;
+    }
+    const float W = (float)width, H = (float)height;
+    const float cx[4] = {0.0f, W, 0.0f, W}, cy[4] = {0.0f, 0.0f, H, H};
+    float ux[4], uy[4];
+    for (int i = 0; i < 4; i++) undistort_point(c, cx[i], cy[i], &ux[i], &uy[i]);
+    out[0] = std::min(ux[0], ux[2]);
+    out[1] = std::max(ux[1], ux[3]);
+    out[2] = std::min(uy[0], uy[1]);
+    out[3] = std::max(uy[2], uy[3]);
+    return JSORB_OK;
+}
+
+int jsorb_set_camera(jsorb_extractor *e, const jsorb_camera *camera)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    const bool on = camera && camera->k1 != 0.0f;
+    if (!on && !e->cam_on) return JSORB_OK;          // nothing to undo, nothing to allocate
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = jsorb_sync(e);
+    if (rc) return rc;
+    frame_graph_drop(e);          // the single-frame graph carries the camera as a kernel argument (or lacks k_undistort): captured again
+    e->un_valid = false;
+    e->un_mirror = false;
+    e->rgbd_images = 0;           // its uRight used the old mvKeysUn
+    e->rgbd_mirror = false;
+    e->cam_on = on;
+    if (!on) return JSORB_OK;
+    e->cam = to_cam(*camera);
+    const size_t T = (size_t)e->g.T;
+    if (!e->un) HIPCHK(e, hipMalloc(&e->un, (size_t)e->B * 2 * T * sizeof(float)));
+    if (!e->h_un) HIPCHK(e, hipHostMalloc(&e->h_un, 2 * T * sizeof(float)));
+    if (e->extracted && e->n_images > 0) {      // the results already there are undistorted with the new camera (device copy only)
+        launch_undistort(e->cam, e->out_kp, e->counts, (int)T, e->un, nullptr, e->n_images, e->stream);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        e->un_valid = true;
+    }
+    return JSORB_OK;
+}
+
+int jsorb_camera_enabled(const jsorb_extractor *e) { return e ? (e->cam_on ? 1 : 0) : JSORB_ERR_INVALID; }
+
+const float *jsorb_keypoints_un_device(const jsorb_extractor *e, int image)
+{
+    return (check_image(e, image) && e->un_valid) ? e->un + (size_t)image * 2 * e->g.T : nullptr;
+}
+
+int jsorb_copy_keypoints_un(const jsorb_extractor *e, int image, float *xy)
+{
+    if (!check_image(e, image) || !xy) return JSORB_ERR_STATE;
+    const int n = jsorb_n_keypoints(e, image);
+    if (n <= 0) return JSORB_OK;
+    if (!e->un_valid) {           // mvKeysUn = mvKeys: the keypoint coordinates as floats
+        std::vector<int32_t> kp((size_t)6 * n);
+        int rc = jsorb_copy_keypoints(e, image, kp.data());
+        if (rc) return rc;
+        for (size_t i = 0; i < (size_t)2 * n; i++) xy[i] = (float)kp[i];
+        return JSORB_OK;
+    }
+    if (e->mirror_valid && e->un_mirror && image == 0) { memcpy(xy, e->h_un, (size_t)n * 2 * sizeof(float)); return JSORB_OK; }
+    return hipMemcpy(xy, jsorb_keypoints_un_device(e, image), (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess ? JSORB_OK : JSORB_ERR_HIP;
+}
+
+int jsorb_unpack_frame_un(jsorb_extractor *e, int image, jsorb_keypoint *keys, jsorb_keypoint *keys_un, uint8_t *descriptors)
+{
+    if (!check_image(e, image)) return JSORB_ERR_STATE;
+    const int n = jsorb_n_keypoints(e, image);
+    if (n <= 0) return JSORB_OK;
+    if (!keys_un) return jsorb_unpack_frame(e, image, keys, descriptors);
+    if (e->mirror_valid && image == 0 && (!e->un_valid || e->un_mirror)) {
+        // synchronous single frame: keypoints, descriptors and x_un / y_un are in pinned host memory already - interleave here (Frame.cpp:139-147, 741-747)
+        int rc = jsorb_unpack_frame(e, 0, keys_un, descriptors);
+        if (rc) return rc;
+        if (keys) memcpy(keys, keys_un, (size_t)n * sizeof(jsorb_keypoint));
+        if (e->un_valid)
+            for (int i = 0; i < n; i++) { keys_un[i].x = e->h_un[i]; keys_un[i].y = e->h_un[n + i]; }
+        return JSORB_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->frame_aos) HIPCHK(e, hipMalloc(&e->frame_aos, (size_t)e->g.T * sizeof(jsorb_keypoint)));
+    std::vector<float> xy(e->un_valid ? (size_t)2 * n : 0);
+    launch_unpack_keypoints(jsorb_keypoints_device(e, image), n, e->frame_aos, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(keys_un, e->frame_aos, (size_t)n * sizeof(jsorb_keypoint), hipMemcpyDeviceToHost, e->stream));
+    if (keys) HIPCHK(e, hipMemcpyAsync(keys, e->frame_aos, (size_t)n * sizeof(jsorb_keypoint), hipMemcpyDeviceToHost, e->stream));
+    if (e->un_valid) HIPCHK(e, hipMemcpyAsync(xy.data(), jsorb_keypoints_un_device(e, image), (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (descriptors) HIPCHK(e, hipMemcpyAsync(descriptors, jsorb_descriptors_device(e, image), (size_t)n * 32, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->un_valid)
+        for (int i = 0; i < n; i++) { keys_un[i].x = xy[i]; keys_un[i].y = xy[n + i]; }
+    return JSORB_OK;
+}
+
+// ---- RGB-D: Frame::ComputeStereoFromRGBD (Frame.cpp:996-1017) + Tracking.cpp:333-334 ----
+static int rgbd_check(jsorb_extractor *e, const void *depth, int format, size_t step_bytes, size_t image_stride, int n_images)
+{
+    if (!e->extracted) { e->err = "RGB-D depth before extract"; return JSORB_ERR_STATE; }
+    const size_t bpp = format == JSORB_DEPTH_U16 ? 2 : format == JSORB_DEPTH_F32 ? 4 : 0;
+    if (!depth || !bpp || step_bytes < (size_t)e->g.lv[0].W * bpp || step_bytes % bpp || image_stride % bpp || (uintptr_t)depth % bpp) {
+        e->err = "RGB-D depth: bad format, step or alignment (rows of W elements, element-aligned)";
+        return JSORB_ERR_INVALID;
+    }
+    if (n_images > 1 && image_stride < (size_t)e->g.lv[0].H * step_bytes) {      // depth images must not overlap
+        e->err = "RGB-D depth batch: image_stride must be at least height * step_bytes";
+        return JSORB_ERR_INVALID;
+    }
+    const size_t T = (size_t)e->g.T;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!e->rg) HIPCHK(e, hipMalloc(&e->rg, (size_t)e->B * 2 * T * sizeof(float)));
+    if (!e->h_rg) HIPCHK(e, hipHostMalloc(&e->h_rg, 2 * T * sizeof(float)));
+    return JSORB_OK;
+}
+
+static RgbdArgs rgbd_args(int format, float factor, float mbf)
+{
+    // Tracking.cpp:333: if ((fabs(mDepthMapFactor - 1.0f) > 1e-5) || imDepth.type() != CV_32F) imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor)
+    const bool scale = format == JSORB_DEPTH_U16 || std::fabs(factor - 1.0f) > 1e-5;
+    return RgbdArgs{format, scale ? 1 : 0, factor, mbf};
+}
+
+int jsorb_rgbd_depth_batch_device_async(jsorb_extractor *e, const void *dev_depths, size_t image_stride, size_t step_bytes, int format, float factor,
+                                        float mbf, int n_images)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (n_images != e->n_images) { e->err = "RGB-D batch: n_images must be the last batch's"; return JSORB_ERR_INVALID; }
+    int rc = rgbd_check(e, dev_depths, format, step_bytes, image_stride, n_images);
+    if (rc) return rc;
+    const size_t T = (size_t)e->g.T;
+    const int CW = JSORB_MAX_LEVELS + 1;
+    const RgbdArgs a = rgbd_args(format, factor, mbf);
+    // the depth images may come from work the caller enqueued on the main stream after the extract call (e.g. torch's current stream through
+    // jsorb_set_stream): every lane that is not the main stream starts after a fork event recorded there
+    bool forked = false;
+    for (int j = 0; j < e->K; j++)
+        if (lane_stream(e, j) != e->stream) {
+            if (!forked) { HIPCHK(e, hipEventRecord(e->ev_fork, e->stream)); forked = true; }
+            HIPCHK(e, hipStreamWaitEvent(lane_stream(e, j), e->ev_fork, 0));
+        }
+    for (int j = 0; j < e->K; j++) {        // lane j samples its own images, behind its extraction (and k_undistort) on its stream
+        hipStream_t st = lane_stream(e, j);
+        const int f = e->lane_first[j], m = e->lane_first[j + 1] - f;
+        TIMED(e, JSORB_K_RGBD, launch_rgbd(e->out_kp + f * T * 6, e->counts + f * CW, (int)T, e->un_valid ? e->un + f * T * 2 : nullptr,
+                                           static_cast<const uint8_t *>(dev_depths) + (size_t)f * image_stride, image_stride, step_bytes, e->g.lv[0].W,
+                                           e->g.lv[0].H, a, e->rg + f * T, e->rg + (size_t)e->B * T + f * T, nullptr, nullptr, m, st));
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipEventRecord(e->lane_done[j], st));
+    }
+    // ... and whatever the caller enqueues on its main stream next (reading jsorb_rgbd_uright_device, say) runs after every lane, as behind an extract
+    if (e->stream != e->own_stream)
+        for (int j = 0; j < e->K; j++)
+            if (lane_stream(e, j) != e->stream) HIPCHK(e, hipStreamWaitEvent(e->stream, e->lane_done[j], 0));
+    e->rgbd_images = n_images;
+    e->rgbd_mirror = false;
+    e->counts_synced = false;
+    return JSORB_OK;
+}
+
+int jsorb_rgbd_depth(jsorb_extractor *e, const void *host_depth, int format, size_t step_bytes, float factor, float mbf, float *u_right, float *depth)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    int rc = rgbd_check(e, host_depth, format, step_bytes, 0, 1);
+    if (rc) return rc;
+    if (e->n_images < 1) return JSORB_ERR_STATE;
+    const int W = e->g.lv[0].W, H = e->g.lv[0].H;
+    const size_t bpp = format == JSORB_DEPTH_U16 ? 2 : 4, row = (size_t)W * bpp, T = (size_t)e->g.T;
+    if (!e->h_depth) HIPCHK(e, hipHostMalloc(&e->h_depth, (size_t)H * W * 4));
+    // the host image reaches the device the way a single host image does: copied into a pinned buffer of the handle by the calling thread,
+    // then read in place over PCIe by the kernel - which reads only the N sampled pixels
+    const uint8_t *src = static_cast<const uint8_t *>(host_depth);
+    if (step_bytes == row) memcpy(e->h_depth, src, row * H);
+    else
+        for (int y = 0; y < H; y++) memcpy(e->h_depth + row * y, src + step_bytes * y, row);
+    hipStream_t st = lane_stream(e, 0);
+    if (e->K != 1 || !st) st = e->stream;
+    for (int j = 0; j < e->K; j++)
+        if (lane_stream(e, j) != st) HIPCHK(e, hipStreamWaitEvent(st, e->lane_done[j], 0));
+    TIMED(e, JSORB_K_RGBD, launch_rgbd(e->out_kp, e->counts, (int)T, e->un_valid ? e->un : nullptr, e->h_depth, 0, row, W, H, rgbd_args(format, factor, mbf),
+                                       e->rg, e->rg + (size_t)e->B * T, e->h_rg, e->h_rg + T, 1, st));
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->lane_done[0], st));
+    if (st != lane_stream(e, 0)) for (int j = 1; j < e->K; j++) HIPCHK(e, hipEventRecord(e->lane_done[j], st));
+    if (e->timing || e->K != 1) rc = jsorb_sync(e);
+    else rc = wait_event(e, e->lane_done[0], e->spin_wait != 0);
+    if (rc) return rc;
+    e->rgbd_images = 1;           // image 0 only
+    e->rgbd_mirror = true;
+    const int n = e->h_counts[JSORB_MAX_LEVELS];
+    if (u_right && n > 0) memcpy(u_right, e->h_rg, (size_t)n * sizeof(float));
+    if (depth && n > 0) memcpy(depth, e->h_rg + T, (size_t)n * sizeof(float));
+    return JSORB_OK;
+}
+
+const float *jsorb_rgbd_uright_device(const jsorb_extractor *e, int image)
+{
+    return (check_image(e, image) && image < e->rgbd_images) ? e->rg + (size_t)image * e->g.T : nullptr;
+}
+const float *jsorb_rgbd_depth_device(const jsorb_extractor *e, int image)
+{
+    return (check_image(e, image) && image < e->rgbd_images) ? e->rg + (size_t)e->B * e->g.T + (size_t)image * e->g.T : nullptr;
+}
+int jsorb_copy_rgbd(const jsorb_extractor *e, int image, float *u_right, float *depth)
+{
+    if (!check_image(e, image) || image >= e->rgbd_images) return JSORB_ERR_STATE;
+    const int n = jsorb_n_keypoints(e, image);
+    if (n <= 0) return JSORB_OK;
+    if (e->rgbd_mirror && image == 0) {
+        if (u_right) memcpy(u_right, e->h_rg, (size_t)n * sizeof(float));
+        if (depth) memcpy(depth, e->h_rg + e->g.T, (size_t)n * sizeof(float));
+        return JSORB_OK;
+    }
+    if (u_right && hipMemcpy(u_right, jsorb_rgbd_uright_device(e, image), (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return JSORB_ERR_HIP;
+    if (depth && hipMemcpy(depth, jsorb_rgbd_depth_device(e, image), (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return JSORB_ERR_HIP;
+    return JSORB_OK;
+}
+
 int jsorb_n_images(const jsorb_extractor *e) { return e ? e->n_images : 0; }
 int jsorb_n_keypoints(const jsorb_extractor *e, int image)
 {
@@ -1619,7 +1865,7 @@ int jsorb_assign_features_to_grid(jsorb_extractor *e, int image, float min_x, fl
         e->grid_cells = n_cells;
     }
     if (!e->grid_items) HIPCHK(e, hipMalloc(&e->grid_items, (size_t)e->g.T * sizeof(int32_t)));
-    launch_assign_grid(jsorb_keypoints_device(e, image), n, min_x, min_y, grid_element_width_inv, grid_element_height_inv, cols, rows,
+    launch_assign_grid(jsorb_keypoints_device(e, image), jsorb_keypoints_un_device(e, image), n, min_x, min_y, grid_element_width_inv, grid_element_height_inv, cols, rows,
                        e->grid_start, e->grid_items, e->stream);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(cell_start, e->grid_start, (size_t)(n_cells + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -1988,7 +2234,7 @@ int jsorb_enable_kernel_timing(jsorb_extractor *e, int on)
 }
 int jsorb_kernel_time(jsorb_extractor *e, int id, double *total_ms, long *launches)
 {
-    if (!e || id < 0 || id >= JSORB_K_COUNT) return JSORB_ERR_INVALID;
+    if (!e || id < 0 || id >= JSORB_K_COUNT_ALL) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
     if (rc) return rc;
     if (total_ms) *total_ms = e->k_ms[id];
@@ -1999,7 +2245,7 @@ int jsorb_reset_kernel_timing(jsorb_extractor *e)
 {
     if (!e) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
-    for (int i = 0; i < JSORB_K_COUNT; i++) { e->k_ms[i] = 0; e->k_n[i] = 0; }
+    for (int i = 0; i < JSORB_K_COUNT_ALL; i++) { e->k_ms[i] = 0; e->k_n[i] = 0; }
     return rc;
 }
 

@@ -7,6 +7,7 @@
 #include "../../include/jsorb.h"
 #include "jsorb_device.h"
 #include "jsorb_env.h"
+#include "undistort.h"
 
 namespace jsorb {
 
@@ -82,8 +83,17 @@ void launch_stereo(const Geometry &g, const ImageSrc &srcL, const uint8_t *slabL
                    float *u_right, float *depth, int *best_l1, unsigned *aux, StereoArgs a, int n_pairs, hipStream_t s, int *diag = nullptr);
 #define JSORB_STEREO_DIAG_INTS 13          // per left keypoint: best right index, its Hamming distance, 11 L1 window sums (jsorb_copy_stereo_diagnostics)
 void launch_unpack_keypoints(const int32_t *soa, int n, jsorb_keypoint *out, hipStream_t s);
-void launch_assign_grid(const int32_t *soa, int n, float min_x, float min_y, float inv_w, float inv_h, int cols, int rows,
-                        int32_t *cell_start, int32_t *cell_items, hipStream_t s);
+void launch_assign_grid(const int32_t *soa, const float *xy_un, int n, float min_x, float min_y, float inv_w, float inv_h, int cols, int rows,
+                        int32_t *cell_start, int32_t *cell_items, hipStream_t s);      // xy_un: x_un[N] y_un[N] to bin instead of the keypoints (NULL: the keypoints)
+// k_undistort / k_rgbd (k_undistort.hip): per-image outputs at the handle's stride T (x_un[N] y_un[N] in 2T floats; uRight / depth in T floats each)
+struct RgbdArgs {
+    int format;                            // JSORB_DEPTH_U16 / JSORB_DEPTH_F32
+    int scale;                             // f32: 1 = multiply by factor (Tracking.cpp:333: |factor - 1| > 1e-5); u16 always converts
+    float factor, mbf;
+};
+void launch_undistort(const UndistortCam &cam, const int32_t *soa, const int *counts, int T, float *un, float *un_host, int n_images, hipStream_t s);
+void launch_rgbd(const int32_t *soa, const int *counts, int T, const float *un, const uint8_t *depth, size_t image_stride, size_t step, int W, int H,
+                 const RgbdArgs &a, float *u_out, float *d_out, float *u_host, float *d_host, int n_images, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -3,10 +3,10 @@
 //   Frame.cpp:119-196  four blocking SyncedMem::to_cpu() + a host loop turning the keypoint SoA into cv::KeyPoint records
 //                      -> k_unpack_keypoints: one AoS record (the memory layout of cv::KeyPoint) per keypoint, so the frame comes
 //                         back with one copy for the keypoints and one for the descriptors
-//   Frame.cpp:463-479, 696-706  AssignFeaturesToGrid / PosInGrid: per keypoint cell = (round((x - minX) * invW),
+//   Frame.cpp:463-479, 696-706  AssignFeaturesToGrid / PosInGrid: per keypoint of mvKeysUn cell = (round((x - minX) * invW),
 //                      round((y - minY) * invH)), appended to mGrid[cx][cy] in keypoint order
 //                      -> k_assign_grid: CSR over cols x rows cells (cell (i, j) at i*rows + j like mGrid[i][j]), items of a cell in
-//                         ascending keypoint order (the reference's push_back order)
+//                         ascending keypoint order (the reference's push_back order); with a camera the undistorted coordinates of k_undistort
 #include "jsorb_launch.h"
 
 namespace jsorb {
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void k_unpack_keypoints(const int32_t *__restr
 }
 
 // one workgroup: histogram -> exclusive scan -> placement -> per-cell insertion sort (cells hold a handful of keypoints)
-__global__ __launch_bounds__(1024) void k_assign_grid(const int32_t *__restrict__ soa, int n, float min_x, float min_y, float inv_w, float inv_h,
+__global__ __launch_bounds__(1024) void k_assign_grid(const int32_t *__restrict__ soa, const float *__restrict__ xy_un, int n, float min_x, float min_y, float inv_w, float inv_h,
                                                        int cols, int rows, int32_t *__restrict__ cell_start, int32_t *__restrict__ cell_items)
 {
     extern __shared__ int s_grid[];          // [n_cells] counts -> starts, [n_cells] cursors, [1024] scan scratch
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(1024) void k_assign_grid(const int32_t *__restrict_
     for (int c = tid; c < n_cells; c += 1024) s_cnt[c] = 0;
     __syncthreads();
     auto cell_of = [&](int i) -> int {
-        const float x = (float)soa[i], y = (float)soa[n + i];
+        const float x = xy_un ? xy_un[i] : (float)soa[i], y = xy_un ? xy_un[n + i] : (float)soa[n + i];      // mvKeysUn (Frame.cpp:468)
         const int px = (int)roundf((x - min_x) * inv_w), py = (int)roundf((y - min_y) * inv_h);      // PosInGrid
         if (px < 0 || px >= cols || py < 0 || py >= rows) return -1;
         return px * rows + py;
@@ -93,11 +93,11 @@ void launch_unpack_keypoints(const int32_t *soa, int n, jsorb_keypoint *out, hip
     hipLaunchKernelGGL(k_unpack_keypoints, dim3((n + 255) / 256), dim3(256), 0, s, soa, n, out);
 }
 
-void launch_assign_grid(const int32_t *soa, int n, float min_x, float min_y, float inv_w, float inv_h, int cols, int rows,
+void launch_assign_grid(const int32_t *soa, const float *xy_un, int n, float min_x, float min_y, float inv_w, float inv_h, int cols, int rows,
                         int32_t *cell_start, int32_t *cell_items, hipStream_t s)
 {
     const size_t lds = (size_t)(2 * cols * rows + 1024) * sizeof(int);
-    hipLaunchKernelGGL(k_assign_grid, dim3(1), dim3(1024), lds, s, soa, n, min_x, min_y, inv_w, inv_h, cols, rows, cell_start, cell_items);
+    hipLaunchKernelGGL(k_assign_grid, dim3(1), dim3(1024), lds, s, soa, xy_un, n, min_x, min_y, inv_w, inv_h, cols, rows, cell_start, cell_items);
 }
 
 } // namespace jsorb

@@ -25,6 +25,9 @@ TH_HIGH, TH_LOW = 100, 50   # ORBmatcher::TH_HIGH / TH_LOW, src/ORBmatcher.cpp:2
 KERNELS = ["k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms"]
 # kernel ids beyond KERNELS (jsorb_kernel_time; KERNELS stays the list of the eight pipeline stages)
 K_RECTIFY = 8
+K_UNDISTORT = 9     # JSORB_K_UNDISTORT (jsorb_set_camera)
+K_RGBD = 10         # JSORB_K_RGBD (jsorb_rgbd_depth*)
+DEPTH_F32, DEPTH_U16 = 0, 1      # JSORB_DEPTH_F32 / JSORB_DEPTH_U16
 
 EXPORTS = [
     "jsorb_create", "jsorb_destroy", "jsorb_last_error", "jsorb_version", "jsorb_plan_launch", "jsorb_extract", "jsorb_extract_into", "jsorb_extract_device",
@@ -41,6 +44,8 @@ EXPORTS = [
     "jsorb_mem_d2d", "jsorb_mem_h2d_async", "jsorb_mem_d2h_async", "jsorb_mem_d2d_async", "jsorb_mem_set_zero", "jsorb_mem_set_zero_async",
     "jsorb_mem_last_error", "jsorb_read_mask_image", "jsorb_mask_image_last_error", "jsorb_create_masked",
     "jsorb_set_rectify_maps", "jsorb_set_rectify_maps_fixed", "jsorb_clear_rectify_maps", "jsorb_rectify_enabled", "jsorb_rectify_convert_maps",
+    "jsorb_set_camera", "jsorb_camera_enabled", "jsorb_image_bounds", "jsorb_keypoints_un_device", "jsorb_copy_keypoints_un", "jsorb_unpack_frame_un",
+    "jsorb_rgbd_depth", "jsorb_rgbd_depth_batch_device_async", "jsorb_rgbd_uright_device", "jsorb_rgbd_depth_device", "jsorb_copy_rgbd",
 ]
 
 
@@ -58,6 +63,19 @@ class JsorbParams(C.Structure):
 class JsorbStereoStats(C.Structure):
     _fields_ = [("n_left", C.c_int), ("n_right", C.c_int), ("n_candidate_pairs", C.c_int), ("n_corr_match", C.c_int),
                 ("n_depth", C.c_int), ("n_final", C.c_int)]
+
+
+class JsorbCamera(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+def make_camera(K, D):
+    """jsorb_camera from Tracking's mK (3x3) and mDistCoef (k1, k2, p1, p2[, k3]) - both taken as float32, as the reference stores them (Tracking.cpp:80-91)"""
+    K = np.asarray(K, np.float32)
+    D = np.asarray(D, np.float32).ravel()
+    assert K.shape == (3, 3) and D.size in (4, 5)
+    k3 = D[4] if D.size == 5 else np.float32(0)
+    return JsorbCamera(K[0, 0], K[1, 1], K[0, 2], K[1, 2], D[0], D[1], D[2], D[3], k3)
 
 
 class JsorbError(RuntimeError):
@@ -146,6 +164,17 @@ def load_library(path=None):
         "jsorb_clear_rectify_maps": (I, [P]),
         "jsorb_rectify_enabled": (I, [P]),
         "jsorb_rectify_convert_maps": (I, [P, P, I, P, P]),
+        "jsorb_set_camera": (I, [P, C.POINTER(JsorbCamera)]),
+        "jsorb_camera_enabled": (I, [P]),
+        "jsorb_image_bounds": (I, [C.POINTER(JsorbCamera), I, I, P]),
+        "jsorb_keypoints_un_device": (P, [P, I]),
+        "jsorb_copy_keypoints_un": (I, [P, I, P]),
+        "jsorb_unpack_frame_un": (I, [P, I, P, P, P]),
+        "jsorb_rgbd_depth": (I, [P, P, I, C.c_size_t, F, F, P, P]),
+        "jsorb_rgbd_depth_batch_device_async": (I, [P, P, C.c_size_t, C.c_size_t, I, F, F, I]),
+        "jsorb_rgbd_uright_device": (P, [P, I]),
+        "jsorb_rgbd_depth_device": (P, [P, I]),
+        "jsorb_copy_rgbd": (I, [P, I, P, P]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -186,6 +215,17 @@ def convert_maps(mapx, mapy):
     if rc != 0:
         raise JsorbError("jsorb_rectify_convert_maps rc=%d" % rc)
     return xy, a
+
+
+def image_bounds(K, D, width, height):
+    """jsorb_image_bounds (host only, no GPU): Frame::ComputeImageBounds (Frame.cpp:750-778) -> float32 [minX, maxX, minY, maxY]"""
+    lib = load_library()
+    out = np.zeros(4, np.float32)
+    cam = make_camera(K, D)
+    rc = lib.jsorb_image_bounds(C.byref(cam), int(width), int(height), out.ctypes.data)
+    if rc != 0:
+        raise JsorbError("jsorb_image_bounds rc=%d" % rc)
+    return out
 
 
 def plan_launch(im_height, im_width, scale_factor, n_levels, tile_h=30, tile_w=30, fixed_multi_scale_tile_size=False, max_batch=1,
@@ -427,6 +467,102 @@ class ORBExtractor:
         if rc < 0:
             self._chk(rc)
         return bool(rc)
+
+    # ---- camera: Frame::UndistortKeyPoints (Frame.cpp:718-748) on the device ----
+    def set_camera(self, K, D):
+        """Tracking's mK / mDistCoef: from now on every extract also undistorts its keypoints (k_undistort) when k1 != 0; a set-up call"""
+        cam = make_camera(K, D)
+        self._chk(self._lib.jsorb_set_camera(self._h, C.byref(cam)))
+
+    def clear_camera(self):
+        self._chk(self._lib.jsorb_set_camera(self._h, None))
+
+    def camera_enabled(self):
+        rc = self._lib.jsorb_camera_enabled(self._h)
+        if rc < 0:
+            self._chk(rc)
+        return bool(rc)
+
+    def keypoints_undistorted(self, image=0):
+        """mvKeysUn coordinates: (x_un float32[N], y_un float32[N]) - the keypoint coordinates without an active camera"""
+        n = self.n_keypoints(image)
+        if n < 0:
+            raise JsorbError("no extract result for image %d" % image)
+        out = np.zeros(2 * n, np.float32)
+        if n:
+            self._chk(self._lib.jsorb_copy_keypoints_un(self._h, image, out.ctypes.data))
+        return out[:n].copy(), out[n:].copy()
+
+    def unpack_frame_undistorted(self, image=0):
+        """(mvKeys, mvKeysUn as cv::KeyPoint-shaped structured arrays, descriptors N x 32) with one synchronisation"""
+        n = self.n_keypoints(image)
+        if n < 0:
+            raise JsorbError("no extract result for image %d" % image)
+        keys, keys_un = np.zeros(n, KEYPOINT_DTYPE), np.zeros(n, KEYPOINT_DTYPE)
+        desc = np.zeros((n, 32), np.uint8)
+        if n:
+            self._chk(self._lib.jsorb_unpack_frame_un(self._h, image, keys.ctypes.data, keys_un.ctypes.data, desc.ctypes.data))
+        return keys, keys_un, desc
+
+    def undistort_kernel_time(self):
+        """(total_ms, launches) of k_undistort (kernel id K_UNDISTORT), measured like kernel_times()."""
+        return self._kernel_time(K_UNDISTORT)
+
+    def rgbd_kernel_time(self):
+        return self._kernel_time(K_RGBD)
+
+    def _kernel_time(self, kid):
+        ms, n = C.c_double(), C.c_long()
+        self._chk(self._lib.jsorb_kernel_time(self._h, kid, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    # ---- RGB-D: Frame::ComputeStereoFromRGBD (Frame.cpp:996-1017) with Tracking.cpp:333-334's conversion ----
+    def rgbd_depth(self, depth, mbf, factor=1.0, image_stride=None, n_images=None):
+        """Host numpy (H, W) uint16 / float32 depth: synchronous, image 0 -> (uRight float32[N], depth float32[N]).
+        A device tensor (uint16 / float32, (B, H, W) or (H, W)): image i of the last batch against depth image i, enqueued (read the results with
+        rgbd_result after sync()).  factor: Tracking's mDepthMapFactor (already inverted, e.g. 1/5000 for TUM)."""
+        if hasattr(depth, "data_ptr"):           # a torch tensor: device memory only, 16-bit (read as uint16) or float32 elements
+            if not getattr(depth, "is_cuda", False):
+                raise JsorbError("rgbd_depth: a torch tensor must be in device memory (pass host depth as a numpy array)")
+            dt = str(depth.dtype)
+            if dt in ("torch.uint16", "torch.int16"):
+                fmt = DEPTH_U16
+            elif dt == "torch.float32":
+                fmt = DEPTH_F32
+            else:
+                raise JsorbError("rgbd_depth: depth must be uint16 / int16 (raw 16-bit) or float32, not %s" % dt)
+            if depth.dim() not in (2, 3) or tuple(depth.shape[-2:]) != (self.params.height, self.params.width) or depth.stride(-1) != 1:
+                raise JsorbError("rgbd_depth: depth must be (H, W) or (B, H, W) of the handle's image size with dense rows")
+            es = depth.element_size()
+            H, W = depth.shape[-2], depth.shape[-1]
+            n = n_images if n_images is not None else (depth.shape[0] if depth.dim() == 3 else 1)
+            if n > (depth.shape[0] if depth.dim() == 3 else 1) and image_stride is None:
+                raise JsorbError("rgbd_depth: %d images asked for, the tensor holds fewer" % n)
+            stride = image_stride if image_stride is not None else (depth.stride(0) * es if depth.dim() == 3 else H * depth.stride(-2) * es)
+            self._keep = (self._keep, depth)
+            self._chk(self._lib.jsorb_rgbd_depth_batch_device_async(self._h, depth.data_ptr(), stride, depth.stride(-2) * es, fmt, factor, mbf, n))
+            return None
+        d = np.asarray(depth)
+        if d.dtype == np.uint16:
+            fmt = DEPTH_U16
+        elif d.dtype == np.float32:
+            fmt = DEPTH_F32
+        else:
+            raise JsorbError("rgbd_depth: depth must be uint16 (raw 16-bit) or float32, not %s" % d.dtype)
+        d = np.ascontiguousarray(d)
+        assert d.shape == (self.params.height, self.params.width)
+        n = self.n_keypoints(0)
+        u = np.full(max(n, 1), -1, np.float32)
+        dd = np.full(max(n, 1), -1, np.float32)
+        self._chk(self._lib.jsorb_rgbd_depth(self._h, d.ctypes.data, fmt, d.strides[0], factor, mbf, u.ctypes.data, dd.ctypes.data))
+        return u[:n], dd[:n]
+
+    def rgbd_result(self, image=0):
+        n = self.n_keypoints(image)
+        u = np.full(max(n, 1), -1, np.float32)
+        d = np.full(max(n, 1), -1, np.float32)
+        self._chk(self._lib.jsorb_copy_rgbd(self._h, image, u.ctypes.data, d.ctypes.data))
+        return u[:n], d[:n]
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
