@@ -65,6 +65,9 @@ typedef struct jsorb_stereo_stats {
 enum { JSORB_K_PYRAMID = 0, JSORB_K_DETECT, JSORB_K_COMPACT, JSORB_K_BLUR, JSORB_K_DESCRIBE, JSORB_K_STEREO, JSORB_K_MEDIAN, JSORB_K_NMS_MS, JSORB_K_RECTIFY, JSORB_K_COUNT };
 /* kernels of the mono / RGB-D Frame steps (jsorb_set_camera, jsorb_rgbd_depth*): ids after the pipeline's; JSORB_K_COUNT_ALL ids in all */
 enum { JSORB_K_UNDISTORT = JSORB_K_COUNT, JSORB_K_RGBD, JSORB_K_COUNT_ALL };
+/* kernels of jsorb_search_local_points*: ids after JSORB_K_COUNT_ALL, which stays the end of the extract / Frame ids above and names no kernel
+ * (jsorb_kernel_name gives ""); JSORB_K_ID_END is one past the last id */
+enum { JSORB_K_ASSIGN_GRID = JSORB_K_COUNT_ALL + 1, JSORB_K_LOCAL_CANDIDATES, JSORB_K_LOCAL_RESOLVE, JSORB_K_ID_END };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -276,6 +279,51 @@ int jsorb_unpack_frame_un(jsorb_extractor *e, int image, jsorb_keypoint *keys, j
  * cols*rows <= 16384. */
 int jsorb_assign_features_to_grid(jsorb_extractor *e, int image, float min_x, float min_y, float grid_element_width_inv,
                                   float grid_element_height_inv, int cols, int rows, int32_t *cell_start, int32_t *cell_items);
+
+/* ---- local map matching: ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cpp:32-116) as called by
+ * Tracking::SearchLocalPoints (src/Tracking.cpp:1346-1805) right after the frustum test ----
+ * Map points i = 0 .. n_points-1 in the order the caller passed them to jsorb_is_in_frustum (the reference's map_points, a subsequence of
+ * mvpLocalMapPoints whose other points have mbTrackInView = false); keypoints k of image `image` of the handle's last extract.  Per point, in order:
+ *   skip i unless in_frustum[i]; L = predicted_level[i] (outside [0, n_levels): no candidate - outside the contract, reads nothing out of bounds)
+ *   r = view_cos[i] >= 0.998f ? 2.5f : 4.0f (RadiusByViewingCos compares the float with the double 0.998, which is this test); if th != 1: r *= th;
+ *   R = r * jsorb_scale(e, L) (mvScaleFactors; every step one float rounding)
+ *   candidates = GetFeaturesInArea(u[i], v[i], R, L-1, L) (src/Frame.cpp:641-694) over the grid min_x, min_y, inv_w, inv_h, cols x rows that
+ *     jsorb_assign_features_to_grid builds: cells max(0, (int)floorf(((x - min_x) - R) * inv_w)) .. min(cols-1, (int)ceilf(((x - min_x) + R) * inv_w)),
+ *     likewise in y, with the reference's early returns (first >= cols / last < 0: none); ix outer, iy inner, a cell's keypoints ascending; kept
+ *     when octave in [L-1, L] and |x_un - x| < R && |y_un - y| < R (x_un, y_un: jsorb_keypoints_un_device with an active camera, else the keypoint)
+ *   dropped: blocked_in[k] != 0 (the caller's F.mvpMapPoints[k] && Observations() > 0 before the call; NULL: none), or a point j < i of this call
+ *     matched k (the reference's F.mvpMapPoints[bestIdx] = pMP: every map point that is not bad has observations - the assumption this rests on)
+ *   dropped: u_right[k] > 0 && fabsf(xr - u_right[k]) > R, xr = u[i] - mbf * invz[i] unfused (two roundings; a reference build that contracts it
+ *     into an FMA - GCC on aarch64 does by default - can differ by one ulp in xr); u_right NULL: monocular, never applies
+ *   dist = popcount Hamming distance of mp_descriptors[32 i ..] and the keypoint's descriptor; best / second best with the reference's strict <
+ *     updates: best = min (dist, candidate position) over dist < 256, second = the same min over the rest; bestLevel / bestLevel2 their octaves
+ *   match iff bestDist <= th_high && !(bestLevel == bestLevel2 && (float)bestDist > nn_ratio * (float)bestDist2)
+ * All arrays are DEVICE pointers, in the layouts jsorb_is_in_frustum writes (u, v, invz, view_cos float; predicted_level int32; in_frustum u8) and
+ * mp_descriptors n_points x 32 bytes, 16-byte aligned; u_right / blocked_in have one entry per keypoint (u_right: jsorb_stereo_uright_device or
+ * jsorb_rgbd_uright_device).  Outputs: match_kp[i] = matched keypoint or -1, match_dist[i] = its distance or -1, kp_match[k] = map point matched
+ * to k in this call or -1 (N entries), *n_matches_dev = nmatches.  The host applies F.mvpMapPoints[match_kp[i]] = map_points[i].
+ * Enqueued on the handle's stream (jsorb_set_stream) behind the last extract; inputs written on other streams must be complete (jsorb_is_in_frustum
+ * returns after its kernel).  Three kernels: the grid (k_assign_grid, into the handle's grid buffers), k_local_candidates, k_local_resolve.
+ * cols * rows <= 16384, N < 262144.  n_points == 0 or N == 0: no match (kp_match all -1). */
+typedef struct jsorb_search_params {
+    float th;                        /* Tracking's th: 1, 3 for RGB-D, 5 right after a relocalisation (Tracking.cpp:1786-1791) */
+    float nn_ratio;                  /* ORBmatcher(0.8) */
+    int th_high;                     /* ORBmatcher::TH_HIGH = 100 */
+    float mbf;
+    float min_x, min_y, inv_w, inv_h; /* Frame::mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* FRAME_GRID_COLS, FRAME_GRID_ROWS */
+} jsorb_search_params;
+int jsorb_search_local_points_async(jsorb_extractor *e, int image, const jsorb_search_params *params, int n_points, const float *u, const float *v,
+                                    const float *invz, const int32_t *predicted_level, const float *view_cos, const uint8_t *in_frustum,
+                                    const uint8_t *mp_descriptors, const float *u_right, const uint8_t *blocked_in, int32_t *match_kp,
+                                    int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the handle; *n_matches = nmatches and match_kp_host[n_points] (host) = match_kp. */
+int jsorb_search_local_points(jsorb_extractor *e, int image, const jsorb_search_params *params, int n_points, const float *u, const float *v,
+                              const float *invz, const int32_t *predicted_level, const float *view_cos, const uint8_t *in_frustum,
+                              const uint8_t *mp_descriptors, const float *u_right, const uint8_t *blocked_in, int32_t *match_kp_host, int *n_matches);
+/* Diagnostics of the last call (waits for it): fixed-point rounds of k_local_resolve, candidates over all points, points whose candidates
+ * overflowed the per-point list (the resolver rescans the grid for them).  Any pointer may be NULL. */
+int jsorb_search_local_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow);
 
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates

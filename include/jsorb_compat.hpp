@@ -609,6 +609,26 @@ inline void AssignFeaturesToGrid(ORBExtractor &ex, float mnMinX, float mnMinY, f
         }
 }
 
+// Tracking::SearchLocalPoints' matcher.SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th) (Tracking.cpp:1782-1791, ORBmatcher.cpp:32-116) on
+// the device, over the SAME SyncedMem buffers compute_isInFrustum_GPU just filled (no copy back of u, v, invz, predictedlevel, viewCos,
+// isinfrustum): descriptors holds the map points' descriptors (32 bytes each, map_points order), u_right_gpu mvuRight on the device
+// (jsorb_stereo_uright_device / jsorb_rgbd_uright_device; nullptr: monocular), blocked_gpu one byte per keypoint (F.mvpMapPoints[k] with
+// observations; nullptr: none).  Returns nmatches; match_kp[i] = keypoint matched to map_points[i] or -1 - the caller applies
+// mCurrentFrame.mvpMapPoints[match_kp[i]] = map_points[i].
+inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params, int n_points, SyncedMem<float> &u, SyncedMem<float> &v,
+                             SyncedMem<float> &invz, SyncedMem<int> &predictedlevel, SyncedMem<float> &viewCos, SyncedMem<unsigned char> &isinfrustum,
+                             SyncedMem<unsigned char> &descriptors, const float *u_right_gpu, const unsigned char *blocked_gpu, std::vector<int> &match_kp)
+{
+    match_kp.assign(n_points > 0 ? n_points : 1, -1);
+    int n_matches = 0;
+    if (jsorb_search_local_points(ex.handle(), 0, &params, n_points, u.gpu_data(), v.gpu_data(), invz.gpu_data(), predictedlevel.gpu_data(),
+                                  viewCos.gpu_data(), isinfrustum.gpu_data(), descriptors.gpu_data(), u_right_gpu, blocked_gpu, match_kp.data(),
+                                  &n_matches) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_local_points: ") + jsorb_last_error(ex.handle()));
+    match_kp.resize(n_points > 0 ? n_points : 0);
+    return n_matches;
+}
+
 // Rectification on the device instead of the host cv::remap of the reference's stereo driver (Examples/Stereo/stereo_euroc.cpp:106-107 build
 // M1l/M2l, M1r/M2r with cv::initUndistortRectifyMap; :145-146 remap both images of every frame with INTER_LINEAR): set the maps ONCE per
 // extractor, then hand every extract() the raw camera image.  Maps of the extractor's image size, rows dense (width floats apart).

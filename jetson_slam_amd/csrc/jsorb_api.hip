@@ -35,6 +35,8 @@ namespace {
 
 const char *k_names[JSORB_K_COUNT_ALL] = {"k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_stereo", "k_median", "k_nms_ms", "k_rectify",
                                           "k_undistort", "k_rgbd"};
+// kernels of jsorb_search_local_points*: ids JSORB_K_ASSIGN_GRID .. JSORB_K_ID_END - 1 (JSORB_K_COUNT_ALL itself names no kernel)
+const char *k_names_local[JSORB_K_ID_END - JSORB_K_ASSIGN_GRID] = {"k_assign_grid", "k_local_candidates", "k_local_resolve"};
 
 struct TimedLaunch { int id; hipEvent_t a, b; };
 
@@ -198,12 +200,19 @@ struct jsorb_extractor {
     uint8_t *h_depth = nullptr;        // pinned staging of one host depth image (dense rows), read in place by k_rgbd
     bool rgbd_mirror = false;
     int rgbd_images = 0;               // images of the last batch the last RGB-D call covered (0: none; the synchronous call covers image 0 only)
+    // jsorb_search_local_points*: allocated on the first call, grown with the number of map points
+    int *sl_cand = nullptr;            // sl_points x search_local_cap() packed candidates, then sl_points counts
+    int sl_points = 0;
+    int *sl_stats = nullptr;           // rounds, candidates, points over the capacity of the last call (device)
+    int32_t *sl_out = nullptr;         // synchronous call: match_kp, match_dist (sl_out_points each), kp_match (T), count
+    int sl_out_points = 0;
+    bool sl_done = false;
     bool extracted = false, stereo_done = false;
     int stereo_pairs = 0;
     bool timing = false;
     std::vector<TimedLaunch> timed;
-    double k_ms[JSORB_K_COUNT_ALL] = {0};
-    long k_n[JSORB_K_COUNT_ALL] = {0};
+    double k_ms[JSORB_K_ID_END] = {0};
+    long k_n[JSORB_K_ID_END] = {0};
     std::string err;
     // JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy
     bool trace_host = false;
@@ -919,7 +928,12 @@ extern "C" {
 
 const char *jsorb_version(void) { return "jsorb 0.1 (gfx950)"; }
 
-const char *jsorb_kernel_name(int id) { return (id >= 0 && id < JSORB_K_COUNT_ALL) ? k_names[id] : ""; }
+const char *jsorb_kernel_name(int id)
+{
+    if (id >= 0 && id < JSORB_K_COUNT_ALL) return k_names[id];
+    if (id >= JSORB_K_ASSIGN_GRID && id < JSORB_K_ID_END) return k_names_local[id - JSORB_K_ASSIGN_GRID];
+    return "";
+}
 
 const char *jsorb_last_error(const jsorb_extractor *e) { return e ? e->err.c_str() : "null handle"; }
 
@@ -1177,7 +1191,7 @@ void jsorb_destroy(jsorb_extractor *e)
         if (e->lane_used[j]) (void)hipStreamSynchronize(e->lane_used[j]);
     for (auto &t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     void *bufs[] = {e->stage[0], e->stage[1], e->slab, e->blur, e->mask, e->lut_bits, e->tile_out, e->kp, e->counts, e->row_tab, e->angles, e->desc,
-                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items, e->rect_buf, e->rect_raw, e->un, e->rg};
+                    e->out_kp, e->st_u, e->st_d, e->st_l1, e->st_stats, e->st_aux, e->st_diag, e->sp_u, e->sp_d, e->sp_stats, e->sp_l1, e->sp_aux, e->ms_grid, e->ms_scratch, e->frame_aos, e->grid_start, e->grid_items, e->rect_buf, e->rect_raw, e->un, e->rg, e->sl_cand, e->sl_stats, e->sl_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     arena_release(e->det_spill);      // (every kernel of this handle has finished: the lanes were synchronised above)
@@ -1875,6 +1889,117 @@ int jsorb_assign_features_to_grid(jsorb_extractor *e, int image, float min_x, fl
     return JSORB_OK;
 }
 
+// ---- local map matching: ORBmatcher::SearchByProjection(Frame&, map points, th) (ORBmatcher.cpp:32-116), k_search_local.hip ----
+int jsorb_search_local_points_async(jsorb_extractor *e, int image, const jsorb_search_params *params, int n_points, const float *u, const float *v,
+                                    const float *invz, const int32_t *predicted_level, const float *view_cos, const uint8_t *in_frustum,
+                                    const uint8_t *mp_descriptors, const float *u_right, const uint8_t *blocked_in, int32_t *match_kp,
+                                    int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!check_image(e, image)) { e->err = "search_local_points: no extract result for this image"; return JSORB_ERR_STATE; }
+    if (!params || !n_matches_dev) { e->err = "search_local_points: NULL params or n_matches"; return JSORB_ERR_INVALID; }
+    const jsorb_search_params &p = *params;
+    if (p.cols < 1 || p.rows < 1 || (long long)p.cols * p.rows > 16384) { e->err = "search_local_points: grid size out of range (cols*rows <= 16384)"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_local_points: n_points < 0"; return JSORB_ERR_INVALID; }
+    const int n = jsorb_n_keypoints(e, image);
+    if (n >= (1 << 18)) { e->err = "search_local_points: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
+    if (n_points > 0 && (!u || !v || !invz || !predicted_level || !view_cos || !in_frustum || !mp_descriptors || !match_kp || !match_dist)) {
+        e->err = "search_local_points: NULL point array or output";
+        return JSORB_ERR_INVALID;
+    }
+    if (n > 0 && !kp_match) { e->err = "search_local_points: NULL kp_match"; return JSORB_ERR_INVALID; }
+    if ((uintptr_t)mp_descriptors % 16) { e->err = "search_local_points: mp_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    const int n_cells = p.cols * p.rows, cap = search_local_cap();
+    if (e->grid_cells < n_cells) {
+        if (e->grid_start) (void)hipFree(e->grid_start);
+        e->grid_start = nullptr;
+        HIPCHK(e, hipMalloc(&e->grid_start, (size_t)(n_cells + 1) * sizeof(int32_t)));
+        e->grid_cells = n_cells;
+    }
+    if (!e->grid_items) HIPCHK(e, hipMalloc(&e->grid_items, (size_t)e->g.T * sizeof(int32_t)));
+    if (e->sl_points < n_points) {
+        if (e->sl_cand) (void)hipFree(e->sl_cand);        // (waits for the device: the last call may still read it)
+        e->sl_cand = nullptr;
+        HIPCHK(e, hipMalloc(&e->sl_cand, (size_t)n_points * (cap + 1) * sizeof(int)));
+        e->sl_points = n_points;
+    }
+    if (!e->sl_stats) HIPCHK(e, hipMalloc(&e->sl_stats, 4 * sizeof(int)));
+    hipStream_t st = e->stream;
+    for (int j = 0; j < e->K; j++)       // the frame (and its uRight) may come from the lanes of a batch
+        if (lane_stream(e, j) && lane_stream(e, j) != st) HIPCHK(e, hipStreamWaitEvent(st, e->lane_done[j], 0));
+    const float *xy_un = jsorb_keypoints_un_device(e, image);
+    TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
+                                                     e->grid_start, e->grid_items, st));
+    HIPCHK(e, hipGetLastError());
+    SearchLocalArgs a{};
+    a.soa = jsorb_keypoints_device(e, image);
+    a.xy_un = xy_un;
+    a.desc = jsorb_descriptors_device(e, image);
+    a.u_right = u_right;
+    a.blocked = blocked_in;
+    a.n_kp = n;
+    a.cell_start = e->grid_start;
+    a.cell_items = e->grid_items;
+    a.min_x = p.min_x; a.min_y = p.min_y; a.inv_w = p.inv_w; a.inv_h = p.inv_h;
+    a.cols = p.cols; a.rows = p.rows;
+    a.n_points = n_points;
+    a.u = u; a.v = v; a.invz = invz; a.view_cos = view_cos; a.level = predicted_level; a.in_frustum = in_frustum; a.mp_desc = mp_descriptors;
+    a.th = p.th; a.nn_ratio = p.nn_ratio; a.mbf = p.mbf; a.th_high = p.th_high;
+    a.n_levels = e->g.L;
+    for (int l = 0; l < e->g.L; l++) a.scale[l] = e->g.lv[l].scale;
+    a.cand = e->sl_cand;
+    a.cand_n = e->sl_cand + (size_t)e->sl_points * cap;
+    a.match_kp = match_kp; a.match_dist = match_dist; a.kp_match = kp_match; a.n_matches = n_matches_dev;
+    a.stats = e->sl_stats;
+    TIMED(e, JSORB_K_LOCAL_CANDIDATES, launch_local_candidates(a, st));
+    HIPCHK(e, hipGetLastError());
+    TIMED(e, JSORB_K_LOCAL_RESOLVE, launch_local_resolve(a, st));
+    HIPCHK(e, hipGetLastError());
+    e->sl_done = true;
+    return JSORB_OK;
+}
+
+int jsorb_search_local_points(jsorb_extractor *e, int image, const jsorb_search_params *params, int n_points, const float *u, const float *v,
+                              const float *invz, const int32_t *predicted_level, const float *view_cos, const uint8_t *in_frustum,
+                              const uint8_t *mp_descriptors, const float *u_right, const uint8_t *blocked_in, int32_t *match_kp_host, int *n_matches)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!n_matches || (n_points > 0 && !match_kp_host)) { e->err = "search_local_points: NULL host output"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_local_points: n_points < 0"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    if (e->sl_out_points < n_points || !e->sl_out) {
+        if (e->sl_out) (void)hipFree(e->sl_out);
+        e->sl_out = nullptr;
+        e->sl_out_points = std::max(n_points, 1);
+        HIPCHK(e, hipMalloc(&e->sl_out, ((size_t)2 * e->sl_out_points + e->g.T + 1) * sizeof(int32_t)));
+    }
+    int32_t *mk = e->sl_out, *md = mk + e->sl_out_points, *km = md + e->sl_out_points, *cnt = km + e->g.T;
+    int rc = jsorb_search_local_points_async(e, image, params, n_points, u, v, invz, predicted_level, view_cos, in_frustum, mp_descriptors, u_right,
+                                             blocked_in, mk, md, km, cnt);
+    if (rc) return rc;
+    int32_t count = 0;
+    HIPCHK(e, hipMemcpyAsync(&count, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (n_points > 0) HIPCHK(e, hipMemcpyAsync(match_kp_host, mk, (size_t)n_points * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n_matches = count;
+    return JSORB_OK;
+}
+
+int jsorb_search_local_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!e->sl_done) { e->err = "search_local_stats before jsorb_search_local_points"; return JSORB_ERR_STATE; }
+    int32_t s[4] = {0, 0, 0, 0};
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipMemcpyAsync(s, e->sl_stats, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (rounds) *rounds = s[0];
+    if (n_candidates) *n_candidates = s[1];
+    if (n_overflow) *n_overflow = s[2];
+    return JSORB_OK;
+}
+
 int jsorb_n_levels(const jsorb_extractor *e) { return e ? e->g.L : 0; }
 int jsorb_total_tiles(const jsorb_extractor *e) { return e ? e->g.T : 0; }
 int jsorb_level_dims(const jsorb_extractor *e, int level, int *h, int *w, int *pitch)
@@ -2234,7 +2359,7 @@ int jsorb_enable_kernel_timing(jsorb_extractor *e, int on)
 }
 int jsorb_kernel_time(jsorb_extractor *e, int id, double *total_ms, long *launches)
 {
-    if (!e || id < 0 || id >= JSORB_K_COUNT_ALL) return JSORB_ERR_INVALID;
+    if (!e || id < 0 || id >= JSORB_K_ID_END || (id >= JSORB_K_COUNT_ALL && id < JSORB_K_ASSIGN_GRID)) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
     if (rc) return rc;
     if (total_ms) *total_ms = e->k_ms[id];
@@ -2245,7 +2370,7 @@ int jsorb_reset_kernel_timing(jsorb_extractor *e)
 {
     if (!e) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
-    for (int i = 0; i < JSORB_K_COUNT_ALL; i++) { e->k_ms[i] = 0; e->k_n[i] = 0; }
+    for (int i = 0; i < JSORB_K_ID_END; i++) { e->k_ms[i] = 0; e->k_n[i] = 0; }
     return rc;
 }
 

@@ -94,6 +94,34 @@ struct RgbdArgs {
 void launch_undistort(const UndistortCam &cam, const int32_t *soa, const int *counts, int T, float *un, float *un_host, int n_images, hipStream_t s);
 void launch_rgbd(const int32_t *soa, const int *counts, int T, const float *un, const uint8_t *depth, size_t image_stride, size_t step, int W, int H,
                  const RgbdArgs &a, float *u_out, float *d_out, float *u_host, float *d_host, int n_images, hipStream_t s);
+// k_local_candidates / k_local_resolve (k_search_local.hip): ORBmatcher::SearchByProjection(Frame&, map points, th) over one image of a handle
+struct SearchLocalArgs {
+    // the frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, mvuRight (NULL: monocular), blocked_in (NULL: none)
+    const int32_t *soa;
+    const float *xy_un;
+    const uint8_t *desc;
+    const float *u_right;
+    const uint8_t *blocked;
+    int n_kp;
+    const int32_t *cell_start, *cell_items;      // grid CSR (k_assign_grid)
+    float min_x, min_y, inv_w, inv_h;
+    int cols, rows;
+    // the map points, in the caller's order
+    int n_points;
+    const float *u, *v, *invz, *view_cos;
+    const int32_t *level;
+    const uint8_t *in_frustum, *mp_desc;
+    float th, nn_ratio, mbf;
+    int th_high, n_levels;
+    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
+    // workspace and outputs
+    int *cand, *cand_n;                          // n_points x search_local_cap() packed candidates, n_points counts
+    int32_t *match_kp, *match_dist, *kp_match, *n_matches;
+    int *stats;                                  // rounds, candidates, points over the capacity
+};
+int search_local_cap();
+void launch_local_candidates(const SearchLocalArgs &a, hipStream_t s);
+void launch_local_resolve(const SearchLocalArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -27,6 +27,8 @@ KERNELS = ["k_pyramid", "k_detect", "k_compact", "k_blur", "k_describe", "k_ster
 K_RECTIFY = 8
 K_UNDISTORT = 9     # JSORB_K_UNDISTORT (jsorb_set_camera)
 K_RGBD = 10         # JSORB_K_RGBD (jsorb_rgbd_depth*)
+# jsorb_search_local_points*: ids after JSORB_K_COUNT_ALL (11, which names no kernel)
+K_ASSIGN_GRID, K_LOCAL_CANDIDATES, K_LOCAL_RESOLVE = 12, 13, 14
 DEPTH_F32, DEPTH_U16 = 0, 1      # JSORB_DEPTH_F32 / JSORB_DEPTH_U16
 
 EXPORTS = [
@@ -46,6 +48,7 @@ EXPORTS = [
     "jsorb_set_rectify_maps", "jsorb_set_rectify_maps_fixed", "jsorb_clear_rectify_maps", "jsorb_rectify_enabled", "jsorb_rectify_convert_maps",
     "jsorb_set_camera", "jsorb_camera_enabled", "jsorb_image_bounds", "jsorb_keypoints_un_device", "jsorb_copy_keypoints_un", "jsorb_unpack_frame_un",
     "jsorb_rgbd_depth", "jsorb_rgbd_depth_batch_device_async", "jsorb_rgbd_uright_device", "jsorb_rgbd_depth_device", "jsorb_copy_rgbd",
+    "jsorb_search_local_points_async", "jsorb_search_local_points", "jsorb_search_local_stats",
 ]
 
 
@@ -67,6 +70,11 @@ class JsorbStereoStats(C.Structure):
 
 class JsorbCamera(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+class JsorbSearchParams(C.Structure):
+    _fields_ = [("th", C.c_float), ("nn_ratio", C.c_float), ("th_high", C.c_int), ("mbf", C.c_float), ("min_x", C.c_float), ("min_y", C.c_float),
+                ("inv_w", C.c_float), ("inv_h", C.c_float), ("cols", C.c_int), ("rows", C.c_int)]
 
 
 def make_camera(K, D):
@@ -175,6 +183,9 @@ def load_library(path=None):
         "jsorb_rgbd_uright_device": (P, [P, I]),
         "jsorb_rgbd_depth_device": (P, [P, I]),
         "jsorb_copy_rgbd": (I, [P, I, P, P]),
+        "jsorb_search_local_points_async": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 13),
+        "jsorb_search_local_points": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 9 + [P, C.POINTER(I)]),
+        "jsorb_search_local_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -563,6 +574,61 @@ class ORBExtractor:
         d = np.full(max(n, 1), -1, np.float32)
         self._chk(self._lib.jsorb_copy_rgbd(self._h, image, u.ctypes.data, d.ctypes.data))
         return u[:n], d[:n]
+
+    # ---- local map matching: ORBmatcher::SearchByProjection(Frame&, map points, th) (ORBmatcher.cpp:32-116) on the device ----
+    def search_local_points(self, u, v, invz, predicted_level, view_cos, in_frustum, mp_descriptors, grid, th=1.0, mbf=0.0, u_right=None,
+                            blocked=None, nn_ratio=0.8, th_high=TH_HIGH, cols=64, rows=48, image=0):
+        """Tracking::SearchLocalPoints' matching step over image `image` of the last extract.  Device tensors, as jsorb_is_in_frustum writes them:
+        u, v, invz, view_cos float32[n]; predicted_level int32[n]; in_frustum uint8[n]; mp_descriptors uint8[n, 32]; u_right float32[N] or None
+        (monocular); blocked uint8 / bool [N] or None.  grid = (mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows.
+        Returns (match_kp int32[n], match_dist int32[n], kp_match int32[N], n_matches int32[1]) as device tensors; the call waits for the
+        current torch stream before it starts and for its own work before it returns."""
+        import torch
+        n = int(u.shape[0]) if u.dim() == 1 else -1
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("search_local_points: no extract result for image %d" % image)
+
+        def chk(t, name, dtypes, shape):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("search_local_points: %s must be a device tensor" % name)
+            if t.dtype not in dtypes:
+                raise JsorbError("search_local_points: %s must be %s, not %s" % (name, " / ".join(str(d) for d in dtypes), t.dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("search_local_points: %s must be a contiguous tensor of shape %s, not %s" % (name, shape, tuple(t.shape)))
+            return t.data_ptr()
+
+        if n < 0:
+            raise JsorbError("search_local_points: u must be one-dimensional")
+        f32, i32, u8 = (torch.float32,), (torch.int32,), (torch.uint8, torch.bool)
+        ptrs = [chk(u, "u", f32, (n,)), chk(v, "v", f32, (n,)), chk(invz, "invz", f32, (n,)), chk(predicted_level, "predicted_level", i32, (n,)),
+                chk(view_cos, "view_cos", f32, (n,)), chk(in_frustum, "in_frustum", u8, (n,)), chk(mp_descriptors, "mp_descriptors", (torch.uint8,), (n, 32))]
+        if n and mp_descriptors.data_ptr() % 16:
+            raise JsorbError("search_local_points: mp_descriptors must be 16-byte aligned")
+        ptrs.append(None if u_right is None else chk(u_right, "u_right", f32, (N,)))
+        ptrs.append(None if blocked is None else chk(blocked, "blocked", u8, (N,)))
+        dev = u.device
+        match_kp = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        match_dist = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        kp_match = torch.full((max(N, 1),), -1, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        prm = JsorbSearchParams(th, nn_ratio, th_high, mbf, grid[0], grid[1], grid[2], grid[3], cols, rows)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_local_points_async(self._h, image, C.byref(prm), n, *ptrs, match_kp.data_ptr(), match_dist.data_ptr(),
+                                                            kp_match.data_ptr(), count.data_ptr()))
+        self.sync()
+        return match_kp[:n], match_dist[:n], kp_match[:N], count
+
+    def search_local_stats(self):
+        """(fixed-point rounds, candidates, points over the per-point candidate list) of the last search_local_points"""
+        r, c, o = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self._lib.jsorb_search_local_stats(self._h, C.byref(r), C.byref(c), C.byref(o)))
+        return r.value, c.value, o.value
+
+    def search_local_kernel_times(self):
+        """{kernel: (total_ms, launches)} of the grid, candidate and resolve kernels, measured like kernel_times()"""
+        return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_local_candidates", K_LOCAL_CANDIDATES),
+                                                           ("k_local_resolve", K_LOCAL_RESOLVE))}
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
