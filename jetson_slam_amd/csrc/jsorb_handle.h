@@ -1,0 +1,381 @@
+// jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
+// (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map search).  include/jsorb.h only
+// forward-declares the handle, so its layout is free to change.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/jsorb.h"
+#include "jsorb_launch.h"
+
+#define JSORB_MAX_LANES 8
+
+using namespace jsorb;
+
+// Stereo match enqueued AHEAD of the call that asks for it (the synchronous single-frame call shape, Frame.cpp:107-125: extract L and R
+// from two threads, join, ComputeStereoMatches).  Between the end of the two extracts on the GPU and the start of the match there is
+// a host round trip (wake-up of two waits, thread joins, the next call's launch) during which the GPU idles: 53 of the 182 us GPU
+// span of a frame.  Once a (left, right) pair has been matched through jsorb_stereo_match, the library repeats that match with the
+// same parameters right behind the NEXT pair of single-image extracts, on the GPU, without a host round trip: whichever of the two
+// extract calls enqueues last also enqueues k_stereo + k_median behind both (into twin output buffers).  The next jsorb_stereo_match
+// on the same pair with the same parameters and no extract in between finds the result finished (or nearly) and adopts it by
+// swapping the twin buffers in; anything else (other parameters, another partner, an extract in between, batches) runs the normal
+// path and the speculative result is dropped.  The outputs are the outputs of the same kernels on the same inputs either way.
+// Shared by the two handles; every field is guarded by `mu` (the two extract calls come from two host threads).
+struct jsorb_spec_state {
+    std::mutex mu;
+    jsorb_extractor *l = nullptr, *r = nullptr;
+    bool armed = false;
+    float mb = 0.f, mbf = 0.f;
+    int th_high = 0, th_low = 0;
+    unsigned long long l_base = 0, r_base = 0;   // extract sequence numbers of the two handles when the pair was armed (same frame)
+    bool inflight = false;                       // a speculative match is enqueued and not yet adopted or invalidated
+    unsigned long long l_seq = 0, r_seq = 0;     // the extracts it matched
+    bool wait_l = false, wait_r = false;         // the handle's next extract has to be ordered after the speculative kernels (they read its buffers)
+    hipEvent_t ev_done = nullptr;
+    long n_adopted = 0, n_dropped = 0;
+};
+
+// The handle: the core (geometry, buffers of the extract pipeline, main stream) directly, then one plain struct per feature.  Each feature's
+// fields are allocated, reset after an extract and released in the translation unit that holds its entry points.
+struct jsorb_extractor {
+    // ---- core buffers and geometry (jsorb_api.hip: jsorb_create_masked / jsorb_destroy) ----
+    jsorb_params p{};
+    Geometry g{};
+    int B = 1;                 // max_batch
+    int n_images = 0;          // images of the last extract
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    int spin_wait = 1;                 // poll instead of block when waiting for a single frame (JSORB_SPIN_WAIT=0 disables)
+    // level 0 has to be copied into the pitched slab first (strided host input, device input with unaligned rows): done per lane, on
+    // the lane's stream, right before its kernels
+    const uint8_t *copy_src = nullptr;
+    size_t copy_stride = 0;
+    int copy_step = 0, copy_kind = 0;      // 0 none, 1 host (hipMemcpy2DAsync per image), 2 device (one copy kernel per lane)
+    bool counts_synced = false;        // h_counts / h_stats reflect the last enqueued batch (set by jsorb_sync)
+    size_t detect_lds = 0, pyr_lds = 0;
+    unsigned *det_spill = nullptr, *det_spill_flags = nullptr;      // compact k_detect: arena of spill chunks (positives beyond a workgroup's LDS pool) and one busy flag per chunk
+    // device buffers
+    uint8_t *slab = nullptr, *blur = nullptr, *mask = nullptr;
+    uint32_t *lut_bits = nullptr;
+    unsigned long long *tile_out = nullptr, *kp = nullptr;
+    int *counts = nullptr, *row_tab = nullptr;
+    float *angles = nullptr;
+    uint8_t *desc = nullptr;
+    int32_t *out_kp = nullptr;
+    bool nms_ms = false;
+    int *ms_grid = nullptr, *ms_scratch = nullptr;   // NMS-MS: level-0 accumulator plane (GPU mode) / mutable scores (CPU mode)
+    int *h_counts = nullptr;           // pinned host mirror
+    ImageSrc src{};            // where level 0 of the last extract lives
+    bool extracted = false;
+    std::string err;
+
+    // ---- lanes and streams (jsorb_api.hip) ----
+    // Lanes: a batch of many images is split into up to JSORB_MAX_LANES contiguous sub-batches, each enqueued on its own HIP stream
+    // (lane 0 = `stream`, the handle's main / caller-provided stream).  The sparse, latency-bound stages of one lane (FAST ring
+    // test / NMS, descriptor gathers, the single-workgroup compaction and median kernels) then overlap the streaming stages of
+    // another one.  A single frame (the reference's call shape) uses lane 0 only.
+    struct {
+        hipStream_t used[JSORB_MAX_LANES] = {};   // the stream lane j of the LAST batch ran on (main stream for a one-lane batch, the device's lane pool otherwise)
+        hipStream_t readers_stream[JSORB_MAX_LANES] = {};
+        hipEvent_t done[JSORB_MAX_LANES] = {};          // after the last work enqueued on lane j
+        hipEvent_t readers_done[JSORB_MAX_LANES] = {};  // recorded on ANOTHER handle's lanes after they read this handle's buffers
+        hipEvent_t ev_fork = nullptr;
+        int max = 4;
+        double min_px = 7.0e6;
+        int K = 1;                 // lanes used by the last batch
+        int first[JSORB_MAX_LANES + 1] = {};
+        bool has_readers = false;
+        int readers_K = 0, readers_n = 0;
+        int cap = JSORB_MAX_LANES;         // transient: cap for the batch being enqueued
+        bool main_stream_dirty = false;    // this call enqueued input copies on the main stream: the lanes must fork after them
+    } lanes;
+
+    // ---- landing buffers (jsorb_extract.hip) ----
+    // host uploads: two dense B x H0 x W0 landing buffers filled by ONE hipMemcpyAsync per batch on a dedicated copy stream, then read
+    // in place as level 0.  Double buffering lets the upload of batch k+1 overlap the kernels of batch k.
+    struct {
+        uint8_t *stage[2] = {nullptr, nullptr};
+        int host_lanes = 1;                     // cap on the lanes of a host-uploaded batch (JSORB_HOST_LANES): PCIe-bound, see extract_batch_host_enqueue
+        hipEvent_t ev_copied[2][JSORB_MAX_LANES] = {};   // per landing buffer and lane: the lane's images have arrived
+        int consumed_n[2] = {0, 0};        // images of the batch that last used the buffer (with consumed_K: its lane partition)
+        hipEvent_t ev_consumed[2][JSORB_MAX_LANES] = {};   // per landing buffer and lane
+        int consumed_K[2] = {0, 0};        // lanes whose ev_consumed must be waited for before the buffer is refilled (0: never used)
+        int cur = 0, last = -1;
+    } land;
+
+    // ---- single-frame upload (jsorb_extract.hip) ----
+    // single frame from pageable host memory: the calling thread copies the image into this pinned buffer and the first kernel of the
+    // frame pulls it over PCIe (JSORB_KERNEL_UPLOAD=0: hipMemcpyAsync instead).  hipMemcpyAsync from pageable memory goes through a
+    // staging buffer of the runtime that the two extractor threads of a stereo frame take turns on: the right image started ~20 us late.
+    struct {
+        uint8_t *h_upload = nullptr;
+        hipEvent_t ev_read = nullptr;   // recorded right behind k_upload_level0: the pinned buffer may be rewritten once it has fired
+        bool inflight = false;
+        bool sync_single = false;       // inside jsorb_extract / jsorb_extract_into: the call itself waits for the frame, nobody needs ev_read (one barrier packet less in front of the match)
+        int kernel = 1;
+        bool pending = false;           // transient: run_pipeline starts the single-image chain with the upload kernel
+    } up;
+
+    // ---- frame graph (jsorb_extract.hip) ----
+    // the 5-kernel chain of a single image as a HIP graph (captured on first use, replayed while the arguments stay the same): one
+    // hipGraphLaunch instead of five kernel launches on the host's critical path (JSORB_FRAME_GRAPH=0 disables)
+    struct {
+        hipGraphExec_t exec = nullptr;
+        hipGraph_t tmpl = nullptr;                   // the captured graph the executable one was instantiated from (owns the node handles)
+        hipGraphNode_t describe_node = nullptr;      // its k_describe node: carries the caller-owned destinations of jsorb_extract_into
+        int32_t *dst_kp = nullptr;                   // ... as currently set in the executable graph
+        uint8_t *dst_desc = nullptr;
+        const void *key[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // l0 source, its pitch, main stream, rectification map, camera, upload node
+        int recaptures = 0;             // consecutive frames whose arguments differed from the captured ones
+        int on = 1;
+    } fg;
+
+    // ---- result mirrors (jsorb_extract.hip) ----
+    // single-image calls (the reference's call shape): the kernels write their results into these pinned mirrors themselves (struct
+    // Deliver), so that SyncedMem::to_cpu() costs a memcpy instead of a blocking D2H
+    struct {
+        int32_t *h_kp = nullptr;
+        uint8_t *h_desc = nullptr;
+        bool mirror_valid = false;
+        bool mirror_pending = false;    // a single-image call is in flight whose kernels write the pinned mirrors themselves (struct Deliver)
+        int32_t *deliver_kp = nullptr;  // jsorb_extract_into: caller-owned device destinations of the next single-image pipeline
+        uint8_t *deliver_desc = nullptr;
+        jsorb_keypoint *frame_aos = nullptr;    // Frame-side unpacking (allocated on first use, then kept): AoS keypoints of one image
+    } res;
+
+    // ---- stereo outputs and speculation (jsorb_stereo.hip) ----
+    struct {
+        float *u = nullptr, *d = nullptr;
+        int *l1 = nullptr, *stats = nullptr;
+        unsigned *aux = nullptr;
+        int *h_stats = nullptr;            // pinned mirrors: statistics of every pair; uRight and depth of a single pair (struct DeliverStereo)
+        float *h_u = nullptr, *h_d = nullptr;
+        bool mirror_valid = false, mirror_pending = false;
+        bool done = false;
+        int pairs = 0;
+        int *diag = nullptr;               // jsorb_set_stereo_diagnostics: 13 int per left keypoint and image (B x T x 13), written by k_stereo when allocated
+        const int *l1_view = nullptr;      // L1 distances of the last match: l1, or sp_l1 after an adopted speculative match (jsorb_copy_stereo_l1)
+        // speculative stereo match of the synchronous single-frame call shape (struct jsorb_spec_state)
+        jsorb_spec_state *spec = nullptr;
+        unsigned long long spec_seq = 0;   // extract calls of this handle (written under spec->mu once paired)
+        bool spec_single = false;          // the last extract was a single image on an untimed handle
+        int speculate = 0;                 // opt-in: jsorb_set_speculative_stereo(l, 1) (the C++ shim does it when it sees Frame's call shape) or JSORB_SPECULATE=1
+        int speculate_env = -1;            // JSORB_SPECULATE, when set, wins over the call (0: never, 1: always)
+        float *sp_u = nullptr, *sp_d = nullptr, *h_sp_u = nullptr, *h_sp_d = nullptr;   // twin output buffers (left handle), swapped in on adoption
+        int *sp_stats = nullptr, *h_sp_stats = nullptr, *sp_l1 = nullptr;   // sp_l1 / sp_aux: scratch of the speculative match (one pair)
+        unsigned *sp_aux = nullptr;
+    } st;
+
+    // ---- rectification map (jsorb_frame.hip, jsorb_set_rectify_maps) ----
+    // the entry points point `src` at the RAW input, run_pipeline remaps it into level 0 of the slab (k_rectify, first kernel of each lane)
+    // and points `src` there
+    struct {
+        bool on = false;
+        RectMap map{};
+        void *buf = nullptr;               // the map's xy, a and tile table in one device allocation (kept until destroy)
+        uint8_t *raw = nullptr;            // strided host input with maps: the raw images land here, dense (B x H x W), allocated on first use
+    } rect;
+
+    // ---- camera / undistortion (jsorb_frame.hip, jsorb_set_camera) ----
+    // with k1 != 0 run_pipeline appends k_undistort to every lane; buffers allocated on the first set, then kept
+    struct {
+        bool on = false;
+        UndistortCam c{};
+        float *un = nullptr;               // B x 2T floats: x_un[N] y_un[N] per image
+        float *h_un = nullptr;             // pinned mirror of image 0, written by k_undistort on the single-frame path
+        bool un_valid = false;             // `un` holds the last batch undistorted with the current camera
+        bool un_mirror = false;            // h_un was written by the last (single-image) pipeline: valid together with res.mirror_valid
+    } cam;
+
+    // ---- RGB-D (jsorb_frame.hip, jsorb_rgbd_depth*): allocated on the first call, then kept ----
+    struct {
+        float *out = nullptr;              // B x T uRight, then B x T depth
+        float *h_out = nullptr;            // pinned: T uRight, T depth of image 0 (synchronous call)
+        uint8_t *h_depth = nullptr;        // pinned staging of one host depth image (dense rows), read in place by k_rgbd
+        bool mirror = false;
+        int images = 0;                    // images of the last batch the last RGB-D call covered (0: none; the synchronous call covers image 0 only)
+    } rgbd;
+
+    // ---- grid CSR (jsorb_frame.hip): allocated on first use, grown with the number of cells ----
+    struct {
+        int32_t *start = nullptr, *items = nullptr;
+        int cells = 0;
+    } grid;
+
+    // ---- local-map search (jsorb_frame.hip, jsorb_search_local_points*): allocated on the first call, grown with the number of map points ----
+    struct {
+        int *cand = nullptr;               // points x search_local_cap() packed candidates, then points counts
+        int points = 0;
+        int *stats = nullptr;              // rounds, candidates, points over the capacity of the last call (device)
+        int32_t *out = nullptr;            // synchronous call: match_kp, match_dist (out_points each), kp_match (T), count
+        int out_points = 0;
+        bool done = false;
+    } sl;
+
+    // ---- per-kernel timing (jsorb_api.hip) ----
+    struct TimedLaunch { int id; hipEvent_t a, b; };
+    struct {
+        bool on = false;
+        std::vector<TimedLaunch> timed;
+        double k_ms[JSORB_K_ID_END] = {0};
+        long k_n[JSORB_K_ID_END] = {0};
+    } tm;
+
+    // ---- JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy ----
+    struct {
+        bool on = false;
+        double h2d = 0, enq = 0, wait = 0, st_enq = 0, st_wait = 0;
+        long n = 0, st_n = 0;
+    } trace;
+};
+
+#define HIPCHK(e, call)                                                                                   \
+    do {                                                                                                  \
+        hipError_t _s = (call);                                                                           \
+        if (_s != hipSuccess) {                                                                           \
+            (e)->err = std::string(#call) + ": " + hipGetErrorString(_s);                                 \
+            return JSORB_ERR_HIP;                                                                         \
+        }                                                                                                 \
+    } while (0)
+// a call that returns JSORB_OK or an error code (which it has reported itself): the error is passed on
+#define RCCHK(call) do { int _rc = (call); if (_rc) return _rc; } while (0)
+
+// Everything below is internal to libjsorb.so (hidden: the exported symbols are the C ABI of include/jsorb.h).
+namespace jsorb_host __attribute__((visibility("hidden"))) {
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline hipStream_t lane_stream(const jsorb_extractor *e, int j) { return e->lanes.used[j]; }      // of the LAST batch
+inline bool check_image(const jsorb_extractor *e, int image) { return e && e->extracted && image >= 0 && image < e->n_images; }
+
+// ---- per-kernel timing: TIMED(e, id, launch) brackets one launch with two events (drained by drain_timed) ----
+inline int enqueue_timed(jsorb_extractor *e, int id)
+{
+    if (!e->tm.on) return JSORB_OK;
+    jsorb_extractor::TimedLaunch t{id, nullptr, nullptr};
+    HIPCHK(e, hipEventCreate(&t.a));
+    HIPCHK(e, hipEventCreate(&t.b));
+    HIPCHK(e, hipEventRecord(t.a, e->stream));          // timing forces one lane: everything runs on the main stream
+    e->tm.timed.push_back(t);
+    return JSORB_OK;
+}
+inline int finish_timed(jsorb_extractor *e)
+{
+    if (e->tm.on) HIPCHK(e, hipEventRecord(e->tm.timed.back().b, e->stream));
+    return JSORB_OK;
+}
+int drain_timed(jsorb_extractor *e);
+
+#define TIMED(e, id, stmt) do { RCCHK(enqueue_timed((e), (id))); stmt; RCCHK(finish_timed((e))); } while (0)
+
+// Polls `query` (hipStreamQuery / hipEventQuery on what is waited for) a bounded number of times before the caller blocks: a single frame is
+// ~100 us of GPU time, and a blocking wait adds tens of microseconds of wake-up latency.  *done: the query reported completion.
+template <class Query> int spin_poll(jsorb_extractor *e, Query query, const char *what, bool *done)
+{
+    *done = false;
+    for (int it = 0; it < 400000; it++) {
+        const hipError_t q = query();
+        if (q == hipSuccess) { *done = true; return JSORB_OK; }
+        if (q != hipErrorNotReady) { e->err = std::string(what) + ": " + hipGetErrorString(q); return JSORB_ERR_HIP; }
+        __builtin_ia32_pause();
+    }
+    return JSORB_OK;
+}
+
+// Stream `s` waits for the events ev[0..K-1] of K lanes that ran on the streams on[0..K-1] (errors are reported on `e`).  A lane that ran on `s`
+// itself is ordered already.  wait_lanes: the last work of every lane of handle `h`.
+inline int wait_events(jsorb_extractor *e, hipStream_t s, const hipStream_t *on, const hipEvent_t *ev, int K)
+{
+    for (int j = 0; j < K; j++)
+        if (on[j] != s) HIPCHK(e, hipStreamWaitEvent(s, ev[j], 0));
+    return JSORB_OK;
+}
+inline int wait_lanes(jsorb_extractor *e, hipStream_t s, const jsorb_extractor *h) { return wait_events(e, s, h->lanes.used, h->lanes.done, h->lanes.K); }
+// The other way round: every lane of the handles `hs` that is not `s` continues after what is enqueued on `s` so far (e->lanes.ev_fork,
+// recorded on `s` once, and only if some lane needs it).
+inline int fork_lanes(jsorb_extractor *e, hipStream_t s, std::initializer_list<const jsorb_extractor *> hs)
+{
+    bool forked = false;
+    for (const jsorb_extractor *h : hs)
+        for (int j = 0; j < h->lanes.K; j++)
+            if (lane_stream(h, j) != s) {
+                if (!forked) { HIPCHK(e, hipEventRecord(e->lanes.ev_fork, s)); forked = true; }
+                HIPCHK(e, hipStreamWaitEvent(lane_stream(h, j), e->lanes.ev_fork, 0));
+            }
+    return JSORB_OK;
+}
+
+// n x elem bytes of one image's result into dst (nothing when dst is NULL or n <= 0): from its pinned mirror when that holds the image
+// (`mirror`, else NULL), otherwise from `dev`, the image's device slice.  Does not touch e->err (the const getters).
+inline int copy_result(void *dst, const void *mirror, const void *dev, int n, size_t elem)
+{
+    if (!dst || n <= 0) return JSORB_OK;
+    if (mirror) { memcpy(dst, mirror, (size_t)n * elem); return JSORB_OK; }
+    return hipMemcpy(dst, dev, (size_t)n * elem, hipMemcpyDeviceToHost) == hipSuccess ? JSORB_OK : JSORB_ERR_HIP;
+}
+
+// A device buffer allocated on first use and then kept.  With `have` (units allocated so far, 0: none) it grows on demand instead: when `want`
+// units exceed *have the old buffer is freed (hipFree waits for the device: the last call may still read it) and `bytes` are allocated for
+// `want` units; the contents are not kept.
+template <class T> int reserve_device(jsorb_extractor *e, T *&p, size_t bytes, int *have = nullptr, int want = 0)
+{
+    if (have ? *have >= want : p != nullptr) return JSORB_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    HIPCHK(e, hipMalloc(&p, bytes));
+    if (have) *have = want;
+    return JSORB_OK;
+}
+template <class T> int reserve_pinned(jsorb_extractor *e, T *&p, size_t bytes) { if (!p) HIPCHK(e, hipHostMalloc(&p, bytes)); return JSORB_OK; }
+// release functions: free (and forget) what a feature allocated
+template <class... T> void free_device(T *&...p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+template <class... T> void free_pinned(T *&...p) { ((p ? (void)hipHostFree(p) : (void)0, p = nullptr), ...); }
+template <class... T> void destroy_event(T &...ev) { ((ev ? (void)hipEventDestroy(ev) : (void)0, ev = nullptr), ...); }
+
+// ---- jsorb_api.hip ----
+int pool_stream(jsorb_extractor *e, int j, hipStream_t *out);      // lane stream j of the device's pool
+int pool_copy_stream(jsorb_extractor *e, hipStream_t *out);         // the device's upload stream
+
+// ---- jsorb_extract.hip ----
+int landing_create(jsorb_extractor *e);
+int results_create(jsorb_extractor *e);
+void frame_graph_drop(jsorb_extractor *e);
+int wait_event(jsorb_extractor *e, hipEvent_t ev, bool spin);
+void mirrors_landed(jsorb_extractor *e);
+void extract_release(jsorb_extractor *e);         // frame graph, single-frame upload, landing buffers, result mirrors
+
+// ---- jsorb_stereo.hip ----
+int stereo_create(jsorb_extractor *e);
+int spec_guard(jsorb_extractor *e, int n);
+void spec_after_extract(jsorb_extractor *e, int n);
+void spec_detach(jsorb_spec_state *S);
+void stereo_after_extract(jsorb_extractor *e);
+void stereo_release(jsorb_extractor *e);
+
+// ---- jsorb_frame.hip ----
+int rectify_reserve_raw(jsorb_extractor *e, size_t image_bytes);
+void rectify_release(jsorb_extractor *e);
+void camera_after_extract(jsorb_extractor *e, bool direct);
+void camera_release(jsorb_extractor *e);
+void rgbd_invalidate(jsorb_extractor *e);
+void rgbd_release(jsorb_extractor *e);
+void grid_release(jsorb_extractor *e);
+void search_local_release(jsorb_extractor *e);
+
+} // namespace jsorb_host
+
+using namespace jsorb_host;

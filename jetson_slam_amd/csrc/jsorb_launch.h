@@ -48,7 +48,7 @@ void rectify_tile_table(const int16_t *xy, const uint16_t *a, int W, int H, int 
 void launch_pyramid(const Geometry &g, const ImageSrc &src, uint8_t *slab, const uint32_t *ctab, int n_images, size_t lds_bytes, hipStream_t s);
 int detect_ring_bit_of_pixel(int k);       // bit of ring pixel k in the index of the arc LUT as k_detect forms it (the host stores the LUT in that order)
 // images with up to this many tiles: k_compact as a launch of its own runs its re-reading form with 256-thread workgroups on batch handles (k_compact.hip), and a
-// batch of one lane takes the fused k_blur_compact launch (jsorb_api.hip: run_pipeline)
+// batch of one lane takes the fused k_blur_compact launch (jsorb_extract.hip: run_pipeline)
 #ifndef CMP_MID_T
 #define CMP_MID_T 8192
 #endif

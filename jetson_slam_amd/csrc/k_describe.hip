@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * WPW, DESC_MIN_WAVES) void k_describe(Geometry 
     }
 }
 
-// for the single-frame graph of jsorb_api.hip: which node of a captured frame is this kernel, and which of its arguments is `dl`
+// for the single-frame graph of jsorb_extract.hip: which node of a captured frame is this kernel, and which of its arguments is `dl`
 const void *describe_kernel_address() { return reinterpret_cast<const void *>(&k_describe); }
 int describe_kernel_deliver_arg() { return 10; }
 

@@ -1,6 +1,6 @@
 // undistort.h - the keypoint undistortion of Frame::UndistortKeyPoints / Frame::ComputeImageBounds (Frame.cpp:718-778): OpenCV 4's
 // cv::undistortPoints(src, dst, K, D, noArray(), K) with its default criteria, for the 4 / 5-coefficient model.  ONE __host__ __device__
-// routine: k_undistort (k_undistort.hip) runs it per keypoint, jsorb_image_bounds (jsorb_api.hip) on the host for the four corners, so the
+// routine: k_undistort (k_undistort.hip) runs it per keypoint, jsorb_image_bounds (jsorb_frame.hip) on the host for the four corners, so the
 // two cannot drift apart.  The library builds with -ffp-contract=off -fno-fast-math: every operation below is one IEEE double operation,
 // `/` is the correctly rounded division on both sides, nothing is fused.
 #pragma once
