@@ -86,6 +86,21 @@ const char *jsorb_version(void);
  * 16-byte loads per lane and row of k_pyramid, the load count its kernel instantiates for that, tile rows of the level.  capacity >= 8 + 8 * levels. */
 int jsorb_plan_launch(const jsorb_params *params, int32_t *out, int capacity);
 
+/* Compaction launches (slot 1 of jsorb_plan_forms / jsorb_handle_forms): k_compact_flat with the candidates in registers (1024 threads: single
+ * images, or small workgroups: batches; T <= 4096), k_compact_flat re-reading the tile list (small workgroups: batches, T <= 8192; 1024 threads:
+ * T <= 65536), and k_compact, which compacts level by level and builds no scan-line buckets (T > 65536). */
+enum { JSORB_COMPACT_REG_1024 = 0, JSORB_COMPACT_REG_BATCH, JSORB_COMPACT_FLAT_BATCH, JSORB_COMPACT_FLAT_1024, JSORB_COMPACT_LEVELS_1024 };
+/* Host-only, touches no device (like jsorb_plan_launch): the kernel forms a handle with these parameters selects from its geometry alone.
+ * out[0..7] = k_detect form (1: compact, 0: full plane - before jsorb_create's device checks), compaction launch (JSORB_COMPACT_*), stereo
+ * candidate scan (1: scan-line buckets, 0: tile rows), k_blur_compact possible for a batch (0 / 1), single frames run k_detect and k_blur as one
+ * launch (0 / 1), levels that replay K3's literal horizontal tree, NMS-MS CPU mode possible (0 / 1), 0 (reserved).  capacity >= 8. */
+int jsorb_plan_forms(const jsorb_params *params, int32_t *out, int capacity);
+/* The same for a created handle, as it actually runs (k_detect's form after any fall-back in jsorb_create), then what the LAST extract call ran:
+ * out[8..11] = lanes K (0: no extract yet), lane order (0: plain order, k_blur_compact where possible; 1: odd lanes run k_blur first; 2: plain
+ * order, nothing fused; -1: no extract yet), bit mask of the lanes that ran k_blur_compact, bit mask of the lanes that ran k_blur before
+ * k_detect.  capacity >= 12. */
+int jsorb_handle_forms(const jsorb_extractor *e, int32_t *out, int capacity);
+
 /* The mask image the reference loads with cv::imread(str_mask) + cvtColor(BGR2GRAY) (orb_gpu.cpp:64-75; yaml keys mask.left / mask.right):
  * decodes a PNG (non-interlaced; gray, gray+alpha, RGB, RGBA, palette; 1-16 bit) or a binary PGM / PPM file to one gray byte per pixel, for
  * callers that do not link OpenCV.  Call with gray_out = NULL to obtain the size first.  JSORB_ERR_STATE: the file cannot be opened (the

@@ -403,6 +403,41 @@ int jsorb_plan_launch(const jsorb_params *params, int32_t *out, int capacity)
     return JSORB_OK;
 }
 
+// NMS-MS in the reference's CPU mode: k_nms_ms's tables of that mode hold at most 32768 tiles
+static bool nms_ms_cpu_supported(const Geometry &g) { return g.T <= 32768 && g.lv[0].nth * g.lv[0].ntw <= 65535; }
+
+// out[0..7] of jsorb_plan_forms / jsorb_handle_forms: the kernel forms the geometry selects, from the same rules the launch code applies
+static void geometry_forms(const Geometry &g, bool frame_fuse, int32_t *out)
+{
+    int replay = 0;
+    for (int i = 0; i < g.L; i++) replay += g.lv[i].tree_rank_ok ? 0 : 1;
+    out[0] = g.det_compact; out[1] = compact_form(g); out[2] = g.epi_rows != 0; out[3] = blur_compact_fusable(g) ? 1 : 0;
+    out[4] = frame_fuse ? 1 : 0; out[5] = replay; out[6] = nms_ms_cpu_supported(g) ? 1 : 0; out[7] = 0;
+}
+
+int jsorb_plan_forms(const jsorb_params *params, int32_t *out, int capacity)
+{
+    if (!params || !out || capacity < 8) return JSORB_ERR_INVALID;
+    Geometry g;
+    std::string err;
+    RCCHK(build_geometry(*params, g, err));
+    plan_detect(g);
+    // (jsorb_create may raise the full-plane k_detect's LDS request, to at most 40 KB: that never crosses the bound of the fused launch)
+    geometry_forms(g, detect_blur_fusable(g, detect_lds_bytes(g)), out);
+    return JSORB_OK;
+}
+
+int jsorb_handle_forms(const jsorb_extractor *e, int32_t *out, int capacity)
+{
+    if (!e || !out || capacity < 12) return JSORB_ERR_INVALID;
+    geometry_forms(e->g, frame_fuses_detect_blur(e), out);
+    out[8] = e->extracted ? e->lanes.K : 0;
+    out[9] = e->extracted ? e->lanes.order : -1;
+    out[10] = e->extracted ? (int32_t)e->lanes.fuse_bc_mask : 0;
+    out[11] = e->extracted ? (int32_t)e->lanes.blur_first_mask : 0;
+    return JSORB_OK;
+}
+
 int jsorb_create_masked(const jsorb_params *params, const uint8_t *mask, int mask_width, int mask_height, jsorb_extractor **out)
 {
     if (!params || !out) return JSORB_ERR_INVALID;
@@ -500,7 +535,7 @@ int jsorb_create_masked(const jsorb_params *params, const uint8_t *mask, int mas
             HIPCHK(e, hipMalloc(&e->ms_grid, n));
             HIPCHK(e, hipMemset(e->ms_grid, 0, n));
         } else {
-            if (g.T > 32768 || g.lv[0].nth * g.lv[0].ntw > 65535) { e->err = "NMS-MS CPU mode supports at most 32768 tiles"; return JSORB_ERR_UNSUPPORTED; }
+            if (!nms_ms_cpu_supported(g)) { e->err = "NMS-MS CPU mode supports at most 32768 tiles"; return JSORB_ERR_UNSUPPORTED; }
             HIPCHK(e, hipMalloc(&e->ms_scratch, B * T * sizeof(int)));
         }
     }

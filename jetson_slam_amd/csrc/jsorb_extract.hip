@@ -70,6 +70,12 @@ void extract_release(jsorb_extractor *e)
     free_device(e->res.frame_aos);
 }
 
+bool frame_fuses_detect_blur(const jsorb_extractor *e)
+{
+    static const bool fuse_env = !env_is(experiment_env("JSORB_FUSED_DETECT_BLUR"), 0);
+    return fuse_env && detect_blur_fusable(e->g, e->detect_lds);
+}
+
 } // namespace jsorb_host
 
 namespace {
@@ -156,6 +162,29 @@ bool frame_graph_set_destinations(jsorb_extractor *e)
     return true;
 }
 
+// Lane order of a batch of n images on K lanes (round 6; every arm measured A/B on one box, profiles/r06_experiments.txt).  The lanes of a batch start together and run
+// the same stages at the same time; on handles with many keypoints per image (the yaml tiles: tile height <= 40) the ODD lanes therefore run
+// k_blur BEFORE k_detect (the two are independent: both read the pyramid), and the even lanes' k_compact rides inside their k_blur launch
+// (k_blur_compact, k_blur.hip; k_compact as a launch of its own is a bubble in its lane): C2 +1.3 %, C5 +1.7 %, C3 +-0 against one order for all
+// lanes.  With large tiles (few keypoints, k_detect most of the step) the same order costs 1-2.5 %: those handles keep the plain order.
+// Not while per-kernel timing is on (stages are timed one by one then).
+// SMALL launches and ODD lane counts (end of round 6): what the alternating order gains grows with the size of a lane's launches, what the fused
+// launch saves - one launch and its dependency gap per extract - does not, and with three lanes the alternation is lopsided.  Below 24 megapixels of
+// pyramid per lane and launch (16 KITTI-shaped images: a 64-pair step), or with an odd number of lanes (64 EuRoC-shaped images: 24 + 24 + 16), every
+// lane runs the plain order with the fused launch: +3 % in both cases; +-0.6 % between 24 and 36 MPx, -1 ... -4.5 % above (twelve geometry / batch
+// combinations, tools/micro/r6_lane_order.sh, log sections 33-35).
+// A batch too small to be split (one lane) takes the fused launch as well when its compaction workgroup is short (<= CMP_MID_T tiles: +8 ... 10 % at 8 / 16
+// EuRoC-shaped and 12 KITTI-shaped pairs; the 21 053 tiles of the KAIST shape outlast so small a k_blur launch: -13 %, those keep k_compact's own launch).
+// JSORB_LANE_ORDER (experiments build): 0 - every lane plain order with the fused launch, 1 - alternating, 2 - plain order, nothing fused.
+int lane_order(const Geometry &g, int n, int K)
+{
+    double lane_mpx = 0;
+    for (int l = 0; l < g.L; l++) lane_mpx += (double)g.lv[l].W * g.lv[l].H;
+    lane_mpx *= (double)n / K * 1e-6;
+    return experiment_env("JSORB_LANE_ORDER") ? atoi(experiment_env("JSORB_LANE_ORDER"))
+                                              : ((K & 1) || lane_mpx < JSORB_FUSE_ALL_BELOW_MPX ? 0 : (g.lv[0].th <= 40 ? 1 : 2));      // (tall tiles as well: C3 / tile 46 +1.1 %, C2 / tile 58 with 64 pairs +1.7 %)
+}
+
 int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = nullptr)
 {
     const Geometry &g = e->g;
@@ -173,6 +202,10 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
     // well); for a single image k_describe also delivers keypoints and descriptors there and into the caller's device buffers
     // (jsorb_extract_into)
     const bool direct = n == 1;
+    // single image: k_detect and k_blur (independent of each other) as ONE launch - a frame is a chain of small launches whose latencies add up
+    const bool fused = direct && !e->tm.on && frame_fuses_detect_blur(e);
+    const int order = lane_order(g, n, K);
+    unsigned fuse_bc_mask = 0, blur_first_mask = 0;
     for (int j = 0; j < K; j++) {
         const int f = first[j], m = first[j + 1] - f;
         hipStream_t st = ls[j];
@@ -230,30 +263,10 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
         if (e->rect.on)
             JSORB_STAGE(JSORB_K_RECTIFY, launch_rectify(e->rect.map, raw.l0, raw.l0_stride, raw.l0_pitch, slab, g.slab_bytes, g.lv[0].pitch, g.lv[0].W, g.lv[0].H, m, st));
         JSORB_STAGE(JSORB_K_PYRAMID, launch_pyramid(g, src, slab, e->lut_bits, m, e->pyr_lds, st));
-        // single image: k_detect and k_blur (independent of each other) as ONE launch - a frame is a chain of small launches whose latencies add up
-        static const bool fuse_env = !env_is(experiment_env("JSORB_FUSED_DETECT_BLUR"), 0);
-        const bool fused = direct && fuse_env && !e->tm.on && g.blur_blocks > 0 && !g.det_compact && e->detect_lds + 12 * 1024 <= 64 * 1024;      // (k_blur's 10 KB of static LDS come on top of k_detect's request)
-        // Lane order of a batch (round 6; every arm measured A/B on one box, profiles/r06_experiments.txt).  The lanes of a batch start together and run
-        // the same stages at the same time; on handles with many keypoints per image (the yaml tiles: tile height <= 40) the ODD lanes therefore run
-        // k_blur BEFORE k_detect (the two are independent: both read the pyramid), and the even lanes' k_compact rides inside their k_blur launch
-        // (k_blur_compact, k_blur.hip; k_compact as a launch of its own is a bubble in its lane): C2 +1.3 %, C5 +1.7 %, C3 +-0 against one order for all
-        // lanes.  With large tiles (few keypoints, k_detect most of the step) the same order costs 1-2.5 %: those handles keep the plain order.
-        // Not while per-kernel timing is on (stages are timed one by one then).
-        // SMALL launches and ODD lane counts (end of round 6): what the alternating order gains grows with the size of a lane's launches, what the fused
-        // launch saves - one launch and its dependency gap per extract - does not, and with three lanes the alternation is lopsided.  Below 24 megapixels of
-        // pyramid per lane and launch (16 KITTI-shaped images: a 64-pair step), or with an odd number of lanes (64 EuRoC-shaped images: 24 + 24 + 16), every
-        // lane runs the plain order with the fused launch: +3 % in both cases; +-0.6 % between 24 and 36 MPx, -1 ... -4.5 % above (twelve geometry / batch
-        // combinations, tools/micro/r6_lane_order.sh, log sections 33-35).
-        // A batch too small to be split (one lane) takes the fused launch as well when its compaction workgroup is short (<= CMP_MID_T tiles: +8 ... 10 % at 8 / 16
-        // EuRoC-shaped and 12 KITTI-shaped pairs; the 21 053 tiles of the KAIST shape outlast so small a k_blur launch: -13 %, those keep k_compact's own launch).
-        // JSORB_LANE_ORDER (experiments build): 0 - every lane plain order with the fused launch, 1 - alternating, 2 - plain order, nothing fused.
-        double lane_mpx = 0;
-        for (int l = 0; l < g.L; l++) lane_mpx += (double)g.lv[l].W * g.lv[l].H;
-        lane_mpx *= (double)n / K * 1e-6;
-        const int lane_order = experiment_env("JSORB_LANE_ORDER") ? atoi(experiment_env("JSORB_LANE_ORDER"))
-                                                                  : ((K & 1) || lane_mpx < JSORB_FUSE_ALL_BELOW_MPX ? 0 : (g.lv[0].th <= 40 ? 1 : 2));      // (tall tiles as well: C3 / tile 46 +1.1 %, C2 / tile 58 with 64 pairs +1.7 %)
-        const bool blur_first = !fused && K > 1 && (j & 1) && lane_order == 1;
-        const bool fuse_bc = !fused && !direct && (K > 1 || g.T <= CMP_MID_T) && !blur_first && !e->tm.on && lane_order != 2 && blur_compact_fusable(g);
+        const bool blur_first = !fused && K > 1 && (j & 1) && order == 1;
+        const bool fuse_bc = !fused && !direct && (K > 1 || g.T <= CMP_MID_T) && !blur_first && !e->tm.on && order != 2 && blur_compact_fusable(g);
+        if (blur_first) blur_first_mask |= 1u << j;
+        if (fuse_bc) fuse_bc_mask |= 1u << j;
         if (blur_first) JSORB_STAGE(JSORB_K_BLUR, launch_blur(g, src, slab, blur, e->lut_bits, m, st));
         if (fused) JSORB_STAGE(JSORB_K_DETECT, launch_detect_blur(g, src, slab, e->mask, e->lut_bits, tile_out, blur, e->detect_lds, st));
         else JSORB_STAGE(JSORB_K_DETECT, launch_detect(g, src, slab, e->mask, e->lut_bits, tile_out, m, e->detect_lds, st, e->det_spill, e->det_spill_flags));
@@ -305,6 +318,7 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
     e->res.deliver_kp = nullptr;
     e->res.deliver_desc = nullptr;
     e->lanes.K = K;
+    e->lanes.order = order; e->lanes.fuse_bc_mask = fuse_bc_mask; e->lanes.blur_first_mask = blur_first_mask;
     for (int j = 0; j <= K; j++) e->lanes.first[j] = first[j];
     for (int j = 0; j < K; j++) e->lanes.used[j] = ls[j];
     // a caller-provided main stream observes the batch: whatever the caller enqueues on it next runs after the lanes

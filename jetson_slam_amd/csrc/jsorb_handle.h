@@ -102,6 +102,8 @@ struct jsorb_extractor {
         int readers_K = 0, readers_n = 0;
         int cap = JSORB_MAX_LANES;         // transient: cap for the batch being enqueued
         bool main_stream_dirty = false;    // this call enqueued input copies on the main stream: the lanes must fork after them
+        int order = -1;                    // schedule of the last batch (jsorb_handle_forms): lane order, lanes that ran k_blur_compact / k_blur before k_detect
+        unsigned fuse_bc_mask = 0, blur_first_mask = 0;
     } lanes;
 
     // ---- landing buffers (jsorb_extract.hip) ----
@@ -357,6 +359,7 @@ void frame_graph_drop(jsorb_extractor *e);
 int wait_event(jsorb_extractor *e, hipEvent_t ev, bool spin);
 void mirrors_landed(jsorb_extractor *e);
 void extract_release(jsorb_extractor *e);         // frame graph, single-frame upload, landing buffers, result mirrors
+bool frame_fuses_detect_blur(const jsorb_extractor *e);      // a single frame of this handle runs k_detect and k_blur as one launch (timing off)
 
 // ---- jsorb_stereo.hip ----
 int stereo_create(jsorb_extractor *e);

@@ -62,8 +62,11 @@ size_t detect_arena_flag_words();                       // one busy flag per chu
 bool detect_arena_covers(int compute_units);           // the arena has a chunk for every workgroup of the compact k_detect that can be resident on a device of this size (8 XCDs of <= 32 CUs)
 int detect_pos_cap(const Geometry &g, int level);   // entries of a k_detect workgroup's pool of positives on that level (compact form)
 void launch_nms_ms(const Geometry &g, unsigned long long *tile_out, int *ms_grid, int *ms_scratch, int mode_gpu, int n_images, hipStream_t s);
+int compact_form(const Geometry &g);      // which of launch_compact's launches compacts this geometry's images (JSORB_COMPACT_*, include/jsorb.h)
 void launch_compact(const Geometry &g, const unsigned long long *tile_out, unsigned long long *kp, int *counts,
                     int *row_tab, int n_images, hipStream_t s, int *counts_host = nullptr);
+// single image: k_detect and k_blur fit one launch (full-plane k_detect; k_blur's 10 KB of static LDS come on top of k_detect's request)
+inline bool detect_blur_fusable(const Geometry &g, size_t detect_lds) { return g.blur_blocks > 0 && !g.det_compact && detect_lds + 12 * 1024 <= 64 * 1024; }
 void launch_detect_blur(const Geometry &g, const ImageSrc &src, const uint8_t *slab, const uint8_t *mask_slab, const uint32_t *lut_bits,
                         unsigned long long *tile_out, uint8_t *blur_slab, size_t lds_bytes, hipStream_t s);      // single image: k_detect and k_blur as one launch
 void fill_blur_layout(Geometry &g);        // k_blur: strips x bands per level, workgroups per level (host side, once per handle)

@@ -85,25 +85,40 @@ __global__ __launch_bounds__(NT) void k_compact_flat(Geometry g, const unsigned 
 #define CMP_NT_BATCH 256
 #endif
 
+// Which launch compacts the images of a geometry (launch_compact; also what jsorb_plan_forms / jsorb_handle_forms report)
+int compact_form(const Geometry &g)
+{
+    // single images (latency layouts): 1024 threads, the kernel is on the frame's critical path and has the chip to itself; batches: small workgroups
+    // (images with more than 4096 tiles keep 1024 threads: the re-reading form with a quarter of the threads took 0.18 instead of 0.07 ms per step at the
+    // KAIST shape and cost more than the starvation it avoids - 35.4 k against 35.7 k pairs/s)
+    if (g.T <= 4 * 1024) return g.latency ? JSORB_COMPACT_REG_1024 : JSORB_COMPACT_REG_BATCH;
+    // (4096 < T <= 8192 - the KITTI-shaped images - in the register form with 512 threads: measured, no difference)
+    if (g.T <= CMP_MID_T && !g.latency) return JSORB_COMPACT_FLAT_BATCH;
+    if (g.T <= CMP_MAX_CHUNKS * 1024) return JSORB_COMPACT_FLAT_1024;
+    return JSORB_COMPACT_LEVELS_1024;
+}
+
 void launch_compact(const Geometry &g, const unsigned long long *tile_out, unsigned long long *kp, int *counts,
                     int *row_tab, int n_images, hipStream_t s, int *counts_host)
 {
     const size_t epi = g.epi_rows ? (size_t)g.L * g.epi_rows * sizeof(int) : 0;
     constexpr int NB = CMP_NT_BATCH;
-    // single images (latency layouts): 1024 threads, the kernel is on the frame's critical path and has the chip to itself; batches: small workgroups
-    // (images with more than 4096 tiles keep 1024 threads: the re-reading form with a quarter of the threads took 0.18 instead of 0.07 ms per step at the
-    // KAIST shape and cost more than the starvation it avoids - 35.4 k against 35.7 k pairs/s)
-    if (g.T <= 4 * 1024 && g.latency)
+    switch (compact_form(g)) {
+    case JSORB_COMPACT_REG_1024:
         hipLaunchKernelGGL((k_compact_flat<4, 1024>), dim3(n_images), dim3(1024), epi, s, g, tile_out, kp, counts, row_tab, counts_host);
-    else if (g.T <= 4 * 1024)
+        break;
+    case JSORB_COMPACT_REG_BATCH:
         hipLaunchKernelGGL((k_compact_flat<4 * 1024 / NB, NB>), dim3(n_images), dim3(NB), epi, s, g, tile_out, kp, counts, row_tab, counts_host);
-    // (4096 < T <= 8192 - the KITTI-shaped images - in the register form with 512 threads: measured, no difference)
-    else if (g.T <= CMP_MID_T && !g.latency)
+        break;
+    case JSORB_COMPACT_FLAT_BATCH:
         hipLaunchKernelGGL((k_compact_flat<0, NB>), dim3(n_images), dim3(NB), epi, s, g, tile_out, kp, counts, row_tab, counts_host);
-    else if (g.T <= CMP_MAX_CHUNKS * 1024)
+        break;
+    case JSORB_COMPACT_FLAT_1024:
         hipLaunchKernelGGL((k_compact_flat<0, 1024>), dim3(n_images), dim3(1024), epi, s, g, tile_out, kp, counts, row_tab, counts_host);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(k_compact, dim3(n_images), dim3(1024), 0, s, g, tile_out, kp, counts, row_tab, counts_host);
+    }
 }
 
 } // namespace jsorb

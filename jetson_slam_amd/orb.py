@@ -48,7 +48,7 @@ EXPORTS = [
     "jsorb_set_rectify_maps", "jsorb_set_rectify_maps_fixed", "jsorb_clear_rectify_maps", "jsorb_rectify_enabled", "jsorb_rectify_convert_maps",
     "jsorb_set_camera", "jsorb_camera_enabled", "jsorb_image_bounds", "jsorb_keypoints_un_device", "jsorb_copy_keypoints_un", "jsorb_unpack_frame_un",
     "jsorb_rgbd_depth", "jsorb_rgbd_depth_batch_device_async", "jsorb_rgbd_uright_device", "jsorb_rgbd_depth_device", "jsorb_copy_rgbd",
-    "jsorb_search_local_points_async", "jsorb_search_local_points", "jsorb_search_local_stats",
+    "jsorb_search_local_points_async", "jsorb_search_local_points", "jsorb_search_local_stats", "jsorb_plan_forms", "jsorb_handle_forms",
 ]
 
 
@@ -186,6 +186,8 @@ def load_library(path=None):
         "jsorb_search_local_points_async": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 13),
         "jsorb_search_local_points": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 9 + [P, C.POINTER(I)]),
         "jsorb_search_local_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+        "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
+        "jsorb_handle_forms": (I, [P, P, I]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -255,6 +257,27 @@ def plan_launch(im_height, im_width, scale_factor, n_levels, tile_h=30, tile_w=3
     lk = ("det_R", "k_tiles", "pool", "score_stride", "list_cap", "pyr_ns16", "pyr_ns_dispatched", "tile_rows")
     res["per_level"] = [dict(zip(lk, (int(v) for v in out[8 + 8 * i:16 + 8 * i]))) for i in range(res["levels"])]
     return res
+
+
+# jsorb_plan_forms / jsorb_handle_forms slots (include/jsorb.h); COMPACT_FORMS names the JSORB_COMPACT_* launches by id
+FORM_KEYS = ("detect_compact", "compact_form", "stereo_buckets", "blur_compact_fusable", "frame_fuses_detect_blur", "tree_replay_levels",
+             "nms_ms_cpu_ok", "reserved")
+LANE_KEYS = ("lanes", "lane_order", "blur_compact_lanes", "blur_first_lanes")
+COMPACT_FORMS = ("flat_reg_1024", "flat_reg_batch", "flat_batch", "flat_1024", "levels_1024")
+
+
+def plan_forms(im_height, im_width, scale_factor, n_levels, tile_h=30, tile_w=30, fixed_multi_scale_tile_size=False, max_batch=1,
+               FAST_N_MIN=9, FAST_N_MAX=14, th_FAST_MAX=20):
+    """jsorb_plan_forms: the kernel forms a handle with these parameters selects from its geometry, computed on the host (no GPU needed).
+    Returns a dict keyed by FORM_KEYS."""
+    lib = load_library()
+    prm = JsorbParams(im_height, im_width, n_levels, scale_factor, FAST_N_MIN, FAST_N_MAX, 7, th_FAST_MAX, tile_h, tile_w,
+                      int(fixed_multi_scale_tile_size), 0, 0, 0, max_batch)
+    out = np.zeros(len(FORM_KEYS), np.int32)
+    rc = lib.jsorb_plan_forms(C.byref(prm), out.ctypes.data, out.size)
+    if rc != 0:
+        raise JsorbError("jsorb_plan_forms rc=%d" % rc)
+    return dict(zip(FORM_KEYS, (int(v) for v in out)))
 
 
 class ORBExtractor:
@@ -343,6 +366,13 @@ class ORBExtractor:
     @property
     def handle(self):
         return self._h
+
+    def launch_forms(self):
+        """jsorb_handle_forms: the kernel forms this handle runs (FORM_KEYS) and the lane schedule of its last extract call (LANE_KEYS;
+        lanes = 0 and lane_order = -1 before the first one)"""
+        out = np.zeros(len(FORM_KEYS) + len(LANE_KEYS), np.int32)
+        self._chk(self._lib.jsorb_handle_forms(self._h, out.ctypes.data, out.size))
+        return dict(zip(FORM_KEYS + LANE_KEYS, (int(v) for v in out)))
 
     # ---- extraction ----
     def extract(self, image):
