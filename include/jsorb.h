@@ -68,6 +68,8 @@ enum { JSORB_K_UNDISTORT = JSORB_K_COUNT, JSORB_K_RGBD, JSORB_K_COUNT_ALL };
 /* kernels of jsorb_search_local_points*: ids after JSORB_K_COUNT_ALL, which stays the end of the extract / Frame ids above and names no kernel
  * (jsorb_kernel_name gives ""); JSORB_K_ID_END is one past the last id */
 enum { JSORB_K_ASSIGN_GRID = JSORB_K_COUNT_ALL + 1, JSORB_K_LOCAL_CANDIDATES, JSORB_K_LOCAL_RESOLVE, JSORB_K_ID_END };
+/* kernels of jsorb_search_last_frame*: ids from JSORB_K_ID_END on (the grid is JSORB_K_ASSIGN_GRID again); JSORB_K_ID_COUNT is one past the last id */
+enum { JSORB_K_LAST_MATCH = JSORB_K_ID_END, JSORB_K_LAST_RESOLVE, JSORB_K_ID_COUNT };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -339,6 +341,67 @@ int jsorb_search_local_points(jsorb_extractor *e, int image, const jsorb_search_
 /* Diagnostics of the last call (waits for it): fixed-point rounds of k_local_resolve, candidates over all points, points whose candidates
  * overflowed the per-point list (the resolver rescans the grid for them).  Any pointer may be NULL. */
 int jsorb_search_local_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow);
+
+/* ---- motion-model matching: ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (src/ORBmatcher.cpp:1314-1965)
+ * as Tracking::TrackWithMotionModel calls it (src/Tracking.cpp:1030-1066), retry included.  The reference runs its GPU branch (use_gpu_ = true,
+ * :1319; the branch :1647-1963), which this restates bit for bit ----
+ * Points i = 0 .. n_points-1: the last frame's keypoints with a map point that are not outliers, in ascending last-frame index (the reference's
+ * idx_map_point_last_frame, :1714-1731; the order matters: the last writer wins below).  Per point: the map point's world position Px, Py, Pz
+ * (GetWorldPosExp), the last frame's octave (mvKeys[].octave) and angle (mvKeysUn[].angle), and the map point's descriptor (GetDescriptorExp,
+ * 32 bytes).  The current frame is image `image` of the handle's last extract (mvKeysUn from k_undistort with an active camera, else the keypoints).
+ * One pass with threshold th:
+ *   project with K14's arithmetic (jsorb_project_points, :1753-1764): Pc = tcw + Rcw P per row as fma(z,R2,fma(x,R0,y*R1)) + t, invz = 1.0f/Pcz,
+ *     u = fma(Pcx*fx, invz, cx), v likewise; no candidate when Pcz <= 0 or (u < min_x || u > max_x || v < min_y || v > max_y)
+ *   R = th * jsorb_scale(e, octave_i) (:1797, one float product); an octave outside [0, n_levels) is outside the contract: no candidate, nothing read
+ *   candidates = GetFeaturesInArea(u, v, invz, R, minLevel, maxLevel) (src/Frame.cpp:569-639) with (minLevel, maxLevel) = (oct, -1) when
+ *     direction = +1 (bForward), (0, oct) when -1 (bBackward), (oct-1, oct+1) when 0 (:1801-1810).  The caller computes direction from its poses
+ *     as :1657-1668 does: bForward = tlc.z > mb && !bMono, bBackward = -tlc.z > mb && !bMono.  Levels are checked only when minLevel > 0 ||
+ *     maxLevel >= 0 (forward with oct == 0 checks none), octave < minLevel or (maxLevel >= 0 and octave > maxLevel) dropped.  Cells, early returns
+ *     and walk order as jsorb_search_local_points (ix outer, iy inner, a cell's keypoints ascending); kept when |x_un - u| < R && |y_un - v| < R;
+ *     dropped when u_right[k] > 0 && fabsf((u - mbf*invz) - u_right[k]) > R (two roundings; u_right NULL: monocular).  No keypoint is blocked:
+ *     TrackWithMotionModel clears mvpMapPoints before each pass (Tracking.cpp:1047, 1063) and every point's candidates are gathered before any
+ *     assignment, so the Observations() test never drops one and points do not claim keypoints from each other
+ *   best = popcount Hamming distance with strict < updates in walk order from bestDist = 256 (:1898-1911): the minimum of (distance, walk position)
+ *     over distances < 256; the point matches iff bestDist <= th_high (TH_HIGH = 100)
+ *   assign in point order (:1913-1916): mvpMapPoints[best] = point i, nmatches++ (two points on one keypoint: both count, the larger i stays)
+ *   check_orientation (ORBmatcher(0.9, true), :1918-1952): rot = last_angle - cur_angle (the current angle: keypoint SoA row 3, float bits),
+ *     rot += 360.0f when rot < 0; bin = (int)roundf(rot * (1.0f/30)) (half away from zero), bin == 30 -> 0 (factor 1/30: only bins 0..12 occur);
+ *     every matched point pushes its keypoint into its bin, duplicates included; ComputeThreeMaxima (:2097-2138: strict >, the earlier bin wins a
+ *     tie; then max2 < 0.1f*(float)max1 drops ind2 and ind3, else max3 < 0.1f*(float)max1 drops ind3); every entry of every other bin sets
+ *     mvpMapPoints[k] = NULL and nmatches-- (a keypoint is nulled when any point that chose it is in a culled bin, even if a later point in a kept
+ *     bin holds it; nmatches can differ from the non-null slots).  A bin outside [0, 30) - angles outside [0, 360) - is never kept
+ * Retry (Tracking.cpp:1056-1064): when retry_below > 0 and the pass returns nmatches < retry_below, a second pass from scratch with 2*th replaces
+ *   the first entirely (TrackWithMotionModel: retry_below = 20).  The device decides: the second pass's kernels are always enqueued (retry_below > 0)
+ *   and return at once when the first pass's count says so - no host decision, capturable into a graph.
+ * All arrays are DEVICE pointers: Px, Py, Pz, last_angle float[n]; last_octave int32[n]; mp_descriptors n x 32 bytes, 16-byte aligned; u_right
+ * float[N] or NULL (jsorb_stereo_uright_device / jsorb_rgbd_uright_device).  Outputs: match_kp[i] / match_dist[i] = the point's best keypoint and
+ * distance when it matched (before culling), -1 otherwise; kp_match[k] = the final mvpMapPoints[k] as a point index or -1 (N entries);
+ * *n_matches_dev = the reference's return value.  Enqueued on the handle's stream behind the last extract (and the lanes of a batch): the grid
+ * (k_assign_grid, into the handle's grid buffers) and k_last_match + k_last_resolve per pass.  cols * rows <= 16384, N < 262144, direction in
+ * {-1, 0, 1}.  n_points == 0 or N == 0: no match, kp_match all -1. */
+typedef struct jsorb_last_frame_params {
+    float th;                        /* 7 stereo / RGB-D, 15 monocular (Tracking.cpp:1051-1054) */
+    int th_high;                     /* ORBmatcher::TH_HIGH = 100 */
+    int check_orientation;           /* ORBmatcher(0.9, true): 1 */
+    int direction;                   /* +1 bForward, -1 bBackward, 0 neither */
+    int retry_below;                 /* a second pass with 2 th when the first finds fewer (20); 0: none */
+    float fx, fy, cx, cy;            /* K14's camera: CurrentFrame.fx .. cy */
+    float min_x, max_x, min_y, max_y; /* Frame::mnMinX, mnMaxX, mnMinY, mnMaxY: K14's bounds and the grid origin */
+    float inv_w, inv_h;              /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* FRAME_GRID_COLS, FRAME_GRID_ROWS */
+    float mbf;
+    float Rcw[9], tcw[3];            /* CurrentFrame.mTcw, row-major rotation and translation */
+} jsorb_last_frame_params;
+int jsorb_search_last_frame_async(jsorb_extractor *e, int image, const jsorb_last_frame_params *params, int n_points, const float *Px, const float *Py,
+                                  const float *Pz, const int32_t *last_octave, const float *last_angle, const uint8_t *mp_descriptors,
+                                  const float *u_right, int32_t *match_kp, int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the handle; kp_match_host[N] (host) = kp_match and *n_matches = nmatches, with one copy back. */
+int jsorb_search_last_frame(jsorb_extractor *e, int image, const jsorb_last_frame_params *params, int n_points, const float *Px, const float *Py,
+                            const float *Pz, const int32_t *last_octave, const float *last_angle, const uint8_t *mp_descriptors, const float *u_right,
+                            int32_t *kp_match_host, int *n_matches);
+/* Diagnostics of the last call (waits for it): passes that ran (1 or 2) and, for the pass whose results stand, the candidates over all points
+ * (the reference's to_be_matched_count) and ComputeThreeMaxima's ind1..3 (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
+int jsorb_search_last_frame_stats(jsorb_extractor *e, int *passes, int *n_candidates, int kept_bins[3]);
 
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates

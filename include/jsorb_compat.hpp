@@ -629,6 +629,26 @@ inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params
     return n_matches;
 }
 
+// TrackWithMotionModel's matcher.SearchByProjection(mCurrentFrame, mLastFrame, th, bMono) and its retry at 2 th (Tracking.cpp:1045-1064,
+// ORBmatcher.cpp:1647-1963) on the device, in one call: Px / Py / Pz hold GetWorldPosExp of the last frame's map points that are not outliers
+// (ascending last-frame index), octave / angle the last frame's mvKeys[].octave and mvKeysUn[].angle of those keypoints, descriptors their
+// GetDescriptorExp rows (32 bytes each); u_right_gpu mvuRight on the device (jsorb_stereo_uright_device / jsorb_rgbd_uright_device; nullptr:
+// monocular).  The buffers are read on the device: upload them (to_gpu) first.  Returns nmatches; kp_match[k] = index of the point now in
+// mCurrentFrame.mvpMapPoints[k] or -1 - the caller applies mvpMapPoints[k] = points[kp_match[k]].
+inline int SearchLastFrame(ORBExtractor &ex, const jsorb_last_frame_params &params, int n_points, SyncedMem<float> &Px, SyncedMem<float> &Py,
+                           SyncedMem<float> &Pz, SyncedMem<int> &octave, SyncedMem<float> &angle, SyncedMem<unsigned char> &descriptors,
+                           const float *u_right_gpu, std::vector<int> &kp_match)
+{
+    const int N = jsorb_n_keypoints(ex.handle(), 0);
+    kp_match.assign(N > 0 ? N : 1, -1);
+    int n_matches = 0;
+    if (jsorb_search_last_frame(ex.handle(), 0, &params, n_points, Px.gpu_data(), Py.gpu_data(), Pz.gpu_data(), octave.gpu_data(), angle.gpu_data(),
+                                descriptors.gpu_data(), u_right_gpu, kp_match.data(), &n_matches) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_last_frame: ") + jsorb_last_error(ex.handle()));
+    kp_match.resize(N > 0 ? N : 0);
+    return n_matches;
+}
+
 // Rectification on the device instead of the host cv::remap of the reference's stereo driver (Examples/Stereo/stereo_euroc.cpp:106-107 build
 // M1l/M2l, M1r/M2r with cv::initUndistortRectifyMap; :145-146 remap both images of every frame with INTER_LINEAR): set the maps ONCE per
 // extractor, then hand every extract() the raw camera image.  Maps of the extractor's image size, rows dense (width floats apart).

@@ -1,5 +1,5 @@
 // jsorb_frame.hip - host side of the Frame- and Tracking-side features around an extract: rectification maps, the camera (undistorted
-// keypoints, image bounds), RGB-D depth, the feature grid and local-map search.  Each feature keeps its state in its own part of the handle
+// keypoints, image bounds), RGB-D depth, the feature grid, local-map search and motion-model search.  Each feature keeps its state in its own part of the handle
 // (jsorb_handle.h); run_pipeline and jsorb_destroy reach it through the *_after_extract / *_release functions here.
 #include "jsorb_handle.h"
 
@@ -21,6 +21,7 @@ void rgbd_release(jsorb_extractor *e) { free_device(e->rgbd.out); free_pinned(e-
 
 void grid_release(jsorb_extractor *e) { free_device(e->grid.start, e->grid.items); }
 void search_local_release(jsorb_extractor *e) { free_device(e->sl.cand, e->sl.stats, e->sl.out); }
+void search_last_release(jsorb_extractor *e) { free_device(e->lf.ws, e->lf.pts, e->lf.out); }
 
 } // namespace jsorb_host
 
@@ -385,6 +386,106 @@ int jsorb_search_local_stats(jsorb_extractor *e, int *rounds, int *n_candidates,
     if (rounds) *rounds = s[0];
     if (n_candidates) *n_candidates = s[1];
     if (n_overflow) *n_overflow = s[2];
+    return JSORB_OK;
+}
+
+// ---- motion-model matching: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cpp:1647-1963), k_search_last.hip ----
+#define LF_CTL 8                   // control and statistics words behind the owner array: run the second pass, passes, candidates, ind1..3
+int jsorb_search_last_frame_async(jsorb_extractor *e, int image, const jsorb_last_frame_params *params, int n_points, const float *Px, const float *Py,
+                                  const float *Pz, const int32_t *last_octave, const float *last_angle, const uint8_t *mp_descriptors,
+                                  const float *u_right, int32_t *match_kp, int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!check_image(e, image)) { e->err = "search_last_frame: no extract result for this image"; return JSORB_ERR_STATE; }
+    if (!params || !n_matches_dev) { e->err = "search_last_frame: NULL params or n_matches"; return JSORB_ERR_INVALID; }
+    const jsorb_last_frame_params &p = *params;
+    if (p.cols < 1 || p.rows < 1 || (long long)p.cols * p.rows > 16384) { e->err = "search_last_frame: grid size out of range (cols*rows <= 16384)"; return JSORB_ERR_INVALID; }
+    if (p.direction < -1 || p.direction > 1) { e->err = "search_last_frame: direction must be -1, 0 or 1"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_last_frame: n_points < 0"; return JSORB_ERR_INVALID; }
+    const int n = jsorb_n_keypoints(e, image);
+    if (n >= (1 << 18)) { e->err = "search_last_frame: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
+    if (n_points > 0 && (!Px || !Py || !Pz || !last_octave || !last_angle || !mp_descriptors || !match_kp || !match_dist)) {
+        e->err = "search_last_frame: NULL point array or output";
+        return JSORB_ERR_INVALID;
+    }
+    if (n > 0 && !kp_match) { e->err = "search_last_frame: NULL kp_match"; return JSORB_ERR_INVALID; }
+    if ((uintptr_t)mp_descriptors % 16) { e->err = "search_last_frame: mp_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    RCCHK(grid_reserve(e, p.cols * p.rows));
+    if (!e->lf.ws) {                   // owner starts at -1; afterwards every k_last_resolve leaves it so
+        RCCHK(reserve_device(e, e->lf.ws, ((size_t)e->g.T + LF_CTL) * sizeof(int)));
+        HIPCHK(e, hipMemsetAsync(e->lf.ws, 0xff, ((size_t)e->g.T + LF_CTL) * sizeof(int), st));
+    }
+    RCCHK(reserve_device(e, e->lf.pts, (size_t)2 * std::max(n_points, 1) * sizeof(int), &e->lf.points, std::max(n_points, 1)));
+    RCCHK(wait_lanes(e, st, e));       // the frame (and its uRight) may come from the lanes of a batch
+    const float *xy_un = jsorb_keypoints_un_device(e, image);
+    TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
+                                                     e->grid.start, e->grid.items, st));
+    HIPCHK(e, hipGetLastError());
+    LastFrameArgs a{};
+    a.soa = jsorb_keypoints_device(e, image);
+    a.xy_un = xy_un;
+    a.desc = jsorb_descriptors_device(e, image);
+    a.u_right = u_right;
+    a.n_kp = n;
+    a.cell_start = e->grid.start;
+    a.cell_items = e->grid.items;
+    a.n_points = n_points;
+    a.Px = Px; a.Py = Py; a.Pz = Pz; a.angle = last_angle; a.octave = last_octave; a.mp_desc = mp_descriptors;
+    a.p = p;
+    a.n_levels = e->g.L;
+    for (int l = 0; l < e->g.L; l++) a.scale[l] = e->g.lv[l].scale;
+    a.owner = e->lf.ws;
+    a.ctl = e->lf.ws + e->g.T;
+    a.bin = e->lf.pts;
+    a.cand = e->lf.pts + e->lf.points;
+    a.match_kp = match_kp; a.match_dist = match_dist; a.kp_match = kp_match; a.n_matches = n_matches_dev;
+    // the second pass is enqueued whenever it may be needed; its kernels return at once when the first pass's count says so
+    for (int pass = 0; pass < (p.retry_below > 0 ? 2 : 1); pass++) {
+        TIMED(e, JSORB_K_LAST_MATCH, launch_last_match(a, pass, st));
+        HIPCHK(e, hipGetLastError());
+        TIMED(e, JSORB_K_LAST_RESOLVE, launch_last_resolve(a, pass, st));
+        HIPCHK(e, hipGetLastError());
+    }
+    e->lf.done = true;
+    return JSORB_OK;
+}
+
+int jsorb_search_last_frame(jsorb_extractor *e, int image, const jsorb_last_frame_params *params, int n_points, const float *Px, const float *Py,
+                            const float *Pz, const int32_t *last_octave, const float *last_angle, const uint8_t *mp_descriptors, const float *u_right,
+                            int32_t *kp_match_host, int *n_matches)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!n_matches) { e->err = "search_last_frame: NULL n_matches"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_last_frame: n_points < 0"; return JSORB_ERR_INVALID; }
+    if (!check_image(e, image)) { e->err = "search_last_frame: no extract result for this image"; return JSORB_ERR_STATE; }
+    const int N = jsorb_n_keypoints(e, image);
+    if (N > 0 && !kp_match_host) { e->err = "search_last_frame: NULL host output"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    const int pts = std::max(n_points, 1);
+    RCCHK(reserve_device(e, e->lf.out, ((size_t)2 * pts + e->g.T + 1) * sizeof(int32_t), &e->lf.out_points, pts));
+    int32_t *cnt = e->lf.out, *km = cnt + 1, *mk = km + e->g.T, *md = mk + e->lf.out_points;
+    RCCHK(jsorb_search_last_frame_async(e, image, params, n_points, Px, Py, Pz, last_octave, last_angle, mp_descriptors, u_right, mk, md, km, cnt));
+    std::vector<int32_t> h((size_t)N + 1);
+    HIPCHK(e, hipMemcpyAsync(h.data(), cnt, ((size_t)N + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));      // count and kp_match in one copy
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n_matches = h[0];
+    if (N > 0) memcpy(kp_match_host, h.data() + 1, (size_t)N * sizeof(int32_t));
+    return JSORB_OK;
+}
+
+int jsorb_search_last_frame_stats(jsorb_extractor *e, int *passes, int *n_candidates, int kept_bins[3])
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!e->lf.done) { e->err = "search_last_frame_stats before jsorb_search_last_frame"; return JSORB_ERR_STATE; }
+    int32_t s[LF_CTL] = {0};
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipMemcpyAsync(s, e->lf.ws + e->g.T, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (passes) *passes = s[1];
+    if (n_candidates) *n_candidates = s[2];
+    if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[3 + b];
     return JSORB_OK;
 }
 

@@ -1,6 +1,6 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
-// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map search).  include/jsorb.h only
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map and motion-model search).  include/jsorb.h only
 // forward-declares the handle, so its layout is free to change.
 #pragma once
 
@@ -228,13 +228,23 @@ struct jsorb_extractor {
         bool done = false;
     } sl;
 
+    // ---- motion-model matching (jsorb_frame.hip, jsorb_search_last_frame*): allocated on the first call, the per-point part grown with the points ----
+    struct {
+        int *ws = nullptr;                 // owner (T entries, -1 between calls: k_last_resolve resets what k_last_match set), then 8 control / statistics words
+        int *pts = nullptr;                // points x 2: rotation bin, then candidates
+        int points = 0;
+        int32_t *out = nullptr;            // synchronous call: count, kp_match (T), match_kp, match_dist (out_points each)
+        int out_points = 0;
+        bool done = false;
+    } lf;
+
     // ---- per-kernel timing (jsorb_api.hip) ----
     struct TimedLaunch { int id; hipEvent_t a, b; };
     struct {
         bool on = false;
         std::vector<TimedLaunch> timed;
-        double k_ms[JSORB_K_ID_END] = {0};
-        long k_n[JSORB_K_ID_END] = {0};
+        double k_ms[JSORB_K_ID_COUNT] = {0};
+        long k_n[JSORB_K_ID_COUNT] = {0};
     } tm;
 
     // ---- JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy ----
@@ -378,6 +388,7 @@ void rgbd_invalidate(jsorb_extractor *e);
 void rgbd_release(jsorb_extractor *e);
 void grid_release(jsorb_extractor *e);
 void search_local_release(jsorb_extractor *e);
+void search_last_release(jsorb_extractor *e);
 
 } // namespace jsorb_host
 

@@ -125,6 +125,31 @@ struct SearchLocalArgs {
 int search_local_cap();
 void launch_local_candidates(const SearchLocalArgs &a, hipStream_t s);
 void launch_local_resolve(const SearchLocalArgs &a, hipStream_t s);
+// k_last_match / k_last_resolve (k_search_last.hip): ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), its GPU branch, over one image
+struct LastFrameArgs {
+    // the current frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, mvuRight (NULL: monocular), grid CSR
+    const int32_t *soa;
+    const float *xy_un;
+    const uint8_t *desc;
+    const float *u_right;
+    int n_kp;
+    const int32_t *cell_start, *cell_items;
+    // the last frame's points, in ascending last-frame index
+    int n_points;
+    const float *Px, *Py, *Pz, *angle;
+    const int32_t *octave;
+    const uint8_t *mp_desc;
+    jsorb_last_frame_params p;                   // threshold, direction, camera, bounds, grid, pose
+    int n_levels;
+    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
+    // workspace and outputs
+    int *owner;                                  // N: largest point index that chose keypoint k (-1 between calls: k_last_resolve resets it)
+    int *bin, *cand;                             // per point: rotation bin (-1: no match), candidates
+    int *ctl;                                    // run the second pass, passes, candidates, ind1, ind2, ind3
+    int32_t *match_kp, *match_dist, *kp_match, *n_matches;
+};
+void launch_last_match(const LastFrameArgs &a, int pass, hipStream_t s);
+void launch_last_resolve(const LastFrameArgs &a, int pass, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -14,6 +14,7 @@
 #include <climits>
 
 #include "jsorb_launch.h"
+#include "k_search_common.h"
 
 namespace jsorb {
 
@@ -26,10 +27,7 @@ namespace jsorb {
 
 int search_local_cap() { return SL_CAP; }
 
-// (int) of a float as x86 truncates it: out of range and NaN -> INT_MIN (the reference's cast is undefined there; this keeps the cell range in bounds)
-__device__ __forceinline__ int sl_to_int(float f) { return (f > -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN; }
-
-// the window of point i: GetFeaturesInArea(u, v, R, L-1, L)'s cell range with its early returns; false: no candidate at all
+// the window of point i: GetFeaturesInArea(u, v, R, L-1, L)'s cell range with its early returns (sl_cells); false: no candidate at all
 struct SlPoint {
     float x, y, R, xr;
     int L, x0, x1, y0, y1;
@@ -47,21 +45,7 @@ __device__ __forceinline__ bool sl_point(const SearchLocalArgs &a, int i, SlPoin
     p.y = a.v[i];
     const float m = a.mbf * a.invz[i];                // mTrackProjXR = u - mbf*invz (Tracking.cpp:1617), two roundings
     p.xr = p.x - m;
-    p.x0 = max(0, sl_to_int(floorf(((p.x - a.min_x) - p.R) * a.inv_w)));
-    if (p.x0 >= a.cols) return false;
-    p.x1 = min(a.cols - 1, sl_to_int(ceilf(((p.x - a.min_x) + p.R) * a.inv_w)));
-    if (p.x1 < 0) return false;
-    p.y0 = max(0, sl_to_int(floorf(((p.y - a.min_y) - p.R) * a.inv_h)));
-    if (p.y0 >= a.rows) return false;
-    p.y1 = min(a.rows - 1, sl_to_int(ceilf(((p.y - a.min_y) + p.R) * a.inv_h)));
-    if (p.y1 < 0) return false;
-    return true;
-}
-
-__device__ __forceinline__ void sl_load_desc(const uint8_t *d, uint4 &lo, uint4 &hi)
-{
-    lo = reinterpret_cast<const uint4 *>(d)[0];
-    hi = reinterpret_cast<const uint4 *>(d)[1];
+    return sl_cells(a, p.x, p.y, p.R, p.x0, p.x1, p.y0, p.y1);
 }
 
 // keypoint k as a candidate of the point: -1 if a filter drops it, else its packed entry
@@ -80,8 +64,7 @@ __device__ __forceinline__ int sl_candidate(const SearchLocalArgs &a, const SlPo
     }
     uint4 lo, hi;
     sl_load_desc(a.desc + 32 * (size_t)k, lo, hi);
-    const int d = __popc(lo.x ^ mlo.x) + __popc(lo.y ^ mlo.y) + __popc(lo.z ^ mlo.z) + __popc(lo.w ^ mlo.w) + __popc(hi.x ^ mhi.x) +
-                  __popc(hi.y ^ mhi.y) + __popc(hi.z ^ mhi.z) + __popc(hi.w ^ mhi.w);
+    const int d = SL_HAMMING(lo, hi, mlo, mhi);
     return SL_PACK(k, oct, d);
 }
 

@@ -29,6 +29,8 @@ K_UNDISTORT = 9     # JSORB_K_UNDISTORT (jsorb_set_camera)
 K_RGBD = 10         # JSORB_K_RGBD (jsorb_rgbd_depth*)
 # jsorb_search_local_points*: ids after JSORB_K_COUNT_ALL (11, which names no kernel)
 K_ASSIGN_GRID, K_LOCAL_CANDIDATES, K_LOCAL_RESOLVE = 12, 13, 14
+# jsorb_search_last_frame*: ids from JSORB_K_ID_END (15) on; the grid is K_ASSIGN_GRID again
+K_LAST_MATCH, K_LAST_RESOLVE = 15, 16
 DEPTH_F32, DEPTH_U16 = 0, 1      # JSORB_DEPTH_F32 / JSORB_DEPTH_U16
 
 EXPORTS = [
@@ -49,6 +51,7 @@ EXPORTS = [
     "jsorb_set_camera", "jsorb_camera_enabled", "jsorb_image_bounds", "jsorb_keypoints_un_device", "jsorb_copy_keypoints_un", "jsorb_unpack_frame_un",
     "jsorb_rgbd_depth", "jsorb_rgbd_depth_batch_device_async", "jsorb_rgbd_uright_device", "jsorb_rgbd_depth_device", "jsorb_copy_rgbd",
     "jsorb_search_local_points_async", "jsorb_search_local_points", "jsorb_search_local_stats", "jsorb_plan_forms", "jsorb_handle_forms",
+    "jsorb_search_last_frame_async", "jsorb_search_last_frame", "jsorb_search_last_frame_stats",
 ]
 
 
@@ -75,6 +78,23 @@ class JsorbCamera(C.Structure):
 class JsorbSearchParams(C.Structure):
     _fields_ = [("th", C.c_float), ("nn_ratio", C.c_float), ("th_high", C.c_int), ("mbf", C.c_float), ("min_x", C.c_float), ("min_y", C.c_float),
                 ("inv_w", C.c_float), ("inv_h", C.c_float), ("cols", C.c_int), ("rows", C.c_int)]
+
+
+class JsorbLastFrameParams(C.Structure):
+    _fields_ = [("th", C.c_float), ("th_high", C.c_int), ("check_orientation", C.c_int), ("direction", C.c_int), ("retry_below", C.c_int)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")] + \
+               [("cols", C.c_int), ("rows", C.c_int), ("mbf", C.c_float), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3)]
+
+
+def make_last_frame_params(Rcw, tcw, camera, bounds, grid, th=7.0, direction=0, mbf=0.0, check_orientation=True, retry_below=20, th_high=TH_HIGH,
+                           cols=64, rows=48):
+    """jsorb_last_frame_params: Rcw (3x3) and tcw (3) of CurrentFrame.mTcw as float32, camera = (fx, fy, cx, cy), bounds = (mnMinX, mnMaxX, mnMinY,
+    mnMaxY), grid = (mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows"""
+    R = np.asarray(Rcw, np.float32).ravel()
+    t = np.asarray(tcw, np.float32).ravel()
+    assert R.size == 9 and t.size == 3
+    return JsorbLastFrameParams(th, th_high, int(check_orientation), direction, retry_below, *camera, *bounds, *grid, cols, rows, mbf,
+                                (C.c_float * 9)(*R.tolist()), (C.c_float * 3)(*t.tolist()))
 
 
 def make_camera(K, D):
@@ -186,6 +206,9 @@ def load_library(path=None):
         "jsorb_search_local_points_async": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 13),
         "jsorb_search_local_points": (I, [P, I, C.POINTER(JsorbSearchParams), I] + [P] * 9 + [P, C.POINTER(I)]),
         "jsorb_search_local_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+        "jsorb_search_last_frame_async": (I, [P, I, C.POINTER(JsorbLastFrameParams), I] + [P] * 11),
+        "jsorb_search_last_frame": (I, [P, I, C.POINTER(JsorbLastFrameParams), I] + [P] * 7 + [P, C.POINTER(I)]),
+        "jsorb_search_last_frame_stats": (I, [P, C.POINTER(I), C.POINTER(I), P]),
         "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
         "jsorb_handle_forms": (I, [P, P, I]),
     }
@@ -659,6 +682,58 @@ class ORBExtractor:
         """{kernel: (total_ms, launches)} of the grid, candidate and resolve kernels, measured like kernel_times()"""
         return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_local_candidates", K_LOCAL_CANDIDATES),
                                                            ("k_local_resolve", K_LOCAL_RESOLVE))}
+
+    # ---- motion-model matching: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cpp:1647-1963) on the device ----
+    def search_last_frame(self, Px, Py, Pz, last_octave, last_angle, mp_descriptors, params, u_right=None, image=0):
+        """TrackWithMotionModel's matching step (retry included) over image `image` of the last extract.  Device tensors: Px, Py, Pz, last_angle
+        float32[n]; last_octave int32[n]; mp_descriptors uint8[n, 32]; u_right float32[N] or None (monocular).  params: make_last_frame_params(...).
+        Returns (match_kp int32[n], match_dist int32[n], kp_match int32[N], n_matches int32[1]) as device tensors; the call waits for the current
+        torch stream before it starts and for its own work before it returns."""
+        import torch
+        n = int(Px.shape[0]) if Px.dim() == 1 else -1
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("search_last_frame: no extract result for image %d" % image)
+        if not isinstance(params, JsorbLastFrameParams):
+            raise JsorbError("search_last_frame: params must come from make_last_frame_params")
+
+        def chk(t, name, dtypes, shape):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("search_last_frame: %s must be a device tensor" % name)
+            if t.dtype not in dtypes:
+                raise JsorbError("search_last_frame: %s must be %s, not %s" % (name, " / ".join(str(d) for d in dtypes), t.dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("search_last_frame: %s must be a contiguous tensor of shape %s, not %s" % (name, shape, tuple(t.shape)))
+            return t.data_ptr()
+
+        if n < 0:
+            raise JsorbError("search_last_frame: Px must be one-dimensional")
+        f32, i32 = (torch.float32,), (torch.int32,)
+        ptrs = [chk(Px, "Px", f32, (n,)), chk(Py, "Py", f32, (n,)), chk(Pz, "Pz", f32, (n,)), chk(last_octave, "last_octave", i32, (n,)),
+                chk(last_angle, "last_angle", f32, (n,)), chk(mp_descriptors, "mp_descriptors", (torch.uint8,), (n, 32))]
+        if n and mp_descriptors.data_ptr() % 16:
+            raise JsorbError("search_last_frame: mp_descriptors must be 16-byte aligned")
+        ptrs.append(None if u_right is None else chk(u_right, "u_right", f32, (N,)))
+        dev = Px.device
+        match_kp = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        match_dist = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        kp_match = torch.full((max(N, 1),), -1, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_last_frame_async(self._h, image, C.byref(params), n, *ptrs, match_kp.data_ptr(), match_dist.data_ptr(),
+                                                          kp_match.data_ptr(), count.data_ptr()))
+        self.sync()
+        return match_kp[:n], match_dist[:n], kp_match[:N], count
+
+    def search_last_frame_stats(self):
+        """(passes, candidates, (ind1, ind2, ind3)) of the last search_last_frame: for the pass whose results stand"""
+        p, c, b = C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_last_frame_stats(self._h, C.byref(p), C.byref(c), b))
+        return p.value, c.value, tuple(b)
+
+    def search_last_frame_kernel_times(self):
+        """{kernel: (total_ms, launches)} of the grid, match and resolve kernels, measured like kernel_times()"""
+        return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_last_match", K_LAST_MATCH), ("k_last_resolve", K_LAST_RESOLVE))}
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
