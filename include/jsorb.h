@@ -271,7 +271,9 @@ int jsorb_project_points(void *hip_stream, int n_points, const float *Px, const 
 int jsorb_hamming_pairs(void *hip_stream, int n_pairs, const int *idx_left, const int *idx_right, const unsigned char *descriptor_left,
                         const unsigned char *descriptor_right, int *distance);
 /* tracking_cuda::compute_isInFrustum_GPU  include/cuda/tracking_gpu.hpp, src/cuda/tracking_isinfrustum.cu:19-160
- * (u, v, invz, predictedlevel, viewCos are written only where is_infrustum becomes 1, as in the reference) */
+ * (u, v, invz, predictedlevel, viewCos are written only where is_infrustum becomes 1, as in the reference).  predictedlevel =
+ * ceil(logf(MaxDistance / dist) / logScaleFactor), converted as the reference's device code does (saturating, NaN -> 0), clamped to
+ * [0, nScaleLevels - 1]: a ratio of +inf gives the last level.  JSORB_ERR_INVALID: n_points < 0, or a NULL array with n_points > 0. */
 int jsorb_is_in_frustum(void *hip_stream, int n_points, const float *Px, const float *Py, const float *Pz, const float *Pnx, const float *Pny,
                         const float *Pnz, const float *MaxDistance, const float *invariance_maxDistance, const float *invariance_minDistance,
                         const float *Rcw, const float *tcw, const float *Ow, float fx, float fy, float cx, float cy, int minX, int maxX, int minY,

@@ -8,6 +8,7 @@
 //                      -> k_assign_grid: CSR over cols x rows cells (cell (i, j) at i*rows + j like mGrid[i][j]), items of a cell in
 //                         ascending keypoint order (the reference's push_back order); with a camera the undistorted coordinates of k_undistort
 #include "jsorb_launch.h"
+#include "k_search_common.h"
 
 namespace jsorb {
 
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(1024) void k_assign_grid(const int32_t *__restrict_
     __syncthreads();
     auto cell_of = [&](int i) -> int {
         const float x = xy_un ? xy_un[i] : (float)soa[i], y = xy_un ? xy_un[n + i] : (float)soa[n + i];      // mvKeysUn (Frame.cpp:468)
-        const int px = (int)roundf((x - min_x) * inv_w), py = (int)roundf((y - min_y) * inv_h);      // PosInGrid
+        const int px = sl_to_int(roundf((x - min_x) * inv_w)), py = sl_to_int(roundf((y - min_y) * inv_h));      // PosInGrid; NaN / beyond int: no cell
         if (px < 0 || px >= cols || py < 0 || py >= rows) return -1;
         return px * rows + py;
     };
