@@ -405,6 +405,68 @@ int jsorb_search_last_frame(jsorb_extractor *e, int image, const jsorb_last_fram
  * (the reference's to_be_matched_count) and ComputeThreeMaxima's ind1..3 (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
 int jsorb_search_last_frame_stats(jsorb_extractor *e, int *passes, int *n_candidates, int kept_bins[3]);
 
+/* ---- monocular initialisation matching: ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+ * (src/ORBmatcher.cpp:392-507) as Tracking::MonocularInitialization calls it on every frame until the map exists (src/Tracking.cpp:724-794:
+ * ORBmatcher matcher(0.9, true), windowSize 50) ----
+ * F2 is image `image` of the handle's last extract: N keypoints, mvKeysUn from k_undistort with an active camera, else the keypoints; its angle
+ * is keypoint SoA row 3 (float bits), its octave row 4.  F1 is given by the caller, one entry per F1 keypoint i1 = 0 .. n1-1: f1_octave int32,
+ * f1_angle float (mvKeysUn[].angle), f1_descriptors n1 x 32 bytes (16-byte aligned), prev_matched float x[n1] then y[n1] (vbPrevMatched, read
+ * and written).  matched_distance[k] = INT_MAX, matches21[k] = -1 per F2 keypoint, matches12[i1] = -1, nmatches = 0; then for i1 in order:
+ *   skip i1 when f1_octave[i1] > 0.  A NEGATIVE octave is not skipped (the reference skips only > 0) and, as in the reference's
+ *     GetFeaturesInArea(x, y, r, level1, level1) with level1 < 0, switches the level check off: keypoints of every F2 octave qualify
+ *   candidates = GetFeaturesInArea(prev_x[i1], prev_y[i1], window, 0, 0) (src/Frame.cpp:641-694): cells, early returns and walk order exactly as
+ *     jsorb_search_local_points (ix outer, iy inner, a cell's keypoints ascending) over the grid min_x, min_y, inv_w, inv_h, cols x rows; kept
+ *     when its octave is 0 and |x_un - x| < window && |y_un - y| < window.  No candidate: next point
+ *   dist = popcount Hamming distance of the two descriptors; a candidate with matched_distance[k] <= dist is skipped
+ *   over the rest, in walk order: if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = k; } else if (dist < bestDist2)
+ *     bestDist2 = dist; from INT_MAX both - bestDist and bestDist2 are the two smallest of the multiset (a tie with the best lowers the second),
+ *     bestIdx2 the first in walk order with the minimum
+ *   claim iff bestDist <= th_low (TH_LOW = 50) && (float)bestDist < (float)bestDist2 * nn_ratio (a float product; bestDist2 = INT_MAX without a
+ *     second candidate).  On a claim of k = bestIdx2: when matches21[k] >= 0 that earlier point loses it (matches12[matches21[k]] = -1,
+ *     nmatches--); then matches12[i1] = k, matches21[k] = i1, matched_distance[k] = bestDist, nmatches++; with check_orientation i1 is pushed
+ *     into the bin of rot = f1_angle[i1] - angle2[k] (+ 360.0f when negative; bin = (int)roundf(rot * (1.0f/30)), 30 -> 0: the arithmetic of
+ *     jsorb_search_last_frame; a bin outside [0, 30) is never kept)
+ * then, with check_orientation, ComputeThreeMaxima (:2097-2138, as for jsorb_search_last_frame) over the bins' sizes - a displaced point still
+ * sits in its bin - and for every entry i1 of every other bin: if matches12[i1] >= 0 it becomes -1 and nmatches--.  Last (:501-504): for every
+ * i1 with matches12[i1] >= 0, prev_matched[i1] = F2's mvKeysUn[matches12[i1]].
+ * All pointers are DEVICE pointers.  Outputs: matches12[n1]; matches21[N] (may be NULL) = the LAST claimant of each F2 keypoint or -1, as the
+ * reference's vnMatches21 stands at its return: it is not touched by the orientation culling, so matches21[k] = i1 does not imply
+ * matches12[i1] = k; *n_matches_dev = the reference's return value; prev_matched updated in place.
+ * Enqueued on the handle's stream behind the last extract (and the lanes of a batch), no host decision, no allocation after the first call of a
+ * size: the grid (k_assign_grid, into the handle's grid buffers), k_init_candidates, k_init_resolve.  cols * rows <= 16384, N < 262144.
+ * n1 == 0 or N == 0: no match, prev_matched untouched. */
+typedef struct jsorb_init_params {
+    float window;                    /* windowSize: np_min = 50 (Tracking.cpp:762) */
+    float nn_ratio;                  /* ORBmatcher(0.9, true) */
+    int th_low;                      /* ORBmatcher::TH_LOW = 50 */
+    int check_orientation;           /* 1 */
+    float min_x, min_y, inv_w, inv_h; /* Frame::mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv of F2 */
+    int cols, rows;                  /* FRAME_GRID_COLS, FRAME_GRID_ROWS */
+} jsorb_init_params;
+int jsorb_search_for_initialization_async(jsorb_extractor *e, int image, const jsorb_init_params *params, int n1, const int32_t *f1_octave,
+                                          const float *f1_angle, const uint8_t *f1_descriptors, float *prev_matched, int32_t *matches12,
+                                          int32_t *matches21, int32_t *n_matches_dev);
+/* Synchronous: the same with matches12 in a buffer of the handle; matches12_host[n1] and prev_matched_host[2 n1] (host, either may be NULL)
+ * receive matches12 and the updated prev_matched, *n_matches the count, with one synchronisation.  prev_matched stays a device pointer. */
+int jsorb_search_for_initialization(jsorb_extractor *e, int image, const jsorb_init_params *params, int n1, const int32_t *f1_octave,
+                                    const float *f1_angle, const uint8_t *f1_descriptors, float *prev_matched, int32_t *matches12_host,
+                                    float *prev_matched_host, int *n_matches);
+/* Diagnostics of the last call (waits for it): fixed-point rounds of k_init_resolve summed over its chunks, candidates over all points, points
+ * whose candidates overflowed the per-point list (rescanned from the grid), claims that took a keypoint from an earlier point, and
+ * ComputeThreeMaxima's ind1..3 (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
+int jsorb_search_for_initialization_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow, int *n_displaced, int kept_bins[3]);
+/* Keeping the initial frame (Tracking's mInitialFrame lives for many frames, the handle's results only until the next extract):
+ * jsorb_init_reference_set copies image `image`'s octave row, angle row, descriptors and mvKeysUn into buffers of the handle (device to
+ * device, on the handle's stream; grown on demand, freed in jsorb_destroy) and sets the stored prev_matched to mvKeysUn (Tracking.cpp:735-737).
+ * jsorb_init_reference_clear drops the copy (the buffers stay), jsorb_init_reference_n returns its keypoint count (-1: none).
+ * jsorb_search_initial_frame runs jsorb_search_for_initialization_async with the stored arrays as F1 against image `image` of the last
+ * extract - the stored prev_matched is consumed and updated - and returns matches12_host[n], prev_matched_host[2 n] (may be NULL) and the count. */
+int jsorb_init_reference_set(jsorb_extractor *e, int image);
+int jsorb_init_reference_clear(jsorb_extractor *e);
+int jsorb_init_reference_n(const jsorb_extractor *e);
+int jsorb_search_initial_frame(jsorb_extractor *e, int image, const jsorb_init_params *params, int32_t *matches12_host, float *prev_matched_host,
+                               int *n_matches);
+
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates
  * pinned-host + device buffer pairs and moves data with cudaMemcpy(Async) on a private stream; these calls are the HIP side of

@@ -649,6 +649,33 @@ inline int SearchLastFrame(ORBExtractor &ex, const jsorb_last_frame_params &para
     return n_matches;
 }
 
+// MonocularInitialization's matcher.SearchForInitialization(mInitialFrame, mCurrentFrame, mvbPrevMatched, mvIniMatches, windowSize)
+// (Tracking.cpp:724-794, ORBmatcher.cpp:392-507) on the device.  KeepInitialFrame right after the extract that becomes mInitialFrame (where the
+// reference fills mvbPrevMatched from mvKeysUn, Tracking.cpp:735-737): the extractor keeps that frame's octaves, angles, descriptors and
+// mvbPrevMatched on the device across the following extracts.  SearchForInitialization after every later extract: returns nmatches, vnMatches12[i1]
+// = keypoint of the current frame matched to keypoint i1 of the initial frame or -1, and (when asked for) the updated mvbPrevMatched as x[n1]
+// then y[n1].  DropInitialFrame where the reference deletes mpInitializer.
+inline int KeepInitialFrame(ORBExtractor &ex)
+{
+    if (jsorb_init_reference_set(ex.handle(), 0) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_init_reference_set: ") + jsorb_last_error(ex.handle()));
+    return jsorb_init_reference_n(ex.handle());
+}
+inline void DropInitialFrame(ORBExtractor &ex) { jsorb_init_reference_clear(ex.handle()); }
+inline int SearchForInitialization(ORBExtractor &ex, const jsorb_init_params &params, std::vector<int> &vnMatches12,
+                                   std::vector<float> *vbPrevMatched = nullptr)
+{
+    const int n1 = jsorb_init_reference_n(ex.handle());
+    vnMatches12.assign(n1 > 0 ? n1 : 1, -1);
+    if (vbPrevMatched) vbPrevMatched->assign(n1 > 0 ? 2 * (std::size_t)n1 : 1, 0.0f);
+    int n_matches = 0;
+    if (jsorb_search_initial_frame(ex.handle(), 0, &params, vnMatches12.data(), vbPrevMatched ? vbPrevMatched->data() : nullptr, &n_matches) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_initial_frame: ") + jsorb_last_error(ex.handle()));
+    vnMatches12.resize(n1 > 0 ? n1 : 0);
+    if (vbPrevMatched) vbPrevMatched->resize(n1 > 0 ? 2 * (std::size_t)n1 : 0);
+    return n_matches;
+}
+
 // Rectification on the device instead of the host cv::remap of the reference's stereo driver (Examples/Stereo/stereo_euroc.cpp:106-107 build
 // M1l/M2l, M1r/M2r with cv::initUndistortRectifyMap; :145-146 remap both images of every frame with INTER_LINEAR): set the maps ONCE per
 // extractor, then hand every extract() the raw camera image.  Maps of the extractor's image size, rows dense (width floats apart).

@@ -635,6 +635,7 @@ void jsorb_destroy(jsorb_extractor *e)
     grid_release(e);
     search_local_release(e);
     search_last_release(e);
+    search_init_release(e);
     core_release(e);
     arena_release(e->det_spill);
     if (e->own_stream) { (void)hipStreamSynchronize(e->own_stream); pool_return_main_stream(e->device, e->own_stream); }

@@ -1,5 +1,5 @@
 // jsorb_frame.hip - host side of the Frame- and Tracking-side features around an extract: rectification maps, the camera (undistorted
-// keypoints, image bounds), RGB-D depth, the feature grid, local-map search and motion-model search.  Each feature keeps its state in its own part of the handle
+// keypoints, image bounds), RGB-D depth, the feature grid, local-map search, motion-model search and monocular-initialisation search.  Each feature keeps its state in its own part of the handle
 // (jsorb_handle.h); run_pipeline and jsorb_destroy reach it through the *_after_extract / *_release functions here.
 #include "jsorb_handle.h"
 
@@ -22,6 +22,7 @@ void rgbd_release(jsorb_extractor *e) { free_device(e->rgbd.out); free_pinned(e-
 void grid_release(jsorb_extractor *e) { free_device(e->grid.start, e->grid.items); }
 void search_local_release(jsorb_extractor *e) { free_device(e->sl.cand, e->sl.stats, e->sl.out); }
 void search_last_release(jsorb_extractor *e) { free_device(e->lf.ws, e->lf.pts, e->lf.out); }
+void search_init_release(jsorb_extractor *e) { free_device(e->si.cand, e->si.ws, e->si.out, e->si.ref); }
 
 } // namespace jsorb_host
 
@@ -487,6 +488,154 @@ int jsorb_search_last_frame_stats(jsorb_extractor *e, int *passes, int *n_candid
     if (n_candidates) *n_candidates = s[2];
     if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[3 + b];
     return JSORB_OK;
+}
+
+// ---- monocular initialisation matching: ORBmatcher::SearchForInitialization (ORBmatcher.cpp:392-507), k_search_init.hip ----
+#define SI_STATS 8                 // statistics words behind state and owner: rounds, candidates, overflowed points, displaced claims, ind1..3
+int jsorb_search_for_initialization_async(jsorb_extractor *e, int image, const jsorb_init_params *params, int n1, const int32_t *f1_octave,
+                                          const float *f1_angle, const uint8_t *f1_descriptors, float *prev_matched, int32_t *matches12,
+                                          int32_t *matches21, int32_t *n_matches_dev)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!check_image(e, image)) { e->err = "search_for_initialization: no extract result for this image"; return JSORB_ERR_STATE; }
+    if (!params || !n_matches_dev) { e->err = "search_for_initialization: NULL params or n_matches"; return JSORB_ERR_INVALID; }
+    const jsorb_init_params &p = *params;
+    if (p.cols < 1 || p.rows < 1 || (long long)p.cols * p.rows > 16384) { e->err = "search_for_initialization: grid size out of range (cols*rows <= 16384)"; return JSORB_ERR_INVALID; }
+    if (n1 < 0) { e->err = "search_for_initialization: n1 < 0"; return JSORB_ERR_INVALID; }
+    const int n = jsorb_n_keypoints(e, image);
+    if (n >= (1 << 18)) { e->err = "search_for_initialization: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
+    if (n1 > 0 && (!f1_octave || !f1_angle || !f1_descriptors || !prev_matched || !matches12)) {
+        e->err = "search_for_initialization: NULL F1 array or output";
+        return JSORB_ERR_INVALID;
+    }
+    if ((uintptr_t)f1_descriptors % 16) { e->err = "search_for_initialization: f1_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    const int cap = search_init_cap(), pts = std::max(n1, 1);
+    const size_t T = (size_t)e->g.T;
+    RCCHK(grid_reserve(e, p.cols * p.rows));
+    RCCHK(reserve_device(e, e->si.cand, (size_t)pts * (cap + 2) * sizeof(int), &e->si.points, pts));
+    RCCHK(reserve_device(e, e->si.ws, (2 * T + SI_STATS) * sizeof(int)));
+    hipStream_t st = e->stream;
+    RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
+    const float *xy_un = jsorb_keypoints_un_device(e, image);
+    TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
+                                                     e->grid.start, e->grid.items, st));
+    HIPCHK(e, hipGetLastError());
+    SearchInitArgs a{};
+    a.soa = jsorb_keypoints_device(e, image);
+    a.xy_un = xy_un;
+    a.desc = jsorb_descriptors_device(e, image);
+    a.n_kp = n;
+    a.cell_start = e->grid.start;
+    a.cell_items = e->grid.items;
+    a.p = p;
+    a.n1 = n1;
+    a.octave = f1_octave; a.angle = f1_angle; a.f1_desc = f1_descriptors; a.prev = prev_matched;
+    a.cand = e->si.cand;
+    a.cand_n = e->si.cand + (size_t)e->si.points * cap;
+    a.order = a.cand_n + e->si.points;
+    a.state = e->si.ws;
+    a.owner = e->si.ws + T;
+    a.stats = e->si.ws + 2 * T;
+    a.matches12 = matches12; a.matches21 = matches21; a.n_matches = n_matches_dev;
+    launch_init_candidates(a, st);
+    HIPCHK(e, hipGetLastError());
+    launch_init_resolve(a, st);
+    HIPCHK(e, hipGetLastError());
+    e->si.done = true;
+    return JSORB_OK;
+}
+
+// the synchronous forms' common end: matches12 in the handle's buffer, the count in front of it
+static int search_init_sync(jsorb_extractor *e, int image, const jsorb_init_params *params, int n1, const int32_t *f1_octave, const float *f1_angle,
+                            const uint8_t *f1_descriptors, float *prev_matched, int32_t *matches12_host, float *prev_matched_host, int *n_matches)
+{
+    HIPCHK(e, hipSetDevice(e->device));
+    const int pts = std::max(n1, 1);
+    RCCHK(reserve_device(e, e->si.out, ((size_t)pts + 1) * sizeof(int32_t), &e->si.out_points, pts));
+    int32_t *cnt = e->si.out, *m12 = cnt + 1;
+    RCCHK(jsorb_search_for_initialization_async(e, image, params, n1, f1_octave, f1_angle, f1_descriptors, prev_matched, m12, nullptr, cnt));
+    int32_t count = 0;
+    HIPCHK(e, hipMemcpyAsync(&count, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (n1 > 0 && matches12_host) HIPCHK(e, hipMemcpyAsync(matches12_host, m12, (size_t)n1 * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (n1 > 0 && prev_matched_host) HIPCHK(e, hipMemcpyAsync(prev_matched_host, prev_matched, (size_t)2 * n1 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n_matches = count;
+    return JSORB_OK;
+}
+
+int jsorb_search_for_initialization(jsorb_extractor *e, int image, const jsorb_init_params *params, int n1, const int32_t *f1_octave,
+                                    const float *f1_angle, const uint8_t *f1_descriptors, float *prev_matched, int32_t *matches12_host,
+                                    float *prev_matched_host, int *n_matches)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!n_matches) { e->err = "search_for_initialization: NULL n_matches"; return JSORB_ERR_INVALID; }
+    if (n1 < 0) { e->err = "search_for_initialization: n1 < 0"; return JSORB_ERR_INVALID; }
+    return search_init_sync(e, image, params, n1, f1_octave, f1_angle, f1_descriptors, prev_matched, matches12_host, prev_matched_host, n_matches);
+}
+
+int jsorb_search_for_initialization_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow, int *n_displaced, int kept_bins[3])
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!e->si.done) { e->err = "search_for_initialization_stats before jsorb_search_for_initialization"; return JSORB_ERR_STATE; }
+    int32_t s[SI_STATS] = {0};
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipMemcpyAsync(s, e->si.ws + 2 * (size_t)e->g.T, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (rounds) *rounds = s[0];
+    if (n_candidates) *n_candidates = s[1];
+    if (n_overflow) *n_overflow = s[2];
+    if (n_displaced) *n_displaced = s[3];
+    if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[4 + b];
+    return JSORB_OK;
+}
+
+// the kept initial frame: ref_cap entries each of descriptors, octave, angle and prev_matched x, y in one allocation
+static uint8_t *ref_desc(const jsorb_extractor *e) { return e->si.ref; }
+static int32_t *ref_octave(const jsorb_extractor *e) { return reinterpret_cast<int32_t *>(e->si.ref + (size_t)32 * e->si.ref_cap); }
+static float *ref_angle(const jsorb_extractor *e) { return reinterpret_cast<float *>(e->si.ref + (size_t)36 * e->si.ref_cap); }
+static float *ref_prev(const jsorb_extractor *e) { return reinterpret_cast<float *>(e->si.ref + (size_t)40 * e->si.ref_cap); }
+
+int jsorb_init_reference_set(jsorb_extractor *e, int image)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!check_image(e, image)) { e->err = "init_reference_set: no extract result for this image"; return JSORB_ERR_STATE; }
+    const int n = jsorb_n_keypoints(e, image), cap = round_up(std::max(n, 1), 64);
+    HIPCHK(e, hipSetDevice(e->device));
+    e->si.ref_n = -1;
+    RCCHK(reserve_device(e, e->si.ref, (size_t)48 * cap, &e->si.ref_cap, cap));
+    hipStream_t st = e->stream;
+    RCCHK(wait_lanes(e, st, e));
+    if (n > 0) {
+        const int32_t *soa = jsorb_keypoints_device(e, image);
+        HIPCHK(e, hipMemcpyAsync(ref_desc(e), jsorb_descriptors_device(e, image), (size_t)32 * n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(ref_octave(e), soa + 4 * (size_t)n, (size_t)4 * n, hipMemcpyDeviceToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(ref_angle(e), soa + 3 * (size_t)n, (size_t)4 * n, hipMemcpyDeviceToDevice, st));
+        launch_init_keys_un(soa, jsorb_keypoints_un_device(e, image), n, ref_prev(e), st);      // vbPrevMatched[i] = mvKeysUn[i].pt
+        HIPCHK(e, hipGetLastError());
+    }
+    e->si.ref_n = n;
+    return JSORB_OK;
+}
+
+int jsorb_init_reference_clear(jsorb_extractor *e)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    e->si.ref_n = -1;
+    return JSORB_OK;
+}
+
+int jsorb_init_reference_n(const jsorb_extractor *e) { return e ? e->si.ref_n : JSORB_ERR_INVALID; }
+
+int jsorb_search_initial_frame(jsorb_extractor *e, int image, const jsorb_init_params *params, int32_t *matches12_host, float *prev_matched_host,
+                               int *n_matches)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!n_matches) { e->err = "search_initial_frame: NULL n_matches"; return JSORB_ERR_INVALID; }
+    if (e->si.ref_n < 0) { e->err = "search_initial_frame: no initial frame kept (jsorb_init_reference_set)"; return JSORB_ERR_STATE; }
+    const int n1 = e->si.ref_n;
+    // prev_matched is x[n1] y[n1] at pitch n1 for the kernels: the stored one is kept at that pitch (jsorb_init_reference_set wrote 2 n1 floats)
+    return search_init_sync(e, image, params, n1, ref_octave(e), ref_angle(e), ref_desc(e), ref_prev(e), matches12_host, prev_matched_host, n_matches);
 }
 
 } // extern "C"

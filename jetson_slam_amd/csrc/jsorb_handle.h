@@ -1,6 +1,6 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
-// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map and motion-model search).  include/jsorb.h only
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map, motion-model and initialisation search).  include/jsorb.h only
 // forward-declares the handle, so its layout is free to change.
 #pragma once
 
@@ -238,6 +238,18 @@ struct jsorb_extractor {
         bool done = false;
     } lf;
 
+    // ---- monocular initialisation matching (jsorb_frame.hip, jsorb_search_for_initialization*, jsorb_init_reference_*): allocated on first use, grown only ----
+    struct {
+        int *cand = nullptr;               // points x search_init_cap() packed candidates, then points counts, then points ordered indices
+        int points = 0;
+        int *ws = nullptr;                 // state (T entries, when it does not fit k_init_resolve's LDS), owner (T), then 8 statistics words
+        int32_t *out = nullptr;            // synchronous calls: count, matches12 (out_points)
+        int out_points = 0;
+        bool done = false;
+        uint8_t *ref = nullptr;            // the kept initial frame, ref_cap entries each: descriptors (32 B), octave, angle, prev_matched x, y
+        int ref_cap = 0, ref_n = -1;       // ref_n: its keypoints (-1: none kept)
+    } si;
+
     // ---- per-kernel timing (jsorb_api.hip) ----
     struct TimedLaunch { int id; hipEvent_t a, b; };
     struct {
@@ -389,6 +401,7 @@ void rgbd_release(jsorb_extractor *e);
 void grid_release(jsorb_extractor *e);
 void search_local_release(jsorb_extractor *e);
 void search_last_release(jsorb_extractor *e);
+void search_init_release(jsorb_extractor *e);
 
 } // namespace jsorb_host
 

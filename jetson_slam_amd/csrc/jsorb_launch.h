@@ -150,6 +150,34 @@ struct LastFrameArgs {
 };
 void launch_last_match(const LastFrameArgs &a, int pass, hipStream_t s);
 void launch_last_resolve(const LastFrameArgs &a, int pass, hipStream_t s);
+// k_init_candidates / k_init_resolve (k_search_init.hip): ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+struct SearchInitArgs {
+    // F2: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, grid CSR
+    const int32_t *soa;
+    const float *xy_un;
+    const uint8_t *desc;
+    int n_kp;
+    const int32_t *cell_start, *cell_items;
+    jsorb_init_params p;                         // window, ratio, threshold, grid
+    // F1, in keypoint order
+    int n1;
+    const int32_t *octave;
+    const float *angle;
+    const uint8_t *f1_desc;
+    float *prev;                                 // vbPrevMatched: x[n1] y[n1], read by k_init_candidates, updated by k_init_resolve
+    // workspace
+    int *cand, *cand_n;                          // n1 x search_init_cap() packed candidates in walk order, n1 counts
+    int *order;                                  // n1: the points with candidates, ascending
+    int *state;                                  // N: matched_distance << 8 | chunk mark, when it does not fit the LDS
+    int *owner;                                  // N: last claimant (vnMatches21)
+    int *stats;                                  // rounds, candidates, points over the capacity, displaced claims, ind1, ind2, ind3
+    // outputs
+    int32_t *matches12, *matches21, *n_matches;  // matches21 may be NULL
+};
+int search_init_cap();
+void launch_init_candidates(const SearchInitArgs &a, hipStream_t s);
+void launch_init_resolve(const SearchInitArgs &a, hipStream_t s);
+void launch_init_keys_un(const int32_t *soa, const float *xy_un, int n, float *dst, hipStream_t s);      // mvKeysUn points: x[n] y[n]
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -52,6 +52,8 @@ EXPORTS = [
     "jsorb_rgbd_depth", "jsorb_rgbd_depth_batch_device_async", "jsorb_rgbd_uright_device", "jsorb_rgbd_depth_device", "jsorb_copy_rgbd",
     "jsorb_search_local_points_async", "jsorb_search_local_points", "jsorb_search_local_stats", "jsorb_plan_forms", "jsorb_handle_forms",
     "jsorb_search_last_frame_async", "jsorb_search_last_frame", "jsorb_search_last_frame_stats",
+    "jsorb_search_for_initialization_async", "jsorb_search_for_initialization", "jsorb_search_for_initialization_stats",
+    "jsorb_init_reference_set", "jsorb_init_reference_clear", "jsorb_init_reference_n", "jsorb_search_initial_frame",
 ]
 
 
@@ -95,6 +97,17 @@ def make_last_frame_params(Rcw, tcw, camera, bounds, grid, th=7.0, direction=0, 
     assert R.size == 9 and t.size == 3
     return JsorbLastFrameParams(th, th_high, int(check_orientation), direction, retry_below, *camera, *bounds, *grid, cols, rows, mbf,
                                 (C.c_float * 9)(*R.tolist()), (C.c_float * 3)(*t.tolist()))
+
+
+class JsorbInitParams(C.Structure):
+    _fields_ = [("window", C.c_float), ("nn_ratio", C.c_float), ("th_low", C.c_int), ("check_orientation", C.c_int), ("min_x", C.c_float),
+                ("min_y", C.c_float), ("inv_w", C.c_float), ("inv_h", C.c_float), ("cols", C.c_int), ("rows", C.c_int)]
+
+
+def make_init_params(grid, window=50.0, nn_ratio=0.9, th_low=TH_LOW, check_orientation=True, cols=64, rows=48):
+    """jsorb_init_params of MonocularInitialization's ORBmatcher(0.9, true) and windowSize 50: grid = (mnMinX, mnMinY, mfGridElementWidthInv,
+    mfGridElementHeightInv) of the current frame over cols x rows"""
+    return JsorbInitParams(window, nn_ratio, th_low, int(check_orientation), grid[0], grid[1], grid[2], grid[3], cols, rows)
 
 
 def make_camera(K, D):
@@ -209,6 +222,13 @@ def load_library(path=None):
         "jsorb_search_last_frame_async": (I, [P, I, C.POINTER(JsorbLastFrameParams), I] + [P] * 11),
         "jsorb_search_last_frame": (I, [P, I, C.POINTER(JsorbLastFrameParams), I] + [P] * 7 + [P, C.POINTER(I)]),
         "jsorb_search_last_frame_stats": (I, [P, C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_search_for_initialization_async": (I, [P, I, C.POINTER(JsorbInitParams), I] + [P] * 7),
+        "jsorb_search_for_initialization": (I, [P, I, C.POINTER(JsorbInitParams), I] + [P] * 6 + [C.POINTER(I)]),
+        "jsorb_search_for_initialization_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_init_reference_set": (I, [P, I]),
+        "jsorb_init_reference_clear": (I, [P]),
+        "jsorb_init_reference_n": (I, [P]),
+        "jsorb_search_initial_frame": (I, [P, I, C.POINTER(JsorbInitParams), P, P, C.POINTER(I)]),
         "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
         "jsorb_handle_forms": (I, [P, P, I]),
     }
@@ -734,6 +754,77 @@ class ORBExtractor:
     def search_last_frame_kernel_times(self):
         """{kernel: (total_ms, launches)} of the grid, match and resolve kernels, measured like kernel_times()"""
         return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_last_match", K_LAST_MATCH), ("k_last_resolve", K_LAST_RESOLVE))}
+
+    # ---- monocular initialisation matching: ORBmatcher::SearchForInitialization (ORBmatcher.cpp:392-507) on the device ----
+    def search_for_initialization(self, f1_octave, f1_angle, f1_descriptors, prev_matched, params, image=0):
+        """MonocularInitialization's matching step: F1 as device tensors (f1_octave int32[n1], f1_angle float32[n1], f1_descriptors uint8[n1, 32],
+        prev_matched float32[2, n1]: x then y, UPDATED IN PLACE) against image `image` of the last extract.  params: make_init_params(...).
+        Returns (matches12 int32[n1], matches21 int32[N], n_matches int32[1]) as device tensors; the call waits for the current torch stream
+        before it starts and for its own work before it returns."""
+        import torch
+        n1 = int(f1_octave.shape[0]) if hasattr(f1_octave, "dim") and f1_octave.dim() == 1 else -1
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("search_for_initialization: no extract result for image %d" % image)
+        if not isinstance(params, JsorbInitParams):
+            raise JsorbError("search_for_initialization: params must come from make_init_params")
+        if n1 < 0:
+            raise JsorbError("search_for_initialization: f1_octave must be a one-dimensional device tensor")
+
+        def chk(t, name, dtype, shape):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("search_for_initialization: %s must be a device tensor" % name)
+            if t.dtype != dtype:
+                raise JsorbError("search_for_initialization: %s must be %s, not %s" % (name, dtype, t.dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("search_for_initialization: %s must be a contiguous tensor of shape %s, not %s" % (name, shape, tuple(t.shape)))
+            return t.data_ptr()
+
+        ptrs = [chk(f1_octave, "f1_octave", torch.int32, (n1,)), chk(f1_angle, "f1_angle", torch.float32, (n1,)),
+                chk(f1_descriptors, "f1_descriptors", torch.uint8, (n1, 32)), chk(prev_matched, "prev_matched", torch.float32, (2, n1))]
+        if n1 and f1_descriptors.data_ptr() % 16:
+            raise JsorbError("search_for_initialization: f1_descriptors must be 16-byte aligned")
+        dev = f1_octave.device
+        matches12 = torch.full((max(n1, 1),), -1, dtype=torch.int32, device=dev)
+        matches21 = torch.full((max(N, 1),), -1, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_for_initialization_async(self._h, image, C.byref(params), n1, *ptrs, matches12.data_ptr(),
+                                                                  matches21.data_ptr(), count.data_ptr()))
+        self.sync()
+        return matches12[:n1], matches21[:N], count
+
+    def search_for_initialization_stats(self):
+        """(fixed-point rounds over all chunks, candidates, points over the per-point list, displaced claims, (ind1, ind2, ind3)) of the last
+        search_for_initialization / search_initial_frame"""
+        r, c, o, d, b = C.c_int(), C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_for_initialization_stats(self._h, C.byref(r), C.byref(c), C.byref(o), C.byref(d), b))
+        return r.value, c.value, o.value, d.value, tuple(b)
+
+    def set_initial_frame(self, image=0):
+        """keep image `image` of the last extract as mInitialFrame on the device (octaves, angles, descriptors; prev_matched = mvKeysUn);
+        returns its keypoint count"""
+        self._chk(self._lib.jsorb_init_reference_set(self._h, image))
+        return self._lib.jsorb_init_reference_n(self._h)
+
+    def clear_initial_frame(self):
+        self._chk(self._lib.jsorb_init_reference_clear(self._h))
+
+    def initial_frame_n(self):
+        """keypoints of the kept initial frame, -1 when none is kept"""
+        return self._lib.jsorb_init_reference_n(self._h)
+
+    def search_initial_frame(self, params, image=0):
+        """the kept initial frame against image `image` of the last extract: (matches12 int32[n1], prev_matched float32[2, n1], n_matches) on the
+        host; the kept prev_matched is consumed and updated"""
+        if not isinstance(params, JsorbInitParams):
+            raise JsorbError("search_initial_frame: params must come from make_init_params")
+        n1 = max(self._lib.jsorb_init_reference_n(self._h), 0)
+        m12 = np.full(max(n1, 1), -1, np.int32)
+        prev = np.zeros((2, max(n1, 1)), np.float32)
+        cnt = C.c_int()
+        self._chk(self._lib.jsorb_search_initial_frame(self._h, image, C.byref(params), m12.ctypes.data, prev.ctypes.data, C.byref(cnt)))
+        return m12[:n1], prev.reshape(-1)[:2 * n1].reshape(2, n1), cnt.value
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
