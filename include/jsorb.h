@@ -70,6 +70,9 @@ enum { JSORB_K_UNDISTORT = JSORB_K_COUNT, JSORB_K_RGBD, JSORB_K_COUNT_ALL };
 enum { JSORB_K_ASSIGN_GRID = JSORB_K_COUNT_ALL + 1, JSORB_K_LOCAL_CANDIDATES, JSORB_K_LOCAL_RESOLVE, JSORB_K_ID_END };
 /* kernels of jsorb_search_last_frame*: ids from JSORB_K_ID_END on (the grid is JSORB_K_ASSIGN_GRID again); JSORB_K_ID_COUNT is one past the last id */
 enum { JSORB_K_LAST_MATCH = JSORB_K_ID_END, JSORB_K_LAST_RESOLVE, JSORB_K_ID_COUNT };
+/* kernels of jsorb_bow_transform* / jsorb_search_by_bow*: ids after JSORB_K_ID_COUNT, which stays the end of the ids above and names no kernel;
+ * JSORB_K_ID_ALL is one past the last id */
+enum { JSORB_K_BOW_TRANSFORM = JSORB_K_ID_COUNT + 1, JSORB_K_BOW_GROUP, JSORB_K_BOW_MATCH, JSORB_K_BOW_RESOLVE, JSORB_K_ID_ALL };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -466,6 +469,91 @@ int jsorb_init_reference_clear(jsorb_extractor *e);
 int jsorb_init_reference_n(const jsorb_extractor *e);
 int jsorb_search_initial_frame(jsorb_extractor *e, int image, const jsorb_init_params *params, int32_t *matches12_host, float *prev_matched_host,
                                int *n_matches);
+
+/* ---- bag of words: Frame::ComputeBoW (src/Frame.cpp:709-716) and ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&)
+ * (src/ORBmatcher.cpp:146-275) as Tracking::TrackReferenceKeyFrame (src/Tracking.cpp:919-932) and the first half of Tracking::Relocalization
+ * (:1954-2004) call them ----
+ * A jsorb_vocabulary is DBoW2's vocabulary tree (m_nodes, Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h) on one device, shared by any number of
+ * handles on that device.  It is created from flat HOST arrays: node 0 is the root; the children of node i are
+ * children[child_start[i] .. child_start[i + 1]) in the order of m_nodes[i].children (that order decides ties); a node without children is a leaf
+ * (isLeaf(), :328); descriptors n_nodes x 32 bytes (the root's row is unused); word_id per node (-1 for inner nodes); weight per node, used only
+ * as weight > 0 (a word with weight 0 is stopped, :1157).  The tree need not be uniform.  levels_up is the 4 of Frame::ComputeBoW, fixed per object.
+ * JSORB_ERR_INVALID unless: n_nodes >= 2; every child id lies in [1, n_nodes) and appears exactly once and every node is reached from the root (a
+ * tree rooted at 0); every leaf has word_id >= 0; depth_L in [1, 16]; levels_up >= 0; the tree is no deeper than depth_L; no node has 2^22 or
+ * more children.  Nothing faults later on what creation accepted. */
+typedef struct jsorb_vocabulary jsorb_vocabulary;
+int jsorb_vocabulary_create(int device_id, int n_nodes, int depth_L, int levels_up, const int32_t *child_start, const int32_t *children,
+                            const uint8_t *descriptors, const int32_t *word_id, const double *weight, jsorb_vocabulary **out);
+void jsorb_vocabulary_destroy(jsorb_vocabulary *v);
+/* n_words: the leaves.  Any pointer may be NULL. */
+int jsorb_vocabulary_info(const jsorb_vocabulary *v, int *n_nodes, int *n_words, int *depth_L, int *levels_up, int *max_children);
+/* The transform, TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup) (:1217-1259) per descriptor: from the root, at every level the
+ * popcount Hamming distance to every child in child order, the smallest wins with a strict < (the first child wins a tie), until a leaf.
+ *   word_id[i] = the leaf's word id
+ *   node_id[i] = the node reached at level depth_L - levels_up (level 1: the root's children), with three cases defined here:
+ *     root case      depth_L - levels_up <= 0: node_id = 0, the root (:1227)
+ *     shallow leaf   the leaf lies above that level (the reference leaves nid uninitialised): node_id = the leaf's own node id; counted in
+ *                    jsorb_bow_transform_stats' n_shallow.  Does not occur with a full tree
+ *     stopped word   the leaf's weight is not > 0: word_id as usual, node_id = -1 - the keypoint is in no FeatureVector entry (:1157-1161)
+ * The host folds word_id into mBowVec with the vocabulary's own double weights in feature order (BowVector::addWeight / addIfNotExist), and node_id
+ * into mFeatVec (addFeature(node_id[i], i) for node_id[i] >= 0, ascending i).
+ * jsorb_bow_transform_descriptors: n descriptors at a DEVICE pointer (n x 32, 16-byte aligned) -> word_id[n], node_id[n] (device, either may be
+ * NULL), enqueued on hip_stream (a hipStream_t on the vocabulary's device, NULL: the null stream); n == 0 launches nothing.
+ * jsorb_bow_transform_async: image `image` of the handle's last extract (-1: every image, one launch) into buffers of the handle, on the handle's
+ * stream behind the extract (and the lanes of a batch).  The buffers are allocated on the first call, freed in jsorb_destroy and stay valid until
+ * the next extract; jsorb_bow_word_device / jsorb_bow_node_device return image `image`'s N entries (NULL before a transform of that image since the
+ * last extract), jsorb_copy_bow waits and copies them to the host (either may be NULL).  JSORB_ERR_INVALID when the vocabulary lives on another
+ * device than the handle. */
+int jsorb_bow_transform_descriptors(void *hip_stream, const jsorb_vocabulary *v, int n, const uint8_t *descriptors, int32_t *word_id, int32_t *node_id);
+int jsorb_bow_transform_async(jsorb_extractor *e, int image, const jsorb_vocabulary *v);
+const int32_t *jsorb_bow_word_device(const jsorb_extractor *e, int image);
+const int32_t *jsorb_bow_node_device(const jsorb_extractor *e, int image);
+int jsorb_copy_bow(const jsorb_extractor *e, int image, int32_t *word_host, int32_t *node_host);
+/* descriptors of the last jsorb_bow_transform_async whose leaf lay above the node level (waits for it) */
+int jsorb_bow_transform_stats(jsorb_extractor *e, int *n_shallow);
+/* The matcher: ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for n_keyframes >= 0 keyframes (at most 256) against one frame, F = image `image`
+ * of the handle's last extract with N keypoints: its descriptors, its angle (keypoint SoA row 3 as float bits, F.mvKeys[k].angle) and f_node[k], the
+ * FeatureVector node of keypoint k or -1 (NULL: what the handle's last jsorb_bow_transform_async of this image wrote).  The keyframes are
+ * concatenated: keyframe i is the entries kf_start[i] .. kf_start[i + 1] (HOST array of n_keyframes + 1 ascending offsets) of kf_node (its
+ * FeatureVector node or -1), kf_valid (pMP && !pMP->isBad()), kf_angle (mvKeysUn[j].angle) and kf_descriptors (32 bytes each, 16-byte aligned) -
+ * DEVICE arrays.  Node ids are arbitrary non-negative int32: they need not come from a jsorb_vocabulary.
+ * The per-keypoint form equals DBoW2's FeatureVector by two facts, which are the contract: addFeature appends i_feature in ascending order
+ * (FeatureVector.cpp:31-44, TemplatedVocabulary.h:1148-1161), and every keypoint is in at most one node - so nodes are independent and the order in
+ * which they are processed changes no output.  Per keyframe, with j local to the keyframe (0 .. kf_start[i+1] - kf_start[i] - 1):
+ *   match_kf[k] = -1 for all k, nmatches = 0 (:150-154)
+ *   for every node id present on both sides (:167-251), for the keyframe's keypoints j of that node in ascending j (:174):
+ *     skip j when !kf_valid[j] (:178-184)
+ *     over the frame's keypoints k of that node in ascending k, skipping those with match_kf[k] >= 0 (:196), from bestDist1 = bestDist2 = 256,
+ *       bestIdxF = -1: if (d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdxF = k; } else if (d < bestDist2) bestDist2 = d; (:203-212)
+ *       - the two smallest of the multiset (a tie with the best lowers the second), the index the first in walk order with the minimum
+ *     claim iff bestDist1 <= th_low && (float)bestDist1 < nn_ratio * (float)bestDist2 (one float product, :215-217) - and bestIdxF >= 0, which the
+ *       reference implies for th_low < 256: match_kf[bestIdxF] = j, nmatches++, and with check_orientation bestIdxF goes into the bin of
+ *       rot = kf_angle[j] - angle_F[bestIdxF] (+ 360.0f when negative; bin = (int)roundf(rot * (1.0f/30)), 30 -> 0: the arithmetic of
+ *       jsorb_search_last_frame) (:219-234)
+ *   then, with check_orientation, ComputeThreeMaxima (:2097-2138, as for jsorb_search_last_frame) over the bins' sizes; every entry k of every
+ *   other bin: match_kf[k] = -1, nmatches-- (:254-272).  A bin outside [0, 30) is never kept.
+ * Outputs (DEVICE): match_kf n_keyframes x N (row i: keyframe i), n_matches_dev[n_keyframes].  Enqueued on the handle's stream behind the last
+ * extract (and the lanes of a batch), no host decision, no allocation after the first call of a size: k_bow_group, k_bow_match, k_bow_resolve.
+ * N < 262144, every keyframe shorter than 262144.  N == 0, n_keyframes == 0 and empty keyframes write -1 / 0 and launch nothing that reads. */
+typedef struct jsorb_bow_params {
+    float nn_ratio;                  /* 0.7 TrackReferenceKeyFrame, 0.75 Relocalization */
+    int th_low;                      /* ORBmatcher::TH_LOW = 50 */
+    int check_orientation;           /* 1 */
+} jsorb_bow_params;
+int jsorb_search_by_bow_async(jsorb_extractor *e, int image, const jsorb_bow_params *params, const int32_t *f_node, int n_keyframes,
+                              const int32_t *kf_start, const int32_t *kf_node, const uint8_t *kf_valid, const float *kf_angle,
+                              const uint8_t *kf_descriptors, int32_t *match_kf, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the handle; match_kf_host[n_keyframes x N] and n_matches_host[n_keyframes] (host), one synchronisation. */
+int jsorb_search_by_bow(jsorb_extractor *e, int image, const jsorb_bow_params *params, const int32_t *f_node, int n_keyframes,
+                        const int32_t *kf_start, const int32_t *kf_node, const uint8_t *kf_valid, const float *kf_angle,
+                        const uint8_t *kf_descriptors, int32_t *match_kf_host, int *n_matches_host);
+/* Diagnostics of the last call (waits for it): (keyframe, node) pairs present on both sides, Hamming distances computed, the most frame keypoints in
+ * a node of such a pair, and keyframe 0's ComputeThreeMaxima ind1..3 (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
+int jsorb_search_by_bow_stats(jsorb_extractor *e, int *n_node_pairs, int *n_distances, int *largest_node, int kept_bins[3]);
+/* The compile-time caps of this build's matcher kernels (no device needed): frame entries of a node a lane of k_bow_match keeps in registers
+ * (2; beyond 64 x that a node's entries are re-read per keyframe keypoint) and the keys k_bow_group sorts in LDS (4096; longer sides are sorted in
+ * global memory).  Test builds lower them (jetson_slam_amd/build.py VARIANTS) and assert on these values.  Either pointer may be NULL. */
+int jsorb_bow_build_caps(int *node_regs, int *sort_lds);
 
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates

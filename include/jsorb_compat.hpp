@@ -480,6 +480,28 @@ inline void compute_isInFrustum_GPU(int n_points, float *Px_gpu, float *Py_gpu, 
 }
 } // namespace tracking_cuda
 
+// The vocabulary tree on the device (jsorb_vocabulary, include/jsorb.h): RAII over the C calls.  Built from DBoW2's m_nodes flattened into host
+// arrays (INTEGRATION.md shows the subclass of ORBVocabulary that does it); shared by every extractor on the device.
+namespace jsorb {
+class Vocabulary {
+public:
+    Vocabulary(int n_nodes, int depth_L, int levels_up, const int32_t *child_start, const int32_t *children, const unsigned char *descriptors,
+               const int32_t *word_id, const double *weight, int device_id = 0)
+    {
+        const int rc = jsorb_vocabulary_create(device_id, n_nodes, depth_L, levels_up, child_start, children, descriptors, word_id, weight, &v_);
+        if (rc != JSORB_OK) throw std::invalid_argument(rc == JSORB_ERR_INVALID ? "jsorb_vocabulary_create: the arrays are not a tree of this depth" : "jsorb_vocabulary_create failed");
+    }
+    Vocabulary(const Vocabulary &) = delete;
+    Vocabulary &operator=(const Vocabulary &) = delete;
+    ~Vocabulary() { jsorb_vocabulary_destroy(v_); }
+    const jsorb_vocabulary *handle() const { return v_; }
+    int words() const { int w = 0; jsorb_vocabulary_info(v_, nullptr, &w, nullptr, nullptr, nullptr); return w; }
+
+private:
+    jsorb_vocabulary *v_ = nullptr;
+};
+} // namespace jsorb
+
 namespace Jetson_SLAM {
 
 using orb_cuda::SyncedMem;
@@ -673,6 +695,41 @@ inline int SearchForInitialization(ORBExtractor &ex, const jsorb_init_params &pa
         throw std::runtime_error(std::string("jsorb_search_initial_frame: ") + jsorb_last_error(ex.handle()));
     vnMatches12.resize(n1 > 0 ? n1 : 0);
     if (vbPrevMatched) vbPrevMatched->resize(n1 > 0 ? 2 * (std::size_t)n1 : 0);
+    return n_matches;
+}
+
+// The bag-of-words side of TrackReferenceKeyFrame (Tracking.cpp:919-932) and Relocalization (:1954-2004) on the device.
+// ComputeBoW after the extract, where the reference calls mCurrentFrame.ComputeBoW() (Frame.cpp:709-716): word and node ids of every keypoint stay
+// on the device for SearchByBoW; asked for on the host, the caller folds them into mBowVec (addWeight / addIfNotExist with the vocabulary's own
+// weights, in feature order) and mFeatVec (addFeature(node_id[i], i) for node_id[i] >= 0).
+inline void ComputeBoW(ORBExtractor &ex, const jsorb::Vocabulary &voc, std::vector<int> *word_id = nullptr, std::vector<int> *node_id = nullptr)
+{
+    if (jsorb_bow_transform_async(ex.handle(), 0, voc.handle()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_bow_transform_async: ") + jsorb_last_error(ex.handle()));
+    if (!word_id && !node_id) return;
+    const int N = jsorb_n_keypoints(ex.handle(), 0);
+    if (word_id) word_id->assign(N > 0 ? N : 1, -1);
+    if (node_id) node_id->assign(N > 0 ? N : 1, -1);
+    if (jsorb_copy_bow(ex.handle(), 0, word_id ? word_id->data() : nullptr, node_id ? node_id->data() : nullptr) != JSORB_OK)
+        throw std::runtime_error("jsorb_copy_bow failed");
+    if (word_id) word_id->resize(N > 0 ? N : 0);
+    if (node_id) node_id->resize(N > 0 ? N : 0);
+}
+// matcher.SearchByBoW(pKF, mCurrentFrame, vpMapPointMatches) (ORBmatcher.cpp:146-275) for one keyframe of n keypoints against the current frame,
+// after ComputeBoW: node = the keyframe's FeatureVector node per keypoint (-1: none), valid = pMP && !pMP->isBad(), angle = mvKeysUn[].angle,
+// descriptors 32 bytes each, uploaded (to_gpu) by the caller.  Returns nmatches; match_kf[k] = the keyframe keypoint whose map point is now in
+// vpMapPointMatches[k], or -1 - the caller applies vpMapPointMatches[k] = vpMapPointsKF[match_kf[k]].
+inline int SearchByBoW(ORBExtractor &ex, const jsorb_bow_params &params, int n, SyncedMem<int> &node, SyncedMem<unsigned char> &valid,
+                       SyncedMem<float> &angle, SyncedMem<unsigned char> &descriptors, std::vector<int> &match_kf)
+{
+    const int N = jsorb_n_keypoints(ex.handle(), 0);
+    match_kf.assign(N > 0 ? N : 1, -1);
+    const int32_t kf_start[2] = {0, n};
+    int n_matches = 0;
+    if (jsorb_search_by_bow(ex.handle(), 0, &params, nullptr, 1, kf_start, node.gpu_data(), valid.gpu_data(), angle.gpu_data(), descriptors.gpu_data(),
+                            match_kf.data(), &n_matches) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_by_bow: ") + jsorb_last_error(ex.handle()));
+    match_kf.resize(N > 0 ? N : 0);
     return n_matches;
 }
 

@@ -19,6 +19,8 @@ const char *k_names[JSORB_K_COUNT_ALL] = {"k_pyramid", "k_detect", "k_compact", 
 const char *k_names_local[JSORB_K_ID_END - JSORB_K_ASSIGN_GRID] = {"k_assign_grid", "k_local_candidates", "k_local_resolve"};
 // kernels of jsorb_search_last_frame*: ids JSORB_K_ID_END .. JSORB_K_ID_COUNT - 1
 const char *k_names_last[JSORB_K_ID_COUNT - JSORB_K_ID_END] = {"k_last_match", "k_last_resolve"};
+// kernels of jsorb_bow_transform* / jsorb_search_by_bow*: ids JSORB_K_BOW_TRANSFORM .. JSORB_K_ID_ALL - 1 (JSORB_K_ID_COUNT itself names no kernel)
+const char *k_names_bow[JSORB_K_ID_ALL - JSORB_K_BOW_TRANSFORM] = {"k_bow_transform", "k_bow_group", "k_bow_match", "k_bow_resolve"};
 
 // HIP multiplexes every stream of a process over GPU_MAX_HW_QUEUES hardware queues (default 4), and a stream that waits for an event
 // holds up every other stream that shares its queue.  This library runs 4 lane streams + 1 upload stream + one main stream per handle;
@@ -357,6 +359,7 @@ const char *jsorb_kernel_name(int id)
     if (id >= 0 && id < JSORB_K_COUNT_ALL) return k_names[id];
     if (id >= JSORB_K_ASSIGN_GRID && id < JSORB_K_ID_END) return k_names_local[id - JSORB_K_ASSIGN_GRID];
     if (id >= JSORB_K_ID_END && id < JSORB_K_ID_COUNT) return k_names_last[id - JSORB_K_ID_END];
+    if (id >= JSORB_K_BOW_TRANSFORM && id < JSORB_K_ID_ALL) return k_names_bow[id - JSORB_K_BOW_TRANSFORM];
     return "";
 }
 
@@ -636,6 +639,7 @@ void jsorb_destroy(jsorb_extractor *e)
     search_local_release(e);
     search_last_release(e);
     search_init_release(e);
+    bow_release(e);
     core_release(e);
     arena_release(e->det_spill);
     if (e->own_stream) { (void)hipStreamSynchronize(e->own_stream); pool_return_main_stream(e->device, e->own_stream); }
@@ -820,7 +824,7 @@ int jsorb_enable_kernel_timing(jsorb_extractor *e, int on)
 }
 int jsorb_kernel_time(jsorb_extractor *e, int id, double *total_ms, long *launches)
 {
-    if (!e || id < 0 || id >= JSORB_K_ID_COUNT || (id >= JSORB_K_COUNT_ALL && id < JSORB_K_ASSIGN_GRID)) return JSORB_ERR_INVALID;
+    if (!e || id < 0 || id >= JSORB_K_ID_ALL || id == JSORB_K_ID_COUNT || (id >= JSORB_K_COUNT_ALL && id < JSORB_K_ASSIGN_GRID)) return JSORB_ERR_INVALID;
     RCCHK(drain_timed(e));
     if (total_ms) *total_ms = e->tm.k_ms[id];
     if (launches) *launches = e->tm.k_n[id];
@@ -830,7 +834,7 @@ int jsorb_reset_kernel_timing(jsorb_extractor *e)
 {
     if (!e) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
-    for (int i = 0; i < JSORB_K_ID_COUNT; i++) { e->tm.k_ms[i] = 0; e->tm.k_n[i] = 0; }
+    for (int i = 0; i < JSORB_K_ID_ALL; i++) { e->tm.k_ms[i] = 0; e->tm.k_n[i] = 0; }
     return rc;
 }
 

@@ -326,6 +326,7 @@ int run_pipeline(jsorb_extractor *e, int n, const hipEvent_t *input_ready = null
     e->n_images = n;
     e->extracted = true;
     stereo_after_extract(e);
+    bow_after_extract(e);
     e->counts_synced = false;
     return JSORB_OK;
 }

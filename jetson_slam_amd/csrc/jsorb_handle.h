@@ -1,6 +1,7 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
-// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map, motion-model and initialisation search).  include/jsorb.h only
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map, motion-model and initialisation search; jsorb_bow.hip: vocabulary, BoW transform
+// and BoW matching).  include/jsorb.h only
 // forward-declares the handle, so its layout is free to change.
 #pragma once
 
@@ -250,13 +251,25 @@ struct jsorb_extractor {
         int ref_cap = 0, ref_n = -1;       // ref_n: its keypoints (-1: none kept)
     } si;
 
+    // ---- bag of words (jsorb_bow.hip, jsorb_bow_transform_async / jsorb_search_by_bow*): allocated on first use, the keyframe parts grown only ----
+    struct {
+        int32_t *ids = nullptr;            // B x T word ids, then B x T node ids, then 2 statistics words (descriptors with a shallow leaf)
+        std::vector<char> have;            // per image: transformed since the last extract
+        unsigned long long *fsort = nullptr, *ksort = nullptr;      // sorted keys of the frame (T) and of the keyframes (kf_cap)
+        int kf_cap = 0;
+        int *stats = nullptr;              // 8 statistics words of the last search
+        int32_t *out = nullptr;            // synchronous call: counts (256), then match_kf (out_cap)
+        int out_cap = 0;
+        bool done = false, transformed = false;
+    } bow;
+
     // ---- per-kernel timing (jsorb_api.hip) ----
     struct TimedLaunch { int id; hipEvent_t a, b; };
     struct {
         bool on = false;
         std::vector<TimedLaunch> timed;
-        double k_ms[JSORB_K_ID_COUNT] = {0};
-        long k_n[JSORB_K_ID_COUNT] = {0};
+        double k_ms[JSORB_K_ID_ALL] = {0};
+        long k_n[JSORB_K_ID_ALL] = {0};
     } tm;
 
     // ---- JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy ----
@@ -402,6 +415,10 @@ void grid_release(jsorb_extractor *e);
 void search_local_release(jsorb_extractor *e);
 void search_last_release(jsorb_extractor *e);
 void search_init_release(jsorb_extractor *e);
+
+// ---- jsorb_bow.hip ----
+void bow_after_extract(jsorb_extractor *e);
+void bow_release(jsorb_extractor *e);
 
 } // namespace jsorb_host
 

@@ -178,6 +178,41 @@ int search_init_cap();
 void launch_init_candidates(const SearchInitArgs &a, hipStream_t s);
 void launch_init_resolve(const SearchInitArgs &a, hipStream_t s);
 void launch_init_keys_un(const int32_t *soa, const float *xy_un, int n, float *dst, hipStream_t s);      // mvKeysUn points: x[n] y[n]
+// k_bow_transform / k_bow_group / k_bow_match / k_bow_resolve (k_bow.hip): Frame::ComputeBoW's descent and ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...)
+struct BowVocab {
+    const int32_t *child_start, *children;       // CSR of the tree: the children of node i are children[child_start[i] .. child_start[i + 1]), in the caller's order
+    const uint8_t *child_desc;                   // the descriptor of children[c] at 32 c: a node's children lie next to each other
+    const int32_t *word;                         // per node: word id (leaves)
+    const uint8_t *live;                         // per node: weight > 0
+    int depth_L, nid_level;                      // nid_level = depth_L - levels_up
+};
+#define JSORB_BOW_MAX_KEYFRAMES 256
+struct BowMatchArgs {
+    // the frame: keypoint SoA (6N), descriptors, node per keypoint (-1: in none)
+    const int32_t *soa;
+    const uint8_t *desc;
+    const int32_t *f_node;
+    int N;
+    // the keyframes, concatenated; keyframe i is kf_start[i] .. kf_start[i + 1] (relative to the pointers below)
+    int n_kf;
+    const int32_t *kf_node;
+    const uint8_t *kf_valid;
+    const float *kf_angle;
+    const uint8_t *kf_desc;
+    jsorb_bow_params p;
+    // workspace and outputs
+    unsigned long long *f_sorted, *kf_sorted;    // keys node << 18 | index, ascending; keypoints in no node last
+    int32_t *match_kf, *n_matches;               // n_kf x N (cleared to -1), n_kf (cleared to 0)
+    int *stats;                                  // node pairs, distances, largest frame node of a pair, ind1 + 1, ind2 + 1, ind3 + 1 of keyframe 0 (cleared to 0)
+    int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
+};
+int bow_node_regs();                            // the compile-time caps of k_bow.hip (jsorb_bow_build_caps)
+int bow_sort_lds();
+void launch_bow_transform(const BowVocab &v, const uint8_t *desc, size_t desc_stride, const int *counts, int counts_stride, int n, int32_t *word,
+                          int32_t *node, size_t out_stride, int *n_shallow, int n_images, hipStream_t s);      // counts NULL: n descriptors; else a grid for n, counts[img * counts_stride] of them per image
+void launch_bow_group(const BowMatchArgs &a, hipStream_t s);
+void launch_bow_match(const BowMatchArgs &a, hipStream_t s);
+void launch_bow_resolve(const BowMatchArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

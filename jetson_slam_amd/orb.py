@@ -31,6 +31,8 @@ K_RGBD = 10         # JSORB_K_RGBD (jsorb_rgbd_depth*)
 K_ASSIGN_GRID, K_LOCAL_CANDIDATES, K_LOCAL_RESOLVE = 12, 13, 14
 # jsorb_search_last_frame*: ids from JSORB_K_ID_END (15) on; the grid is K_ASSIGN_GRID again
 K_LAST_MATCH, K_LAST_RESOLVE = 15, 16
+# jsorb_bow_transform* / jsorb_search_by_bow*: ids after JSORB_K_ID_COUNT (17, which names no kernel)
+K_BOW_TRANSFORM, K_BOW_GROUP, K_BOW_MATCH, K_BOW_RESOLVE = 18, 19, 20, 21
 DEPTH_F32, DEPTH_U16 = 0, 1      # JSORB_DEPTH_F32 / JSORB_DEPTH_U16
 
 EXPORTS = [
@@ -54,6 +56,9 @@ EXPORTS = [
     "jsorb_search_last_frame_async", "jsorb_search_last_frame", "jsorb_search_last_frame_stats",
     "jsorb_search_for_initialization_async", "jsorb_search_for_initialization", "jsorb_search_for_initialization_stats",
     "jsorb_init_reference_set", "jsorb_init_reference_clear", "jsorb_init_reference_n", "jsorb_search_initial_frame",
+    "jsorb_vocabulary_create", "jsorb_vocabulary_destroy", "jsorb_vocabulary_info", "jsorb_bow_transform_descriptors", "jsorb_bow_transform_async",
+    "jsorb_bow_word_device", "jsorb_bow_node_device", "jsorb_copy_bow", "jsorb_bow_transform_stats", "jsorb_search_by_bow_async",
+    "jsorb_search_by_bow", "jsorb_search_by_bow_stats", "jsorb_bow_build_caps",
 ]
 
 
@@ -108,6 +113,15 @@ def make_init_params(grid, window=50.0, nn_ratio=0.9, th_low=TH_LOW, check_orien
     """jsorb_init_params of MonocularInitialization's ORBmatcher(0.9, true) and windowSize 50: grid = (mnMinX, mnMinY, mfGridElementWidthInv,
     mfGridElementHeightInv) of the current frame over cols x rows"""
     return JsorbInitParams(window, nn_ratio, th_low, int(check_orientation), grid[0], grid[1], grid[2], grid[3], cols, rows)
+
+
+class JsorbBowParams(C.Structure):
+    _fields_ = [("nn_ratio", C.c_float), ("th_low", C.c_int), ("check_orientation", C.c_int)]
+
+
+def make_bow_params(nn_ratio=0.7, th_low=TH_LOW, check_orientation=True):
+    """jsorb_bow_params: ORBmatcher matcher(0.7, true) of TrackReferenceKeyFrame (Tracking.cpp:925), (0.75, true) of Relocalization (:1975)"""
+    return JsorbBowParams(nn_ratio, th_low, int(check_orientation))
 
 
 def make_camera(K, D):
@@ -229,6 +243,19 @@ def load_library(path=None):
         "jsorb_init_reference_clear": (I, [P]),
         "jsorb_init_reference_n": (I, [P]),
         "jsorb_search_initial_frame": (I, [P, I, C.POINTER(JsorbInitParams), P, P, C.POINTER(I)]),
+        "jsorb_vocabulary_create": (I, [I, I, I, I, P, P, P, P, P, C.POINTER(P)]),
+        "jsorb_vocabulary_destroy": (None, [P]),
+        "jsorb_vocabulary_info": (I, [P] + [C.POINTER(I)] * 5),
+        "jsorb_bow_transform_descriptors": (I, [P, P, I, P, P, P]),
+        "jsorb_bow_transform_async": (I, [P, I, P]),
+        "jsorb_bow_word_device": (P, [P, I]),
+        "jsorb_bow_node_device": (P, [P, I]),
+        "jsorb_copy_bow": (I, [P, I, P, P]),
+        "jsorb_bow_transform_stats": (I, [P, C.POINTER(I)]),
+        "jsorb_search_by_bow_async": (I, [P, I, C.POINTER(JsorbBowParams), P, I] + [P] * 7),
+        "jsorb_search_by_bow": (I, [P, I, C.POINTER(JsorbBowParams), P, I] + [P] * 7),
+        "jsorb_search_by_bow_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_bow_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
         "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
         "jsorb_handle_forms": (I, [P, P, I]),
     }
@@ -321,6 +348,81 @@ def plan_forms(im_height, im_width, scale_factor, n_levels, tile_h=30, tile_w=30
     if rc != 0:
         raise JsorbError("jsorb_plan_forms rc=%d" % rc)
     return dict(zip(FORM_KEYS, (int(v) for v in out)))
+
+
+class Vocabulary:
+    """jsorb_vocabulary: a vocabulary tree on one device (include/jsorb.h).  `tree` is a dict of flat host arrays as jetson_slam_amd.vocabulary
+    builds them (load_text, random_tree, sampled_tree): child_start, children, descriptors, word_id, weight, depth_L.  levels_up is the 4 of
+    Frame::ComputeBoW.  Raises JsorbError when the arrays are not a tree the library accepts."""
+
+    def __init__(self, tree, levels_up=4, device_id=0):
+        self._lib = load_library()
+        self._v = C.c_void_p()
+        cs = np.ascontiguousarray(tree["child_start"], np.int32)
+        ch = np.ascontiguousarray(tree["children"], np.int32)
+        de = np.ascontiguousarray(tree["descriptors"], np.uint8)
+        wi = np.ascontiguousarray(tree["word_id"], np.int32)
+        we = np.ascontiguousarray(tree["weight"], np.float64)
+        n = len(wi)
+        if len(cs) != n + 1 or de.size != 32 * n or len(we) != n or (n >= 1 and len(ch) < max(int(cs[-1]), 0)):
+            raise JsorbError("Vocabulary: array lengths do not fit n_nodes = %d" % n)
+        rc = self._lib.jsorb_vocabulary_create(device_id, n, int(tree["depth_L"]), int(levels_up), cs.ctypes.data, ch.ctypes.data, de.ctypes.data,
+                                               wi.ctypes.data, we.ctypes.data, C.byref(self._v))
+        if rc != 0:
+            self._v = C.c_void_p()
+            raise JsorbError("jsorb_vocabulary_create rc=%d" % rc)
+        self.levels_up = int(levels_up)
+
+    def info(self):
+        """dict(n_nodes, n_words, depth_L, levels_up, max_children)"""
+        v = [C.c_int() for _ in range(5)]
+        rc = self._lib.jsorb_vocabulary_info(self._v, *[C.byref(t) for t in v])
+        if rc != 0:
+            raise JsorbError("jsorb_vocabulary_info rc=%d" % rc)
+        return dict(zip(("n_nodes", "n_words", "depth_L", "levels_up", "max_children"), (t.value for t in v)))
+
+    @property
+    def handle(self):
+        return self._v
+
+    def close(self):
+        if getattr(self, "_v", None):
+            self._lib.jsorb_vocabulary_destroy(self._v)
+            self._v = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bow_build_caps():
+    """jsorb_bow_build_caps of the loaded library: (frame entries per lane k_bow_match keeps in registers, keys k_bow_group sorts in LDS)"""
+    r, l = C.c_int(), C.c_int()
+    load_library().jsorb_bow_build_caps(C.byref(r), C.byref(l))
+    return r.value, l.value
+
+
+def bow_transform_descriptors(voc, descriptors):
+    """jsorb_bow_transform_descriptors: a device tensor uint8[n, 32] (16-byte aligned) -> (word_id int32[n], node_id int32[n]) device tensors;
+    waits for the current torch stream before it starts and for its own work before it returns"""
+    import torch
+    if not hasattr(descriptors, "data_ptr") or not getattr(descriptors, "is_cuda", False) or descriptors.dtype != torch.uint8:
+        raise JsorbError("bow_transform_descriptors: descriptors must be a uint8 device tensor")
+    if descriptors.dim() != 2 or descriptors.shape[1] != 32 or not descriptors.is_contiguous():
+        raise JsorbError("bow_transform_descriptors: descriptors must be a contiguous tensor of shape (n, 32)")
+    n = int(descriptors.shape[0])
+    if n and descriptors.data_ptr() % 16:
+        raise JsorbError("bow_transform_descriptors: descriptors must be 16-byte aligned")
+    word = torch.full((max(n, 1),), -1, dtype=torch.int32, device=descriptors.device)
+    node = torch.full((max(n, 1),), -1, dtype=torch.int32, device=descriptors.device)
+    torch.cuda.current_stream(descriptors.device).synchronize()
+    rc = voc._lib.jsorb_bow_transform_descriptors(None, voc.handle, n, descriptors.data_ptr() if n else None, word.data_ptr(), node.data_ptr())
+    if rc != 0:
+        raise JsorbError("jsorb_bow_transform_descriptors rc=%d" % rc)
+    torch.cuda.synchronize(descriptors.device)
+    return word[:n], node[:n]
 
 
 class ORBExtractor:
@@ -825,6 +927,110 @@ class ORBExtractor:
         cnt = C.c_int()
         self._chk(self._lib.jsorb_search_initial_frame(self._h, image, C.byref(params), m12.ctypes.data, prev.ctypes.data, C.byref(cnt)))
         return m12[:n1], prev.reshape(-1)[:2 * n1].reshape(2, n1), cnt.value
+
+    # ---- bag of words: Frame::ComputeBoW (Frame.cpp:709-716) and ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (ORBmatcher.cpp:146-275) ----
+    def bow_transform(self, voc, image=0):
+        """jsorb_bow_transform_async: word and node ids of image `image` of the last extract (-1: every image, one launch) into buffers of the
+        handle, enqueued on its stream; read them with bow() or use them through search_by_bow(f_node=None)"""
+        if not isinstance(voc, Vocabulary):
+            raise JsorbError("bow_transform: voc must be a Vocabulary")
+        self._chk(self._lib.jsorb_bow_transform_async(self._h, image, voc.handle))
+
+    def bow(self, image=0):
+        """(word_id int32[N], node_id int32[N]) of the last bow_transform of this image, on the host (waits).  node_id -1: a stopped word"""
+        n = self.n_keypoints(image)
+        if n < 0:
+            raise JsorbError("no extract result for image %d" % image)
+        word, node = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+        rc = self._lib.jsorb_copy_bow(self._h, image, word.ctypes.data, node.ctypes.data)
+        if rc != 0:
+            raise JsorbError("jsorb_copy_bow rc=%d: no bow_transform of image %d since the last extract" % (rc, image))
+        return word[:n], node[:n]
+
+    def bow_device_pointers(self, image=0):
+        """(jsorb_bow_word_device, jsorb_bow_node_device) as integers, 0 when the image has no transform since the last extract"""
+        return self._lib.jsorb_bow_word_device(self._h, image) or 0, self._lib.jsorb_bow_node_device(self._h, image) or 0
+
+    def bow_transform_stats(self):
+        """descriptors of the last bow_transform whose leaf lay above the node level"""
+        s = C.c_int()
+        self._chk(self._lib.jsorb_bow_transform_stats(self._h, C.byref(s)))
+        return s.value
+
+    def _bow_keyframes(self, what, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors):
+        import torch
+        ks = np.ascontiguousarray(kf_start, np.int32)
+        if ks.ndim != 1 or len(ks) < 1:
+            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
+        total = int(ks[-1])
+
+        def chk(t, name, dtypes, shape):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("%s: %s must be a device tensor" % (what, name))
+            if t.dtype not in dtypes:
+                raise JsorbError("%s: %s must be %s, not %s" % (what, name, " / ".join(str(d) for d in dtypes), t.dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("%s: %s must be a contiguous tensor of shape %s, not %s" % (what, name, shape, tuple(t.shape)))
+            return t.data_ptr()
+
+        ptrs = [chk(kf_node, "kf_node", (torch.int32,), (total,)), chk(kf_valid, "kf_valid", (torch.uint8, torch.bool), (total,)),
+                chk(kf_angle, "kf_angle", (torch.float32,), (total,)), chk(kf_descriptors, "kf_descriptors", (torch.uint8,), (total, 32))]
+        if total and kf_descriptors.data_ptr() % 16:
+            raise JsorbError("%s: kf_descriptors must be 16-byte aligned" % what)
+        return ks, ptrs, chk
+
+    def search_by_bow(self, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors, params, f_node=None, image=0):
+        """TrackReferenceKeyFrame's / Relocalization's matching step: len(kf_start) - 1 keyframes against image `image` of the last extract.
+        kf_start: HOST int32 offsets; device tensors kf_node int32[n], kf_valid uint8 / bool [n], kf_angle float32[n], kf_descriptors uint8[n, 32];
+        f_node int32[N] device tensor, or None: the handle's last bow_transform of this image.  params: make_bow_params(...).  Returns (match_kf
+        int32[n_keyframes, N], n_matches int32[n_keyframes]) as device tensors; the call waits for the current torch stream before it starts
+        and for its own work before it returns."""
+        import torch
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("search_by_bow: no extract result for image %d" % image)
+        if not isinstance(params, JsorbBowParams):
+            raise JsorbError("search_by_bow: params must come from make_bow_params")
+        ks, ptrs, chk = self._bow_keyframes("search_by_bow", kf_start, kf_node, kf_valid, kf_angle, kf_descriptors)
+        fn = None if f_node is None else chk(f_node, "f_node", (torch.int32,), (N,))
+        nk = len(ks) - 1
+        dev = kf_node.device
+        match_kf = torch.full((max(nk, 1), max(N, 1)), -7, dtype=torch.int32, device=dev)
+        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_by_bow_async(self._h, image, C.byref(params), fn, nk, ks.ctypes.data, *ptrs, match_kf.data_ptr(), count.data_ptr()))
+        self.sync()
+        return match_kf.reshape(-1)[:nk * N].reshape(nk, N), count[:nk]
+
+    def search_by_bow_host(self, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors, params, f_node=None, image=0):
+        """jsorb_search_by_bow, the synchronous form: the same inputs, (match_kf int32[n_keyframes, N], n_matches int32[n_keyframes]) on the host
+        with one synchronisation"""
+        import torch
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("search_by_bow: no extract result for image %d" % image)
+        if not isinstance(params, JsorbBowParams):
+            raise JsorbError("search_by_bow: params must come from make_bow_params")
+        ks, ptrs, chk = self._bow_keyframes("search_by_bow", kf_start, kf_node, kf_valid, kf_angle, kf_descriptors)
+        fn = None if f_node is None else chk(f_node, "f_node", (torch.int32,), (N,))
+        nk = len(ks) - 1
+        match_kf = np.full(max(nk * N, 1), -7, np.int32)
+        count = np.full(max(nk, 1), -7, np.int32)
+        torch.cuda.current_stream(kf_node.device).synchronize()
+        self._chk(self._lib.jsorb_search_by_bow(self._h, image, C.byref(params), fn, nk, ks.ctypes.data, *ptrs, match_kf.ctypes.data, count.ctypes.data))
+        return match_kf[:nk * N].reshape(nk, N), count[:nk]
+
+    def search_by_bow_stats(self):
+        """((keyframe, node) pairs on both sides, Hamming distances, most frame keypoints in such a node, keyframe 0's (ind1, ind2, ind3)) of the
+        last search_by_bow"""
+        p, d, m, b = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_by_bow_stats(self._h, C.byref(p), C.byref(d), C.byref(m), b))
+        return p.value, d.value, m.value, tuple(b)
+
+    def bow_kernel_times(self):
+        """{kernel: (total_ms, launches)} of the transform, group, match and resolve kernels, measured like kernel_times()"""
+        return {name: self._kernel_time(k) for name, k in (("k_bow_transform", K_BOW_TRANSFORM), ("k_bow_group", K_BOW_GROUP),
+                                                           ("k_bow_match", K_BOW_MATCH), ("k_bow_resolve", K_BOW_RESOLVE))}
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):

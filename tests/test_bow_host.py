@@ -1,0 +1,653 @@
+"""CPU: the bag-of-words transform and matcher of jsorb_bow_transform* / jsorb_search_by_bow* (include/jsorb.h) - TemplatedVocabulary::transform
+(Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1217-1259) as Frame::ComputeBoW calls it, and ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...)
+(ORBmatcher.cpp:146-275) with ComputeThreeMaxima (:2097-2138).  Literal, sequential transcriptions are the yardstick (the matcher with the
+map-style merge over ascending node ids).  The restatements are the kernels' formulation: lane-strided keys distance << 22 | child position
+reduced with a minimum; the keys node << 18 | index sorted by the all-ascending bitonic network; per-node buckets taken in arbitrary order; 64
+lanes that each keep the two smallest distances of their entries, folded to (bestDist1, first position, bestDist2).  They must equal the
+transcriptions on random and on constructed cases.  tests/test_gpu_bow.py holds the device to both."""
+import ctypes
+import os
+import re
+from bisect import bisect_left
+
+import numpy as np
+import pytest
+
+from jetson_slam_amd import vocabulary as V
+from test_search_last_frame_host import HISTO_LENGTH, compute_three_maxima, rot_bin
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+BW_LANES, BW_POS, BW_IDX, BW_NODE_REGS, BW_SORT_LDS = 16, 22, 18, 2, 4096      # k_bow.hip
+
+
+def default_params(**kw):
+    """ORBmatcher matcher(0.7, true) of TrackReferenceKeyFrame (Tracking.cpp:925), TH_LOW = 50"""
+    p = dict(nn_ratio=f32(0.7), th_low=50, check_orientation=1)
+    p.update(kw)
+    return p
+
+
+def as_ints(desc):
+    """descriptors uint8[n, 32] as Python ints: DescriptorDistance is the popcount of the xor"""
+    return [int.from_bytes(bytes(r), "little") for r in np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)]
+
+
+def dist(a, b):
+    return (a ^ b).bit_count()
+
+
+def _voc_ints(voc):
+    if "_ints" not in voc:
+        voc["_ints"] = as_ints(voc["descriptors"])
+    return voc["_ints"]
+
+
+# ---- the yardsticks: literal transcriptions, sequential ----
+def transform_reference(voc, desc, levels_up):
+    """TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup) per descriptor -> (word_id[n], node_id[n], n_shallow) with the three
+    definitions of include/jsorb.h: the root case is the reference's own (:1227); a leaf above the node level leaves nid unset in the reference -
+    here it is the leaf's id, counted in n_shallow; a stopped word (weight not > 0, :1157) has node_id -1"""
+    cs, ch, D = voc["child_start"], voc["children"], _voc_ints(voc)
+    word, node, n_shallow = [], [], 0
+    for feature in as_ints(desc):
+        nid = None
+        nid_level = voc["depth_L"] - levels_up
+        if nid_level <= 0:
+            nid = 0
+        final_id = 0
+        current_level = 0
+        while True:
+            current_level += 1
+            nodes = ch[cs[final_id]:cs[final_id + 1]]
+            final_id = int(nodes[0])
+            best_d = dist(feature, D[final_id])
+            for id_ in nodes[1:]:
+                d = dist(feature, D[int(id_)])
+                if d < best_d:
+                    best_d = d
+                    final_id = int(id_)
+            if current_level == nid_level:
+                nid = final_id
+            if cs[final_id] == cs[final_id + 1]:     # isLeaf()
+                break
+        if nid is None:
+            n_shallow += 1
+            nid = final_id
+        word.append(int(voc["word_id"][final_id]))
+        node.append(nid if voc["weight"][final_id] > 0 else -1)
+    return np.asarray(word, np.int32).reshape(-1), np.asarray(node, np.int32).reshape(-1), n_shallow
+
+
+def feature_vector(node):
+    """DBoW2::FeatureVector from the per-keypoint form: addFeature(node[i], i) in ascending i for node[i] >= 0 (FeatureVector.cpp:31-44) - a std::map,
+    here (sorted node ids, {node: indices})"""
+    fv = {}
+    for i, v in enumerate(node):
+        if v >= 0:
+            fv.setdefault(int(v), []).append(i)
+    return sorted(fv), fv
+
+
+def search_by_bow_reference(KF, F, prm):
+    """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches): (match_kf[N] = the keyframe keypoint whose map point sits in vpMapPointMatches[k] or -1,
+    nmatches, trace).  KF: node, valid, angle, desc; F: node, angle, desc."""
+    N = len(F["node"])
+    dK, dF = as_ints(KF["desc"]), as_ints(F["desc"])
+    ratio = f32(prm["nn_ratio"])
+    vpMapPointMatches = np.full(N, -1, np.int64)
+    nmatches = 0
+    rotHist = [[] for _ in range(HISTO_LENGTH + 1)]
+    kf_keys, vFeatVecKF = feature_vector(KF["node"])
+    f_keys, vFeatVecF = feature_vector(F["node"])
+    tr = dict(node_pairs=0, distances=0, largest_node=0, claims=0, culled=0, ind=(-1, -1, -1), second_choice=0, ratio_fail=0)
+    KFit, Fit = 0, 0
+    while KFit != len(kf_keys) and Fit != len(f_keys):
+        if kf_keys[KFit] == f_keys[Fit]:
+            vIndicesKF, vIndicesF = vFeatVecKF[kf_keys[KFit]], vFeatVecF[f_keys[Fit]]
+            tr["node_pairs"] += 1
+            tr["largest_node"] = max(tr["largest_node"], len(vIndicesF))
+            for realIdxKF in vIndicesKF:
+                if not KF["valid"][realIdxKF]:
+                    continue
+                bestDist1, bestIdxF, bestDist2 = 256, -1, 256
+                freeDist, freeIdx = 256, -1                  # trace only: the best over all entries, matched or not
+                for realIdxF in vIndicesF:
+                    d_all = dist(dK[realIdxKF], dF[realIdxF])
+                    if d_all < freeDist:
+                        freeDist, freeIdx = d_all, realIdxF
+                    if vpMapPointMatches[realIdxF] >= 0:
+                        continue
+                    d = d_all
+                    tr["distances"] += 1
+                    if d < bestDist1:
+                        bestDist2 = bestDist1
+                        bestDist1 = d
+                        bestIdxF = realIdxF
+                    elif d < bestDist2:
+                        bestDist2 = d
+                if bestDist1 <= prm["th_low"] and bestIdxF >= 0:
+                    if f32(bestDist1) < f32(ratio * f32(bestDist2)):
+                        vpMapPointMatches[bestIdxF] = realIdxKF
+                        tr["second_choice"] += bestIdxF != freeIdx
+                        if prm["check_orientation"]:
+                            rotHist[rot_bin(KF["angle"][realIdxKF], F["angle"][bestIdxF])].append(bestIdxF)
+                        nmatches += 1
+                        tr["claims"] += 1
+                    else:
+                        tr["ratio_fail"] += 1
+            KFit += 1
+            Fit += 1
+        elif kf_keys[KFit] < f_keys[Fit]:
+            KFit = bisect_left(kf_keys, f_keys[Fit])         # vFeatVecKF.lower_bound(Fit->first)
+        else:
+            Fit = bisect_left(f_keys, kf_keys[KFit])
+    if prm["check_orientation"]:
+        ind = compute_three_maxima([len(h) for h in rotHist])
+        tr["ind"] = tuple(ind)
+        for i in range(HISTO_LENGTH + 1):
+            if i in ind:
+                continue
+            for k in rotHist[i]:
+                vpMapPointMatches[k] = -1
+                nmatches -= 1
+                tr["culled"] += 1
+    return vpMapPointMatches, nmatches, tr
+
+
+# ---- the restatement of the kernels ----
+def transform_restated(voc, desc, levels_up, lanes=BW_LANES):
+    """k_bow_transform: per level every lane's minimum of distance << 22 | child position over the children lane, lane + lanes, ..., then the minimum
+    over the lanes; at most depth_L levels"""
+    cs, ch = voc["child_start"], voc["children"]
+    D = _voc_ints(voc)
+    child_desc = [D[int(c)] for c in ch]                     # the vocabulary's device image: descriptors in child order
+    live = voc["weight"] > 0
+    nid_level = voc["depth_L"] - levels_up
+    word, node, n_shallow = [], [], 0
+    for f in as_ints(desc):
+        cur, nid, level = 0, 0, 0
+        for _ in range(voc["depth_L"]):
+            b, e = int(cs[cur]), int(cs[cur + 1])
+            if b == e:
+                break
+            keys = [min((dist(f, child_desc[c]) << BW_POS | (c - b) for c in range(b + lane, e, lanes)), default=2 ** 32 - 1) for lane in range(lanes)]
+            cur = int(ch[b + (min(keys) & (2 ** BW_POS - 1))])
+            level += 1
+            if level == nid_level:
+                nid = cur
+        assert cs[cur] == cs[cur + 1]
+        shallow = nid_level > 0 and level < nid_level
+        if nid_level <= 0:
+            nid = 0
+        elif shallow:
+            nid = cur
+        n_shallow += shallow
+        word.append(int(voc["word_id"][cur]))
+        node.append(nid if live[cur] else -1)
+    return np.asarray(word, np.int32).reshape(-1), np.asarray(node, np.int32).reshape(-1), n_shallow
+
+
+def bitonic_sort_restated(keys):
+    """bw_sort: merges of size 2, 4, ...; the first step of a merge pairs i with its mirror image in the block (i ^ (size - 1)), the others with
+    i ^ stride; every exchange leaves the minimum at the lower index, so the padding above n never moves and is never stored"""
+    k = [int(v) for v in keys]
+    n = len(k)
+    size = 2
+    while size // 2 < n:
+        stride = size // 2
+        while stride > 0:
+            for i in range(n):
+                l = i ^ (size - 1) if stride == size // 2 else i ^ stride
+                if i < l < n and k[l] < k[i]:
+                    k[i], k[l] = k[l], k[i]
+            stride //= 2
+        size *= 2
+    return k
+
+
+def sort_keys(node, network=False):
+    """k_bow_group: node << 18 | index of the keypoints in a node, ascending; the others (all ones) last"""
+    keys = [(int(v) << BW_IDX | i) if v >= 0 else 2 ** 64 - 1 for i, v in enumerate(node)]
+    return bitonic_sort_restated(keys) if network else sorted(keys)
+
+
+def search_by_bow_restated(KF, F, prm, rng=None, network=False):
+    """k_bow_group + k_bow_match + k_bow_resolve for one keyframe: (match_kf[N], nmatches, (node pairs, distances, largest node, (ind1..3)))"""
+    N = len(F["node"])
+    dK, dF = as_ints(KF["desc"]), as_ints(F["desc"])
+    ratio = f32(prm["nn_ratio"])
+    mask = 2 ** BW_IDX - 1
+    fs = [k for k in sort_keys(F["node"], network) if k != 2 ** 64 - 1]
+    ks = [k for k in sort_keys(KF["node"], network) if k != 2 ** 64 - 1]
+    heads = [p for p in range(len(ks)) if p == 0 or ks[p - 1] >> BW_IDX != ks[p] >> BW_IDX]
+    if rng is not None:
+        heads = [heads[i] for i in rng.permutation(len(heads))]      # one wave per node: any order
+    row = np.full(N, -1, np.int64)
+    pairs = distances = largest = 0
+    for p in heads:
+        v = ks[p] >> BW_IDX
+        fb, fe = bisect_left(fs, v << BW_IDX), bisect_left(fs, (v + 1) << BW_IDX)
+        m = fe - fb
+        if m == 0:
+            continue
+        pe = bisect_left(ks, (v + 1) << BW_IDX)
+        pairs += 1
+        largest = max(largest, m)
+        entry = [fs[fb + t] & mask for t in range(m)]
+        claimed = [False] * m
+        for q in range(p, pe):
+            j = ks[q] & mask
+            if not KF["valid"][j]:
+                continue
+            lanes = []
+            for lane in range(min(64, m)):
+                d1, d2, best = 256, 256, 2 ** 32 - 1
+                for t in range(lane, m, 64):
+                    if claimed[t]:
+                        continue
+                    d = dist(dK[j], dF[entry[t]])
+                    distances += 1
+                    if d < d1:
+                        d2, d1, best = d1, d, d << BW_IDX | t
+                    elif d < d2:
+                        d2 = d
+                lanes.append((d1, d2, best))
+            d1, d2, best = 256, 256, 2 ** 32 - 1
+            for o1, o2, ob in lanes:                         # the xor butterfly's step, folded
+                d2 = min(max(d1, o1), min(d2, o2))
+                d1 = min(d1, o1)
+                best = min(best, ob)
+            if best == 2 ** 32 - 1 or d1 > prm["th_low"] or not f32(d1) < f32(ratio * f32(d2)):
+                continue
+            t = best & mask
+            claimed[t] = True
+            row[entry[t]] = j
+    ind = (-1, -1, -1)
+    nmatches = int((row >= 0).sum())
+    if prm["check_orientation"]:
+        bins = {int(k): rot_bin(KF["angle"][row[k]], F["angle"][k]) for k in np.nonzero(row >= 0)[0]}
+        hist = [0] * (HISTO_LENGTH + 1)
+        for b in bins.values():
+            hist[b] += 1
+        ind = tuple(compute_three_maxima(hist))
+        for k, b in bins.items():
+            if b not in ind:
+                row[k] = -1
+                nmatches -= 1
+    return row, nmatches, (pairs, distances, largest, ind)
+
+
+def agree(ref, res):
+    assert np.array_equal(ref[0], res[0]) and ref[1] == res[1], (ref[1], res[1])
+    tr = ref[2]
+    assert (tr["node_pairs"], tr["distances"], tr["largest_node"], tr["ind"]) == res[2], (tr, res[2])
+    return res[2]
+
+
+# ---- random cases ----
+def flip_bits(rng, desc, lo, hi):
+    bits = np.unpackbits(np.ascontiguousarray(desc, np.uint8), axis=1)
+    for i, nb in enumerate(rng.integers(lo, hi, len(bits))):
+        bits[i, rng.choice(256, int(nb), replace=False)] ^= 1
+    return np.packbits(bits, axis=1)
+
+
+def random_voc(rng):
+    """k in 1..12, L in 1..5, uniform (kept below 3000 nodes) or ragged, with duplicated child descriptors and zero weights"""
+    while True:
+        k, L = int(rng.integers(1, 13)), int(rng.integers(1, 6))
+        ragged = bool(rng.random() < 0.5)
+        if ragged or sum(k ** l for l in range(L + 1)) <= 3000:
+            break
+    return V.random_tree(int(rng.integers(1 << 30)), k, L, ragged=ragged, tie=float(rng.choice([0.0, 0.3, 0.8])), zero_weight=float(rng.choice([0.0, 0.1, 0.5])),
+                         leaf_prob=float(rng.choice([0.1, 0.4])), max_nodes=600)
+
+
+def random_sides(rng, voc, levels_up, n_f, n_k):
+    """a frame and a keyframe drawn from one pool of descriptors (0..12 bits flipped), each descriptor taken down the tree"""
+    pool = rng.integers(0, 256, (max(1, (n_f + n_k) // 3), 32), dtype=np.uint8)
+    near = rng.random(len(pool)) < 0.3                       # some of the pool next to the tree's own descriptors
+    pool[near] = voc["descriptors"][rng.integers(1, voc["n_nodes"], int(near.sum()))]
+    sides = []
+    base_angle = rng.uniform(0, 360, len(pool))
+    for n in (n_f, n_k):
+        src = rng.integers(0, len(pool), n)
+        desc = flip_bits(rng, pool[src], 0, 13) if n else np.zeros((0, 32), np.uint8)
+        ang = np.mod(base_angle[src] + np.where(rng.random(n) < 0.25, rng.uniform(0, 360, n), 14.0), 360.0).astype(np.float32)
+        sides.append(dict(desc=desc, angle=ang, node=transform_reference(voc, desc, levels_up)[1]))
+    F, KF = sides
+    KF["valid"] = (rng.random(n_k) < 0.9).astype(np.uint8)
+    return KF, F
+
+
+@pytest.mark.parametrize("block", range(8))
+def test_restatements_equal_the_transcriptions_on_random_cases(block):
+    """8 x 250 = 2000 seeded cases: k 1..12, L 1..5, uniform and ragged trees, levels_up 0..L + 1, 0..400 keypoints, tied children, zero weights"""
+    rng = np.random.default_rng(1000 + block)
+    seen = dict(matches=0, shallow=0, stopped=0, culled=0, second_choice=0, ratio_fail=0, big_node=0, root=0)
+    for case in range(250):
+        voc = random_voc(rng)
+        levels_up = int(rng.integers(0, voc["depth_L"] + 2))
+        n_f, n_k = (int(400 * rng.random() ** 4) for _ in range(2))
+        if case % 50 == 0:
+            n_f, n_k = 400, 400
+        if case % 50 == 1:
+            n_f = 0
+        KF, F = random_sides(rng, voc, levels_up, n_f, n_k)
+        for side in (F, KF):
+            ref = transform_reference(voc, side["desc"], levels_up)
+            res = transform_restated(voc, side["desc"], levels_up)
+            assert np.array_equal(ref[0], res[0]) and np.array_equal(ref[1], res[1]) and ref[2] == res[2]
+            seen["shallow"] += ref[2]
+            seen["stopped"] += int((ref[1] == -1).sum())
+            seen["root"] += levels_up >= voc["depth_L"] and len(ref[1]) > 0
+        prm = default_params(nn_ratio=f32(rng.choice([0.7, 0.75, 0.9, 0.5])), th_low=int(rng.choice([50, 30, 80])), check_orientation=int(rng.random() < 0.7))
+        ref = search_by_bow_reference(KF, F, prm)
+        st = agree(ref, search_by_bow_restated(KF, F, prm, rng=rng, network=case % 5 == 0))
+        seen["matches"] += ref[1]
+        seen["big_node"] += st[2] > 64
+        for k in ("culled", "second_choice", "ratio_fail"):
+            seen[k] += ref[2][k]
+    assert all(v > 0 for v in seen.values()), seen
+
+
+def test_the_sorting_network_sorts_every_length():
+    rng = np.random.default_rng(5)
+    for n in list(range(0, 70)) + [127, 128, 129, 255, 300, 513]:
+        keys = [int(v) for v in rng.integers(0, 50, n)]
+        assert bitonic_sort_restated(keys) == sorted(keys), n
+
+
+# ---- constructed cases: the transform ----
+def tree_from_parents(parent, desc, weight, L):
+    """a vocabulary from explicit parents (node ids in order), a node without children being a leaf"""
+    n = len(parent)
+    is_leaf = ~np.isin(np.arange(n), np.asarray(parent[1:]))
+    is_leaf[0] = False
+    return V._finish(parent, is_leaf, desc, weight, 0, L)
+
+
+def _bits(d, start=0):
+    """a descriptor with exactly d bits set from bit `start` on: its distance to the zero descriptor is d"""
+    b = np.zeros(256, np.uint8)
+    b[start:start + d] = 1
+    return np.packbits(b)
+
+
+def both_transforms(voc, desc, levels_up):
+    ref = transform_reference(voc, desc, levels_up)
+    res = transform_restated(voc, desc, levels_up)
+    assert np.array_equal(ref[0], res[0]) and np.array_equal(ref[1], res[1]) and ref[2] == res[2]
+    return ref
+
+
+def tied_tree(k=17, L=3):
+    """every inner node's first and last child carry the same descriptor, the children between them its complement: the first child wins at every level"""
+    t = V.random_tree(3, k, L)
+    d0 = _bits(100, 17)
+    for i in range(t["n_nodes"]):
+        c = t["children"][t["child_start"][i]:t["child_start"][i + 1]]
+        if len(c):
+            t["descriptors"][c] = ~d0
+            t["descriptors"][c[0]] = d0
+            t["descriptors"][c[-1]] = d0
+    return t, d0
+
+
+def test_a_tie_between_the_first_and_the_last_child_at_every_level():
+    t, d0 = tied_tree()
+    desc = flip_bits(np.random.default_rng(0), np.repeat(d0[None], 20, 0), 0, 9)
+    for levels_up in range(0, 5):
+        word, node, shallow = both_transforms(t, desc, levels_up)
+        # always the first child: the leftmost leaf (word 0), and the leftmost node of the level
+        first = [0]
+        for _ in range(3):
+            first.append(int(t["children"][t["child_start"][first[-1]]]))
+        assert (word == 0).all() and shallow == 0 and (node == first[max(3 - levels_up, 0)]).all()
+
+
+def chain_and_shallow_tree():
+    """root -> 1 (one child) -> 2 -> 3 (leaf, depth 3); root -> 4 (leaf at depth 1, stopped); root -> 5 (leaf at depth 1)"""
+    parent = [0, 0, 1, 2, 0, 0]
+    desc = np.stack([_bits(0), _bits(0), _bits(7), _bits(9), _bits(64, 64), _bits(64, 160)])
+    return tree_from_parents(parent, desc, np.array([0, 0, 0, 2.5, 0.0, 1.0]), 3)
+
+
+def test_one_child_shallow_leaf_root_case_and_stopped_word():
+    t = chain_and_shallow_tree()
+    desc = np.stack([_bits(3), _bits(60, 64), _bits(60, 160)])           # down the chain, to the stopped leaf, to the shallow leaf
+    word, node, shallow = both_transforms(t, desc, 0)                    # node level 3
+    assert list(word) == [0, 1, 2] and list(node) == [3, -1, 5] and shallow == 2      # the stopped leaf is shallow too, and stopped wins
+    word, node, shallow = both_transforms(t, desc, 1)                    # node level 2: node 2 on the chain
+    assert list(node) == [2, -1, 5] and shallow == 2
+    word, node, shallow = both_transforms(t, desc, 2)                    # node level 1: the leaves at depth 1 are at the level
+    assert list(node) == [1, -1, 5] and shallow == 0
+    for levels_up in (3, 4, 9):                                          # the root case
+        word, node, shallow = both_transforms(t, desc, levels_up)
+        assert list(word) == [0, 1, 2] and list(node) == [0, -1, 0] and shallow == 0
+
+
+# ---- constructed cases: the matcher ----
+def sides(kf_dist, f_dist, kf_node=None, f_node=None, kf_angle=None, f_angle=None, valid=None):
+    """keyframe keypoints with the zero descriptor... unless kf_dist gives bits to set; frame keypoint k at distance f_dist[k] from the zero descriptor"""
+    nk, nf = len(kf_dist), len(f_dist)
+    KF = dict(desc=np.stack([_bits(d) for d in kf_dist]), node=np.asarray(kf_node if kf_node is not None else [0] * nk, np.int32),
+              angle=np.asarray(kf_angle if kf_angle is not None else [0] * nk, np.float32), valid=np.asarray(valid if valid is not None else [1] * nk, np.uint8))
+    F = dict(desc=np.stack([_bits(d) for d in f_dist]), node=np.asarray(f_node if f_node is not None else [0] * nf, np.int32),
+             angle=np.asarray(f_angle if f_angle is not None else [0] * nf, np.float32))
+    return KF, F
+
+
+def both_searches(KF, F, prm):
+    ref = search_by_bow_reference(KF, F, prm)
+    agree(ref, search_by_bow_restated(KF, F, prm, rng=np.random.default_rng(0), network=True))
+    return ref
+
+
+CONSTRUCTED = {
+    # name: (sides(...), params, match_kf, nmatches)
+    "second keyframe keypoint takes its next best": (sides([0, 0], [5, 20, 40]), default_params(), [0, 1, -1], 2),
+    "second keyframe keypoint fails the ratio on what is left": (sides([0, 0], [5, 20, 25]), default_params(), [0, -1, -1], 1),
+    "a tie of bestDist1 fails the ratio": (sides([0], [10, 10, 40]), default_params(), [-1, -1, -1], 0),
+    "bestDist1 == th_low claims": (sides([0], [50]), default_params(), [0], 1),
+    "bestDist1 == th_low + 1 does not": (sides([0], [51]), default_params(), [-1], 0),
+    "a ratio product exactly equal": (sides([0], [10, 20]), default_params(nn_ratio=f32(0.5)), [-1, -1], 0),
+    "just under the equal product": (sides([0], [9, 20]), default_params(nn_ratio=f32(0.5)), [0, -1], 1),
+    "an invalid keyframe keypoint is skipped": (sides([0, 0], [5, 20], valid=[0, 1]), default_params(), [1, -1], 1),
+    "nodes on one side only": (sides([0, 0, 0], [5, 5, 5], kf_node=[1, 5, -1], f_node=[2, 5, -1]), default_params(), [-1, 1, -1], 1),
+    # 11 matches with rotation 0 and one with rotation 90, each in a node of its own: 1 < 0.1 * 11 culls it
+    "a match culled by orientation": (sides([0] * 12, [3] * 12, kf_node=range(12), f_node=range(12), kf_angle=[10] * 11 + [100], f_angle=[10] * 12),
+                                      default_params(), list(range(11)) + [-1], 11),
+    "the same without check_orientation": (sides([0] * 12, [3] * 12, kf_node=range(12), f_node=range(12), kf_angle=[10] * 11 + [100], f_angle=[10] * 12),
+                                           default_params(check_orientation=0), list(range(12)), 12),
+    # rot = 900 rounds to bin 30, which is bin 0; rot = 1200 is bin 40: never kept
+    "an angle difference that rounds to bin 30": (sides([0, 0, 0], [3, 3, 3], kf_node=[0, 1, 2], f_node=[0, 1, 2], kf_angle=[900, 5, 1200], f_angle=[0, 0, 0]),
+                                                  default_params(), [0, 1, -1], 2),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CONSTRUCTED))
+def test_constructed_matcher_cases(name):
+    (KF, F), prm, want, count = CONSTRUCTED[name]
+    ref = both_searches(KF, F, prm)
+    assert list(ref[0]) == want and ref[1] == count, (name, ref[0], ref[1])
+
+
+def single_node_case(n=360, seed=4):
+    """levels_up >= L: every keypoint with a live word lands in node 0 - one node of more than 300 entries on both sides"""
+    rng = np.random.default_rng(seed)
+    voc = V.random_tree(11, 5, 2, zero_weight=0.1)
+    KF, F = random_sides(rng, voc, 2, n, n)
+    return voc, KF, F
+
+
+def test_levels_up_at_least_L_makes_one_large_node():
+    voc, KF, F = single_node_case()
+    assert set(F["node"]) <= {0, -1} and (F["node"] == 0).sum() >= 300 and (F["node"] == -1).any()
+    for prm in (default_params(), default_params(nn_ratio=f32(0.9), check_orientation=0)):
+        ref = both_searches(KF, F, prm)
+        assert ref[1] > 20 and ref[2]["node_pairs"] == 1 and ref[2]["largest_node"] == (F["node"] == 0).sum() and ref[2]["second_choice"] > 0
+
+
+# ---- the text format ----
+def test_load_text_reads_back_what_save_text_wrote(tmp_path):
+    for seed, kw in ((1, dict(ragged=True, tie=0.3, zero_weight=0.2)), (2, dict())):
+        t = V.random_tree(seed, 4, 3, **kw)
+        p = str(tmp_path / ("voc%d.txt" % seed))
+        V.save_text(p, t, scoring=0, weighting=0)
+        head = open(p).readline().split()
+        assert head == ["4", "3", "0", "0"]
+        u = V.load_text(p)
+        assert u["n_nodes"] == t["n_nodes"] and u["depth_L"] == 3 and u["k"] == 4
+        for key in ("child_start", "children", "descriptors", "word_id", "weight"):
+            assert np.array_equal(t[key], u[key]) and t[key].dtype == u[key].dtype, key
+    # node ids 1, 2, .. in line order, word ids in the order of the leaves, children in line order
+    p = str(tmp_path / "hand.txt")
+    zeros = " ".join(["0"] * 32)
+    open(p, "w").write("2 2 0 0\n0 0 %s 0\n0 1 %s 1.5\n\n1 1 %s 0.25\n1 1 %s 0\n" % (zeros, zeros, zeros, zeros))
+    u = V.load_text(p)
+    assert list(u["child_start"]) == [0, 2, 4, 4, 4, 4] and list(u["children"]) == [1, 2, 3, 4] and list(u["word_id"]) == [-1, -1, 0, 1, 2]
+    assert list(u["weight"]) == [0, 0, 1.5, 0.25, 0]
+
+
+# ---- real frames: the inputs of tests/test_gpu_bow.py, on the CPU oracle's extraction ----
+REAL_SEED = 41                                     # synth_stereo_pair seed; the vocabulary's sample and centres use VOC_SEED
+VOC_SEED = 7
+
+
+def frame_side(kp, desc):
+    """node-less side of one extraction: descriptors and the angle row (float bits) of the keypoint SoA"""
+    n = len(kp) // 6
+    return dict(desc=np.asarray(desc, np.uint8).reshape(n, 32).copy(), angle=kp[3 * n:4 * n].astype(np.int32).view(np.float32).copy())
+
+
+def sampled_voc(desc, seed=VOC_SEED, k=10, L=3):
+    """the vocabulary of the real-frame tests: from a seeded sample of half the left image's descriptors"""
+    rng = np.random.default_rng(seed)
+    sample = desc[rng.choice(len(desc), len(desc) // 2, replace=False)]
+    return V.sampled_tree(seed, sample, k, L)
+
+
+def test_real_frames_on_the_oracle_extraction(po, configs):
+    from jetson_slam_amd.synth import synth_stereo_pair
+    c = configs["c1"]
+    frames = []
+    for img in synth_stereo_pair(REAL_SEED, c["h"], c["w"]):
+        o = po.OracleExtractor(height=c["h"], width=c["w"], n_levels=c["L"], tile_h=c["tile"], tile_w=c["tile"], th_fast_max=c["th"])
+        o.extract(img)
+        frames.append(frame_side(o.keypoints().copy(), o.descriptors().copy()))
+    left, right = frames
+    voc = sampled_voc(left["desc"])
+    assert voc["depth_L"] == 3 and voc["child_start"][1] == 10
+    for s in frames:
+        ref = both_transforms(voc, s["desc"], 1)
+        s["word"], s["node"] = ref[0], ref[1]
+        s["valid"] = np.ones(len(s["node"]), np.uint8)
+        assert (s["node"] >= 0).all()
+    # the frame against itself: a keypoint whose descriptor is unique in its node matches itself
+    ref = both_searches(left, left, default_params())
+    ints = as_ints(left["desc"])
+    by_node = {}
+    for i, v in enumerate(left["node"]):
+        by_node.setdefault(int(v), []).append(ints[i])
+    unique = [i for i, v in enumerate(left["node"]) if by_node[int(v)].count(ints[i]) == 1]
+    assert len(unique) > 100 and all(ref[0][i] == i for i in unique) and ref[1] >= len(unique)
+    # left as the keyframe of the right image: TrackReferenceKeyFrame's own bar (Tracking.cpp:931) so that the device comparison is not vacuous
+    for ratio in (0.7, 0.75):
+        for rot in (1, 0):
+            ref = both_searches(left, right, default_params(nn_ratio=f32(ratio), check_orientation=rot))
+            assert ref[1] >= 15, (ratio, rot, ref[1])
+    assert ref[2]["node_pairs"] > 20
+
+
+# ---- the declarations ----
+NAMES = ("jsorb_bow_build_caps", "jsorb_vocabulary_create", "jsorb_vocabulary_destroy", "jsorb_vocabulary_info", "jsorb_bow_transform_descriptors", "jsorb_bow_transform_async",
+         "jsorb_bow_word_device", "jsorb_bow_node_device", "jsorb_copy_bow", "jsorb_bow_transform_stats", "jsorb_search_by_bow_async",
+         "jsorb_search_by_bow", "jsorb_search_by_bow_stats")
+
+
+def test_header_binding_and_build_declare_the_new_entry_points(orb):
+    lib = ctypes.CDLL(os.path.join(ROOT, "jetson_slam_amd", "libjsorb.so"))
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "jsorb.h")).read(), flags=re.S)
+    src = open(orb.__file__).read()
+    for n in NAMES:
+        assert hasattr(lib, n) and n in orb.EXPORTS and re.search(r"\b%s\s*\(" % n, hdr) and '"%s": (' % n in src, n
+    assert ctypes.sizeof(orb.JsorbBowParams) == 12
+    assert "enum { JSORB_K_BOW_TRANSFORM = JSORB_K_ID_COUNT + 1, JSORB_K_BOW_GROUP, JSORB_K_BOW_MATCH, JSORB_K_BOW_RESOLVE, JSORB_K_ID_ALL };" in hdr
+    lib.jsorb_kernel_name.restype = ctypes.c_char_p
+    ids = (orb.K_BOW_TRANSFORM, orb.K_BOW_GROUP, orb.K_BOW_MATCH, orb.K_BOW_RESOLVE)
+    assert [lib.jsorb_kernel_name(k) for k in ids + (ids[0] - 1, ids[-1] + 1)] == [b"k_bow_transform", b"k_bow_group", b"k_bow_match", b"k_bow_resolve", b"", b""]
+    for m in ("bow_transform", "bow", "bow_transform_stats", "search_by_bow", "search_by_bow_host", "search_by_bow_stats", "bow_kernel_times"):
+        assert callable(getattr(orb.ORBExtractor, m))
+    assert callable(orb.bow_transform_descriptors) and callable(orb.make_bow_params) and callable(orb.Vocabulary)
+    from jetson_slam_amd import build as jb
+    assert "k_bow.hip" in jb.SOURCES and "jsorb_bow.hip" in jb.SOURCES and jb.VARIANTS["tiny_bow_wave"] == (["-DBW_NODE_REGS=1"], ["k_bow.hip"])
+    assert "track_reference_keyframe" in jb.EXAMPLES and jb.VARIANTS["tiny_bow_sort"] == (["-DBW_SORT_LDS=64"], ["k_bow.hip"])
+    assert orb.bow_build_caps() == (BW_NODE_REGS, BW_SORT_LDS)
+    ksrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "k_bow.hip")).read()
+    for name, val in (("BW_NODE_REGS", BW_NODE_REGS), ("BW_LANES", BW_LANES), ("BW_POS", BW_POS), ("BW_IDX", BW_IDX), ("BW_SORT_LDS", BW_SORT_LDS)):
+        assert re.search(r"#define %s %d\b" % (name, val), ksrc), name
+    shim = open(os.path.join(ROOT, "include", "jsorb_compat.hpp")).read()
+    assert re.search(r"inline int SearchByBoW\(", shim) and re.search(r"inline void ComputeBoW\(", shim) and re.search(r"class Vocabulary \{", shim)
+
+
+def test_example_compiles_against_the_opencv_double(orb, tmp_path):
+    from jetson_slam_amd import build as jb
+    exe = jb.build_example("track_reference_keyframe", str(tmp_path / "track_reference_keyframe"), ["-I", os.path.join(ROOT, "tests", "cpp", "opencv_double")])
+    assert os.path.exists(exe)
+
+
+def voc_create(lib, t, levels_up=1, **over):
+    """jsorb_vocabulary_create on a tree's arrays with some replaced -> (rc, handle)"""
+    a = dict(n_nodes=t["n_nodes"], depth_L=t["depth_L"], child_start=t["child_start"], children=t["children"], descriptors=t["descriptors"],
+             word_id=t["word_id"], weight=t["weight"])
+    a.update(over)
+    v = ctypes.c_void_p()
+    keep = [np.ascontiguousarray(a[k]) if a[k] is not None else None for k in ("child_start", "children", "descriptors", "word_id", "weight")]
+    rc = lib.jsorb_vocabulary_create(0, a["n_nodes"], a["depth_L"], levels_up, *[None if x is None else x.ctypes.data for x in keep], ctypes.byref(v))
+    return rc, v
+
+
+def bad_vocabularies():
+    """(name, overrides) that jsorb_vocabulary_create must refuse - before it touches a device"""
+    t = V.random_tree(1, 3, 2)                                           # 13 nodes: root, 3 inner, 9 leaves
+    ch, cs = t["children"], t["child_start"]
+    dup = ch.copy(); dup[5] = dup[4]                                     # a child id twice (another never)
+    zero = ch.copy(); zero[0] = 0                                        # the root as a child
+    big = ch.copy(); big[0] = 13
+    word = t["word_id"].copy(); word[12] = -1                            # a leaf without a word
+    desc_cs = cs.copy(); desc_cs[3] = desc_cs[2] - 1                     # offsets not ascending
+    short_cs = cs.copy(); short_cs[-1] -= 1
+    cases = [("n_nodes < 2", dict(n_nodes=1)), ("depth_L 0", dict(depth_L=0)), ("depth_L 17", dict(depth_L=17)), ("deeper than depth_L", dict(depth_L=1)),
+             ("duplicate child", dict(children=dup)), ("root as child", dict(children=zero)), ("child id out of range", dict(children=big)),
+             ("leaf without word", dict(word_id=word)), ("offsets descend", dict(child_start=desc_cs)), ("offsets short", dict(child_start=short_cs)),
+             ("NULL array", dict(weight=None))]
+    # every id once, but nodes 2 and 3 are each other's child: not reached from the root
+    cyc = dict(n_nodes=4, depth_L=3, child_start=np.array([0, 1, 1, 2, 3], np.int32), children=np.array([1, 3, 2], np.int32),
+               descriptors=np.zeros((4, 32), np.uint8), word_id=np.array([-1, 0, -1, -1], np.int32), weight=np.ones(4))
+    return t, cases + [("a cycle beside the tree", cyc)]
+
+
+def test_validation_without_a_device(orb):
+    """argument checks that need no GPU: null handles and arrays that are no tree"""
+    lib = orb.load_library()
+    prm = orb.make_bow_params()
+    assert (prm.th_low, prm.check_orientation) == (50, 1) and abs(prm.nn_ratio - 0.7) < 1e-7
+    t, cases = bad_vocabularies()
+    for name, over in cases:
+        rc, v = voc_create(lib, t, **over)
+        assert rc == -1 and not v.value, name
+    assert voc_create(lib, t, levels_up=-1)[0] == -1
+    assert lib.jsorb_vocabulary_create(0, 13, 2, 1, None, None, None, None, None, None) == -1
+    lib.jsorb_vocabulary_destroy(None)
+    assert lib.jsorb_vocabulary_info(None, None, None, None, None, None) != 0
+    assert lib.jsorb_bow_transform_descriptors(None, None, 0, None, None, None) != 0
+    assert lib.jsorb_bow_transform_async(None, 0, None) != 0 and lib.jsorb_bow_transform_stats(None, None) != 0
+    assert not lib.jsorb_bow_word_device(None, 0) and not lib.jsorb_bow_node_device(None, 0) and lib.jsorb_copy_bow(None, 0, None, None) != 0
+    ks = np.zeros(2, np.int32)
+    assert lib.jsorb_search_by_bow_async(None, 0, ctypes.byref(prm), None, 1, ks.ctypes.data, *([None] * 6)) != 0
+    assert lib.jsorb_search_by_bow(None, 0, ctypes.byref(prm), None, 1, ks.ctypes.data, *([None] * 6)) != 0
+    assert lib.jsorb_search_by_bow_stats(None, None, None, None, None) != 0
+    with pytest.raises(orb.JsorbError):
+        orb.Vocabulary(dict(t, word_id=t["word_id"][:-1]))
