@@ -203,7 +203,11 @@ const float *jsorb_rgbd_uright_device(const jsorb_extractor *e, int image);
 const float *jsorb_rgbd_depth_device(const jsorb_extractor *e, int image);
 int jsorb_copy_rgbd(const jsorb_extractor *e, int image, float *u_right, float *depth);
 
-/* ---- results (valid after a synchronous call or jsorb_sync, until the next extract on the handle) ---- */
+/* ---- results (valid after a synchronous call or jsorb_sync, until the next extract on the handle) ----
+ * Work the library enqueued on the handle that reads an extract's results (the matchers, jsorb_bow_transform_async, jsorb_init_reference_set, ...)
+ * completes before the next extract overwrites them, with no wait needed from the caller: extract, matcher, next extract - of any batch size, on
+ * the handle's own stream or on one given with jsorb_set_stream - may be enqueued back to back.  (Buffers the CALLER reads on a stream of its own
+ * are the caller's to order: jsorb_stream_wait_done.) */
 int jsorb_n_images(const jsorb_extractor *e);
 int jsorb_n_keypoints(const jsorb_extractor *e, int image);
 int jsorb_level_n_keypoints(const jsorb_extractor *e, int image, int level);

@@ -653,6 +653,10 @@ int jsorb_set_stream(jsorb_extractor *e, void *hip_stream)
     if (ns != e->stream && e->extracted) {      // the new main stream continues after whatever the old one (and the lanes) were doing
         HIPCHK(e, hipSetDevice(e->device));
         RCCHK(wait_lanes(e, ns, e));
+        if (e->lanes.main_stream_dirty) {       // ... and after the readers of the last results the old one still carries (the mark stays: the lanes have not seen them)
+            HIPCHK(e, hipEventRecord(e->lanes.ev_fork, e->stream));
+            HIPCHK(e, hipStreamWaitEvent(ns, e->lanes.ev_fork, 0));
+        }
     }
     e->stream = ns;
     return JSORB_OK;
@@ -677,6 +681,7 @@ int jsorb_sync(jsorb_extractor *e)
     if (e->extracted)
         for (int j = 0; j < e->lanes.K; j++) HIPCHK(e, hipStreamSynchronize(lane_stream(e, j)));
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->lanes.main_stream_dirty = false;       // nothing is left on the main stream for the next batch's lanes to wait for
     e->counts_synced = true;
     mirrors_landed(e);
     return drain_timed(e);

@@ -162,6 +162,7 @@ int jsorb_bow_transform_async(jsorb_extractor *e, int image, const jsorb_vocabul
     RCCHK(bow_reserve_ids(e));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the descriptors may come from the lanes of a batch
+    mark_main_stream(e);               // ... and the next batch's lanes must not rewrite them before the kernel has read them
     const int first = image < 0 ? 0 : image, count = image < 0 ? e->n_images : 1, CW = JSORB_MAX_LEVELS + 1;
     const size_t T = (size_t)e->g.T;
     HIPCHK(e, hipMemsetAsync(bow_shallow(e), 0, sizeof(int), st));
@@ -234,6 +235,7 @@ int jsorb_search_by_bow_async(jsorb_extractor *e, int image, const jsorb_bow_par
     RCCHK(reserve_device(e, e->bow.ksort, (size_t)std::max(total, 1) * sizeof(unsigned long long), &e->bow.kf_cap, std::max(total, 1)));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
+    mark_main_stream(e);
     HIPCHK(e, hipMemsetAsync(e->bow.stats, 0, BOW_STATS * sizeof(int), st));
     e->bow.done = true;
     if (n_keyframes == 0) return JSORB_OK;

@@ -99,15 +99,18 @@ int plan_lanes(const jsorb_extractor *e, int n, int *first)
 }
 
 // Orders the lanes of a NEW batch (K lanes over n images) after everything that touched the handle's buffers before:
-//  * work the caller (or this handle) enqueued on the main stream: lanes >= 1 wait for a fork event recorded on lane 0
+//  * work the caller enqueued on a main stream of its own, or readers of the last results this handle enqueued on its main stream
+//    (mark_main_stream): every lane that is not the main stream waits for a fork event recorded there
 //  * the previous batch of this handle, when its lane partition differs (same partition: same-stream order is enough)
 //  * a stereo match enqueued on ANOTHER handle's lanes that may still read this handle's previous results
 //  * `input_ready` (optional, one event per lane): e.g. the upload of the lane's images on the copy stream
 int order_lanes_for_new_batch(jsorb_extractor *e, int K, int n, const hipStream_t *ls, const hipEvent_t *input_ready)
 {
     if ((K > 1 || ls[0] != e->stream) && (e->stream != e->own_stream || e->lanes.main_stream_dirty)) {
-        // a caller-provided main stream (or copies this call put on the main stream) may carry work the images depend on.  The
-        // handle's OWN stream only ever carries this handle's work, which the lanes order themselves against below.
+        // a caller-provided main stream may carry work the images depend on.  The handle's OWN stream carries this handle's work only: single frames
+        // and one-lane batches, which the lanes order themselves against below through their `done` events - and whatever the library enqueued there
+        // behind the last extract to read its results (matchers, BoW transform, the kept initial frame: mark_main_stream), which no `done` event covers
+        // and which must have read out_kp / desc / counts / cam.un before this batch rewrites them.
         HIPCHK(e, hipEventRecord(e->lanes.ev_fork, e->stream));
         for (int j = 0; j < K; j++)
             if (ls[j] != e->stream) HIPCHK(e, hipStreamWaitEvent(ls[j], e->lanes.ev_fork, 0));
@@ -513,6 +516,7 @@ int unpack_frame(jsorb_extractor *e, int image, jsorb_keypoint *keys, jsorb_keyp
     }
     HIPCHK(e, hipSetDevice(e->device));
     std::vector<float> xy(un ? (size_t)2 * n : 0);
+    mark_main_stream(e);
     if (out) {
         RCCHK(reserve_device(e, e->res.frame_aos, (size_t)e->g.T * sizeof(jsorb_keypoint)));
         launch_unpack_keypoints(jsorb_keypoints_device(e, image), n, e->res.frame_aos, e->stream);

@@ -178,6 +178,7 @@ int jsorb_set_camera(jsorb_extractor *e, const jsorb_camera *camera)
     RCCHK(reserve_device(e, e->cam.un, (size_t)e->B * 2 * T * sizeof(float)));
     RCCHK(reserve_pinned(e, e->cam.h_un, 2 * T * sizeof(float)));
     if (e->extracted && e->n_images > 0) {      // the results already there are undistorted with the new camera (device copy only)
+        mark_main_stream(e);
         launch_undistort(e->cam.c, e->out_kp, e->counts, (int)T, e->cam.un, nullptr, e->n_images, e->stream);
         HIPCHK(e, hipGetLastError());
         HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -286,6 +287,7 @@ int jsorb_assign_features_to_grid(jsorb_extractor *e, int image, float min_x, fl
     const int n = jsorb_n_keypoints(e, image), n_cells = cols * rows;
     HIPCHK(e, hipSetDevice(e->device));
     RCCHK(grid_reserve(e, n_cells));
+    mark_main_stream(e);
     launch_assign_grid(jsorb_keypoints_device(e, image), jsorb_keypoints_un_device(e, image), n, min_x, min_y, grid_element_width_inv, grid_element_height_inv, cols, rows,
                        e->grid.start, e->grid.items, e->stream);
     HIPCHK(e, hipGetLastError());
@@ -323,6 +325,7 @@ int jsorb_search_local_points_async(jsorb_extractor *e, int image, const jsorb_s
     RCCHK(reserve_device(e, e->sl.stats, 4 * sizeof(int)));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the frame (and its uRight) may come from the lanes of a batch
+    mark_main_stream(e);               // ... and the next batch's lanes must not rewrite it before these kernels have read it
     const float *xy_un = jsorb_keypoints_un_device(e, image);
     TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
                                                      e->grid.start, e->grid.items, st));
@@ -420,6 +423,7 @@ int jsorb_search_last_frame_async(jsorb_extractor *e, int image, const jsorb_las
     }
     RCCHK(reserve_device(e, e->lf.pts, (size_t)2 * std::max(n_points, 1) * sizeof(int), &e->lf.points, std::max(n_points, 1)));
     RCCHK(wait_lanes(e, st, e));       // the frame (and its uRight) may come from the lanes of a batch
+    mark_main_stream(e);               // ... and the next batch's lanes must not rewrite it before these kernels have read it
     const float *xy_un = jsorb_keypoints_un_device(e, image);
     TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
                                                      e->grid.start, e->grid.items, st));
@@ -517,6 +521,7 @@ int jsorb_search_for_initialization_async(jsorb_extractor *e, int image, const j
     RCCHK(reserve_device(e, e->si.ws, (2 * T + SI_STATS) * sizeof(int)));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
+    mark_main_stream(e);
     const float *xy_un = jsorb_keypoints_un_device(e, image);
     TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
                                                      e->grid.start, e->grid.items, st));
@@ -606,6 +611,7 @@ int jsorb_init_reference_set(jsorb_extractor *e, int image)
     RCCHK(reserve_device(e, e->si.ref, (size_t)48 * cap, &e->si.ref_cap, cap));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));
+    mark_main_stream(e);
     if (n > 0) {
         const int32_t *soa = jsorb_keypoints_device(e, image);
         HIPCHK(e, hipMemcpyAsync(ref_desc(e), jsorb_descriptors_device(e, image), (size_t)32 * n, hipMemcpyDeviceToDevice, st));

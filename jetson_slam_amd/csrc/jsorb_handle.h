@@ -102,7 +102,7 @@ struct jsorb_extractor {
         bool has_readers = false;
         int readers_K = 0, readers_n = 0;
         int cap = JSORB_MAX_LANES;         // transient: cap for the batch being enqueued
-        bool main_stream_dirty = false;    // this call enqueued input copies on the main stream: the lanes must fork after them
+        bool main_stream_dirty = false;    // the main stream carries work the lanes' `done` events do not cover (mark_main_stream): the next batch's lanes fork after it
         int order = -1;                    // schedule of the last batch (jsorb_handle_forms): lane order, lanes that ran k_blur_compact / k_blur before k_detect
         unsigned fuse_bc_mask = 0, blur_first_mask = 0;
     } lanes;
@@ -355,6 +355,13 @@ inline int fork_lanes(jsorb_extractor *e, hipStream_t s, std::initializer_list<c
             }
     return JSORB_OK;
 }
+
+// Work that reads the last extract's results was enqueued on the main stream outside run_pipeline (a matcher, a transform, a copy into kept
+// buffers): the lanes' `done` events were recorded before it, so the pool lanes of the next multi-lane batch - which rewrites those results -
+// must fork behind it (order_lanes_for_new_batch), and a new main stream must continue after it (jsorb_set_stream).  A flag, not a fork on
+// every batch: a batch that follows only batches and stereo matches (which run on the lanes) enqueues no event for it.  jsorb_sync, which
+// waits for the main stream, clears it.
+inline void mark_main_stream(jsorb_extractor *e) { e->lanes.main_stream_dirty = true; }
 
 // n x elem bytes of one image's result into dst (nothing when dst is NULL or n <= 0): from its pinned mirror when that holds the image
 // (`mirror`, else NULL), otherwise from `dev`, the image's device slice.  Does not touch e->err (the const getters).
