@@ -73,6 +73,9 @@ enum { JSORB_K_LAST_MATCH = JSORB_K_ID_END, JSORB_K_LAST_RESOLVE, JSORB_K_ID_COU
 /* kernels of jsorb_bow_transform* / jsorb_search_by_bow*: ids after JSORB_K_ID_COUNT, which stays the end of the ids above and names no kernel;
  * JSORB_K_ID_ALL is one past the last id */
 enum { JSORB_K_BOW_TRANSFORM = JSORB_K_ID_COUNT + 1, JSORB_K_BOW_GROUP, JSORB_K_BOW_MATCH, JSORB_K_BOW_RESOLVE, JSORB_K_ID_ALL };
+/* kernels of jsorb_search_by_projection_kf*: ids after JSORB_K_ID_ALL, which stays the end of the ids above and names no kernel (the grid is
+ * JSORB_K_ASSIGN_GRID again); JSORB_K_ID_LAST is one past the last id */
+enum { JSORB_K_KF_CANDIDATES = JSORB_K_ID_ALL + 1, JSORB_K_KF_RESOLVE, JSORB_K_ID_LAST };
 
 /* ---- lifetime ---- */
 /* mask: NULL (no mask => all 255) or a height*width u8 level-0 mask in host memory. */
@@ -558,6 +561,72 @@ int jsorb_search_by_bow_stats(jsorb_extractor *e, int *n_node_pairs, int *n_dist
  * (2; beyond 64 x that a node's entries are re-read per keyframe keypoint) and the keys k_bow_group sorts in LDS (4096; longer sides are sorted in
  * global memory).  Test builds lower them (jetson_slam_amd/build.py VARIANTS) and assert on these values.  Either pointer may be NULL. */
 int jsorb_bow_build_caps(int *node_regs, int *sort_lds);
+
+/* ---- relocalisation matching: ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, const float th,
+ * const int ORBdist) (src/ORBmatcher.cpp:1968-2095) as Tracking::Relocalization calls it twice per pose hypothesis (src/Tracking.cpp:2062-2092:
+ * (.., 10, 100), PoseOptimization, (.., 3, 64)) ----
+ * The frame is image `image` of the handle's last extract: N keypoints, mvKeysUn from k_undistort with an active camera, else the keypoints; its
+ * angle is keypoint SoA row 3 (float bits), its octave row 4.  Points i = 0 .. n_points-1 are the keyframe's slots with pMP && !pMP->isBad() &&
+ * !sAlreadyFound.count(pMP) in ascending slot index, compacted by the caller - the order decides the result.  Per point: the map point's world
+ * position Px, Py, Pz (GetWorldPos), max_distance (mfMaxDistance), max_dist_inv / min_dist_inv (GetMaxDistanceInvariance / GetMinDistanceInvariance),
+ * kf_angle (pKF->mvKeysUn[slot].angle) and the map point's descriptor (GetDescriptor, 32 bytes).  Per point, in order:
+ *   1. project with K14's arithmetic (jsorb_project_points): Pc = tcw + Rcw P per row as fma(z,R2,fma(x,R0,y*R1)) + t, invz = 1.0f/Pcz,
+ *      u = fma(Pcx*fx, invz, cx), v likewise; no candidate when Pcz <= 0 or (u < min_x || u > max_x || v < min_y || v > max_y)
+ *   2. gate and level with K16's arithmetic (jsorb_is_in_frustum): o = P - Ow, dist = sqrtf(fma(oz,oz,fma(ox,ox,oy*oy))); no candidate when
+ *      dist < min_dist_inv[i] || dist > max_dist_inv[i] (written so: a NaN passes, as in K16);
+ *      L = clamp(cvt_rzi_s32(ceilf(logf(max_distance[i] / dist) / log_scale_factor)), 0, n_levels-1) with K16's logf and the device's float -> int
+ *      rule (truncate, saturate, NaN -> 0): MapPoint::PredictScale with mfMaxDistance itself
+ *   3. R = th * jsorb_scale(e, L) (one float product); candidates = GetFeaturesInArea(u, v, R, L-1, L+1) (src/Frame.cpp:641-694): cells, early returns
+ *      and walk order as jsorb_search_local_points (ix outer, iy inner, a cell's keypoints ascending); kept when octave in [L-1, L+1] and
+ *      |x_un - u| < R && |y_un - v| < R.  There is no uRight test
+ *   4. dropped: blocked_in[k] != 0 (the caller's CurrentFrame.mvpMapPoints[k] != NULL before the call; NULL: none), or a point j < i of this call
+ *      matched k (:2037, :2053) - also when that match is culled in step 6: culling comes after the loop
+ *   5. best = popcount Hamming distance with strict < updates in walk order from bestDist = 256: the minimum of (distance, walk position) over
+ *      distances < 256; point i matches iff bestDist <= orb_dist: mvpMapPoints[best] = point i, nmatches++
+ *   6. check_orientation: rot = kf_angle[i] - frame angle, + 360.0f when negative; bin = (int)roundf(rot * (1.0f/30)), 30 -> 0 (the arithmetic of
+ *      jsorb_search_last_frame; a bin outside [0, 30) is never kept).  A keypoint is matched at most once, so a bin holds each keypoint at most
+ *      once.  After all points ComputeThreeMaxima (:2097-2138, as for jsorb_search_last_frame); every entry of every other bin:
+ *      mvpMapPoints[k] = NULL, nmatches--
+ * The reference's host code does steps 1 and 2 through cv::Mat products, cv::norm and the host's log, whose rounding depends on the OpenCV build and
+ * is pinned by nothing in its tree; this library defines them as the arithmetic of K14 and K16, which the reference's own GPU branches use for the
+ * same quantities (SearchByProjection(CurrentFrame, LastFrame, ..), isInFrustum).  Two differences from the host text follow:
+ *   - K14's Pcz > 0 rule: the host code would project a point behind the camera through the centre; here it has no candidate
+ *   - the level is converted with the device's float -> int rule (cvt_rzi_s32), as in jsorb_is_in_frustum: a ratio of +inf (max_distance = inf or
+ *     dist = 0) gives the last level and NaN level 0, where the host's cast is undefined
+ * Control flow, order, ties and the claim rule are the reference's.
+ * All arrays are DEVICE pointers: Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle float[n]; mp_descriptors n x 32 bytes, 16-byte
+ * aligned; blocked_in uint8[N] or NULL.  Outputs: match_kp[i] / match_dist[i] = the point's keypoint and distance when it matched (before culling),
+ * -1 otherwise; kp_match[k] = the point index finally matched to k or -1 (N entries); *n_matches_dev = the reference's return value.  Enqueued on
+ * the handle's stream behind the last extract (and the lanes of a batch), no host wait: the grid (k_assign_grid, into the handle's grid buffers),
+ * k_kf_candidates, k_kf_resolve.  cols * rows <= 16384, N < 262144.  n_points == 0 or N == 0: no match, kp_match all -1. */
+typedef struct jsorb_kf_projection_params {
+    float th;                        /* 10, then 3 (Tracking.cpp:2065, 2079) */
+    int orb_dist;                    /* 100, then 64 */
+    int check_orientation;           /* ORBmatcher matcher2(0.9, true): 1 */
+    float fx, fy, cx, cy;            /* K14's camera: CurrentFrame.fx .. cy */
+    float min_x, max_x, min_y, max_y; /* Frame::mnMinX, mnMaxX, mnMinY, mnMaxY: K14's bounds and the grid origin */
+    float inv_w, inv_h;              /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* FRAME_GRID_COLS, FRAME_GRID_ROWS */
+    float log_scale_factor;          /* Frame::mfLogScaleFactor */
+    float Rcw[9], tcw[3], Ow[3];     /* CurrentFrame.mTcw, row-major rotation and translation; the camera centre -Rcw^T tcw */
+} jsorb_kf_projection_params;
+int jsorb_search_by_projection_kf_async(jsorb_extractor *e, int image, const jsorb_kf_projection_params *params, int n_points, const float *Px,
+                                        const float *Py, const float *Pz, const float *max_distance, const float *max_dist_inv,
+                                        const float *min_dist_inv, const float *kf_angle, const uint8_t *mp_descriptors, const uint8_t *blocked_in,
+                                        int32_t *match_kp, int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the handle; kp_match_host[N] (host) = kp_match and *n_matches = nmatches, with one copy back. */
+int jsorb_search_by_projection_kf(jsorb_extractor *e, int image, const jsorb_kf_projection_params *params, int n_points, const float *Px,
+                                  const float *Py, const float *Pz, const float *max_distance, const float *max_dist_inv, const float *min_dist_inv,
+                                  const float *kf_angle, const uint8_t *mp_descriptors, const uint8_t *blocked_in, int32_t *kp_match_host,
+                                  int *n_matches);
+/* Diagnostics of the last call (waits for it): fixed-point rounds of k_kf_resolve, candidates over all points (step 3's survivors that blocked_in
+ * does not drop), points whose candidates overflowed the per-point list (the resolver walks their windows again) and ComputeThreeMaxima's ind1..3
+ * (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
+int jsorb_search_by_projection_kf_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow, int kept_bins[3]);
+/* The compile-time caps of this build's k_search_kf.hip (no device needed): keys kept per point (128) and the keypoint count up to which
+ * k_kf_resolve keeps its claims in LDS (16384; beyond it they live in kp_match).  Test builds lower them (jetson_slam_amd/build.py VARIANTS) and
+ * assert on these values.  Either pointer may be NULL. */
+int jsorb_search_kf_build_caps(int *list_cap, int *lds_claims);
 
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates

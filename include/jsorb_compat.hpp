@@ -733,6 +733,28 @@ inline int SearchByBoW(ORBExtractor &ex, const jsorb_bow_params &params, int n, 
     return n_matches;
 }
 
+// Relocalization's matcher2.SearchByProjection(mCurrentFrame, vpCandidateKFs[i], sFound, th, ORBdist) (Tracking.cpp:2065 with (10, 100), :2079 with
+// (3, 64); ORBmatcher.cpp:1968-2095) on the device.  The caller compacts the keyframe's slots with pMP && !pMP->isBad() && !sFound.count(pMP) in
+// ascending slot order: Px / Py / Pz hold GetWorldPos, max_distance mfMaxDistance, max_dist_inv / min_dist_inv GetMaxDistanceInvariance /
+// GetMinDistanceInvariance, angle pKF->mvKeysUn[slot].angle and descriptors GetDescriptor (32 bytes each) of those points, uploaded (to_gpu) first;
+// blocked_gpu one byte per keypoint of the current frame (mCurrentFrame.mvpMapPoints[k] != NULL before the call; nullptr: none).  params carries
+// mCurrentFrame.mTcw, its camera centre, the camera and the grid.  Returns nadditional; kp_match[k] = index (into the compacted points) of the point
+// now in mCurrentFrame.mvpMapPoints[k], or -1 where this call put none - the caller applies mvpMapPoints[k] = points[kp_match[k]].
+inline int SearchByProjection(ORBExtractor &ex, const jsorb_kf_projection_params &params, int n_points, SyncedMem<float> &Px, SyncedMem<float> &Py,
+                              SyncedMem<float> &Pz, SyncedMem<float> &max_distance, SyncedMem<float> &max_dist_inv, SyncedMem<float> &min_dist_inv,
+                              SyncedMem<float> &angle, SyncedMem<unsigned char> &descriptors, const unsigned char *blocked_gpu, std::vector<int> &kp_match)
+{
+    const int N = jsorb_n_keypoints(ex.handle(), 0);
+    kp_match.assign(N > 0 ? N : 1, -1);
+    int n_matches = 0;
+    if (jsorb_search_by_projection_kf(ex.handle(), 0, &params, n_points, Px.gpu_data(), Py.gpu_data(), Pz.gpu_data(), max_distance.gpu_data(),
+                                      max_dist_inv.gpu_data(), min_dist_inv.gpu_data(), angle.gpu_data(), descriptors.gpu_data(), blocked_gpu,
+                                      kp_match.data(), &n_matches) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_by_projection_kf: ") + jsorb_last_error(ex.handle()));
+    kp_match.resize(N > 0 ? N : 0);
+    return n_matches;
+}
+
 // Rectification on the device instead of the host cv::remap of the reference's stereo driver (Examples/Stereo/stereo_euroc.cpp:106-107 build
 // M1l/M2l, M1r/M2r with cv::initUndistortRectifyMap; :145-146 remap both images of every frame with INTER_LINEAR): set the maps ONCE per
 // extractor, then hand every extract() the raw camera image.  Maps of the extractor's image size, rows dense (width floats apart).

@@ -21,6 +21,8 @@ const char *k_names_local[JSORB_K_ID_END - JSORB_K_ASSIGN_GRID] = {"k_assign_gri
 const char *k_names_last[JSORB_K_ID_COUNT - JSORB_K_ID_END] = {"k_last_match", "k_last_resolve"};
 // kernels of jsorb_bow_transform* / jsorb_search_by_bow*: ids JSORB_K_BOW_TRANSFORM .. JSORB_K_ID_ALL - 1 (JSORB_K_ID_COUNT itself names no kernel)
 const char *k_names_bow[JSORB_K_ID_ALL - JSORB_K_BOW_TRANSFORM] = {"k_bow_transform", "k_bow_group", "k_bow_match", "k_bow_resolve"};
+// kernels of jsorb_search_by_projection_kf*: ids JSORB_K_KF_CANDIDATES .. JSORB_K_ID_LAST - 1 (JSORB_K_ID_ALL itself names no kernel)
+const char *k_names_kf[JSORB_K_ID_LAST - JSORB_K_KF_CANDIDATES] = {"k_kf_candidates", "k_kf_resolve"};
 
 // HIP multiplexes every stream of a process over GPU_MAX_HW_QUEUES hardware queues (default 4), and a stream that waits for an event
 // holds up every other stream that shares its queue.  This library runs 4 lane streams + 1 upload stream + one main stream per handle;
@@ -360,6 +362,7 @@ const char *jsorb_kernel_name(int id)
     if (id >= JSORB_K_ASSIGN_GRID && id < JSORB_K_ID_END) return k_names_local[id - JSORB_K_ASSIGN_GRID];
     if (id >= JSORB_K_ID_END && id < JSORB_K_ID_COUNT) return k_names_last[id - JSORB_K_ID_END];
     if (id >= JSORB_K_BOW_TRANSFORM && id < JSORB_K_ID_ALL) return k_names_bow[id - JSORB_K_BOW_TRANSFORM];
+    if (id >= JSORB_K_KF_CANDIDATES && id < JSORB_K_ID_LAST) return k_names_kf[id - JSORB_K_KF_CANDIDATES];
     return "";
 }
 
@@ -638,6 +641,7 @@ void jsorb_destroy(jsorb_extractor *e)
     grid_release(e);
     search_local_release(e);
     search_last_release(e);
+    search_kf_release(e);
     search_init_release(e);
     bow_release(e);
     core_release(e);
@@ -829,7 +833,7 @@ int jsorb_enable_kernel_timing(jsorb_extractor *e, int on)
 }
 int jsorb_kernel_time(jsorb_extractor *e, int id, double *total_ms, long *launches)
 {
-    if (!e || id < 0 || id >= JSORB_K_ID_ALL || id == JSORB_K_ID_COUNT || (id >= JSORB_K_COUNT_ALL && id < JSORB_K_ASSIGN_GRID)) return JSORB_ERR_INVALID;
+    if (!e || id < 0 || id >= JSORB_K_ID_LAST || id == JSORB_K_ID_ALL || id == JSORB_K_ID_COUNT || (id >= JSORB_K_COUNT_ALL && id < JSORB_K_ASSIGN_GRID)) return JSORB_ERR_INVALID;
     RCCHK(drain_timed(e));
     if (total_ms) *total_ms = e->tm.k_ms[id];
     if (launches) *launches = e->tm.k_n[id];
@@ -839,7 +843,7 @@ int jsorb_reset_kernel_timing(jsorb_extractor *e)
 {
     if (!e) return JSORB_ERR_INVALID;
     int rc = drain_timed(e);
-    for (int i = 0; i < JSORB_K_ID_ALL; i++) { e->tm.k_ms[i] = 0; e->tm.k_n[i] = 0; }
+    for (int i = 0; i < JSORB_K_ID_LAST; i++) { e->tm.k_ms[i] = 0; e->tm.k_n[i] = 0; }
     return rc;
 }
 

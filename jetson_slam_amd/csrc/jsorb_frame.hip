@@ -1,5 +1,5 @@
 // jsorb_frame.hip - host side of the Frame- and Tracking-side features around an extract: rectification maps, the camera (undistorted
-// keypoints, image bounds), RGB-D depth, the feature grid, local-map search, motion-model search and monocular-initialisation search.  Each feature keeps its state in its own part of the handle
+// keypoints, image bounds), RGB-D depth, the feature grid, local-map search, motion-model search, monocular-initialisation search and keyframe-projection search.  Each feature keeps its state in its own part of the handle
 // (jsorb_handle.h); run_pipeline and jsorb_destroy reach it through the *_after_extract / *_release functions here.
 #include "jsorb_handle.h"
 
@@ -23,6 +23,7 @@ void grid_release(jsorb_extractor *e) { free_device(e->grid.start, e->grid.items
 void search_local_release(jsorb_extractor *e) { free_device(e->sl.cand, e->sl.stats, e->sl.out); }
 void search_last_release(jsorb_extractor *e) { free_device(e->lf.ws, e->lf.pts, e->lf.out); }
 void search_init_release(jsorb_extractor *e) { free_device(e->si.cand, e->si.ws, e->si.out, e->si.ref); }
+void search_kf_release(jsorb_extractor *e) { free_device(e->kf.cand, e->kf.stats, e->kf.out); }
 
 } // namespace jsorb_host
 
@@ -491,6 +492,112 @@ int jsorb_search_last_frame_stats(jsorb_extractor *e, int *passes, int *n_candid
     if (passes) *passes = s[1];
     if (n_candidates) *n_candidates = s[2];
     if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[3 + b];
+    return JSORB_OK;
+}
+
+// ---- relocalisation matching: ORBmatcher::SearchByProjection(CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1968-2095), k_search_kf.hip ----
+#define KF_STATS 8                 // statistics words: rounds, candidates, overflowed points, ind1..3
+int jsorb_search_by_projection_kf_async(jsorb_extractor *e, int image, const jsorb_kf_projection_params *params, int n_points, const float *Px,
+                                        const float *Py, const float *Pz, const float *max_distance, const float *max_dist_inv,
+                                        const float *min_dist_inv, const float *kf_angle, const uint8_t *mp_descriptors, const uint8_t *blocked_in,
+                                        int32_t *match_kp, int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!check_image(e, image)) { e->err = "search_by_projection_kf: no extract result for this image"; return JSORB_ERR_STATE; }
+    if (!params || !n_matches_dev) { e->err = "search_by_projection_kf: NULL params or n_matches"; return JSORB_ERR_INVALID; }
+    const jsorb_kf_projection_params &p = *params;
+    if (p.cols < 1 || p.rows < 1 || (long long)p.cols * p.rows > 16384) { e->err = "search_by_projection_kf: grid size out of range (cols*rows <= 16384)"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_by_projection_kf: n_points < 0"; return JSORB_ERR_INVALID; }
+    const int n = jsorb_n_keypoints(e, image);
+    if (n >= (1 << 18)) { e->err = "search_by_projection_kf: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
+    if (n_points > 0 && (!Px || !Py || !Pz || !max_distance || !max_dist_inv || !min_dist_inv || !kf_angle || !mp_descriptors || !match_kp || !match_dist)) {
+        e->err = "search_by_projection_kf: NULL point array or output";
+        return JSORB_ERR_INVALID;
+    }
+    if (n > 0 && !kp_match) { e->err = "search_by_projection_kf: NULL kp_match"; return JSORB_ERR_INVALID; }
+    if ((uintptr_t)mp_descriptors % 16) { e->err = "search_by_projection_kf: mp_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    const int cap = search_kf_cap(), pts = std::max(n_points, 1);
+    RCCHK(grid_reserve(e, p.cols * p.rows));
+    RCCHK(reserve_device(e, e->kf.cand, (size_t)pts * (cap + 1) * sizeof(int), &e->kf.points, pts));
+    RCCHK(reserve_device(e, e->kf.stats, KF_STATS * sizeof(int)));
+    hipStream_t st = e->stream;
+    RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
+    mark_main_stream(e);               // ... and the next batch's lanes must not rewrite it before these kernels have read it
+    const float *xy_un = jsorb_keypoints_un_device(e, image);
+    TIMED(e, JSORB_K_ASSIGN_GRID, launch_assign_grid(jsorb_keypoints_device(e, image), xy_un, n, p.min_x, p.min_y, p.inv_w, p.inv_h, p.cols, p.rows,
+                                                     e->grid.start, e->grid.items, st));
+    HIPCHK(e, hipGetLastError());
+    SearchKfArgs a{};
+    a.soa = jsorb_keypoints_device(e, image);
+    a.xy_un = xy_un;
+    a.desc = jsorb_descriptors_device(e, image);
+    a.blocked = blocked_in;
+    a.n_kp = n;
+    a.cell_start = e->grid.start;
+    a.cell_items = e->grid.items;
+    a.n_points = n_points;
+    a.Px = Px; a.Py = Py; a.Pz = Pz; a.max_distance = max_distance; a.max_dist_inv = max_dist_inv; a.min_dist_inv = min_dist_inv;
+    a.angle = kf_angle; a.mp_desc = mp_descriptors;
+    a.p = p;
+    a.n_levels = e->g.L;
+    for (int l = 0; l < e->g.L; l++) a.scale[l] = e->g.lv[l].scale;
+    a.cand = e->kf.cand;
+    a.cand_n = e->kf.cand + (size_t)e->kf.points * cap;
+    a.match_kp = match_kp; a.match_dist = match_dist; a.kp_match = kp_match; a.n_matches = n_matches_dev;
+    a.stats = e->kf.stats;
+    TIMED(e, JSORB_K_KF_CANDIDATES, launch_kf_candidates(a, st));
+    HIPCHK(e, hipGetLastError());
+    TIMED(e, JSORB_K_KF_RESOLVE, launch_kf_resolve(a, st));
+    HIPCHK(e, hipGetLastError());
+    e->kf.done = true;
+    return JSORB_OK;
+}
+
+int jsorb_search_by_projection_kf(jsorb_extractor *e, int image, const jsorb_kf_projection_params *params, int n_points, const float *Px,
+                                  const float *Py, const float *Pz, const float *max_distance, const float *max_dist_inv, const float *min_dist_inv,
+                                  const float *kf_angle, const uint8_t *mp_descriptors, const uint8_t *blocked_in, int32_t *kp_match_host,
+                                  int *n_matches)
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!n_matches) { e->err = "search_by_projection_kf: NULL n_matches"; return JSORB_ERR_INVALID; }
+    if (n_points < 0) { e->err = "search_by_projection_kf: n_points < 0"; return JSORB_ERR_INVALID; }
+    if (!check_image(e, image)) { e->err = "search_by_projection_kf: no extract result for this image"; return JSORB_ERR_STATE; }
+    const int N = jsorb_n_keypoints(e, image);
+    if (N > 0 && !kp_match_host) { e->err = "search_by_projection_kf: NULL host output"; return JSORB_ERR_INVALID; }
+    HIPCHK(e, hipSetDevice(e->device));
+    const int pts = std::max(n_points, 1);
+    RCCHK(reserve_device(e, e->kf.out, ((size_t)2 * pts + e->g.T + 1) * sizeof(int32_t), &e->kf.out_points, pts));
+    int32_t *cnt = e->kf.out, *km = cnt + 1, *mk = km + e->g.T, *md = mk + e->kf.out_points;
+    RCCHK(jsorb_search_by_projection_kf_async(e, image, params, n_points, Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors,
+                                              blocked_in, mk, md, km, cnt));
+    std::vector<int32_t> h((size_t)N + 1);
+    HIPCHK(e, hipMemcpyAsync(h.data(), cnt, ((size_t)N + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));      // count and kp_match in one copy
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n_matches = h[0];
+    if (N > 0) memcpy(kp_match_host, h.data() + 1, (size_t)N * sizeof(int32_t));
+    return JSORB_OK;
+}
+
+int jsorb_search_by_projection_kf_stats(jsorb_extractor *e, int *rounds, int *n_candidates, int *n_overflow, int kept_bins[3])
+{
+    if (!e) return JSORB_ERR_INVALID;
+    if (!e->kf.done) { e->err = "search_by_projection_kf_stats before jsorb_search_by_projection_kf"; return JSORB_ERR_STATE; }
+    int32_t s[KF_STATS] = {0};
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipMemcpyAsync(s, e->kf.stats, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (rounds) *rounds = s[0];
+    if (n_candidates) *n_candidates = s[1];
+    if (n_overflow) *n_overflow = s[2];
+    if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[3 + b];
+    return JSORB_OK;
+}
+
+int jsorb_search_kf_build_caps(int *list_cap, int *lds_claims)
+{
+    if (list_cap) *list_cap = search_kf_cap();
+    if (lds_claims) *lds_claims = search_kf_lds_claims();
     return JSORB_OK;
 }
 

@@ -251,6 +251,16 @@ struct jsorb_extractor {
         int ref_cap = 0, ref_n = -1;       // ref_n: its keypoints (-1: none kept)
     } si;
 
+    // ---- keyframe projection matching (jsorb_frame.hip, jsorb_search_by_projection_kf*): allocated on the first call, grown with the number of points ----
+    struct {
+        int *cand = nullptr;               // points x search_kf_cap() keys, then points counts
+        int points = 0;
+        int *stats = nullptr;              // rounds, candidates, points over the capacity, ind1..3 of the last call (device)
+        int32_t *out = nullptr;            // synchronous call: count, kp_match (T), match_kp, match_dist (out_points each)
+        int out_points = 0;
+        bool done = false;
+    } kf;
+
     // ---- bag of words (jsorb_bow.hip, jsorb_bow_transform_async / jsorb_search_by_bow*): allocated on first use, the keyframe parts grown only ----
     struct {
         int32_t *ids = nullptr;            // B x T word ids, then B x T node ids, then 2 statistics words (descriptors with a shallow leaf)
@@ -268,8 +278,8 @@ struct jsorb_extractor {
     struct {
         bool on = false;
         std::vector<TimedLaunch> timed;
-        double k_ms[JSORB_K_ID_ALL] = {0};
-        long k_n[JSORB_K_ID_ALL] = {0};
+        double k_ms[JSORB_K_ID_LAST] = {0};
+        long k_n[JSORB_K_ID_LAST] = {0};
     } tm;
 
     // ---- JSORB_TRACE_HOST=1: host-side time of the single-frame calls (H2D enqueue, kernel enqueue, wait), printed at destroy ----
@@ -422,6 +432,7 @@ void grid_release(jsorb_extractor *e);
 void search_local_release(jsorb_extractor *e);
 void search_last_release(jsorb_extractor *e);
 void search_init_release(jsorb_extractor *e);
+void search_kf_release(jsorb_extractor *e);
 
 // ---- jsorb_bow.hip ----
 void bow_after_extract(jsorb_extractor *e);

@@ -150,6 +150,31 @@ struct LastFrameArgs {
 };
 void launch_last_match(const LastFrameArgs &a, int pass, hipStream_t s);
 void launch_last_resolve(const LastFrameArgs &a, int pass, hipStream_t s);
+// k_kf_candidates / k_kf_resolve (k_search_kf.hip): ORBmatcher::SearchByProjection(CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) over one image
+struct SearchKfArgs {
+    // the current frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, blocked_in (NULL: none), grid CSR
+    const int32_t *soa;
+    const float *xy_un;
+    const uint8_t *desc;
+    const uint8_t *blocked;
+    int n_kp;
+    const int32_t *cell_start, *cell_items;
+    // the keyframe's points, in ascending keyframe slot
+    int n_points;
+    const float *Px, *Py, *Pz, *max_distance, *max_dist_inv, *min_dist_inv, *angle;
+    const uint8_t *mp_desc;
+    jsorb_kf_projection_params p;                // window, threshold, camera, bounds, grid, pose
+    int n_levels;
+    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
+    // workspace and outputs
+    int *cand, *cand_n;                          // n_points x search_kf_cap() keys (distance << 18 | CSR position) in walk order, n_points counts
+    int32_t *match_kp, *match_dist, *kp_match, *n_matches;
+    int *stats;                                  // rounds, candidates, points over the capacity, ind1, ind2, ind3
+};
+int search_kf_cap();                            // the compile-time caps of k_search_kf.hip (jsorb_search_kf_build_caps)
+int search_kf_lds_claims();
+void launch_kf_candidates(const SearchKfArgs &a, hipStream_t s);
+void launch_kf_resolve(const SearchKfArgs &a, hipStream_t s);
 // k_init_candidates / k_init_resolve (k_search_init.hip): ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
 struct SearchInitArgs {
     // F2: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, grid CSR

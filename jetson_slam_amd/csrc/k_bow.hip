@@ -154,7 +154,7 @@ __device__ __forceinline__ int bw_lower_bound(const unsigned long long *keys, in
     return lo;
 }
 
-// ORBmatcher.cpp:225-230, the arithmetic of k_search_last.hip's lf_bin: rot = angle of the keyframe - angle of the frame, + 360 when negative;
+// ORBmatcher.cpp:225-230, the arithmetic of lf_bin (k_search_common.h): rot = angle of the keyframe - angle of the frame, + 360 when negative;
 // bin = round(rot * (1.0f / 30)) half away from zero, 30 -> 0.  A bin outside [0, 30) (angles outside [0, 360)) is BW_BINS: never kept.
 __device__ __forceinline__ int bw_bin(float a1, float a2)
 {

@@ -18,7 +18,7 @@
 //                      the previous round (SI_FREE: none): a point scans the lower points' choices only for candidates so marked.
 //                      Then the claims' last owners (vnMatches21), the rotation histogram over ALL claims, ComputeThreeMaxima, the culling, the
 //                      count and vbPrevMatched.
-// lf_bin / ComputeThreeMaxima restate k_search_last.hip's (kept there as they are: that file's kernels compile to the same instructions as before).
+// lf_bin / ComputeThreeMaxima restate those of k_search_common.h / k_search_last.hip (kept as they are: this file's kernels compile to the same instructions as before).
 // The contract (include/jsorb.h, jsorb_search_for_initialization_async) is restated in numpy in tests/test_search_init_host.py.
 #include <climits>
 
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void k_init_candidates(SearchInitArgs a)
     if (lane == 0) a.cand_n[i] = count;
 }
 
-// ORBmatcher.cpp:462-467, the arithmetic of k_search_last.hip's lf_bin: rot = angle1 - angle2, + 360 when negative; bin = round(rot * (1.0f / 30))
+// ORBmatcher.cpp:462-467, the arithmetic of lf_bin (k_search_common.h): rot = angle1 - angle2, + 360 when negative; bin = round(rot * (1.0f / 30))
 // half away from zero, 30 -> 0.  A bin outside [0, 30) (angles outside [0, 360)) is SI_BINS: never kept.
 __device__ __forceinline__ int si_bin(float a1, float a2)
 {

@@ -17,19 +17,7 @@
 namespace jsorb {
 
 #define SL_LANES 16                              // lanes per point (4 points per wave), as k_local_candidates
-#define LF_BINS 30                               // ORBmatcher::HISTO_LENGTH
 #define LF_KEY(d, j) ((d) << 18 | (j))           // distance <= 256, CSR position < 2^18
-
-// ORBmatcher.cpp:1918-1929: rot = last - current angle, + 360 when negative; bin = round(rot * (1.0f / 30)) half away from zero, 30 -> 0.  Angles in
-// [0, 360) reach bins 0..12 only (factor is 1/30, not 30/360: kept).  A bin outside [0, 30) (angles outside that range) is LF_BINS: never kept.
-__device__ __forceinline__ int lf_bin(float last, float cur)
-{
-    float rot = last - cur;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = sl_to_int(roundf(rot * (1.0f / LF_BINS)));
-    if (bin == LF_BINS) bin = 0;
-    return (unsigned)bin < LF_BINS ? bin : LF_BINS;
-}
 
 // the second pass, when the first found enough matches (or retry is off): nothing to do
 __device__ __forceinline__ bool lf_skip(const LastFrameArgs &a, int pass) { return pass && !a.ctl[0]; }

@@ -33,6 +33,8 @@ K_ASSIGN_GRID, K_LOCAL_CANDIDATES, K_LOCAL_RESOLVE = 12, 13, 14
 K_LAST_MATCH, K_LAST_RESOLVE = 15, 16
 # jsorb_bow_transform* / jsorb_search_by_bow*: ids after JSORB_K_ID_COUNT (17, which names no kernel)
 K_BOW_TRANSFORM, K_BOW_GROUP, K_BOW_MATCH, K_BOW_RESOLVE = 18, 19, 20, 21
+# jsorb_search_by_projection_kf*: ids after JSORB_K_ID_ALL (22, which names no kernel); the grid is K_ASSIGN_GRID again
+K_KF_CANDIDATES, K_KF_RESOLVE = 23, 24
 DEPTH_F32, DEPTH_U16 = 0, 1      # JSORB_DEPTH_F32 / JSORB_DEPTH_U16
 
 EXPORTS = [
@@ -59,6 +61,7 @@ EXPORTS = [
     "jsorb_vocabulary_create", "jsorb_vocabulary_destroy", "jsorb_vocabulary_info", "jsorb_bow_transform_descriptors", "jsorb_bow_transform_async",
     "jsorb_bow_word_device", "jsorb_bow_node_device", "jsorb_copy_bow", "jsorb_bow_transform_stats", "jsorb_search_by_bow_async",
     "jsorb_search_by_bow", "jsorb_search_by_bow_stats", "jsorb_bow_build_caps",
+    "jsorb_search_by_projection_kf_async", "jsorb_search_by_projection_kf", "jsorb_search_by_projection_kf_stats", "jsorb_search_kf_build_caps",
 ]
 
 
@@ -102,6 +105,25 @@ def make_last_frame_params(Rcw, tcw, camera, bounds, grid, th=7.0, direction=0, 
     assert R.size == 9 and t.size == 3
     return JsorbLastFrameParams(th, th_high, int(check_orientation), direction, retry_below, *camera, *bounds, *grid, cols, rows, mbf,
                                 (C.c_float * 9)(*R.tolist()), (C.c_float * 3)(*t.tolist()))
+
+
+class JsorbKfProjectionParams(C.Structure):
+    _fields_ = [("th", C.c_float), ("orb_dist", C.c_int), ("check_orientation", C.c_int)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")] + \
+               [("cols", C.c_int), ("rows", C.c_int), ("log_scale_factor", C.c_float), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)]
+
+
+def make_kf_projection_params(Rcw, tcw, camera, bounds, grid, log_scale_factor, th=10.0, orb_dist=100, check_orientation=True, cols=64, rows=48, Ow=None):
+    """jsorb_kf_projection_params: Rcw (3x3) and tcw (3) of CurrentFrame.mTcw as float32, camera = (fx, fy, cx, cy), bounds = (mnMinX, mnMaxX, mnMinY,
+    mnMaxY), grid = (mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows, log_scale_factor = mfLogScaleFactor.  Ow: the camera centre
+    as float32 (None: -Rcw^T tcw computed in float32, ORBmatcher.cpp:1974)"""
+    R = np.asarray(Rcw, np.float32).reshape(3, 3)
+    t = np.asarray(tcw, np.float32).ravel()
+    assert t.size == 3
+    o = (-(R.T @ t)).astype(np.float32) if Ow is None else np.asarray(Ow, np.float32).ravel()
+    assert o.size == 3
+    return JsorbKfProjectionParams(th, orb_dist, int(check_orientation), *camera, *bounds, *grid, cols, rows, log_scale_factor,
+                                   (C.c_float * 9)(*R.ravel().tolist()), (C.c_float * 3)(*t.tolist()), (C.c_float * 3)(*o.tolist()))
 
 
 class JsorbInitParams(C.Structure):
@@ -256,6 +278,10 @@ def load_library(path=None):
         "jsorb_search_by_bow": (I, [P, I, C.POINTER(JsorbBowParams), P, I] + [P] * 7),
         "jsorb_search_by_bow_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
         "jsorb_bow_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
+        "jsorb_search_by_projection_kf_async": (I, [P, I, C.POINTER(JsorbKfProjectionParams), I] + [P] * 13),
+        "jsorb_search_by_projection_kf": (I, [P, I, C.POINTER(JsorbKfProjectionParams), I] + [P] * 9 + [P, C.POINTER(I)]),
+        "jsorb_search_by_projection_kf_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_search_kf_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
         "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
         "jsorb_handle_forms": (I, [P, P, I]),
     }
@@ -402,6 +428,13 @@ def bow_build_caps():
     r, l = C.c_int(), C.c_int()
     load_library().jsorb_bow_build_caps(C.byref(r), C.byref(l))
     return r.value, l.value
+
+
+def search_kf_build_caps():
+    """jsorb_search_kf_build_caps of the loaded library: (keys k_kf_candidates keeps per point, keypoints up to which k_kf_resolve claims in LDS)"""
+    c, l = C.c_int(), C.c_int()
+    load_library().jsorb_search_kf_build_caps(C.byref(c), C.byref(l))
+    return c.value, l.value
 
 
 def bow_transform_descriptors(voc, descriptors):
@@ -1031,6 +1064,77 @@ class ORBExtractor:
         """{kernel: (total_ms, launches)} of the transform, group, match and resolve kernels, measured like kernel_times()"""
         return {name: self._kernel_time(k) for name, k in (("k_bow_transform", K_BOW_TRANSFORM), ("k_bow_group", K_BOW_GROUP),
                                                            ("k_bow_match", K_BOW_MATCH), ("k_bow_resolve", K_BOW_RESOLVE))}
+
+    # ---- relocalisation matching: ORBmatcher::SearchByProjection(CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cpp:1968-2095) ----
+    def _kf_points(self, Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors, params, blocked, image):
+        import torch
+        what = "search_by_projection_kf"
+        n = int(Px.shape[0]) if hasattr(Px, "dim") and Px.dim() == 1 else -1
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("%s: no extract result for image %d" % (what, image))
+        if not isinstance(params, JsorbKfProjectionParams):
+            raise JsorbError("%s: params must come from make_kf_projection_params" % what)
+        if n < 0:
+            raise JsorbError("%s: Px must be a one-dimensional device tensor" % what)
+
+        def chk(t, name, dtypes, shape):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("%s: %s must be a device tensor" % (what, name))
+            if t.dtype not in dtypes:
+                raise JsorbError("%s: %s must be %s, not %s" % (what, name, " / ".join(str(d) for d in dtypes), t.dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("%s: %s must be a contiguous tensor of shape %s, not %s" % (what, name, shape, tuple(t.shape)))
+            return t.data_ptr()
+
+        f32 = (torch.float32,)
+        ptrs = [chk(t, name, f32, (n,)) for t, name in ((Px, "Px"), (Py, "Py"), (Pz, "Pz"), (max_distance, "max_distance"), (max_dist_inv, "max_dist_inv"),
+                                                        (min_dist_inv, "min_dist_inv"), (kf_angle, "kf_angle"))]
+        ptrs.append(chk(mp_descriptors, "mp_descriptors", (torch.uint8,), (n, 32)))
+        if n and mp_descriptors.data_ptr() % 16:
+            raise JsorbError("%s: mp_descriptors must be 16-byte aligned" % what)
+        ptrs.append(None if blocked is None else chk(blocked, "blocked", (torch.uint8, torch.bool), (N,)))
+        return n, N, ptrs
+
+    def search_by_projection_kf(self, Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors, params, blocked=None, image=0):
+        """Relocalization's projection matcher over image `image` of the last extract.  Device tensors, one entry per keyframe point in ascending
+        keyframe slot: Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle float32[n]; mp_descriptors uint8[n, 32]; blocked uint8 /
+        bool [N] or None (CurrentFrame.mvpMapPoints[k] != NULL before the call).  params: make_kf_projection_params(...).  Returns (match_kp
+        int32[n], match_dist int32[n], kp_match int32[N], n_matches int32[1]) as device tensors; the call waits for the current torch stream before
+        it starts and for its own work before it returns."""
+        import torch
+        n, N, ptrs = self._kf_points(Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors, params, blocked, image)
+        dev = Px.device
+        match_kp = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        match_dist = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        kp_match = torch.full((max(N, 1),), -1, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_by_projection_kf_async(self._h, image, C.byref(params), n, *ptrs, match_kp.data_ptr(), match_dist.data_ptr(),
+                                                                kp_match.data_ptr(), count.data_ptr()))
+        self.sync()
+        return match_kp[:n], match_dist[:n], kp_match[:N], count
+
+    def search_by_projection_kf_host(self, Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors, params, blocked=None, image=0):
+        """jsorb_search_by_projection_kf, the synchronous form: the same inputs, (kp_match int32[N] on the host, n_matches) with one copy back"""
+        import torch
+        n, N, ptrs = self._kf_points(Px, Py, Pz, max_distance, max_dist_inv, min_dist_inv, kf_angle, mp_descriptors, params, blocked, image)
+        kp_match = np.full(max(N, 1), -7, np.int32)
+        count = C.c_int(-7)
+        torch.cuda.current_stream(Px.device).synchronize()
+        self._chk(self._lib.jsorb_search_by_projection_kf(self._h, image, C.byref(params), n, *ptrs, kp_match.ctypes.data, C.byref(count)))
+        return kp_match[:N], count.value
+
+    def search_by_projection_kf_stats(self):
+        """(fixed-point rounds, candidates, points over the per-point list, (ind1, ind2, ind3)) of the last search_by_projection_kf"""
+        r, c, o, b = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_by_projection_kf_stats(self._h, C.byref(r), C.byref(c), C.byref(o), b))
+        return r.value, c.value, o.value, tuple(b)
+
+    def search_by_projection_kf_kernel_times(self):
+        """{kernel: (total_ms, launches)} of the grid, candidate and resolve kernels, measured like kernel_times()"""
+        return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_kf_candidates", K_KF_CANDIDATES),
+                                                           ("k_kf_resolve", K_KF_RESOLVE))}
 
     # ---- profiling plumbing ----
     def set_stream(self, stream_ptr):
