@@ -628,6 +628,91 @@ int jsorb_search_by_projection_kf_stats(jsorb_extractor *e, int *rounds, int *n_
  * assert on these values.  Either pointer may be NULL. */
 int jsorb_search_kf_build_caps(int *list_cap, int *lds_claims);
 
+/* ---- triangulation matching: ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cpp:644-810) with
+ * CheckDistEpipolarLine (:127-144), as LocalMapping::CreateNewMapPoints calls it once per covisible neighbour of a new keyframe
+ * (src/LocalMapping.cpp:216-274: 10 neighbours with a stereo or RGB-D sensor, 20 with a monocular one) - all neighbours in one call ----
+ * LocalMapping runs beside Tracking on its own thread, so this matcher belongs to no extractor handle: a jsorb_keyframe_matcher owns a non-blocking
+ * stream and its scratch (sorted keys, statistics, the synchronous form's outputs; allocated on the first call of a size, never inside a later call
+ * of the same or a smaller size; the first call of a LARGER size frees the old buffer with hipFree, which waits for the whole device once - the
+ * extractors' streams included).  One matcher is single-threaded; distinct matchers and extractor handles may be used concurrently from different
+ * host threads.  jsorb_keyframe_matcher_set_stream / _get_stream work like jsorb_set_stream (NULL restores the matcher's own stream).
+ *
+ * One fact about the reference decides the form: vbMatched2 is declared (:664) and read (:712) but NEVER SET in this tree (ORB-SLAM3 later added
+ * vbMatched2[bestIdx2]=true; this reference does not have it).  So the result of a KF1 keypoint depends on no other KF1 keypoint, two of them may
+ * take the same KF2 keypoint, and there is no sequential claim rule.  The device form reproduces exactly that.  An "exclusive" mode would be a
+ * different algorithm pinned by nothing in the reference; it is out of scope.
+ *
+ * Inputs, DEVICE arrays unless said otherwise.  KF1, n1 entries: node1 int32 (the FeatureVector node of the keypoint or -1), free1 uint8
+ * (GetMapPoint(idx1) == NULL), stereo1 uint8 (mvuRight[idx1] >= 0), x1, y1, angle1 float (mvKeysUn), desc1 n1 x 32 bytes, 16-byte aligned.  The
+ * KF2s are concatenated: keyframe i is the entries kf_start[i] .. kf_start[i + 1] (HOST array of n_keyframes + 1 ascending offsets) of node2, free2,
+ * stereo2, x2, y2, octave2 int32, angle2, desc2.  Per keyframe i, HOST arrays copied into the launch arguments: F12[9 i ..] row-major float from
+ * ComputeF12, and epipole[2 i ..] = ex, ey of :651-657 - the caller computes both from cv::Mat as the reference does; the library does not redo
+ * cv::Mat products whose rounding nothing pins.  params: th_low (TH_LOW = 50), check_orientation, only_stereo, n_levels in [1, JSORB_MAX_LEVELS]
+ * (as jsorb_params), scale_factor[] and level_sigma2[] = the floats mvScaleFactors and mvLevelSigma2 of the KF2s.
+ * Per keyframe, with j local to the keyframe:
+ *   1. match12[k] = -1 for all k, nmatches = 0
+ *   2. the two facts of jsorb_search_by_bow_async hold here too: ascending indices within a node, every keypoint in at most one node - so nodes
+ *      are independent
+ *   3. for every node on both sides and every idx1 of it: skip when !free1[idx1]; skip when only_stereo && !stereo1[idx1]
+ *   4. walk the KF2 keypoints idx2 of the node in ascending order from bestDist = th_low, bestIdx2 = -1:
+ *        skip when !free2; skip when only_stereo && !stereo2
+ *        d = popcount Hamming distance; skip when d > th_low || d > bestDist - d == bestDist GOES ON, so among equal distances the last one in
+ *          walk order that passes the geometry wins
+ *        epipole gate, only when !stereo1 && !stereo2: skip when distex*distex + distey*distey < 100.0f * scale_factor[octave2] with
+ *          distex = ex - x2, distey = ey - y2: two float products, one float add, no contraction, strict <, one float product on the right
+ *        epipolar line (CheckDistEpipolarLine): a = x1*F00 + y1*F10 + F20, b = x1*F01 + y1*F11 + F21, c = x1*F02 + y1*F12 + F22,
+ *          num = a*x2 + b*y2 + c, den = a*a + b*b - all float, left to right, separate multiplies and adds, no fma; den == 0 rejects;
+ *          dsqr = num*num/den (one float product, one correctly rounded float division); accept iff
+ *          (double)dsqr < 3.84 * (double)level_sigma2[octave2] - a DOUBLE comparison, as the C++ promotes it.  A NaN anywhere rejects
+ *        on accept bestIdx2 = idx2, bestDist = d; a geometry failure leaves bestDist unchanged
+ *      net rule: the winner is the minimum distance <= th_low over the entries that pass the geometry, ties to the largest walk position
+ *   5. if bestIdx2 >= 0: match12[idx1] = bestIdx2, nmatches++, and with check_orientation idx1 goes into the bin of
+ *      rot = angle1[idx1] - angle2[bestIdx2] (+ 360.0f when negative; bin = (int)roundf(rot * (1.0f/30)), 30 -> 0: the arithmetic of
+ *      jsorb_search_last_frame).  A bin outside [0, 30) is never kept
+ *   6. then, with check_orientation, ComputeThreeMaxima (:2097-2138, as for jsorb_search_last_frame); every idx1 of every other bin:
+ *      match12[idx1] = -1, nmatches--
+ *   7. vMatchedPairs is the (idx1, match12[idx1]) with match12 >= 0 in ascending idx1; the shim (include/jsorb_compat.hpp) builds it
+ *   8. octave2 outside [0, n_levels): the entry never passes (after its distance was computed).  Defined here - the reference would read out of
+ *      bounds.  Nothing faults on any device input
+ *   9. n1 == 0, n_keyframes == 0 and empty keyframes write -1 / 0 and launch nothing that reads
+ *  10. JSORB_ERR_INVALID: a NULL required pointer, descending (or negative) kf_start, more than 256 keyframes, n1 or a keyframe of 2^18 = 262144
+ *      or more, n_levels out of range, descriptors not 16-byte aligned
+ * Outputs (DEVICE): match12 n_keyframes x n1 (row i: keyframe i), n_matches_dev[n_keyframes].  Enqueued on the matcher's stream, no host decision
+ * after the argument checks, capturable once the scratch has its size: k_bow_group (KF1 as the frame side), k_tri_match (32 keyframes per launch),
+ * k_tri_resolve. */
+typedef struct jsorb_keyframe_matcher jsorb_keyframe_matcher;
+typedef struct jsorb_triangulation_params {
+    int th_low;                      /* ORBmatcher::TH_LOW = 50 */
+    int check_orientation;           /* 0 in CreateNewMapPoints: ORBmatcher matcher(0.6, false), LocalMapping.cpp:221 */
+    int only_stereo;                 /* bOnlyStereo: false in LocalMapping::CreateNewMapPoints */
+    int n_levels;                    /* pKF2->mnScaleLevels */
+    float scale_factor[JSORB_MAX_LEVELS];   /* mvScaleFactors */
+    float level_sigma2[JSORB_MAX_LEVELS];   /* mvLevelSigma2 */
+} jsorb_triangulation_params;
+int jsorb_keyframe_matcher_create(int device_id, jsorb_keyframe_matcher **out);
+void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m);
+int jsorb_keyframe_matcher_set_stream(jsorb_keyframe_matcher *m, void *hip_stream);
+void *jsorb_keyframe_matcher_get_stream(const jsorb_keyframe_matcher *m);
+const char *jsorb_keyframe_matcher_last_error(const jsorb_keyframe_matcher *m);
+int jsorb_search_for_triangulation_async(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, int n1, const int32_t *node1,
+                                         const uint8_t *free1, const uint8_t *stereo1, const float *x1, const float *y1, const float *angle1,
+                                         const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2, const uint8_t *free2,
+                                         const uint8_t *stereo2, const float *x2, const float *y2, const int32_t *octave2, const float *angle2,
+                                         const uint8_t *desc2, const float *F12, const float *epipole, int32_t *match12, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the matcher; match12_host[n_keyframes x n1] and n_matches_host[n_keyframes] (host), one copy back. */
+int jsorb_search_for_triangulation(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, int n1, const int32_t *node1,
+                                   const uint8_t *free1, const uint8_t *stereo1, const float *x1, const float *y1, const float *angle1,
+                                   const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2, const uint8_t *free2,
+                                   const uint8_t *stereo2, const float *x2, const float *y2, const int32_t *octave2, const float *angle2,
+                                   const uint8_t *desc2, const float *F12, const float *epipole, int32_t *match12_host, int *n_matches_host);
+/* Diagnostics of the last call (waits for it): n_node_pairs = (keyframe, node) pairs present on both sides; n_distances = Hamming distances
+ * computed (step 3's KF1 keypoints x step 4's entries that pass the flags); n_line_tests = of those, the candidates that come to the epipolar-line
+ * test in the order-free sense: d <= th_low, octave2 in range and the epipole gate passed or not applied (the `d > bestDist` skip of step 4, which
+ * only drops entries that cannot win and depends on the walk so far, is not counted off); largest_node = the most KF2 keypoints in a node of such
+ * a pair; kept_bins = keyframe 0's ComputeThreeMaxima ind1..3 (-1: none, all -1 without check_orientation).  Any pointer may be NULL. */
+int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *n_line_tests, int *largest_node,
+                                         int kept_bins[3]);
+
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates
  * pinned-host + device buffer pairs and moves data with cudaMemcpy(Async) on a private stream; these calls are the HIP side of

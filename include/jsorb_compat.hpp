@@ -23,6 +23,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <type_traits>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -500,6 +501,36 @@ public:
 private:
     jsorb_vocabulary *v_ = nullptr;
 };
+// The keyframe-to-keyframe matcher of LocalMapping (jsorb_keyframe_matcher, include/jsorb.h): RAII over the C calls.  It owns its stream and
+// scratch, so LocalMapping's thread never touches Tracking's extractors.  One object per thread.
+class KeyframeMatcher {
+public:
+    explicit KeyframeMatcher(int device_id = 0)
+    {
+        if (jsorb_keyframe_matcher_create(device_id, &m_) != JSORB_OK) throw std::runtime_error("jsorb_keyframe_matcher_create failed");
+    }
+    KeyframeMatcher(const KeyframeMatcher &) = delete;
+    KeyframeMatcher &operator=(const KeyframeMatcher &) = delete;
+    ~KeyframeMatcher() { jsorb_keyframe_matcher_destroy(m_); }
+    jsorb_keyframe_matcher *handle() const { return m_; }
+    void set_stream(void *hip_stream) { jsorb_keyframe_matcher_set_stream(m_, hip_stream); }
+    void *stream() const { return jsorb_keyframe_matcher_get_stream(m_); }
+
+private:
+    jsorb_keyframe_matcher *m_ = nullptr;
+};
+// One side of SearchForTriangulation as DEVICE arrays (SyncedMem<T>::gpu_data() after to_gpu()): n keypoints; node = the FeatureVector node per
+// keypoint (-1: none), is_free = GetMapPoint(i) == NULL, stereo = mvuRight[i] >= 0, x / y / angle / octave from mvKeysUn (octave: the KF2 side
+// only), descriptors 32 bytes each.  The KF2 side holds all neighbours one after the other.
+struct KeyframeSide {
+    int n = 0;
+    const int32_t *node = nullptr;
+    const unsigned char *is_free = nullptr, *stereo = nullptr;
+    const float *x = nullptr, *y = nullptr;
+    const int32_t *octave = nullptr;
+    const float *angle = nullptr;
+    const unsigned char *descriptors = nullptr;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -731,6 +762,31 @@ inline int SearchByBoW(ORBExtractor &ex, const jsorb_bow_params &params, int n, 
         throw std::runtime_error(std::string("jsorb_search_by_bow: ") + jsorb_last_error(ex.handle()));
     match_kf.resize(N > 0 ? N : 0);
     return n_matches;
+}
+
+// matcher.SearchForTriangulation(mpCurrentKeyFrame, pKF2, F12, vMatchedIndices, false) (ORBmatcher.cpp:644-810) for ALL n_kf neighbours of
+// LocalMapping::CreateNewMapPoints' loop (LocalMapping.cpp:243-275) in one call: kf2 holds the neighbours concatenated, neighbour i at
+// kf_start[i] .. kf_start[i + 1]; F12s 9 floats (row-major ComputeF12) and epipoles 2 floats (ex, ey of :651-657) per neighbour, on the host.
+// vMatchedPairs[i] is the reference's vMatchedPairs for neighbour i ((idx1, idx2) with idx2 local to the neighbour, ascending idx1); returns the
+// reference's return value per neighbour.
+inline std::vector<int> SearchForTriangulation(jsorb::KeyframeMatcher &matcher, const jsorb_triangulation_params &params, const jsorb::KeyframeSide &kf1,
+                                               int n_kf, const int32_t *kf_start, const jsorb::KeyframeSide &kf2, const float *F12s, const float *epipoles,
+                                               std::vector<std::vector<std::pair<size_t, size_t>>> &vMatchedPairs)
+{
+    std::vector<int32_t> match12((size_t)(n_kf > 0 ? n_kf : 0) * (kf1.n > 0 ? kf1.n : 0) + 1, -1);
+    std::vector<int> counts(n_kf > 0 ? n_kf : 1, 0);
+    if (jsorb_search_for_triangulation(matcher.handle(), &params, kf1.n, kf1.node, kf1.is_free, kf1.stereo, kf1.x, kf1.y, kf1.angle, kf1.descriptors, n_kf,
+                                       kf_start, kf2.node, kf2.is_free, kf2.stereo, kf2.x, kf2.y, kf2.octave, kf2.angle, kf2.descriptors, F12s, epipoles,
+                                       match12.data(), counts.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_for_triangulation: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    counts.resize(n_kf > 0 ? n_kf : 0);
+    vMatchedPairs.assign(counts.size(), {});
+    for (size_t i = 0; i < counts.size(); i++) {
+        vMatchedPairs[i].reserve(counts[i] > 0 ? counts[i] : 0);
+        for (int k = 0; k < kf1.n; k++)
+            if (match12[i * kf1.n + k] >= 0) vMatchedPairs[i].push_back(std::make_pair((size_t)k, (size_t)match12[i * kf1.n + k]));
+    }
+    return counts;
 }
 
 // Relocalization's matcher2.SearchByProjection(mCurrentFrame, vpCandidateKFs[i], sFound, th, ORBdist) (Tracking.cpp:2065 with (10, 100), :2079 with

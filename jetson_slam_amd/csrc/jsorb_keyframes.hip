@@ -1,0 +1,204 @@
+// jsorb_keyframes.hip - host side of the keyframe-to-keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*).
+// The matcher belongs to no extractor handle: it owns its stream and scratch, so LocalMapping's thread never enqueues on Tracking's handles.  The
+// kernels are in k_triangulate.hip; the grouping is k_bow.hip's k_bow_group with KF1 as the frame side.
+#include "jsorb_handle.h"
+
+struct jsorb_keyframe_matcher {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev_switch = nullptr;                             // orders a new stream behind the old one (jsorb_keyframe_matcher_set_stream)
+    unsigned long long *sort1 = nullptr, *sort2 = nullptr;      // sorted keys of KF1 (cap1) and of the KF2s (cap2): grown only
+    int cap1 = 0, cap2 = 0;
+    int *stats = nullptr;                                       // TRI_STATS statistics words of the last search
+    int32_t *out = nullptr;                                     // synchronous call: counts (256), then match12 (out_cap)
+    int out_cap = 0;
+    bool done = false;
+    std::string err;
+};
+
+namespace {
+
+#define TRI_STATS 8
+
+// grows on demand (jsorb_handle.h: reserve_device); hipFree waits for the device: the last call may still read the old buffer
+template <class T> int tri_reserve(jsorb_keyframe_matcher *m, T *&p, size_t bytes, int *have, int want)
+{
+    if (*have >= want) return JSORB_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    *have = 0;
+    HIPCHK(m, hipMalloc(&p, bytes));
+    *have = want;
+    return JSORB_OK;
+}
+
+int tri_fail(jsorb_keyframe_matcher *m, const char *msg, int rc = JSORB_ERR_INVALID)
+{
+    m->err = msg;
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int jsorb_keyframe_matcher_create(int device_id, jsorb_keyframe_matcher **out)
+{
+    if (!out) return JSORB_ERR_INVALID;
+    *out = nullptr;
+    if (device_id < 0) return JSORB_ERR_INVALID;
+    jsorb_keyframe_matcher *m = new (std::nothrow) jsorb_keyframe_matcher;
+    if (!m) return JSORB_ERR_HIP;
+    m->device = device_id;
+    if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&m->ev_switch, hipEventDisableTiming) != hipSuccess || hipMalloc(&m->stats, TRI_STATS * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (m->ev_switch) (void)hipEventDestroy(m->ev_switch);
+        if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
+        delete m;
+        return JSORB_ERR_HIP;
+    }
+    m->stream = m->own_stream;
+    *out = m;
+    return JSORB_OK;
+}
+
+void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    (void)hipStreamSynchronize(m->stream);
+    free_device(m->sort1, m->sort2, m->stats, m->out);
+    destroy_event(m->ev_switch);
+    if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
+    delete m;
+}
+
+int jsorb_keyframe_matcher_set_stream(jsorb_keyframe_matcher *m, void *hip_stream)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    hipStream_t ns = hip_stream ? (hipStream_t)hip_stream : m->own_stream;
+    if (ns != m->stream && m->done) {               // the new stream continues after what the old one still carries (it reads the same scratch)
+        HIPCHK(m, hipSetDevice(m->device));
+        HIPCHK(m, hipEventRecord(m->ev_switch, m->stream));
+        HIPCHK(m, hipStreamWaitEvent(ns, m->ev_switch, 0));
+    }
+    m->stream = ns;
+    return JSORB_OK;
+}
+void *jsorb_keyframe_matcher_get_stream(const jsorb_keyframe_matcher *m) { return m ? (void *)m->stream : nullptr; }
+const char *jsorb_keyframe_matcher_last_error(const jsorb_keyframe_matcher *m) { return m ? m->err.c_str() : "NULL matcher"; }
+
+int jsorb_search_for_triangulation_async(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, int n1, const int32_t *node1,
+                                         const uint8_t *free1, const uint8_t *stereo1, const float *x1, const float *y1, const float *angle1,
+                                         const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2, const uint8_t *free2,
+                                         const uint8_t *stereo2, const float *x2, const float *y2, const int32_t *octave2, const float *angle2,
+                                         const uint8_t *desc2, const float *F12, const float *epipole, int32_t *match12, int32_t *n_matches_dev)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    if (!params) return tri_fail(m, "search_for_triangulation: NULL params");
+    if (params->n_levels < 1 || params->n_levels > JSORB_MAX_LEVELS) return tri_fail(m, "search_for_triangulation: n_levels out of range");
+    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "search_for_triangulation: n_keyframes must be in [0, 256]");
+    if (n1 < 0 || n1 >= (1 << 18)) return tri_fail(m, "search_for_triangulation: n1 must be in [0, 262143]");
+    if (n_keyframes > 0 && (!kf_start || !n_matches_dev || !F12 || !epipole)) return tri_fail(m, "search_for_triangulation: NULL kf_start, F12, epipole or n_matches");
+    for (int i = 0; i < n_keyframes; i++) {
+        const long long len = (long long)kf_start[i + 1] - kf_start[i];
+        if (kf_start[i] < 0 || len < 0) return tri_fail(m, "search_for_triangulation: kf_start must be ascending offsets");
+        if (len >= (1 << 18)) return tri_fail(m, "search_for_triangulation: a keyframe with more than 262143 keypoints");
+    }
+    const int base = n_keyframes > 0 ? kf_start[0] : 0, total = n_keyframes > 0 ? kf_start[n_keyframes] - base : 0;
+    if (n1 > 0 && (!node1 || !free1 || !stereo1 || !x1 || !y1 || !angle1 || !desc1)) return tri_fail(m, "search_for_triangulation: NULL KF1 array");
+    if (total > 0 && (!node2 || !free2 || !stereo2 || !x2 || !y2 || !octave2 || !angle2 || !desc2)) return tri_fail(m, "search_for_triangulation: NULL KF2 array");
+    if ((uintptr_t)desc1 % 16 || (uintptr_t)desc2 % 16) return tri_fail(m, "search_for_triangulation: descriptors must be 16-byte aligned");
+    if (n_keyframes > 0 && n1 > 0 && !match12) return tri_fail(m, "search_for_triangulation: NULL match12");
+    HIPCHK(m, hipSetDevice(m->device));
+    RCCHK(tri_reserve(m, m->sort1, (size_t)std::max(n1, 1) * sizeof(unsigned long long), &m->cap1, std::max(n1, 1)));
+    RCCHK(tri_reserve(m, m->sort2, (size_t)std::max(total, 1) * sizeof(unsigned long long), &m->cap2, std::max(total, 1)));
+    hipStream_t st = m->stream;
+    HIPCHK(m, hipMemsetAsync(m->stats, 0, TRI_STATS * sizeof(int), st));
+    m->done = true;
+    if (n_keyframes == 0) return JSORB_OK;
+    HIPCHK(m, hipMemsetAsync(n_matches_dev, 0, (size_t)n_keyframes * sizeof(int32_t), st));
+    if (n1 == 0) return JSORB_OK;
+    HIPCHK(m, hipMemsetAsync(match12, 0xff, (size_t)n_keyframes * n1 * sizeof(int32_t), st));
+    if (total == 0) return JSORB_OK;
+    // the grouping: KF1 as the frame side of k_bow_group, the KF2s as its keyframes
+    BowMatchArgs b{};
+    TriArgs a{};
+    for (int i = 0; i <= n_keyframes; i++) a.kf_start[i] = b.kf_start[i] = kf_start[i] - base;
+    b.f_node = node1; b.N = n1; b.n_kf = n_keyframes; b.kf_node = node2 + base;
+    b.f_sorted = m->sort1; b.kf_sorted = m->sort2;
+    a.n1 = n1; a.free1 = free1; a.stereo1 = stereo1; a.x1 = x1; a.y1 = y1; a.angle1 = angle1; a.desc1 = desc1;
+    a.n_kf = n_keyframes;
+    a.free2 = free2 + base; a.stereo2 = stereo2 + base; a.x2 = x2 + base; a.y2 = y2 + base; a.angle2 = angle2 + base; a.octave2 = octave2 + base;
+    a.desc2 = desc2 + (size_t)32 * base;
+    a.th_low = params->th_low; a.check_orientation = params->check_orientation; a.only_stereo = params->only_stereo; a.n_levels = params->n_levels;
+    for (int l = 0; l < params->n_levels; l++) {
+        a.gate[l] = 100.0f * params->scale_factor[l];            // :734, one float product
+        a.line[l] = 3.84 * (double)params->level_sigma2[l];      // :143, the double product of the promoted comparison
+    }
+    a.sorted1 = m->sort1; a.sorted2 = m->sort2;
+    a.match12 = match12; a.n_matches = n_matches_dev; a.stats = m->stats;
+    launch_bow_group(b, st);
+    HIPCHK(m, hipGetLastError());
+    for (int k0 = 0; k0 < n_keyframes; k0 += TR_KF_CHUNK) {
+        TriGeom g{};
+        g.kf0 = k0; g.n = std::min(TR_KF_CHUNK, n_keyframes - k0);
+        for (int i = 0; i < g.n; i++) {
+            memcpy(g.f[i], F12 + 9 * (size_t)(k0 + i), 9 * sizeof(float));
+            g.f[i][9] = epipole[2 * (size_t)(k0 + i)];
+            g.f[i][10] = epipole[2 * (size_t)(k0 + i) + 1];
+        }
+        launch_tri_match(a, g, st);
+        HIPCHK(m, hipGetLastError());
+    }
+    launch_tri_resolve(a, st);
+    HIPCHK(m, hipGetLastError());
+    return JSORB_OK;
+}
+
+int jsorb_search_for_triangulation(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, int n1, const int32_t *node1,
+                                   const uint8_t *free1, const uint8_t *stereo1, const float *x1, const float *y1, const float *angle1,
+                                   const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2, const uint8_t *free2,
+                                   const uint8_t *stereo2, const float *x2, const float *y2, const int32_t *octave2, const float *angle2,
+                                   const uint8_t *desc2, const float *F12, const float *epipole, int32_t *match12_host, int *n_matches_host)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "search_for_triangulation: n_keyframes must be in [0, 256]");
+    if (n1 < 0 || n1 >= (1 << 18)) return tri_fail(m, "search_for_triangulation: n1 must be in [0, 262143]");
+    if (n_keyframes > 0 && (!n_matches_host || (n1 > 0 && !match12_host))) return tri_fail(m, "search_for_triangulation: NULL host output");
+    HIPCHK(m, hipSetDevice(m->device));
+    const size_t rows = (size_t)n_keyframes * n1;
+    if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "search_for_triangulation: n_keyframes x n1 too large", JSORB_ERR_UNSUPPORTED);
+    const int want = (int)std::max(rows, (size_t)1);
+    RCCHK(tri_reserve(m, m->out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &m->out_cap, want));
+    int32_t *cnt = m->out, *mk = cnt + JSORB_BOW_MAX_KEYFRAMES;
+    RCCHK(jsorb_search_for_triangulation_async(m, params, n1, node1, free1, stereo1, x1, y1, angle1, desc1, n_keyframes, kf_start, node2, free2, stereo2,
+                                               x2, y2, octave2, angle2, desc2, F12, epipole, mk, cnt));
+    if (n_keyframes == 0) return JSORB_OK;
+    std::vector<int32_t> h((size_t)n_keyframes);
+    HIPCHK(m, hipMemcpyAsync(h.data(), cnt, (size_t)n_keyframes * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    if (rows > 0) HIPCHK(m, hipMemcpyAsync(match12_host, mk, rows * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    for (int i = 0; i < n_keyframes; i++) n_matches_host[i] = h[i];
+    return JSORB_OK;
+}
+
+int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *n_line_tests, int *largest_node,
+                                         int kept_bins[3])
+{
+    if (!m) return JSORB_ERR_INVALID;
+    if (!m->done) return tri_fail(m, "search_for_triangulation_stats before jsorb_search_for_triangulation", JSORB_ERR_STATE);
+    int32_t s[TRI_STATS] = {0};
+    HIPCHK(m, hipSetDevice(m->device));
+    HIPCHK(m, hipMemcpyAsync(s, m->stats, sizeof(s), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    if (n_node_pairs) *n_node_pairs = s[0];
+    if (n_distances) *n_distances = s[1];
+    if (n_line_tests) *n_line_tests = s[2];
+    if (largest_node) *largest_node = s[3];
+    if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[4 + b] - 1;
+    return JSORB_OK;
+}
+
+} // extern "C"

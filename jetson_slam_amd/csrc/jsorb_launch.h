@@ -238,6 +238,36 @@ void launch_bow_transform(const BowVocab &v, const uint8_t *desc, size_t desc_st
 void launch_bow_group(const BowMatchArgs &a, hipStream_t s);
 void launch_bow_match(const BowMatchArgs &a, hipStream_t s);
 void launch_bow_resolve(const BowMatchArgs &a, hipStream_t s);
+// k_tri_match / k_tri_resolve (k_triangulate.hip): ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) for several KF2;
+// the grouping is launch_bow_group over a BowMatchArgs whose frame side is KF1
+struct TriArgs {
+    // KF1: n1 keypoints
+    int n1;
+    const uint8_t *free1, *stereo1;
+    const float *x1, *y1, *angle1;
+    const uint8_t *desc1;
+    // the KF2s, concatenated; keyframe i is kf_start[i] .. kf_start[i + 1] (relative to the pointers below)
+    int n_kf;
+    const uint8_t *free2, *stereo2;
+    const float *x2, *y2, *angle2;
+    const int32_t *octave2;
+    const uint8_t *desc2;
+    int th_low, check_orientation, only_stereo, n_levels;
+    float gate[JSORB_MAX_LEVELS];                // 100.0f * mvScaleFactors[l]: the epipole gate's right side
+    double line[JSORB_MAX_LEVELS];               // 3.84 * (double)mvLevelSigma2[l]: the line test's right side
+    // workspace and outputs
+    const unsigned long long *sorted1, *sorted2; // k_bow_group's keys
+    int32_t *match12, *n_matches;                // n_kf x n1 (cleared to -1), n_kf (cleared to 0)
+    int *stats;                                  // node pairs, distances, line tests, largest KF2 node of a pair, ind1 + 1, ind2 + 1, ind3 + 1 of keyframe 0 (cleared to 0)
+    int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
+};
+#define TR_KF_CHUNK 32                          // keyframes whose geometry one k_tri_match launch carries in its arguments
+struct TriGeom {
+    int kf0, n;                                  // the launch's keyframes kf0 .. kf0 + n
+    float f[TR_KF_CHUNK][11];                    // F12 row-major, ex, ey
+};
+void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s);
+void launch_tri_resolve(const TriArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

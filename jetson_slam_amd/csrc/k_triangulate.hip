@@ -1,0 +1,189 @@
+// k_triangulate.hip - the matcher of LocalMapping::CreateNewMapPoints (LocalMapping.cpp:216-274) on the device:
+//   ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (ORBmatcher.cpp:644-810) with CheckDistEpipolarLine (:127-144)
+//   and ComputeThreeMaxima (:2097-2138), one keyframe KF1 against several neighbours KF2 in one call.
+// In this reference vbMatched2 (:664) is read (:712) and never set: the result of a KF1 keypoint depends on no other KF1 keypoint, two of them may
+// take the same KF2 keypoint and there is no sequential claim rule.  The kernels reproduce exactly that; an "exclusive" mode is out of scope.
+// Grouping     k_bow_group (k_bow.hip, as it is): KF1 is the frame side of a BowMatchArgs, the KF2s are its keyframe sides - the keys
+//              node << 18 | index sorted ascending, a node's keypoints one run in ascending index.
+// k_tri_match  grid (positions of KF1's sorted keys, keyframe of the launch's chunk); TR_LANES lanes take one sorted KF1 position: its descriptor,
+//              point and flags once, the KF2 run of its node by bisection, the epipolar line a, b, c once.  The lanes take the run's entries
+//              lane, lane + TR_LANES, ...: flags before the descriptor, the distance before the geometry.  Every lane keeps the minimum of
+//              d << 18 | (BW_IDX_MASK - t) over the entries that pass the geometry (a lane meets its entries in ascending t, so a later equal d
+//              is the smaller key and replaces the earlier one: the last position in walk order wins a tie, as `dist > bestDist` at :725 lets it);
+//              the minimum over the lanes is the reference's winner.  An entry whose distance lies above the lane's best so far cannot win and
+//              skips the line test, as :725 does in walk order.  No LDS, no barrier; the per-keyframe geometry (F12, epipole) comes in the launch
+//              arguments, TR_KF_CHUNK keyframes per launch.
+// k_tri_resolve one workgroup per keyframe: the rotation histogram over idx1, ComputeThreeMaxima, the culling and the count (:778-797).
+// The contract (include/jsorb.h, jsorb_search_for_triangulation_async) is restated in numpy in tests/test_triangulation_host.py.
+#include "jsorb_launch.h"
+#include "k_search_common.h"
+
+namespace jsorb {
+
+#define TR_LANES 16                              // lanes per KF1 keypoint in k_tri_match (provisional: DESIGN.md section 16)
+#define TR_IDX 18                                // BW_IDX of k_bow.hip: the keys k_bow_group writes
+#define TR_IDX_MASK ((1u << TR_IDX) - 1)
+#define TR_NOKEY (~0ull)                         // BW_NOKEY
+
+// first position of keys[0 .. n) whose key is not below x (k_bow.hip's bw_lower_bound)
+__device__ __forceinline__ int tr_lower_bound(const unsigned long long *keys, int n, unsigned long long x)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (keys[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
+{
+    const int lane = threadIdx.x % TR_LANES, kf = g.kf0 + blockIdx.y;
+    const int p = blockIdx.x * (256 / TR_LANES) + threadIdx.x / TR_LANES;
+    const int off = a.kf_start[kf], len = a.kf_start[kf + 1] - off;
+    const float *G = g.f[blockIdx.y];                // F12 row-major, ex, ey
+    // every lane stays to the end (the reductions below take whole waves); a group's trip count is uniform
+    const unsigned long long k1 = p < a.n1 && len > 0 ? a.sorted1[p] : TR_NOKEY;
+    const bool in_node = k1 != TR_NOKEY;
+    const unsigned long long v = k1 >> TR_IDX;       // the node
+    const int idx1 = (int)(k1 & TR_IDX_MASK);
+    const bool head = in_node && (p == 0 || a.sorted1[p - 1] >> TR_IDX != v);      // the first KF1 keypoint of the node: it counts the pair
+    bool stereo1 = false, take = false;
+    if (in_node) {
+        stereo1 = a.stereo1[idx1] != 0;
+        take = a.free1[idx1] != 0 && (!a.only_stereo || stereo1);                  // :686-696
+    }
+    const unsigned long long *ks = a.sorted2 + off;
+    int fb = 0, m = 0;
+    if (head || take) {
+        fb = tr_lower_bound(ks, len, v << TR_IDX);
+        m = tr_lower_bound(ks, len, (v + 1) << TR_IDX) - fb;
+    }
+    unsigned key = ~0u;
+    int n_dist = 0, n_line = 0;
+    if (take && m > 0) {
+        uint4 lo, hi;
+        sl_load_desc(a.desc1 + 32 * (size_t)idx1, lo, hi);
+        const float x1 = a.x1[idx1], y1 = a.y1[idx1];
+        // :130-136, left to right, separate multiplies and adds
+        const float la = x1 * G[0] + y1 * G[3] + G[6];
+        const float lb = x1 * G[1] + y1 * G[4] + G[7];
+        const float lc = x1 * G[2] + y1 * G[5] + G[8];
+        const float den = la * la + lb * lb;
+        const float ex = G[9], ey = G[10];
+        for (int t = lane; t < m; t += TR_LANES) {
+            const int j = off + (int)(ks[fb + t] & TR_IDX_MASK);
+            if (!a.free2[j]) continue;                                             // :712
+            const bool stereo2 = a.stereo2[j] != 0;
+            if (a.only_stereo && !stereo2) continue;                               // :717-719
+            uint4 mlo, mhi;
+            sl_load_desc(a.desc2 + 32 * (size_t)j, mlo, mhi);
+            const int d = SL_HAMMING(lo, hi, mlo, mhi);
+            n_dist++;
+            if (d > a.th_low) continue;                                            // :725 (bestDist starts at TH_LOW and only falls)
+            const int oct = a.octave2[j];
+            if ((unsigned)oct >= (unsigned)a.n_levels) continue;                   // defined here: the entry never passes
+            const float x2 = a.x2[j], y2 = a.y2[j];
+            if (!stereo1 && !stereo2) {                                            // :730-736
+                const float distex = ex - x2, distey = ey - y2;
+                if (distex * distex + distey * distey < a.gate[oct]) continue;
+            }
+            n_line++;
+            if ((unsigned)d > key >> TR_IDX) continue;                             // above the lane's best: it cannot win
+            const float num = la * x2 + lb * y2 + lc;
+            if (den == 0) continue;                                                // :138
+            const float dsqr = num * num / den;
+            if (!((double)dsqr < a.line[oct])) continue;                           // :143, a double comparison; a NaN rejects
+            key = min(key, (unsigned)d << TR_IDX | (TR_IDX_MASK - (unsigned)t));
+        }
+    }
+    for (int s = TR_LANES / 2; s > 0; s >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, s, TR_LANES));
+    if (lane == 0 && key != ~0u)                                                   // :745-748
+        a.match12[(size_t)kf * a.n1 + idx1] = (int)(ks[fb + (int)(TR_IDX_MASK - (key & TR_IDX_MASK))] & TR_IDX_MASK);
+    int pairs = head && m > 0 && lane == 0 ? 1 : 0, largest = head ? m : 0;
+    for (int s = 32; s > 0; s >>= 1) {
+        pairs += __shfl_xor(pairs, s);
+        n_dist += __shfl_xor(n_dist, s);
+        n_line += __shfl_xor(n_line, s);
+        largest = max(largest, __shfl_xor(largest, s));
+    }
+    if (threadIdx.x % 64 == 0) {
+        if (pairs) atomicAdd(&a.stats[0], pairs);
+        if (n_dist) atomicAdd(&a.stats[1], n_dist);
+        if (n_line) atomicAdd(&a.stats[2], n_line);
+        if (largest) atomicMax(&a.stats[3], largest);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tri_resolve(TriArgs a)
+{
+    __shared__ int s_hist[LF_BINS + 1], s_keep[LF_BINS + 1], s_found, s_culled;
+    const int kf = blockIdx.x, tid = threadIdx.x, n1 = a.n1;
+    const int off = a.kf_start[kf];
+    if (a.kf_start[kf + 1] - off <= 0) return;       // an empty keyframe: its row and count were cleared with the others
+    int32_t *row = a.match12 + (size_t)kf * n1;
+    const bool rot = a.check_orientation != 0;
+    if (tid <= LF_BINS) s_hist[tid] = 0;
+    if (tid == 0) { s_found = 0; s_culled = 0; }
+    __syncthreads();
+    int found = 0;
+    for (int k = tid; k < n1; k += 256) {
+        const int j = row[k];
+        if (j < 0) continue;
+        found++;
+        if (rot) atomicAdd(&s_hist[lf_bin(a.angle1[k], a.angle2[off + j])], 1);      // :753-760
+    }
+    atomicAdd(&s_found, found);
+    __syncthreads();
+    if (tid == 0) {
+        int ind1 = -1, ind2 = -1, ind3 = -1;
+        if (rot) {                                   // ComputeThreeMaxima (k_search_common.h: three_maxima, written out so that the indices stay in registers)
+            int max1 = 0, max2 = 0, max3 = 0;
+            for (int b = 0; b < LF_BINS; b++) {
+                const int s = s_hist[b];
+                if (s > max1) {
+                    max3 = max2; max2 = max1; max1 = s;
+                    ind3 = ind2; ind2 = ind1; ind1 = b;
+                } else if (s > max2) {
+                    max3 = max2; max2 = s;
+                    ind3 = ind2; ind2 = b;
+                } else if (s > max3) {
+                    max3 = s; ind3 = b;
+                }
+            }
+            if ((float)max2 < 0.1f * (float)max1) {
+                ind2 = -1; ind3 = -1;
+            } else if ((float)max3 < 0.1f * (float)max1) {
+                ind3 = -1;
+            }
+        }
+        for (int b = 0; b <= LF_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;      // (bin LF_BINS, outside [0, 30), is never kept)
+        if (kf == 0) { a.stats[4] = ind1 + 1; a.stats[5] = ind2 + 1; a.stats[6] = ind3 + 1; }      // (0: none - the cleared state)
+    }
+    __syncthreads();
+    if (rot) {
+        int culled = 0;
+        for (int k = tid; k < n1; k += 256) {
+            const int j = row[k];
+            if (j < 0) continue;
+            if (!s_keep[lf_bin(a.angle1[k], a.angle2[off + j])]) {
+                row[k] = -1;                         // :792-793
+                culled++;
+            }
+        }
+        atomicAdd(&s_culled, culled);
+        __syncthreads();
+    }
+    if (tid == 0) a.n_matches[kf] = s_found - s_culled;
+}
+
+void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s)
+{
+    if (a.n1 <= 0 || g.n <= 0) return;
+    const int per_block = 256 / TR_LANES;
+    hipLaunchKernelGGL(k_tri_match, dim3((a.n1 + per_block - 1) / per_block, g.n), dim3(256), 0, s, a, g);
+}
+
+void launch_tri_resolve(const TriArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_tri_resolve, dim3(a.n_kf), dim3(256), 0, s, a); }
+
+} // namespace jsorb

@@ -62,6 +62,9 @@ EXPORTS = [
     "jsorb_bow_word_device", "jsorb_bow_node_device", "jsorb_copy_bow", "jsorb_bow_transform_stats", "jsorb_search_by_bow_async",
     "jsorb_search_by_bow", "jsorb_search_by_bow_stats", "jsorb_bow_build_caps",
     "jsorb_search_by_projection_kf_async", "jsorb_search_by_projection_kf", "jsorb_search_by_projection_kf_stats", "jsorb_search_kf_build_caps",
+    "jsorb_keyframe_matcher_create", "jsorb_keyframe_matcher_destroy", "jsorb_keyframe_matcher_set_stream", "jsorb_keyframe_matcher_get_stream",
+    "jsorb_keyframe_matcher_last_error", "jsorb_search_for_triangulation_async", "jsorb_search_for_triangulation",
+    "jsorb_search_for_triangulation_stats",
 ]
 
 
@@ -144,6 +147,26 @@ class JsorbBowParams(C.Structure):
 def make_bow_params(nn_ratio=0.7, th_low=TH_LOW, check_orientation=True):
     """jsorb_bow_params: ORBmatcher matcher(0.7, true) of TrackReferenceKeyFrame (Tracking.cpp:925), (0.75, true) of Relocalization (:1975)"""
     return JsorbBowParams(nn_ratio, th_low, int(check_orientation))
+
+
+class JsorbTriangulationParams(C.Structure):
+    _fields_ = [("th_low", C.c_int), ("check_orientation", C.c_int), ("only_stereo", C.c_int), ("n_levels", C.c_int),
+                ("scale_factor", C.c_float * MAX_LEVELS), ("level_sigma2", C.c_float * MAX_LEVELS)]
+
+
+def make_triangulation_params(scale_factor, level_sigma2=None, th_low=TH_LOW, check_orientation=True, only_stereo=False):
+    """jsorb_triangulation_params: ORBmatcher matcher(0.6, false) of LocalMapping::CreateNewMapPoints (LocalMapping.cpp:221) has
+    check_orientation=False; scale_factor / level_sigma2 are the float tables mvScaleFactors / mvLevelSigma2 of the neighbours (level_sigma2 None:
+    scale_factor squared in float32, ORBextractor.cpp:43-71)"""
+    sf = np.ascontiguousarray(scale_factor, np.float32).ravel()
+    s2 = (sf * sf).astype(np.float32) if level_sigma2 is None else np.ascontiguousarray(level_sigma2, np.float32).ravel()
+    if len(s2) != len(sf):
+        raise JsorbError("make_triangulation_params: scale_factor and level_sigma2 must have one entry per level")
+    p = JsorbTriangulationParams(int(th_low), int(check_orientation), int(only_stereo), len(sf))
+    for l in range(min(len(sf), MAX_LEVELS)):
+        p.scale_factor[l] = sf[l]
+        p.level_sigma2[l] = s2[l]
+    return p
 
 
 def make_camera(K, D):
@@ -284,6 +307,14 @@ def load_library(path=None):
         "jsorb_search_kf_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
         "jsorb_plan_forms": (I, [C.POINTER(JsorbParams), P, I]),
         "jsorb_handle_forms": (I, [P, P, I]),
+        "jsorb_keyframe_matcher_create": (I, [I, C.POINTER(P)]),
+        "jsorb_keyframe_matcher_destroy": (None, [P]),
+        "jsorb_keyframe_matcher_set_stream": (I, [P, P]),
+        "jsorb_keyframe_matcher_get_stream": (P, [P]),
+        "jsorb_keyframe_matcher_last_error": (C.c_char_p, [P]),
+        "jsorb_search_for_triangulation_async": (I, [P, C.POINTER(JsorbTriangulationParams), I] + [P] * 7 + [I] + [P] * 13),
+        "jsorb_search_for_triangulation": (I, [P, C.POINTER(JsorbTriangulationParams), I] + [P] * 7 + [I] + [P] * 13),
+        "jsorb_search_for_triangulation_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -456,6 +487,134 @@ def bow_transform_descriptors(voc, descriptors):
         raise JsorbError("jsorb_bow_transform_descriptors rc=%d" % rc)
     torch.cuda.synchronize(descriptors.device)
     return word[:n], node[:n]
+
+
+class KeyframeMatcher:
+    """jsorb_keyframe_matcher: the keyframe-to-keyframe matcher of LocalMapping (include/jsorb.h), with a stream and scratch of its own - it
+    belongs to no ORBExtractor and may be used from another thread than the extractors.  A keyframe side is a dict of device tensors: node int32[n],
+    free uint8 / bool [n], stereo uint8 / bool [n], x, y, angle float32[n], desc uint8[n, 32] (16-byte aligned) and, for the KF2 side, octave
+    int32[n]."""
+    KF1_KEYS = ("node", "free", "stereo", "x", "y", "angle", "desc")
+    KF2_KEYS = ("node", "free", "stereo", "x", "y", "octave", "angle", "desc")
+
+    def __init__(self, device_id=0):
+        self._lib = load_library()
+        self._m = C.c_void_p()
+        rc = self._lib.jsorb_keyframe_matcher_create(int(device_id), C.byref(self._m))
+        if rc != 0:
+            self._m = C.c_void_p()
+            raise JsorbError("jsorb_keyframe_matcher_create rc=%d" % rc)
+        self.device_id = int(device_id)
+
+    @property
+    def handle(self):
+        return self._m
+
+    def close(self):
+        if getattr(self, "_m", None):
+            self._lib.jsorb_keyframe_matcher_destroy(self._m)
+            self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise JsorbError("libjsorb rc=%d: %s" % (rc, self._lib.jsorb_keyframe_matcher_last_error(self._m).decode()))
+
+    def set_stream(self, stream_ptr):
+        """use an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream); None restores the matcher's own"""
+        self._chk(self._lib.jsorb_keyframe_matcher_set_stream(self._m, stream_ptr))
+
+    def get_stream(self):
+        return self._lib.jsorb_keyframe_matcher_get_stream(self._m) or 0
+
+    def sync(self):
+        rc = self._lib.jsorb_mem_stream_sync(C.c_void_p(self.get_stream()))
+        if rc != 0:
+            raise JsorbError("KeyframeMatcher.sync: jsorb_mem_stream_sync rc=%d" % rc)
+
+    def _args(self, kf1, kf_start, kf2, F12, epipole, params):
+        import torch
+        what = "search_for_triangulation"
+        if not isinstance(params, JsorbTriangulationParams):
+            raise JsorbError("%s: params must come from make_triangulation_params" % what)
+        ks = np.ascontiguousarray(kf_start, np.int32)
+        if ks.ndim != 1 or len(ks) < 1:
+            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
+        nk, total = len(ks) - 1, int(ks[-1])
+        F = np.ascontiguousarray(F12, np.float32).reshape(-1)
+        E = np.ascontiguousarray(epipole, np.float32).reshape(-1)
+        if len(F) != 9 * nk or len(E) != 2 * nk:
+            raise JsorbError("%s: F12 must hold 9 and epipole 2 floats per keyframe" % what)
+        dt = dict(node=(torch.int32,), octave=(torch.int32,), free=(torch.uint8, torch.bool), stereo=(torch.uint8, torch.bool), x=(torch.float32,),
+                  y=(torch.float32,), angle=(torch.float32,), desc=(torch.uint8,))
+
+        def side(kf, keys, name, n):
+            ptrs = []
+            for k in keys:
+                t = kf[k]
+                if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
+                shape = (n, 32) if k == "desc" else (n,)
+                if t.dtype not in dt[k] or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(d) for d in dt[k]), shape))
+                ptrs.append(t.data_ptr() if n else None)
+            if n and kf["desc"].data_ptr() % 16:
+                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
+            return ptrs
+
+        n1 = int(kf1["node"].shape[0])
+        p1, p2 = side(kf1, self.KF1_KEYS, "kf1", n1), side(kf2, self.KF2_KEYS, "kf2", total)
+        return n1, nk, ks, F, E, [C.byref(params), n1] + p1 + [nk, ks.ctypes.data] + p2 + [F.ctypes.data, E.ctypes.data]
+
+    def search_for_triangulation(self, kf1, kf_start, kf2, F12, epipole, params, wait=True):
+        """jsorb_search_for_triangulation_async: KF1 against the len(kf_start) - 1 concatenated KF2s (kf_start: HOST int32 offsets; F12 host
+        float32[n_keyframes, 9] row-major, epipole host float32[n_keyframes, 2]).  Returns (match12 int32[n_keyframes, n1], n_matches
+        int32[n_keyframes]) as device tensors, enqueued on the matcher's stream.  wait=True: the call waits for the current torch stream before
+        it starts and for its own work before it returns; wait=False only enqueues - the caller orders the streams (set_stream).  With
+        wait=False the returned tensors come from torch's caching allocator on the CURRENT torch stream but are written on the matcher's stream:
+        keep them alive until the matcher's stream has finished (or make that stream the current torch stream, as set_stream with
+        torch.cuda.current_stream().cuda_stream does), or the allocator may hand their memory out again while the kernels still write it."""
+        import torch
+        n1, nk, ks, F, E, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
+        dev = kf1["node"].device
+        match12 = torch.full((max(nk, 1), max(n1, 1)), -7, dtype=torch.int32, device=dev)
+        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_for_triangulation_async(self._m, *args, match12.data_ptr(), count.data_ptr()))
+        if wait:
+            self.sync()
+        return match12.reshape(-1)[:nk * n1].reshape(nk, n1), count[:nk]
+
+    def search_for_triangulation_host(self, kf1, kf_start, kf2, F12, epipole, params):
+        """jsorb_search_for_triangulation, the synchronous form: the same inputs, (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) on
+        the host with one copy back"""
+        import torch
+        n1, nk, ks, F, E, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
+        match12 = np.full(max(nk * n1, 1), -7, np.int32)
+        count = np.full(max(nk, 1), -7, np.int32)
+        torch.cuda.current_stream(kf1["node"].device).synchronize()
+        self._chk(self._lib.jsorb_search_for_triangulation(self._m, *args, match12.ctypes.data, count.ctypes.data))
+        return match12[:nk * n1].reshape(nk, n1), count[:nk]
+
+    def stats(self):
+        """((keyframe, node) pairs on both sides, Hamming distances, candidates at the line test, most KF2 keypoints in such a node, keyframe 0's
+        (ind1, ind2, ind3)) of the last search_for_triangulation"""
+        p, d, l, m, b = C.c_int(), C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_for_triangulation_stats(self._m, C.byref(p), C.byref(d), C.byref(l), C.byref(m), b))
+        return p.value, d.value, l.value, m.value, tuple(b)
+
+
+def matched_pairs(match12_row):
+    """vMatchedPairs of ORBmatcher::SearchForTriangulation (ORBmatcher.cpp:799-807) from one row of match12: int64[k, 2] of (idx1, idx2), ascending idx1"""
+    row = np.asarray(match12_row)
+    idx1 = np.nonzero(row >= 0)[0]
+    return np.stack([idx1, row[idx1]], axis=1).astype(np.int64) if len(idx1) else np.zeros((0, 2), np.int64)
 
 
 class ORBExtractor:
