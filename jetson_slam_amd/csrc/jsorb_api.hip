@@ -1,7 +1,7 @@
 // jsorb_api.hip - host side of libjsorb, the C ABI declared in include/jsorb.h: handle creation and destruction, geometry and launch plan,
 // the lane / copy / main stream pools and the spill arena, streams and synchronisation, level getters, the memory calls and kernel timing.
-// The extract pipeline is in jsorb_extract.hip, the stereo match in jsorb_stereo.hip, the Frame-side features in jsorb_frame.hip; the handle
-// and the host helpers they share in jsorb_handle.h.
+// The extract pipeline is in jsorb_extract.hip, the stereo match in jsorb_stereo.hip, the Frame-side features in jsorb_frame.hip, the grid
+// matchers in jsorb_search.hip; the handle and the host helpers they share in jsorb_handle.h.
 //
 // Mirrors ORB_GPU's host orchestration (src/cuda/orb_gpu.cpp) with an MI355X-first structure:
 //   reference: ~7L+1 launches on L streams + 3 blocking copies + 2 full stream-sync rounds per image,

@@ -194,11 +194,8 @@ int jsorb_copy_bow(const jsorb_extractor *e, int image, int32_t *word_host, int3
 int jsorb_bow_transform_stats(jsorb_extractor *e, int *n_shallow)
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!e->bow.transformed) { e->err = "bow_transform_stats before jsorb_bow_transform_async"; return JSORB_ERR_STATE; }
     int32_t s = 0;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(&s, bow_shallow(e), sizeof(s), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    RCCHK(read_stats(e, e->bow.transformed, "bow_transform_stats before jsorb_bow_transform_async", bow_shallow(e), &s, 1));
     if (n_shallow) *n_shallow = s;
     return JSORB_OK;
 }
@@ -215,13 +212,8 @@ int jsorb_search_by_bow_async(jsorb_extractor *e, int image, const jsorb_bow_par
     const int N = jsorb_n_keypoints(e, image);
     if (N >= (1 << 18)) { e->err = "search_by_bow: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
     BowMatchArgs a{};
-    for (int i = 0; i < n_keyframes; i++) {
-        const long long len = (long long)kf_start[i + 1] - kf_start[i];
-        if (kf_start[i] < 0 || len < 0) { e->err = "search_by_bow: kf_start must be ascending offsets"; return JSORB_ERR_INVALID; }
-        if (len >= (1 << 18)) { e->err = "search_by_bow: a keyframe with more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
-    }
-    const int base = n_keyframes > 0 ? kf_start[0] : 0, total = n_keyframes > 0 ? kf_start[n_keyframes] - base : 0;
-    for (int i = 0; i <= n_keyframes && n_keyframes > 0; i++) a.kf_start[i] = kf_start[i] - base;
+    int base = 0, total = 0, rc = 0;
+    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, a.kf_start, &base, &total, &rc)) { e->err = std::string("search_by_bow: ") + bad; return rc; }
     if (total > 0 && (!kf_node || !kf_valid || !kf_angle || !kf_descriptors)) { e->err = "search_by_bow: NULL keyframe array"; return JSORB_ERR_INVALID; }
     if ((uintptr_t)kf_descriptors % 16) { e->err = "search_by_bow: kf_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
     if (n_keyframes > 0 && N > 0 && !match_kf) { e->err = "search_by_bow: NULL match_kf"; return JSORB_ERR_INVALID; }
@@ -236,13 +228,10 @@ int jsorb_search_by_bow_async(jsorb_extractor *e, int image, const jsorb_bow_par
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
     mark_main_stream(e);
-    HIPCHK(e, hipMemsetAsync(e->bow.stats, 0, BOW_STATS * sizeof(int), st));
+    bool run = false;
+    RCCHK(clear_kf_outputs(e, st, e->bow.stats, BOW_STATS, n_keyframes, N, total, n_matches_dev, match_kf, &run));
     e->bow.done = true;
-    if (n_keyframes == 0) return JSORB_OK;
-    HIPCHK(e, hipMemsetAsync(n_matches_dev, 0, (size_t)n_keyframes * sizeof(int32_t), st));
-    if (N == 0) return JSORB_OK;
-    HIPCHK(e, hipMemsetAsync(match_kf, 0xff, (size_t)n_keyframes * N * sizeof(int32_t), st));
-    if (total == 0) return JSORB_OK;
+    if (!run) return JSORB_OK;
     a.soa = jsorb_keypoints_device(e, image);
     a.desc = jsorb_descriptors_device(e, image);
     a.f_node = f_node;
@@ -278,23 +267,14 @@ int jsorb_search_by_bow(jsorb_extractor *e, int image, const jsorb_bow_params *p
     RCCHK(reserve_device(e, e->bow.out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &e->bow.out_cap, want));
     int32_t *cnt = e->bow.out, *mk = cnt + JSORB_BOW_MAX_KEYFRAMES;
     RCCHK(jsorb_search_by_bow_async(e, image, params, f_node, n_keyframes, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors, mk, cnt));
-    if (n_keyframes == 0) return JSORB_OK;
-    std::vector<int32_t> h((size_t)n_keyframes);
-    HIPCHK(e, hipMemcpyAsync(h.data(), cnt, (size_t)n_keyframes * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    if (rows > 0) HIPCHK(e, hipMemcpyAsync(match_kf_host, mk, rows * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    for (int i = 0; i < n_keyframes; i++) n_matches_host[i] = h[i];
-    return JSORB_OK;
+    return copy_kf_results(e, n_keyframes, rows, cnt, mk, match_kf_host, n_matches_host);
 }
 
 int jsorb_search_by_bow_stats(jsorb_extractor *e, int *n_node_pairs, int *n_distances, int *largest_node, int kept_bins[3])
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!e->bow.done) { e->err = "search_by_bow_stats before jsorb_search_by_bow"; return JSORB_ERR_STATE; }
     int32_t s[BOW_STATS] = {0};
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, hipMemcpyAsync(s, e->bow.stats, sizeof(s), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    RCCHK(read_stats(e, e->bow.done, "search_by_bow_stats before jsorb_search_by_bow", e->bow.stats, s, BOW_STATS));
     if (n_node_pairs) *n_node_pairs = s[0];
     if (n_distances) *n_distances = s[1];
     if (largest_node) *largest_node = s[2];

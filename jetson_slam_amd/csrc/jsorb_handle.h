@@ -1,8 +1,8 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
-// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid, local-map, motion-model and initialisation search; jsorb_bow.hip: vocabulary, BoW transform
-// and BoW matching).  include/jsorb.h only
-// forward-declares the handle, so its layout is free to change.
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid; jsorb_search.hip: the four grid matchers; jsorb_bow.hip:
+// vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip: the keyframe matcher, which shares the helpers that take any owner).
+// include/jsorb.h only forward-declares the handle, so its layout is free to change.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -219,7 +219,7 @@ struct jsorb_extractor {
         int cells = 0;
     } grid;
 
-    // ---- local-map search (jsorb_frame.hip, jsorb_search_local_points*): allocated on the first call, grown with the number of map points ----
+    // ---- local-map search (jsorb_search.hip, jsorb_search_local_points*): allocated on the first call, grown with the number of map points ----
     struct {
         int *cand = nullptr;               // points x search_local_cap() packed candidates, then points counts
         int points = 0;
@@ -229,7 +229,7 @@ struct jsorb_extractor {
         bool done = false;
     } sl;
 
-    // ---- motion-model matching (jsorb_frame.hip, jsorb_search_last_frame*): allocated on the first call, the per-point part grown with the points ----
+    // ---- motion-model matching (jsorb_search.hip, jsorb_search_last_frame*): allocated on the first call, the per-point part grown with the points ----
     struct {
         int *ws = nullptr;                 // owner (T entries, -1 between calls: k_last_resolve resets what k_last_match set), then 8 control / statistics words
         int *pts = nullptr;                // points x 2: rotation bin, then candidates
@@ -239,7 +239,7 @@ struct jsorb_extractor {
         bool done = false;
     } lf;
 
-    // ---- monocular initialisation matching (jsorb_frame.hip, jsorb_search_for_initialization*, jsorb_init_reference_*): allocated on first use, grown only ----
+    // ---- monocular initialisation matching (jsorb_search.hip, jsorb_search_for_initialization*, jsorb_init_reference_*): allocated on first use, grown only ----
     struct {
         int *cand = nullptr;               // points x search_init_cap() packed candidates, then points counts, then points ordered indices
         int points = 0;
@@ -251,7 +251,7 @@ struct jsorb_extractor {
         int ref_cap = 0, ref_n = -1;       // ref_n: its keypoints (-1: none kept)
     } si;
 
-    // ---- keyframe projection matching (jsorb_frame.hip, jsorb_search_by_projection_kf*): allocated on the first call, grown with the number of points ----
+    // ---- keyframe projection matching (jsorb_search.hip, jsorb_search_by_projection_kf*): allocated on the first call, grown with the number of points ----
     struct {
         int *cand = nullptr;               // points x search_kf_cap() keys, then points counts
         int points = 0;
@@ -384,14 +384,69 @@ inline int copy_result(void *dst, const void *mirror, const void *dev, int n, si
 
 // A device buffer allocated on first use and then kept.  With `have` (units allocated so far, 0: none) it grows on demand instead: when `want`
 // units exceed *have the old buffer is freed (hipFree waits for the device: the last call may still read it) and `bytes` are allocated for
-// `want` units; the contents are not kept.
-template <class T> int reserve_device(jsorb_extractor *e, T *&p, size_t bytes, int *have = nullptr, int want = 0)
+// `want` units; the contents are not kept.  The owner is a handle or a keyframe matcher: whatever has `err`.
+template <class H, class T> int reserve_device(H *e, T *&p, size_t bytes, int *have = nullptr, int want = 0)
 {
     if (have ? *have >= want : p != nullptr) return JSORB_OK;
     if (p) (void)hipFree(p);
     p = nullptr;
+    if (have) *have = 0;
     HIPCHK(e, hipMalloc(&p, bytes));
     if (have) *have = want;
+    return JSORB_OK;
+}
+
+// The `_stats` calls' common part: n statistics words of the owner's last search from the device, behind what its stream carries (owner: a handle
+// or a keyframe matcher - `device`, `stream`, `err`).  `before`: the error when no search has run.
+template <class H> int read_stats(H *h, bool done, const char *before, const int *dev, int32_t *s, int n)
+{
+    if (!done) { h->err = before; return JSORB_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(s, dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return JSORB_OK;
+}
+
+// ---- keyframes given as concatenated arrays (jsorb_search_by_bow*, jsorb_search_for_triangulation*) ----
+// kf_start of n_keyframes keyframes (keyframe i is kf_start[i] .. kf_start[i + 1]): ascending offsets, every keyframe below 2^18 keypoints.
+// rel[] = the offsets relative to *base = kf_start[0], *total = the keypoints of all of them.  NULL, or the error's text behind the feature's
+// name with its code in *rc.
+inline const char *rebase_kf_start(const int32_t *kf_start, int n_keyframes, int *rel, int *base, int *total, int *rc)
+{
+    for (int i = 0; i < n_keyframes; i++) {
+        const long long len = (long long)kf_start[i + 1] - kf_start[i];
+        if (kf_start[i] < 0 || len < 0) { *rc = JSORB_ERR_INVALID; return "kf_start must be ascending offsets"; }
+        if (len >= (1 << 18)) { *rc = JSORB_ERR_UNSUPPORTED; return "a keyframe with more than 262143 keypoints"; }
+    }
+    *base = n_keyframes > 0 ? kf_start[0] : 0;
+    *total = n_keyframes > 0 ? kf_start[n_keyframes] - *base : 0;
+    for (int i = 0; i <= n_keyframes && n_keyframes > 0; i++) rel[i] = kf_start[i] - *base;
+    return nullptr;
+}
+
+// The outputs of a search over n_kf keyframes x n keypoints in their "nothing matched" state, on st: the statistics words, the counts (0) and the
+// match rows (-1).  *run: the kernels have something to do (a keyframe, a keypoint on this side and one on the other).
+template <class H> int clear_kf_outputs(H *h, hipStream_t st, int *stats, int n_stats, int n_kf, int n, int total, int32_t *n_matches, int32_t *match, bool *run)
+{
+    *run = false;
+    HIPCHK(h, hipMemsetAsync(stats, 0, (size_t)n_stats * sizeof(int), st));
+    if (n_kf == 0) return JSORB_OK;
+    HIPCHK(h, hipMemsetAsync(n_matches, 0, (size_t)n_kf * sizeof(int32_t), st));
+    if (n == 0) return JSORB_OK;
+    HIPCHK(h, hipMemsetAsync(match, 0xff, (size_t)n_kf * n * sizeof(int32_t), st));
+    *run = total > 0;
+    return JSORB_OK;
+}
+
+// The synchronous forms' end: the n_kf counts and the `rows` match entries behind what the owner's stream carries
+template <class H> int copy_kf_results(H *h, int n_kf, size_t rows, const int32_t *cnt, const int32_t *match, int32_t *match_host, int *n_matches_host)
+{
+    if (n_kf == 0) return JSORB_OK;
+    std::vector<int32_t> c((size_t)n_kf);
+    HIPCHK(h, hipMemcpyAsync(c.data(), cnt, (size_t)n_kf * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (rows > 0) HIPCHK(h, hipMemcpyAsync(match_host, match, rows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n_kf; i++) n_matches_host[i] = c[i];
     return JSORB_OK;
 }
 template <class T> int reserve_pinned(jsorb_extractor *e, T *&p, size_t bytes) { if (!p) HIPCHK(e, hipHostMalloc(&p, bytes)); return JSORB_OK; }
@@ -429,6 +484,9 @@ void camera_release(jsorb_extractor *e);
 void rgbd_invalidate(jsorb_extractor *e);
 void rgbd_release(jsorb_extractor *e);
 void grid_release(jsorb_extractor *e);
+int grid_reserve(jsorb_extractor *e, int n_cells);      // the grid CSR for n_cells cells (grown on demand)
+
+// ---- jsorb_search.hip ----
 void search_local_release(jsorb_extractor *e);
 void search_last_release(jsorb_extractor *e);
 void search_init_release(jsorb_extractor *e);

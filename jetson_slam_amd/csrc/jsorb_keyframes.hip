@@ -20,19 +20,7 @@ namespace {
 
 #define TRI_STATS 8
 
-// grows on demand (jsorb_handle.h: reserve_device); hipFree waits for the device: the last call may still read the old buffer
-template <class T> int tri_reserve(jsorb_keyframe_matcher *m, T *&p, size_t bytes, int *have, int want)
-{
-    if (*have >= want) return JSORB_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    *have = 0;
-    HIPCHK(m, hipMalloc(&p, bytes));
-    *have = want;
-    return JSORB_OK;
-}
-
-int tri_fail(jsorb_keyframe_matcher *m, const char *msg, int rc = JSORB_ERR_INVALID)
+int tri_fail(jsorb_keyframe_matcher *m, const std::string &msg, int rc = JSORB_ERR_INVALID)
 {
     m->err = msg;
     return rc;
@@ -101,31 +89,24 @@ int jsorb_search_for_triangulation_async(jsorb_keyframe_matcher *m, const jsorb_
     if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "search_for_triangulation: n_keyframes must be in [0, 256]");
     if (n1 < 0 || n1 >= (1 << 18)) return tri_fail(m, "search_for_triangulation: n1 must be in [0, 262143]");
     if (n_keyframes > 0 && (!kf_start || !n_matches_dev || !F12 || !epipole)) return tri_fail(m, "search_for_triangulation: NULL kf_start, F12, epipole or n_matches");
-    for (int i = 0; i < n_keyframes; i++) {
-        const long long len = (long long)kf_start[i + 1] - kf_start[i];
-        if (kf_start[i] < 0 || len < 0) return tri_fail(m, "search_for_triangulation: kf_start must be ascending offsets");
-        if (len >= (1 << 18)) return tri_fail(m, "search_for_triangulation: a keyframe with more than 262143 keypoints");
-    }
-    const int base = n_keyframes > 0 ? kf_start[0] : 0, total = n_keyframes > 0 ? kf_start[n_keyframes] - base : 0;
+    TriArgs a{};
+    int base = 0, total = 0, rc = 0;
+    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, a.kf_start, &base, &total, &rc)) return tri_fail(m, std::string("search_for_triangulation: ") + bad);      // (both are JSORB_ERR_INVALID here: rc is the BoW matcher's)
     if (n1 > 0 && (!node1 || !free1 || !stereo1 || !x1 || !y1 || !angle1 || !desc1)) return tri_fail(m, "search_for_triangulation: NULL KF1 array");
     if (total > 0 && (!node2 || !free2 || !stereo2 || !x2 || !y2 || !octave2 || !angle2 || !desc2)) return tri_fail(m, "search_for_triangulation: NULL KF2 array");
     if ((uintptr_t)desc1 % 16 || (uintptr_t)desc2 % 16) return tri_fail(m, "search_for_triangulation: descriptors must be 16-byte aligned");
     if (n_keyframes > 0 && n1 > 0 && !match12) return tri_fail(m, "search_for_triangulation: NULL match12");
     HIPCHK(m, hipSetDevice(m->device));
-    RCCHK(tri_reserve(m, m->sort1, (size_t)std::max(n1, 1) * sizeof(unsigned long long), &m->cap1, std::max(n1, 1)));
-    RCCHK(tri_reserve(m, m->sort2, (size_t)std::max(total, 1) * sizeof(unsigned long long), &m->cap2, std::max(total, 1)));
+    RCCHK(reserve_device(m, m->sort1, (size_t)std::max(n1, 1) * sizeof(unsigned long long), &m->cap1, std::max(n1, 1)));
+    RCCHK(reserve_device(m, m->sort2, (size_t)std::max(total, 1) * sizeof(unsigned long long), &m->cap2, std::max(total, 1)));
     hipStream_t st = m->stream;
-    HIPCHK(m, hipMemsetAsync(m->stats, 0, TRI_STATS * sizeof(int), st));
+    bool run = false;
+    RCCHK(clear_kf_outputs(m, st, m->stats, TRI_STATS, n_keyframes, n1, total, n_matches_dev, match12, &run));
     m->done = true;
-    if (n_keyframes == 0) return JSORB_OK;
-    HIPCHK(m, hipMemsetAsync(n_matches_dev, 0, (size_t)n_keyframes * sizeof(int32_t), st));
-    if (n1 == 0) return JSORB_OK;
-    HIPCHK(m, hipMemsetAsync(match12, 0xff, (size_t)n_keyframes * n1 * sizeof(int32_t), st));
-    if (total == 0) return JSORB_OK;
+    if (!run) return JSORB_OK;
     // the grouping: KF1 as the frame side of k_bow_group, the KF2s as its keyframes
     BowMatchArgs b{};
-    TriArgs a{};
-    for (int i = 0; i <= n_keyframes; i++) a.kf_start[i] = b.kf_start[i] = kf_start[i] - base;
+    memcpy(b.kf_start, a.kf_start, sizeof(b.kf_start));
     b.f_node = node1; b.N = n1; b.n_kf = n_keyframes; b.kf_node = node2 + base;
     b.f_sorted = m->sort1; b.kf_sorted = m->sort2;
     a.n1 = n1; a.free1 = free1; a.stereo1 = stereo1; a.x1 = x1; a.y1 = y1; a.angle1 = angle1; a.desc1 = desc1;
@@ -171,28 +152,19 @@ int jsorb_search_for_triangulation(jsorb_keyframe_matcher *m, const jsorb_triang
     const size_t rows = (size_t)n_keyframes * n1;
     if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "search_for_triangulation: n_keyframes x n1 too large", JSORB_ERR_UNSUPPORTED);
     const int want = (int)std::max(rows, (size_t)1);
-    RCCHK(tri_reserve(m, m->out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &m->out_cap, want));
+    RCCHK(reserve_device(m, m->out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &m->out_cap, want));
     int32_t *cnt = m->out, *mk = cnt + JSORB_BOW_MAX_KEYFRAMES;
     RCCHK(jsorb_search_for_triangulation_async(m, params, n1, node1, free1, stereo1, x1, y1, angle1, desc1, n_keyframes, kf_start, node2, free2, stereo2,
                                                x2, y2, octave2, angle2, desc2, F12, epipole, mk, cnt));
-    if (n_keyframes == 0) return JSORB_OK;
-    std::vector<int32_t> h((size_t)n_keyframes);
-    HIPCHK(m, hipMemcpyAsync(h.data(), cnt, (size_t)n_keyframes * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    if (rows > 0) HIPCHK(m, hipMemcpyAsync(match12_host, mk, rows * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
-    for (int i = 0; i < n_keyframes; i++) n_matches_host[i] = h[i];
-    return JSORB_OK;
+    return copy_kf_results(m, n_keyframes, rows, cnt, mk, match12_host, n_matches_host);
 }
 
 int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *n_line_tests, int *largest_node,
                                          int kept_bins[3])
 {
     if (!m) return JSORB_ERR_INVALID;
-    if (!m->done) return tri_fail(m, "search_for_triangulation_stats before jsorb_search_for_triangulation", JSORB_ERR_STATE);
     int32_t s[TRI_STATS] = {0};
-    HIPCHK(m, hipSetDevice(m->device));
-    HIPCHK(m, hipMemcpyAsync(s, m->stats, sizeof(s), hipMemcpyDeviceToHost, m->stream));
-    HIPCHK(m, hipStreamSynchronize(m->stream));
+    RCCHK(read_stats(m, m->done, "search_for_triangulation_stats before jsorb_search_for_triangulation", m->stats, s, TRI_STATS));
     if (n_node_pairs) *n_node_pairs = s[0];
     if (n_distances) *n_distances = s[1];
     if (n_line_tests) *n_line_tests = s[2];

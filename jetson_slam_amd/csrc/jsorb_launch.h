@@ -97,16 +97,25 @@ struct RgbdArgs {
 void launch_undistort(const UndistortCam &cam, const int32_t *soa, const int *counts, int T, float *un, float *un_host, int n_images, hipStream_t s);
 void launch_rgbd(const int32_t *soa, const int *counts, int T, const float *un, const uint8_t *depth, size_t image_stride, size_t step, int W, int H,
                  const RgbdArgs &a, float *u_out, float *d_out, float *u_host, float *d_host, int n_images, hipStream_t s);
-// k_local_candidates / k_local_resolve (k_search_local.hip): ORBmatcher::SearchByProjection(Frame&, map points, th) over one image of a handle
-struct SearchLocalArgs {
-    // the frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, mvuRight (NULL: monocular), blocked_in (NULL: none)
-    const int32_t *soa;
-    const float *xy_un;
+// The frame side of the four grid matchers: one image of a handle and the grid CSR the call built over it (jsorb_search.hip: search_begin)
+struct FrameView {
+    const int32_t *soa;                          // keypoint SoA (6N): x, y, ., angle (float bits), octave, .
+    const float *xy_un;                          // mvKeysUn as x_un[N] y_un[N] (NULL: the keypoints themselves)
     const uint8_t *desc;
-    const float *u_right;
-    const uint8_t *blocked;
+    const float *u_right;                        // mvuRight (NULL: monocular, or a matcher that does not read it)
+    const uint8_t *blocked;                      // blocked_in (NULL: none)
     int n_kp;
     const int32_t *cell_start, *cell_items;      // grid CSR (k_assign_grid)
+    int n_levels;
+    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
+    __device__ __forceinline__ float x(int k) const { return xy_un ? xy_un[k] : (float)soa[k]; }      // mvKeysUn[k].pt
+    __device__ __forceinline__ float y(int k) const { return xy_un ? xy_un[n_kp + k] : (float)soa[n_kp + k]; }
+    __device__ __forceinline__ float angle(int k) const { return __int_as_float(soa[3 * (size_t)n_kp + k]); }
+    __device__ __forceinline__ int octave(int k) const { return soa[4 * (size_t)n_kp + k]; }
+};
+// k_local_candidates / k_local_resolve (k_search_local.hip): ORBmatcher::SearchByProjection(Frame&, map points, th) over one image of a handle
+struct SearchLocalArgs {
+    FrameView f;
     float min_x, min_y, inv_w, inv_h;
     int cols, rows;
     // the map points, in the caller's order
@@ -115,8 +124,7 @@ struct SearchLocalArgs {
     const int32_t *level;
     const uint8_t *in_frustum, *mp_desc;
     float th, nn_ratio, mbf;
-    int th_high, n_levels;
-    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
+    int th_high;
     // workspace and outputs
     int *cand, *cand_n;                          // n_points x search_local_cap() packed candidates, n_points counts
     int32_t *match_kp, *match_dist, *kp_match, *n_matches;
@@ -127,21 +135,13 @@ void launch_local_candidates(const SearchLocalArgs &a, hipStream_t s);
 void launch_local_resolve(const SearchLocalArgs &a, hipStream_t s);
 // k_last_match / k_last_resolve (k_search_last.hip): ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), its GPU branch, over one image
 struct LastFrameArgs {
-    // the current frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, mvuRight (NULL: monocular), grid CSR
-    const int32_t *soa;
-    const float *xy_un;
-    const uint8_t *desc;
-    const float *u_right;
-    int n_kp;
-    const int32_t *cell_start, *cell_items;
+    FrameView f;                                 // the current frame (blocked unused)
     // the last frame's points, in ascending last-frame index
     int n_points;
     const float *Px, *Py, *Pz, *angle;
     const int32_t *octave;
     const uint8_t *mp_desc;
     jsorb_last_frame_params p;                   // threshold, direction, camera, bounds, grid, pose
-    int n_levels;
-    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
     // workspace and outputs
     int *owner;                                  // N: largest point index that chose keypoint k (-1 between calls: k_last_resolve resets it)
     int *bin, *cand;                             // per point: rotation bin (-1: no match), candidates
@@ -152,20 +152,12 @@ void launch_last_match(const LastFrameArgs &a, int pass, hipStream_t s);
 void launch_last_resolve(const LastFrameArgs &a, int pass, hipStream_t s);
 // k_kf_candidates / k_kf_resolve (k_search_kf.hip): ORBmatcher::SearchByProjection(CurrentFrame, KeyFrame*, sAlreadyFound, th, ORBdist) over one image
 struct SearchKfArgs {
-    // the current frame: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, blocked_in (NULL: none), grid CSR
-    const int32_t *soa;
-    const float *xy_un;
-    const uint8_t *desc;
-    const uint8_t *blocked;
-    int n_kp;
-    const int32_t *cell_start, *cell_items;
+    FrameView f;                                 // the current frame (u_right unused)
     // the keyframe's points, in ascending keyframe slot
     int n_points;
     const float *Px, *Py, *Pz, *max_distance, *max_dist_inv, *min_dist_inv, *angle;
     const uint8_t *mp_desc;
     jsorb_kf_projection_params p;                // window, threshold, camera, bounds, grid, pose
-    int n_levels;
-    float scale[JSORB_MAX_LEVELS];               // mvScaleFactors
     // workspace and outputs
     int *cand, *cand_n;                          // n_points x search_kf_cap() keys (distance << 18 | CSR position) in walk order, n_points counts
     int32_t *match_kp, *match_dist, *kp_match, *n_matches;
@@ -177,12 +169,7 @@ void launch_kf_candidates(const SearchKfArgs &a, hipStream_t s);
 void launch_kf_resolve(const SearchKfArgs &a, hipStream_t s);
 // k_init_candidates / k_init_resolve (k_search_init.hip): ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
 struct SearchInitArgs {
-    // F2: keypoint SoA (6N), mvKeysUn (x_un[N] y_un[N], NULL: the keypoints), descriptors, grid CSR
-    const int32_t *soa;
-    const float *xy_un;
-    const uint8_t *desc;
-    int n_kp;
-    const int32_t *cell_start, *cell_items;
+    FrameView f;                                 // F2 (u_right, blocked and the levels unused)
     jsorb_init_params p;                         // window, ratio, threshold, grid
     // F1, in keypoint order
     int n1;

@@ -19,7 +19,7 @@
 //                  position with it, bestDist2) and the owner of the winning entry claims it.  Every keypoint is in at most one node, so no two
 //                  waves touch the same entry of match_kf and no order of nodes can change a result.
 // k_bow_resolve    one workgroup per keyframe: the rotation histogram of the claims, ComputeThreeMaxima, the culling and the count (:254-272).
-// bw_bin / the three maxima restate k_search_last.hip's and k_search_init.hip's (kept there as they are).
+// The rotation check, the key layout and the bisection are k_search_common.h's (rot_bin, rot_keep; BW_IDX, bw_lower_bound).
 // The contract (include/jsorb.h, jsorb_bow_transform_async / jsorb_search_by_bow_async) is restated in numpy in tests/test_bow_host.py.
 #include <climits>
 
@@ -35,11 +35,7 @@ namespace jsorb {
 #ifndef BW_SORT_LDS
 #define BW_SORT_LDS 4096                         // k_bow_group sorts up to this many keys in LDS (32 KiB; a test build lowers it: build.py VARIANTS)
 #endif
-#define BW_BINS 30                               // ORBmatcher::HISTO_LENGTH
-#define BW_IDX 18                                // bits of a keypoint index (N < 2^18)
-#define BW_IDX_MASK ((1u << BW_IDX) - 1)
 #define BW_POS 22                                // bits of a child position in k_bow_transform's key (max_children < 2^22)
-#define BW_NOKEY (~0ull)                         // key of a keypoint that is in no node: behind every node
 
 int bow_node_regs() { return BW_NODE_REGS; }
 int bow_sort_lds() { return BW_SORT_LDS; }
@@ -143,28 +139,6 @@ __global__ __launch_bounds__(1024) void k_bow_group(BowMatchArgs a)
     }
 }
 
-// first position of keys[0 .. n) whose key is not below x
-__device__ __forceinline__ int bw_lower_bound(const unsigned long long *keys, int n, unsigned long long x)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// ORBmatcher.cpp:225-230, the arithmetic of lf_bin (k_search_common.h): rot = angle of the keyframe - angle of the frame, + 360 when negative;
-// bin = round(rot * (1.0f / 30)) half away from zero, 30 -> 0.  A bin outside [0, 30) (angles outside [0, 360)) is BW_BINS: never kept.
-__device__ __forceinline__ int bw_bin(float a1, float a2)
-{
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = sl_to_int(roundf(rot * (1.0f / BW_BINS)));
-    if (bin == BW_BINS) bin = 0;
-    return (unsigned)bin < BW_BINS ? bin : BW_BINS;
-}
-
 __global__ __launch_bounds__(256) void k_bow_match(BowMatchArgs a)
 {
     const int lane = threadIdx.x % 64, kf = blockIdx.y;
@@ -249,13 +223,13 @@ __global__ __launch_bounds__(256) void k_bow_match(BowMatchArgs a)
 
 __global__ __launch_bounds__(256) void k_bow_resolve(BowMatchArgs a)
 {
-    __shared__ int s_hist[BW_BINS + 1], s_keep[BW_BINS + 1], s_claims, s_culled;
+    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_claims, s_culled;
     const int kf = blockIdx.x, tid = threadIdx.x, N = a.N;
     const int off = a.kf_start[kf];
     if (a.kf_start[kf + 1] - off <= 0) return;       // an empty keyframe: its row and count were cleared with the others
     int32_t *row = a.match_kf + (size_t)kf * N;
     const bool rot = a.p.check_orientation != 0;
-    if (tid <= BW_BINS) s_hist[tid] = 0;
+    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) { s_claims = 0; s_culled = 0; }
     __syncthreads();
     int claims = 0;
@@ -263,34 +237,13 @@ __global__ __launch_bounds__(256) void k_bow_resolve(BowMatchArgs a)
         const int j = row[k];
         if (j < 0) continue;
         claims++;
-        if (rot) atomicAdd(&s_hist[bw_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))], 1);
+        if (rot) atomicAdd(&s_hist[rot_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))], 1);
     }
     atomicAdd(&s_claims, claims);
     __syncthreads();
     if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (rot) {                                   // ComputeThreeMaxima: strict >, the earlier bin wins a tie
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < BW_BINS; b++) {
-                const int s = s_hist[b];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = b;
-                } else if (s > max3) {
-                    max3 = s; ind3 = b;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                ind2 = -1; ind3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-        }
-        for (int b = 0; b <= BW_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;
-        if (kf == 0) { a.stats[3] = ind1 + 1; a.stats[4] = ind2 + 1; a.stats[5] = ind3 + 1; }      // (0: none - the cleared state)
+        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);
+        if (kf == 0) { a.stats[3] = t.ind1 + 1; a.stats[4] = t.ind2 + 1; a.stats[5] = t.ind3 + 1; }      // (0: none - the cleared state)
     }
     __syncthreads();
     if (rot) {
@@ -298,7 +251,7 @@ __global__ __launch_bounds__(256) void k_bow_resolve(BowMatchArgs a)
         for (int k = tid; k < N; k += 256) {
             const int j = row[k];
             if (j < 0) continue;
-            if (!s_keep[bw_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))]) {
+            if (!s_keep[rot_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))]) {
                 row[k] = -1;                         // :268-269
                 culled++;
             }

@@ -5,11 +5,11 @@
 // hides k from every LATER point whose distance to k is not smaller - and a later point with a smaller distance takes k away.  Point i therefore
 // depends on the claims of the points j < i only, through md_i[k] = min over the j < i that claimed k of their distance (the claims on one
 // keypoint have strictly decreasing distances, so the minimum is the last one).  Here:
-//   k_init_candidates  SI_LANES lanes per F1 point: the window's grid cells in the reference's order (ix outer, iy inner, a cell's items ascending),
+//   k_init_candidates  SL_LANES lanes per F1 point: the window's grid cells in the reference's order (ix outer, iy inner, a cell's items ascending),
 //                      the octave and window filters, the Hamming distance; the first SI_CAP survivors packed (keypoint, distance) in walk order
 //                      and the count of all of them.  A point over SI_CAP is rescanned from the grid by the resolver.
 //   k_init_resolve     one workgroup.  The points that have candidates, in ascending order, in chunks of SI_CHUNK (one wave's worth of points,
-//                      SI_LANES lanes each).  state[k] = md of all FINISHED chunks << 8 | mark.  Inside a chunk the rule is iterated to its fixed
+//                      SL_LANES lanes each).  state[k] = md of all FINISHED chunks << 8 | mark.  Inside a chunk the rule is iterated to its fixed
 //                      point: every round each point chooses over md = min(finished md, distances of the LOWER points of the chunk that chose k
 //                      in the previous round).  The first point of a chunk depends on finished chunks only, so it is final after round 1; point
 //                      p of the chunk sees final lower points from round p + 1 on, so it is final after round p + 1: all SI_CHUNK points
@@ -18,7 +18,8 @@
 //                      the previous round (SI_FREE: none): a point scans the lower points' choices only for candidates so marked.
 //                      Then the claims' last owners (vnMatches21), the rotation histogram over ALL claims, ComputeThreeMaxima, the culling, the
 //                      count and vbPrevMatched.
-// lf_bin / ComputeThreeMaxima restate those of k_search_common.h / k_search_last.hip (kept as they are: this file's kernels compile to the same instructions as before).
+// The window walk, its compaction and the rotation check are k_search_common.h's (walk_window, compact_window; rot_bin, rot_keep).  The chunked
+// claim rule is this matcher's own: a later point takes a keypoint away, so it is not claim_resolve's fixed point.
 // The contract (include/jsorb.h, jsorb_search_for_initialization_async) is restated in numpy in tests/test_search_init_host.py.
 #include <climits>
 
@@ -31,9 +32,7 @@ namespace jsorb {
 #define SI_CAP 192                               // candidates kept per F1 point (a test build lowers it: jetson_slam_amd/build.py VARIANTS)
 #endif
 #define SI_LDS_STATE 12288                       // k_init_resolve keeps state[] in LDS up to this many keypoints (48 KiB)
-#define SI_LANES 16                              // lanes per point in both kernels
-#define SI_CHUNK 64                              // points per chunk of k_init_resolve (1024 threads / SI_LANES)
-#define SI_BINS 30                               // ORBmatcher::HISTO_LENGTH
+#define SI_CHUNK 64                              // points per chunk of k_init_resolve (1024 threads / SL_LANES)
 #define SI_NONE 511                              // vMatchedDistance = INT_MAX: above every distance (<= 256)
 #define SI_FREE 0xff                             // mark: no point of the running chunk chose the keypoint in the previous round
 #define SI_PACK(k, d) ((k) << 9 | (d))           // keypoint < 2^18, distance <= 256
@@ -59,22 +58,20 @@ __device__ __forceinline__ bool si_point(const SearchInitArgs &a, int i, SiPoint
 // keypoint k as a candidate of the point: -1 if a filter drops it, else its Hamming distance
 __device__ __forceinline__ int si_candidate(const SearchInitArgs &a, const SiPoint &p, uint4 mlo, uint4 mhi, int k)
 {
-    const int n = a.n_kp;
-    if (p.levels && a.soa[4 * (size_t)n + k] != 0) return -1;      // octave < 0 or > 0 against (minLevel, maxLevel) = (0, 0)
-    const float kx = a.xy_un ? a.xy_un[k] : (float)a.soa[k];
-    const float ky = a.xy_un ? a.xy_un[n + k] : (float)a.soa[n + k];
+    const FrameView &f = a.f;
+    if (p.levels && f.octave(k) != 0) return -1;      // octave < 0 or > 0 against (minLevel, maxLevel) = (0, 0)
     const float R = a.p.window;
-    if (!(fabsf(kx - p.x) < R && fabsf(ky - p.y) < R)) return -1;
+    if (!(fabsf(f.x(k) - p.x) < R && fabsf(f.y(k) - p.y) < R)) return -1;
     uint4 lo, hi;
-    sl_load_desc(a.desc + 32 * (size_t)k, lo, hi);
+    sl_load_desc(f.desc + 32 * (size_t)k, lo, hi);
     return SL_HAMMING(lo, hi, mlo, mhi);
 }
 
 __global__ __launch_bounds__(256) void k_init_candidates(SearchInitArgs a)
 {
-    const int lane = threadIdx.x % SI_LANES;
-    const int i = blockIdx.x * (256 / SI_LANES) + threadIdx.x / SI_LANES;
-    if (i >= a.n1) return;                           // (whole groups of SI_LANES lanes leave together)
+    const int lane = threadIdx.x % SL_LANES;
+    const int i = blockIdx.x * (256 / SL_LANES) + threadIdx.x / SL_LANES;
+    if (i >= a.n1) return;                           // (whole groups of SL_LANES lanes leave together)
     if (lane == 0) a.matches12[i] = -1;
     SiPoint p;
     if (!si_point(a, i, p)) {
@@ -83,51 +80,29 @@ __global__ __launch_bounds__(256) void k_init_candidates(SearchInitArgs a)
     }
     uint4 mlo, mhi;
     sl_load_desc(a.f1_desc + 32 * (size_t)i, mlo, mhi);
-    const int shift = threadIdx.x % 64 / SI_LANES * SI_LANES;
-    int *out = a.cand + (size_t)i * SI_CAP;
-    int count = 0;
-    for (int ix = p.x0; ix <= p.x1; ix++) {
-        const int b = a.cell_start[ix * a.p.rows + p.y0], e = a.cell_start[ix * a.p.rows + p.y1 + 1];
-        for (int base = b; base < e; base += SI_LANES) {
-            const int j = base + lane;
-            const int k = j < e ? a.cell_items[j] : 0;
-            const int d = j < e ? si_candidate(a, p, mlo, mhi, k) : -1;
-            const unsigned m = (unsigned)(__ballot(d >= 0) >> shift) & ((1u << SI_LANES) - 1);
-            const int pos = count + __popc(m & ((1u << lane) - 1));
-            if (d >= 0 && pos < SI_CAP) out[pos] = SI_PACK(k, d);
-            count += __popc(m);
-        }
-    }
+    const int count = compact_window<SI_CAP>(a.f.cell_start, a.p.rows, p.x0, p.x1, p.y0, p.y1, a.cand + (size_t)i * SI_CAP, [&](int j) {
+        const int k = a.f.cell_items[j], d = si_candidate(a, p, mlo, mhi, k);
+        return d >= 0 ? SI_PACK(k, d) : -1;
+    });
     if (lane == 0) a.cand_n[i] = count;
-}
-
-// ORBmatcher.cpp:462-467, the arithmetic of lf_bin (k_search_common.h): rot = angle1 - angle2, + 360 when negative; bin = round(rot * (1.0f / 30))
-// half away from zero, 30 -> 0.  A bin outside [0, 30) (angles outside [0, 360)) is SI_BINS: never kept.
-__device__ __forceinline__ int si_bin(float a1, float a2)
-{
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = sl_to_int(roundf(rot * (1.0f / SI_BINS)));
-    if (bin == SI_BINS) bin = 0;
-    return (unsigned)bin < SI_BINS ? bin : SI_BINS;
 }
 
 // a word that other waves of the workgroup update with atomics (state in global memory, owner): read past the vector cache, where a line fetched
 // before the atomic could still sit
 __device__ __forceinline__ int si_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// One workgroup of SI_CHUNK x SI_LANES threads.  state: LDS when the frame's keypoints fit (dynamic LDS of n_kp ints), else global memory.
+// One workgroup of SI_CHUNK x SL_LANES threads.  state: LDS when the frame's keypoints fit (dynamic LDS of n_kp ints), else global memory.
 __global__ __launch_bounds__(1024) void k_init_resolve(SearchInitArgs a, int state_in_lds)
 {
     extern __shared__ int s_state[];
-    __shared__ int s_k[SI_CHUNK], s_d[SI_CHUNK], s_wave[1024 / 64], s_hist[SI_BINS + 1], s_keep[SI_BINS + 1], s_claims, s_owned, s_culled, s_cand, s_over;
-    const int tid = threadIdx.x, n1 = a.n1, N = a.n_kp;
+    __shared__ int s_k[SI_CHUNK], s_d[SI_CHUNK], s_wave[1024 / 64], s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_claims, s_owned, s_culled, s_cand, s_over;
+    const int tid = threadIdx.x, n1 = a.n1, N = a.f.n_kp;
     int *state = state_in_lds ? s_state : a.state;
     for (int k = tid; k < N; k += 1024) {
         state[k] = SI_NONE << 8 | SI_FREE;
         a.owner[k] = -1;
     }
-    if (tid <= SI_BINS) s_hist[tid] = 0;
+    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) { s_claims = 0; s_owned = 0; s_culled = 0; s_cand = 0; s_over = 0; }
     // order[]: the points that have candidates, ascending (the others claim nothing and hide nothing)
     int total = 0, cand = 0, over = 0;
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(1024) void k_init_resolve(SearchInitArgs a, int sta
     atomicAdd(&s_over, over);
     __syncthreads();
 
-    const int p = tid / SI_LANES, lane = tid % SI_LANES;
+    const int p = tid / SL_LANES, lane = tid % SL_LANES;
     const float ratio = a.p.nn_ratio;
     int rounds = 0;
     for (int base = 0; base < total; base += SI_CHUNK) {
@@ -187,23 +162,20 @@ __global__ __launch_bounds__(1024) void k_init_resolve(SearchInitArgs a, int sta
                 }
             };
             if (cnt <= SI_CAP) {
-                for (int t = lane; t < cnt; t += SI_LANES) {
+                for (int t = lane; t < cnt; t += SL_LANES) {
                     const int c = list[t];
                     take(c >> 9, c & 511, t);
                 }
             } else {
-                for (int ix = pt.x0; ix <= pt.x1; ix++) {
-                    const int e = a.cell_start[ix * a.p.rows + pt.y1 + 1];
-                    for (int j = a.cell_start[ix * a.p.rows + pt.y0] + lane; j < e; j += SI_LANES) {
-                        const int k = a.cell_items[j];
-                        const int d = si_candidate(a, pt, mlo, mhi, k);
-                        if (d >= 0) take(k, d, j);   // the CSR position grows with the walk
-                    }
-                }
+                walk_window<false>(a.f.cell_start, a.p.rows, pt.x0, pt.x1, pt.y0, pt.y1, lane, SL_LANES, [&](int j, bool) {
+                    const int k = a.f.cell_items[j];
+                    const int d = si_candidate(a, pt, mlo, mhi, k);
+                    if (d >= 0) take(k, d, j);       // the CSR position grows with the walk
+                });
             }
-            for (int s = SI_LANES / 2; s > 0; s >>= 1) {      // the point's lanes are all here: the two smallest over them
-                const unsigned long long ob = __shfl_xor(best, s, SI_LANES);
-                const int o1 = __shfl_xor(d1, s, SI_LANES), o2 = __shfl_xor(d2, s, SI_LANES);
+            for (int s = SL_LANES / 2; s > 0; s >>= 1) {      // the point's lanes are all here: the two smallest over them
+                const unsigned long long ob = __shfl_xor(best, s, SL_LANES);
+                const int o1 = __shfl_xor(d1, s, SL_LANES), o2 = __shfl_xor(d2, s, SL_LANES);
                 d2 = min(max(d1, o1), min(d2, o2));
                 d1 = min(d1, o1);
                 best = min(best, ob);
@@ -244,35 +216,14 @@ __global__ __launch_bounds__(1024) void k_init_resolve(SearchInitArgs a, int sta
         if (k < 0) continue;
         claims++;
         owned += si_ld(&a.owner[k]) == i;
-        if (rot) atomicAdd(&s_hist[si_bin(a.angle[i], __int_as_float(a.soa[3 * (size_t)N + k]))], 1);
+        if (rot) atomicAdd(&s_hist[rot_bin(a.angle[i], a.f.angle(k))], 1);
     }
     atomicAdd(&s_claims, claims);
     atomicAdd(&s_owned, owned);
     __syncthreads();
     if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (rot) {                                   // ComputeThreeMaxima: strict >, the earlier bin wins a tie
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < SI_BINS; b++) {
-                const int s = s_hist[b];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = b;
-                } else if (s > max3) {
-                    max3 = s; ind3 = b;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                ind2 = -1; ind3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-        }
-        for (int b = 0; b <= SI_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;
-        a.stats[4] = ind1; a.stats[5] = ind2; a.stats[6] = ind3;
+        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);
+        a.stats[4] = t.ind1; a.stats[5] = t.ind2; a.stats[6] = t.ind3;
     }
     __syncthreads();
     int culled = 0;
@@ -280,14 +231,14 @@ __global__ __launch_bounds__(1024) void k_init_resolve(SearchInitArgs a, int sta
         const int k = a.matches12[i];
         if (k < 0) continue;
         int m = si_ld(&a.owner[k]) == i ? k : -1;            // vnMatches12[vnMatches21[bestIdx2]] = -1
-        if (m >= 0 && rot && !s_keep[si_bin(a.angle[i], __int_as_float(a.soa[3 * (size_t)N + k]))]) {
+        if (m >= 0 && rot && !s_keep[rot_bin(a.angle[i], a.f.angle(k))]) {
             m = -1;                                  // a culled bin: vnMatches12[idx1] = -1, nmatches--
             culled++;
         }
         a.matches12[i] = m;
         if (m >= 0) {                                // vbPrevMatched[i1] = F2.mvKeysUn[vnMatches12[i1]].pt
-            a.prev[i] = a.xy_un ? a.xy_un[m] : (float)a.soa[m];
-            a.prev[n1 + i] = a.xy_un ? a.xy_un[N + m] : (float)a.soa[N + m];
+            a.prev[i] = a.f.x(m);
+            a.prev[n1 + i] = a.f.y(m);
         }
     }
     atomicAdd(&s_culled, culled);
@@ -314,14 +265,14 @@ __global__ __launch_bounds__(256) void k_init_keys_un(const int32_t *soa, const 
 void launch_init_candidates(const SearchInitArgs &a, hipStream_t s)
 {
     if (a.n1 <= 0) return;
-    const int per_block = 256 / SI_LANES;
+    const int per_block = 256 / SL_LANES;
     hipLaunchKernelGGL(k_init_candidates, dim3((a.n1 + per_block - 1) / per_block), dim3(256), 0, s, a);
 }
 
 void launch_init_resolve(const SearchInitArgs &a, hipStream_t s)
 {
-    const int lds = a.n_kp <= SI_LDS_STATE;
-    hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(1024), lds ? (size_t)a.n_kp * sizeof(int) : 0, s, a, lds);
+    const int lds = a.f.n_kp <= SI_LDS_STATE;
+    hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(1024), lds ? (size_t)a.f.n_kp * sizeof(int) : 0, s, a, lds);
 }
 
 void launch_init_keys_un(const int32_t *soa, const float *xy_un, int n, float *dst, hipStream_t s)

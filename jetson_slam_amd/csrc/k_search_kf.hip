@@ -8,10 +8,9 @@
 //                    a cell's items ascending: the CSR position grows with the walk), the level / window / blocked_in filters and the Hamming
 //                    distance; the first SK_CAP survivors are written as distance << 18 | CSR position in that order, and the count of all of them.
 //                    The reference's strict-< best over any subset of the survivors is the minimum key of the subset.
-//   k_kf_resolve     one workgroup: the claim rule as the fixed point k_local_resolve runs.  Every round each point takes its minimum key over the
-//                    candidates no point j < i claimed in the previous round (a match iff its distance <= orb_dist), then claim[k] = min i whose
-//                    choice is k.  Point i depends only on the choices of j < i, so after round r the points < r are final: at most n + 1 rounds.  A
-//                    point with more than SK_CAP survivors walks its window again, serially, in the same order.  Then the rotation histogram (one
+//   k_kf_resolve     one workgroup: the claim rule as the fixed point k_local_resolve runs (claim_resolve, k_search_common.h).  Every round each
+//                    point takes its minimum key over the candidates no point j < i claimed in the previous round (a match iff its distance <=
+//                    orb_dist).  A point with more than SK_CAP survivors walks its window again, serially, in the same order.  Then the rotation histogram (one
 //                    entry per matched point: a keypoint is matched at most once), ComputeThreeMaxima, and the cull - after every claim, as the
 //                    reference culls after its loop: a culled keypoint stayed hidden from the later points.
 // The contract (include/jsorb.h, jsorb_search_by_projection_kf_async) is restated in numpy in tests/test_search_kf_host.py.
@@ -28,7 +27,6 @@ namespace jsorb {
 #ifndef SK_LDS_CLAIMS
 #define SK_LDS_CLAIMS 16384                      // k_kf_resolve keeps claim[] in LDS up to this many keypoints (64 KiB; a test build lowers it)
 #endif
-#define SL_LANES 16                              // lanes per point (4 points per wave), as k_local_candidates
 #define SK_POS ((1 << 18) - 1)
 #define SK_KEY(d, j) ((d) << 18 | (j))           // distance <= 256, CSR position < 2^18
 
@@ -48,23 +46,22 @@ __device__ __forceinline__ bool kf_point(const SearchKfArgs &a, int i, KfPoint &
     if (!k14_project(p.Rcw, p.tcw, x, y, z, p.fx, p.fy, p.cx, p.cy, p.min_x, p.max_x, p.min_y, p.max_y, w.u, w.v, invz)) return false;
     float ox, oy, oz, dist;
     if (!k16_gate(p.Ow, x, y, z, a.min_dist_inv + i, a.max_dist_inv + i, ox, oy, oz, dist)) return false;
-    w.L = k16_level(a.max_distance[i], dist, p.log_scale_factor, a.n_levels);
-    w.R = p.th * a.scale[w.L];                       // radius = th * mvScaleFactors[nPredictedLevel], one float product
+    w.L = k16_level(a.max_distance[i], dist, p.log_scale_factor, a.f.n_levels);
+    w.R = p.th * a.f.scale[w.L];                       // radius = th * mvScaleFactors[nPredictedLevel], one float product
     return sl_cells(p, w.u, w.v, w.R, w.x0, w.x1, w.y0, w.y1);
 }
 
 // the item at CSR position j as a candidate of the point: -1 if a filter drops it, else its key
 __device__ __forceinline__ int kf_candidate(const SearchKfArgs &a, const KfPoint &w, uint4 mlo, uint4 mhi, int j)
 {
-    const int n = a.n_kp, k = a.cell_items[j];
-    const int oct = a.soa[4 * (size_t)n + k];
+    const FrameView &f = a.f;
+    const int k = f.cell_items[j];
+    const int oct = f.octave(k);
     if (oct < w.L - 1 || oct > w.L + 1) return -1;
-    const float kx = a.xy_un ? a.xy_un[k] : (float)a.soa[k];
-    const float ky = a.xy_un ? a.xy_un[n + k] : (float)a.soa[n + k];
-    if (!(fabsf(kx - w.u) < w.R && fabsf(ky - w.v) < w.R)) return -1;
-    if (a.blocked && a.blocked[k]) return -1;          // CurrentFrame.mvpMapPoints[k] before the call
+    if (!(fabsf(f.x(k) - w.u) < w.R && fabsf(f.y(k) - w.v) < w.R)) return -1;
+    if (f.blocked && f.blocked[k]) return -1;          // CurrentFrame.mvpMapPoints[k] before the call
     uint4 lo, hi;
-    sl_load_desc(a.desc + 32 * (size_t)k, lo, hi);
+    sl_load_desc(f.desc + 32 * (size_t)k, lo, hi);
     const int d = SL_HAMMING(lo, hi, mlo, mhi);
     return SK_KEY(d, j);
 }
@@ -81,20 +78,8 @@ __global__ __launch_bounds__(256) void k_kf_candidates(SearchKfArgs a)
     }
     uint4 mlo, mhi;
     sl_load_desc(a.mp_desc + 32 * (size_t)i, mlo, mhi);
-    const int shift = threadIdx.x % 64 / SL_LANES * SL_LANES;
-    int *out = a.cand + (size_t)i * SK_CAP;
-    int count = 0;
-    for (int ix = w.x0; ix <= w.x1; ix++) {
-        const int b = a.cell_start[ix * a.p.rows + w.y0], e = a.cell_start[ix * a.p.rows + w.y1 + 1];
-        for (int base = b; base < e; base += SL_LANES) {
-            const int j = base + lane;
-            const int c = j < e ? kf_candidate(a, w, mlo, mhi, j) : -1;
-            const unsigned m = (unsigned)(__ballot(c >= 0) >> shift) & ((1u << SL_LANES) - 1);
-            const int pos = count + __popc(m & ((1u << lane) - 1));
-            if (c >= 0 && pos < SK_CAP) out[pos] = c;
-            count += __popc(m);
-        }
-    }
+    const int count = compact_window<SK_CAP>(a.f.cell_start, a.p.rows, w.x0, w.x1, w.y0, w.y1, a.cand + (size_t)i * SK_CAP,
+                                             [&](int j) { return kf_candidate(a, w, mlo, mhi, j); });
     if (lane == 0) a.cand_n[i] = count;
 }
 
@@ -107,26 +92,23 @@ __device__ void kf_best(const SearchKfArgs &a, const int *claim, int i, int &mat
         const int *l = a.cand + (size_t)i * SK_CAP;
         for (int t = 0; t < cnt; t++) {
             const int c = l[t];
-            if (claim[a.cell_items[c & SK_POS]] >= i) best = min(best, c);      // (< i: CurrentFrame.mvpMapPoints[k] = an earlier point of this call)
+            if (claim[a.f.cell_items[c & SK_POS]] >= i) best = min(best, c);      // (< i: CurrentFrame.mvpMapPoints[k] = an earlier point of this call)
         }
     } else {                                         // overflow: walk the window again, serially, in the same order
         KfPoint w;
         kf_point(a, i, w);
         uint4 mlo, mhi;
         sl_load_desc(a.mp_desc + 32 * (size_t)i, mlo, mhi);
-        for (int ix = w.x0; ix <= w.x1; ix++) {
-            const int b = a.cell_start[ix * a.p.rows + w.y0], e = a.cell_start[ix * a.p.rows + w.y1 + 1];
-            for (int j = b; j < e; j++) {
-                const int c = kf_candidate(a, w, mlo, mhi, j);
-                if (c >= 0 && claim[a.cell_items[j]] >= i) best = min(best, c);
-            }
-        }
+        walk_window<false>(a.f.cell_start, a.p.rows, w.x0, w.x1, w.y0, w.y1, 0, 1, [&](int j, bool) {
+            const int c = kf_candidate(a, w, mlo, mhi, j);
+            if (c >= 0 && claim[a.f.cell_items[j]] >= i) best = min(best, c);
+        });
     }
     match = -1;
     match_dist = -1;
     const int d = best >> 18;
     if (d < 256 && d <= a.p.orb_dist) {
-        match = a.cell_items[best & SK_POS];
+        match = a.f.cell_items[best & SK_POS];
         match_dist = d;
     }
 }
@@ -135,80 +117,40 @@ __device__ void kf_best(const SearchKfArgs &a, const int *claim, int i, int &mat
 __global__ __launch_bounds__(1024) void k_kf_resolve(SearchKfArgs a, int claim_in_lds)
 {
     extern __shared__ int s_claim[];
-    __shared__ int s_hist[LF_BINS + 1], s_keep[LF_BINS + 1], s_count, s_cand, s_over, s_culled;
-    const int tid = threadIdx.x, n = a.n_points, N = a.n_kp;
+    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_count, s_culled;
+    const int tid = threadIdx.x, n = a.n_points;
     const bool rot = a.p.check_orientation != 0;
-    int *claim = claim_in_lds ? s_claim : a.kp_match;
-    if (tid <= LF_BINS) s_hist[tid] = 0;
-    if (tid == 0) { s_count = 0; s_cand = 0; s_over = 0; s_culled = 0; }
-    for (int k = tid; k < N; k += 1024) claim[k] = INT_MAX;
-    int cand = 0, over = 0;
-    for (int i = tid; i < n; i += 1024) {
-        a.match_kp[i] = -2;                          // no choice yet: the first round changes every point
-        const int c = a.cand_n[i];
-        cand += c;
-        over += c > SK_CAP;
-    }
-    __syncthreads();
-    atomicAdd(&s_cand, cand);
-    atomicAdd(&s_over, over);
-    int rounds = 0;
-    while (true) {
-        rounds++;
-        int changed = 0;
-        for (int i = tid; i < n; i += 1024) {
-            int m, d;
-            kf_best(a, claim, i, m, d);
-            if (m != a.match_kp[i]) { changed = 1; a.match_kp[i] = m; }
-            a.match_dist[i] = d;
-        }
-        if (!__syncthreads_or(changed) || rounds > n) break;      // (the bound is never reached: n + 1 rounds suffice)
-        for (int k = tid; k < N; k += 1024) claim[k] = INT_MAX;
-        __syncthreads();
-        for (int i = tid; i < n; i += 1024) {
-            const int m = a.match_kp[i];
-            if (m >= 0) atomicMin(&claim[m], i);
-        }
-        __syncthreads();
-    }
+    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
+    if (tid == 0) { s_count = 0; s_culled = 0; }
+    claim_resolve<SK_CAP>(claim_in_lds ? s_claim : a.kp_match, n, a.f.n_kp, a.cand_n, a.match_kp, a.match_dist, a.kp_match, a.stats,
+                          [&](const int *claim, int i, int &m, int &d) { kf_best(a, claim, i, m, d); });
     // the fixed point: claim[match_kp[i]] == i for every matched point.  kp_match before the cull, the histogram over the matched points
     int matched = 0;
     for (int i = tid; i < n; i += 1024) {
         const int m = a.match_kp[i];
         if (m < 0) continue;
         matched++;
-        if (rot) atomicAdd(&s_hist[lf_bin(a.angle[i], __int_as_float(a.soa[3 * (size_t)N + m]))], 1);      // rotHist[bin].push_back(bestIdx2)
-    }
-    for (int k = tid; k < N; k += 1024) {
-        const int c = claim[k];
-        a.kp_match[k] = c == INT_MAX ? -1 : c;
+        if (rot) atomicAdd(&s_hist[rot_bin(a.angle[i], a.f.angle(m))], 1);      // rotHist[bin].push_back(bestIdx2)
     }
     atomicAdd(&s_count, matched);
     __syncthreads();
     if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (rot) three_maxima(s_hist, ind1, ind2, ind3);
-        for (int b = 0; b <= LF_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;
-        a.stats[3] = ind1; a.stats[4] = ind2; a.stats[5] = ind3;
+        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);
+        a.stats[3] = t.ind1; a.stats[4] = t.ind2; a.stats[5] = t.ind3;
     }
     __syncthreads();
     int culled = 0;
     if (rot)
         for (int i = tid; i < n; i += 1024) {
             const int m = a.match_kp[i];
-            if (m >= 0 && !s_keep[lf_bin(a.angle[i], __int_as_float(a.soa[3 * (size_t)N + m]))]) {      // CurrentFrame.mvpMapPoints[rotHist[i][j]] = NULL; nmatches--
+            if (m >= 0 && !s_keep[rot_bin(a.angle[i], a.f.angle(m))]) {      // CurrentFrame.mvpMapPoints[rotHist[i][j]] = NULL; nmatches--
                 a.kp_match[m] = -1;
                 culled++;
             }
         }
     atomicAdd(&s_culled, culled);
     __syncthreads();
-    if (tid == 0) {
-        *a.n_matches = s_count - s_culled;
-        a.stats[0] = rounds;
-        a.stats[1] = s_cand;
-        a.stats[2] = s_over;
-    }
+    if (tid == 0) *a.n_matches = s_count - s_culled;
 }
 
 void launch_kf_candidates(const SearchKfArgs &a, hipStream_t s)
@@ -220,8 +162,8 @@ void launch_kf_candidates(const SearchKfArgs &a, hipStream_t s)
 
 void launch_kf_resolve(const SearchKfArgs &a, hipStream_t s)
 {
-    const int lds = a.n_kp <= SK_LDS_CLAIMS;
-    hipLaunchKernelGGL(k_kf_resolve, dim3(1), dim3(1024), lds ? (size_t)a.n_kp * sizeof(int) : 0, s, a, lds);
+    const int lds = a.f.n_kp <= SK_LDS_CLAIMS;
+    hipLaunchKernelGGL(k_kf_resolve, dim3(1), dim3(1024), lds ? (size_t)a.f.n_kp * sizeof(int) : 0, s, a, lds);
 }
 
 } // namespace jsorb

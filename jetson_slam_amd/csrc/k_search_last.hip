@@ -8,6 +8,7 @@
 //                   the minimum of (distance, CSR position) over the lanes, which is the reference's strict-< best.  Writes the point's match, its
 //                   rotation bin and candidate count, and atomicMax(owner[k], i): of the points that choose k the last one stays.
 //   k_last_resolve  one workgroup: the rotation histogram, ComputeThreeMaxima, kp_match = owner with the keypoints of culled entries nulled, the count.
+// The window walk and the rotation check are k_search_common.h's (walk_window; rot_bin, rot_keep).
 // A second pass with 2 th replaces the first when it found fewer than retry_below matches: its two kernels are enqueued behind the first pass's
 // and return at once when the first pass's count (ctl[0], written by its k_last_resolve) says no.
 // The contract (include/jsorb.h, jsorb_search_last_frame_async) is restated in numpy in tests/test_search_last_frame_host.py.
@@ -16,7 +17,6 @@
 
 namespace jsorb {
 
-#define SL_LANES 16                              // lanes per point (4 points per wave), as k_local_candidates
 #define LF_KEY(d, j) ((d) << 18 | (j))           // distance <= 256, CSR position < 2^18
 
 // the second pass, when the first found enough matches (or retry is off): nothing to do
@@ -29,16 +29,16 @@ __global__ __launch_bounds__(256) void k_last_match(LastFrameArgs a, int pass)
     const int i = blockIdx.x * (256 / SL_LANES) + threadIdx.x / SL_LANES;
     if (i >= a.n_points) return;                     // (whole groups of SL_LANES lanes leave together)
     const jsorb_last_frame_params &p = a.p;
-    const int n = a.n_kp;
+    const FrameView &f = a.f;
     float u, v, invz;
     const bool valid = k14_project(p.Rcw, p.tcw, a.Px[i], a.Py[i], a.Pz[i], p.fx, p.fy, p.cx, p.cy, p.min_x, p.max_x, p.min_y, p.max_y, u, v, invz);
     const int L = a.octave[i];
     int best = INT_MAX, count = 0;
     int x0, x1, y0, y1;
     float R = 0.0f;
-    if (valid && L >= 0 && L < a.n_levels) R = (pass ? 2.0f * p.th : p.th) * a.scale[L];     // radius = th * mvScaleFactors[last_octave]
+    if (valid && L >= 0 && L < f.n_levels) R = (pass ? 2.0f * p.th : p.th) * f.scale[L];     // radius = th * mvScaleFactors[last_octave]
     // everything up to here is uniform across the lanes of a point
-    if (valid && L >= 0 && L < a.n_levels && sl_cells(p, u, v, R, x0, x1, y0, y1)) {
+    if (valid && L >= 0 && L < f.n_levels && sl_cells(p, u, v, R, x0, x1, y0, y1)) {
         // GetFeaturesInArea's level window: (L, -1) forward, (0, L) backward, (L-1, L+1) otherwise; levels only checked when minLevel > 0 || maxLevel >= 0
         const int lo = p.direction > 0 ? L : p.direction < 0 ? 0 : L - 1;
         const int hi = p.direction > 0 ? -1 : p.direction < 0 ? L : L + 1;
@@ -47,25 +47,20 @@ __global__ __launch_bounds__(256) void k_last_match(LastFrameArgs a, int pass)
         const float xr = u - m;
         uint4 mlo, mhi;
         sl_load_desc(a.mp_desc + 32 * (size_t)i, mlo, mhi);
-        for (int ix = x0; ix <= x1; ix++) {
-            const int e = a.cell_start[ix * p.rows + y1 + 1];
-            for (int j = a.cell_start[ix * p.rows + y0] + lane; j < e; j += SL_LANES) {
-                const int k = a.cell_items[j];
-                const int oct = a.soa[4 * (size_t)n + k];
-                if (levels && (oct < lo || (hi >= 0 && oct > hi))) continue;
-                const float kx = a.xy_un ? a.xy_un[k] : (float)a.soa[k];
-                const float ky = a.xy_un ? a.xy_un[n + k] : (float)a.soa[n + k];
-                if (!(fabsf(kx - u) < R && fabsf(ky - v) < R)) continue;
-                if (a.u_right) {
-                    const float ur = a.u_right[k];
-                    if (ur > 0 && fabsf(xr - ur) > R) continue;
-                }
-                count++;
-                uint4 lo4, hi4;
-                sl_load_desc(a.desc + 32 * (size_t)k, lo4, hi4);
-                best = min(best, LF_KEY(SL_HAMMING(lo4, hi4, mlo, mhi), j));
+        walk_window<false>(f.cell_start, p.rows, x0, x1, y0, y1, lane, SL_LANES, [&](int j, bool) {
+            const int k = f.cell_items[j];
+            const int oct = f.octave(k);
+            if (levels && (oct < lo || (hi >= 0 && oct > hi))) return;
+            if (!(fabsf(f.x(k) - u) < R && fabsf(f.y(k) - v) < R)) return;
+            if (f.u_right) {
+                const float ur = f.u_right[k];
+                if (ur > 0 && fabsf(xr - ur) > R) return;
             }
-        }
+            count++;
+            uint4 lo4, hi4;
+            sl_load_desc(f.desc + 32 * (size_t)k, lo4, hi4);
+            best = min(best, LF_KEY(SL_HAMMING(lo4, hi4, mlo, mhi), j));
+        });
     }
     for (int s = SL_LANES / 2; s > 0; s >>= 1) {      // the point's lanes are all here: reduce over them
         best = min(best, __shfl_xor(best, s, SL_LANES));
@@ -76,10 +71,10 @@ __global__ __launch_bounds__(256) void k_last_match(LastFrameArgs a, int pass)
     const int d = best >> 18;
     int match = -1, dist = -1, bin = -1;
     if (d < 256 && d <= p.th_high) {
-        match = a.cell_items[best & ((1 << 18) - 1)];
+        match = f.cell_items[best & ((1 << 18) - 1)];
         dist = d;
         atomicMax(&a.owner[match], i);               // CurrentFrame.mvpMapPoints[bestIdx2] = point i, in point order: the largest i stays
-        if (p.check_orientation) bin = lf_bin(a.angle[i], __int_as_float(a.soa[3 * (size_t)n + match]));
+        if (p.check_orientation) bin = rot_bin(a.angle[i], f.angle(match));
     }
     a.match_kp[i] = match;
     a.match_dist[i] = dist;
@@ -90,11 +85,11 @@ __global__ __launch_bounds__(256) void k_last_match(LastFrameArgs a, int pass)
 // One workgroup: the histogram over the matched points, ComputeThreeMaxima, kp_match and the count; owner is reset to -1 for the next call.
 __global__ __launch_bounds__(1024) void k_last_resolve(LastFrameArgs a, int pass)
 {
-    __shared__ int s_hist[LF_BINS + 1], s_keep[LF_BINS + 1], s_matched, s_culled, s_cand;
+    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_matched, s_culled, s_cand;
     if (lf_skip(a, pass)) return;
-    const int tid = threadIdx.x, n = a.n_points, N = a.n_kp;
+    const int tid = threadIdx.x, n = a.n_points, N = a.f.n_kp;
     const bool rot = a.p.check_orientation != 0;
-    if (tid <= LF_BINS) s_hist[tid] = 0;
+    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) { s_matched = 0; s_culled = 0; s_cand = 0; }
     __syncthreads();
     int matched = 0, cand = 0;
@@ -113,29 +108,8 @@ __global__ __launch_bounds__(1024) void k_last_resolve(LastFrameArgs a, int pass
     }
     __syncthreads();
     if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (rot) {                                   // ComputeThreeMaxima: strict >, the earlier bin wins a tie
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < LF_BINS; b++) {
-                const int s = s_hist[b];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = b;
-                } else if (s > max3) {
-                    max3 = s; ind3 = b;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                ind2 = -1; ind3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-        }
-        for (int b = 0; b <= LF_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;
-        a.ctl[3] = ind1; a.ctl[4] = ind2; a.ctl[5] = ind3;
+        const ThreeMaxima m = rot_keep(s_hist, s_keep, rot);
+        a.ctl[3] = m.ind1; a.ctl[4] = m.ind2; a.ctl[5] = m.ind3;
     }
     __syncthreads();
     int culled = 0;

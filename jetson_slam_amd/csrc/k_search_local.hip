@@ -6,10 +6,9 @@
 //                       ascending; the cells of one ix form one contiguous range of the CSR), level / window / blocked_in / uRight filters,
 //                       Hamming distance; the first SL_CAP survivors are written packed (keypoint, octave, distance) in that order, and the
 //                       count of all of them.  A point with more than SL_CAP candidates is flagged by its count and rescanned by the resolver.
-//   k_local_resolve     one workgroup: the claim rule as a fixed point.  Every round each point takes its best / second best over the candidates
-//                       no point j < i has claimed in the previous round; then claim[k] = min i whose choice is k.  Point i depends only on the
-//                       choices of j < i, so after round r the points < r are final: at most n + 1 rounds, and the fixed point is the
-//                       sequential result.
+//   k_local_resolve     one workgroup: the claim rule as a fixed point (claim_resolve, k_search_common.h).  Every round each point takes its
+//                       best / second best over the candidates no point j < i has claimed in the previous round.
+// The window walk, its compaction and the fixed point are k_search_common.h's (walk_window, compact_window, claim_resolve).
 // The contract (include/jsorb.h, jsorb_search_local_points_async) is restated in numpy in tests/test_search_local_host.py.
 #include <climits>
 
@@ -22,7 +21,6 @@ namespace jsorb {
 #define SL_CAP 128                               // candidates kept per map point (a test build lowers it: jetson_slam_amd/build.py VARIANTS)
 #endif
 #define SL_LDS_CLAIMS 16384                      // k_local_resolve keeps claim[] in LDS up to this many keypoints (64 KiB)
-#define SL_LANES 16                              // lanes per map point in k_local_candidates (4 points per wave)
 #define SL_PACK(k, oct, d) ((k) << 13 | (oct) << 9 | (d))      // keypoint < 2^18, octave < 16, distance <= 256
 
 int search_local_cap() { return SL_CAP; }
@@ -36,11 +34,11 @@ __device__ __forceinline__ bool sl_point(const SearchLocalArgs &a, int i, SlPoin
 {
     if (!a.in_frustum[i]) return false;              // !pMP->mbTrackInView
     p.L = a.level[i];
-    if (p.L < 0 || p.L >= a.n_levels) return false;  // outside the contract: matches nothing
+    if (p.L < 0 || p.L >= a.f.n_levels) return false;  // outside the contract: matches nothing
     // RadiusByViewingCos (ORBmatcher.cpp:118-124) compares the float with the DOUBLE 0.998: (double)c > 0.998 <=> c >= 0.998f
     float r = a.view_cos[i] >= 0.998f ? 2.5f : 4.0f;
     if (a.th != 1.0f) r *= a.th;
-    p.R = r * a.scale[p.L];
+    p.R = r * a.f.scale[p.L];
     p.x = a.u[i];
     p.y = a.v[i];
     const float m = a.mbf * a.invz[i];                // mTrackProjXR = u - mbf*invz (Tracking.cpp:1617), two roundings
@@ -51,19 +49,17 @@ __device__ __forceinline__ bool sl_point(const SearchLocalArgs &a, int i, SlPoin
 // keypoint k as a candidate of the point: -1 if a filter drops it, else its packed entry
 __device__ __forceinline__ int sl_candidate(const SearchLocalArgs &a, const SlPoint &p, uint4 mlo, uint4 mhi, int k)
 {
-    const int n = a.n_kp;
-    const int oct = a.soa[4 * (size_t)n + k];
+    const FrameView &f = a.f;
+    const int oct = f.octave(k);
     if (oct < p.L - 1 || oct > p.L) return -1;
-    const float kx = a.xy_un ? a.xy_un[k] : (float)a.soa[k];
-    const float ky = a.xy_un ? a.xy_un[n + k] : (float)a.soa[n + k];
-    if (!(fabsf(kx - p.x) < p.R && fabsf(ky - p.y) < p.R)) return -1;
-    if (a.blocked && a.blocked[k]) return -1;          // F.mvpMapPoints[idx] && Observations() > 0
-    if (a.u_right) {
-        const float ur = a.u_right[k];
+    if (!(fabsf(f.x(k) - p.x) < p.R && fabsf(f.y(k) - p.y) < p.R)) return -1;
+    if (f.blocked && f.blocked[k]) return -1;          // F.mvpMapPoints[idx] && Observations() > 0
+    if (f.u_right) {
+        const float ur = f.u_right[k];
         if (ur > 0 && fabsf(p.xr - ur) > p.R) return -1;
     }
     uint4 lo, hi;
-    sl_load_desc(a.desc + 32 * (size_t)k, lo, hi);
+    sl_load_desc(f.desc + 32 * (size_t)k, lo, hi);
     const int d = SL_HAMMING(lo, hi, mlo, mhi);
     return SL_PACK(k, oct, d);
 }
@@ -80,20 +76,8 @@ __global__ __launch_bounds__(256) void k_local_candidates(SearchLocalArgs a)
     }
     uint4 mlo, mhi;
     sl_load_desc(a.mp_desc + 32 * (size_t)i, mlo, mhi);
-    const int shift = threadIdx.x % 64 / SL_LANES * SL_LANES;
-    int *out = a.cand + (size_t)i * SL_CAP;
-    int count = 0;
-    for (int ix = p.x0; ix <= p.x1; ix++) {
-        const int b = a.cell_start[ix * a.rows + p.y0], e = a.cell_start[ix * a.rows + p.y1 + 1];
-        for (int base = b; base < e; base += SL_LANES) {
-            const int j = base + lane;
-            const int c = j < e ? sl_candidate(a, p, mlo, mhi, a.cell_items[j]) : -1;
-            const unsigned m = (unsigned)(__ballot(c >= 0) >> shift) & ((1u << SL_LANES) - 1);
-            const int pos = count + __popc(m & ((1u << lane) - 1));
-            if (c >= 0 && pos < SL_CAP) out[pos] = c;
-            count += __popc(m);
-        }
-    }
+    const int count = compact_window<SL_CAP>(a.f.cell_start, a.rows, p.x0, p.x1, p.y0, p.y1, a.cand + (size_t)i * SL_CAP,
+                                             [&](int j) { return sl_candidate(a, p, mlo, mhi, a.f.cell_items[j]); });
     if (lane == 0) a.cand_n[i] = count;
 }
 
@@ -121,13 +105,10 @@ __device__ void sl_best(const SearchLocalArgs &a, const int *claim, int i, int &
         sl_point(a, i, p);
         uint4 mlo, mhi;
         sl_load_desc(a.mp_desc + 32 * (size_t)i, mlo, mhi);
-        for (int ix = p.x0; ix <= p.x1; ix++) {
-            const int b = a.cell_start[ix * a.rows + p.y0], e = a.cell_start[ix * a.rows + p.y1 + 1];
-            for (int j = b; j < e; j++) {
-                const int c = sl_candidate(a, p, mlo, mhi, a.cell_items[j]);
-                if (c >= 0) take(c);
-            }
-        }
+        walk_window<false>(a.f.cell_start, a.rows, p.x0, p.x1, p.y0, p.y1, 0, 1, [&](int j, bool) {
+            const int c = sl_candidate(a, p, mlo, mhi, a.f.cell_items[j]);
+            if (c >= 0) take(c);
+        });
     }
     match = -1;
     match_dist = -1;
@@ -141,54 +122,16 @@ __device__ void sl_best(const SearchLocalArgs &a, const int *claim, int i, int &
 __global__ __launch_bounds__(1024) void k_local_resolve(SearchLocalArgs a, int claim_in_lds)
 {
     extern __shared__ int s_claim[];
-    __shared__ int s_count, s_cand, s_over;
-    const int tid = threadIdx.x, n = a.n_points, N = a.n_kp;
-    int *claim = claim_in_lds ? s_claim : a.kp_match;
-    if (tid == 0) { s_count = 0; s_cand = 0; s_over = 0; }
-    for (int k = tid; k < N; k += 1024) claim[k] = INT_MAX;
-    int cand = 0, over = 0;
-    for (int i = tid; i < n; i += 1024) {
-        a.match_kp[i] = -2;                          // no choice yet: the first round changes every point
-        const int c = a.cand_n[i];
-        cand += c;
-        over += c > SL_CAP;
-    }
-    __syncthreads();
-    atomicAdd(&s_cand, cand);
-    atomicAdd(&s_over, over);
-    int rounds = 0;
-    while (true) {
-        rounds++;
-        int changed = 0;
-        for (int i = tid; i < n; i += 1024) {
-            int m, d;
-            sl_best(a, claim, i, m, d);
-            if (m != a.match_kp[i]) { changed = 1; a.match_kp[i] = m; }
-            a.match_dist[i] = d;
-        }
-        if (!__syncthreads_or(changed) || rounds > n) break;      // (the bound is never reached: n + 1 rounds suffice)
-        for (int k = tid; k < N; k += 1024) claim[k] = INT_MAX;
-        __syncthreads();
-        for (int i = tid; i < n; i += 1024) {
-            const int m = a.match_kp[i];
-            if (m >= 0) atomicMin(&claim[m], i);
-        }
-        __syncthreads();
-    }
+    __shared__ int s_count;
+    const int tid = threadIdx.x, n = a.n_points;
+    if (tid == 0) s_count = 0;
+    claim_resolve<SL_CAP>(claim_in_lds ? s_claim : a.kp_match, n, a.f.n_kp, a.cand_n, a.match_kp, a.match_dist, a.kp_match, a.stats,
+                          [&](const int *claim, int i, int &m, int &d) { sl_best(a, claim, i, m, d); });
     int matched = 0;
     for (int i = tid; i < n; i += 1024) matched += a.match_kp[i] >= 0;
-    for (int k = tid; k < N; k += 1024) {
-        const int c = claim[k];
-        a.kp_match[k] = c == INT_MAX ? -1 : c;
-    }
     atomicAdd(&s_count, matched);
     __syncthreads();
-    if (tid == 0) {
-        *a.n_matches = s_count;
-        a.stats[0] = rounds;
-        a.stats[1] = s_cand;
-        a.stats[2] = s_over;
-    }
+    if (tid == 0) *a.n_matches = s_count;
 }
 
 void launch_local_candidates(const SearchLocalArgs &a, hipStream_t s)
@@ -200,8 +143,8 @@ void launch_local_candidates(const SearchLocalArgs &a, hipStream_t s)
 
 void launch_local_resolve(const SearchLocalArgs &a, hipStream_t s)
 {
-    const int lds = a.n_kp <= SL_LDS_CLAIMS;
-    hipLaunchKernelGGL(k_local_resolve, dim3(1), dim3(1024), lds ? (size_t)a.n_kp * sizeof(int) : 0, s, a, lds);
+    const int lds = a.f.n_kp <= SL_LDS_CLAIMS;
+    hipLaunchKernelGGL(k_local_resolve, dim3(1), dim3(1024), lds ? (size_t)a.f.n_kp * sizeof(int) : 0, s, a, lds);
 }
 
 } // namespace jsorb

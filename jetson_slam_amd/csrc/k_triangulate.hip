@@ -3,7 +3,7 @@
 //   and ComputeThreeMaxima (:2097-2138), one keyframe KF1 against several neighbours KF2 in one call.
 // In this reference vbMatched2 (:664) is read (:712) and never set: the result of a KF1 keypoint depends on no other KF1 keypoint, two of them may
 // take the same KF2 keypoint and there is no sequential claim rule.  The kernels reproduce exactly that; an "exclusive" mode is out of scope.
-// Grouping     k_bow_group (k_bow.hip, as it is): KF1 is the frame side of a BowMatchArgs, the KF2s are its keyframe sides - the keys
+// Grouping     k_bow_group (k_bow.hip, as it is; its key layout and bisection are k_search_common.h's BW_IDX / bw_lower_bound): KF1 is the frame side of a BowMatchArgs, the KF2s are its keyframe sides - the keys
 //              node << 18 | index sorted ascending, a node's keypoints one run in ascending index.
 // k_tri_match  grid (positions of KF1's sorted keys, keyframe of the launch's chunk); TR_LANES lanes take one sorted KF1 position: its descriptor,
 //              point and flags once, the KF2 run of its node by bisection, the epipolar line a, b, c once.  The lanes take the run's entries
@@ -21,21 +21,6 @@
 namespace jsorb {
 
 #define TR_LANES 16                              // lanes per KF1 keypoint in k_tri_match (provisional: DESIGN.md section 16)
-#define TR_IDX 18                                // BW_IDX of k_bow.hip: the keys k_bow_group writes
-#define TR_IDX_MASK ((1u << TR_IDX) - 1)
-#define TR_NOKEY (~0ull)                         // BW_NOKEY
-
-// first position of keys[0 .. n) whose key is not below x (k_bow.hip's bw_lower_bound)
-__device__ __forceinline__ int tr_lower_bound(const unsigned long long *keys, int n, unsigned long long x)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
 {
     const int lane = threadIdx.x % TR_LANES, kf = g.kf0 + blockIdx.y;
@@ -43,11 +28,11 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
     const int off = a.kf_start[kf], len = a.kf_start[kf + 1] - off;
     const float *G = g.f[blockIdx.y];                // F12 row-major, ex, ey
     // every lane stays to the end (the reductions below take whole waves); a group's trip count is uniform
-    const unsigned long long k1 = p < a.n1 && len > 0 ? a.sorted1[p] : TR_NOKEY;
-    const bool in_node = k1 != TR_NOKEY;
-    const unsigned long long v = k1 >> TR_IDX;       // the node
-    const int idx1 = (int)(k1 & TR_IDX_MASK);
-    const bool head = in_node && (p == 0 || a.sorted1[p - 1] >> TR_IDX != v);      // the first KF1 keypoint of the node: it counts the pair
+    const unsigned long long k1 = p < a.n1 && len > 0 ? a.sorted1[p] : BW_NOKEY;
+    const bool in_node = k1 != BW_NOKEY;
+    const unsigned long long v = k1 >> BW_IDX;       // the node
+    const int idx1 = (int)(k1 & BW_IDX_MASK);
+    const bool head = in_node && (p == 0 || a.sorted1[p - 1] >> BW_IDX != v);      // the first KF1 keypoint of the node: it counts the pair
     bool stereo1 = false, take = false;
     if (in_node) {
         stereo1 = a.stereo1[idx1] != 0;
@@ -56,8 +41,8 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
     const unsigned long long *ks = a.sorted2 + off;
     int fb = 0, m = 0;
     if (head || take) {
-        fb = tr_lower_bound(ks, len, v << TR_IDX);
-        m = tr_lower_bound(ks, len, (v + 1) << TR_IDX) - fb;
+        fb = bw_lower_bound(ks, len, v << BW_IDX);
+        m = bw_lower_bound(ks, len, (v + 1) << BW_IDX) - fb;
     }
     unsigned key = ~0u;
     int n_dist = 0, n_line = 0;
@@ -72,7 +57,7 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
         const float den = la * la + lb * lb;
         const float ex = G[9], ey = G[10];
         for (int t = lane; t < m; t += TR_LANES) {
-            const int j = off + (int)(ks[fb + t] & TR_IDX_MASK);
+            const int j = off + (int)(ks[fb + t] & BW_IDX_MASK);
             if (!a.free2[j]) continue;                                             // :712
             const bool stereo2 = a.stereo2[j] != 0;
             if (a.only_stereo && !stereo2) continue;                               // :717-719
@@ -89,17 +74,17 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
                 if (distex * distex + distey * distey < a.gate[oct]) continue;
             }
             n_line++;
-            if ((unsigned)d > key >> TR_IDX) continue;                             // above the lane's best: it cannot win
+            if ((unsigned)d > key >> BW_IDX) continue;                             // above the lane's best: it cannot win
             const float num = la * x2 + lb * y2 + lc;
             if (den == 0) continue;                                                // :138
             const float dsqr = num * num / den;
             if (!((double)dsqr < a.line[oct])) continue;                           // :143, a double comparison; a NaN rejects
-            key = min(key, (unsigned)d << TR_IDX | (TR_IDX_MASK - (unsigned)t));
+            key = min(key, (unsigned)d << BW_IDX | (BW_IDX_MASK - (unsigned)t));
         }
     }
     for (int s = TR_LANES / 2; s > 0; s >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, s, TR_LANES));
     if (lane == 0 && key != ~0u)                                                   // :745-748
-        a.match12[(size_t)kf * a.n1 + idx1] = (int)(ks[fb + (int)(TR_IDX_MASK - (key & TR_IDX_MASK))] & TR_IDX_MASK);
+        a.match12[(size_t)kf * a.n1 + idx1] = (int)(ks[fb + (int)(BW_IDX_MASK - (key & BW_IDX_MASK))] & BW_IDX_MASK);
     int pairs = head && m > 0 && lane == 0 ? 1 : 0, largest = head ? m : 0;
     for (int s = 32; s > 0; s >>= 1) {
         pairs += __shfl_xor(pairs, s);
@@ -117,13 +102,13 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
 
 __global__ __launch_bounds__(256) void k_tri_resolve(TriArgs a)
 {
-    __shared__ int s_hist[LF_BINS + 1], s_keep[LF_BINS + 1], s_found, s_culled;
+    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_found, s_culled;
     const int kf = blockIdx.x, tid = threadIdx.x, n1 = a.n1;
     const int off = a.kf_start[kf];
     if (a.kf_start[kf + 1] - off <= 0) return;       // an empty keyframe: its row and count were cleared with the others
     int32_t *row = a.match12 + (size_t)kf * n1;
     const bool rot = a.check_orientation != 0;
-    if (tid <= LF_BINS) s_hist[tid] = 0;
+    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) { s_found = 0; s_culled = 0; }
     __syncthreads();
     int found = 0;
@@ -131,34 +116,13 @@ __global__ __launch_bounds__(256) void k_tri_resolve(TriArgs a)
         const int j = row[k];
         if (j < 0) continue;
         found++;
-        if (rot) atomicAdd(&s_hist[lf_bin(a.angle1[k], a.angle2[off + j])], 1);      // :753-760
+        if (rot) atomicAdd(&s_hist[rot_bin(a.angle1[k], a.angle2[off + j])], 1);      // :753-760
     }
     atomicAdd(&s_found, found);
     __syncthreads();
     if (tid == 0) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (rot) {                                   // ComputeThreeMaxima (k_search_common.h: three_maxima, written out so that the indices stay in registers)
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < LF_BINS; b++) {
-                const int s = s_hist[b];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = b;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = b;
-                } else if (s > max3) {
-                    max3 = s; ind3 = b;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                ind2 = -1; ind3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-        }
-        for (int b = 0; b <= LF_BINS; b++) s_keep[b] = !rot || b == ind1 || b == ind2 || b == ind3;      // (bin LF_BINS, outside [0, 30), is never kept)
-        if (kf == 0) { a.stats[4] = ind1 + 1; a.stats[5] = ind2 + 1; a.stats[6] = ind3 + 1; }      // (0: none - the cleared state)
+        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);      // (bin HISTO_LENGTH, outside [0, 30), is never kept)
+        if (kf == 0) { a.stats[4] = t.ind1 + 1; a.stats[5] = t.ind2 + 1; a.stats[6] = t.ind3 + 1; }      // (0: none - the cleared state)
     }
     __syncthreads();
     if (rot) {
@@ -166,7 +130,7 @@ __global__ __launch_bounds__(256) void k_tri_resolve(TriArgs a)
         for (int k = tid; k < n1; k += 256) {
             const int j = row[k];
             if (j < 0) continue;
-            if (!s_keep[lf_bin(a.angle1[k], a.angle2[off + j])]) {
+            if (!s_keep[rot_bin(a.angle1[k], a.angle2[off + j])]) {
                 row[k] = -1;                         // :792-793
                 culled++;
             }

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from jetson_slam_amd import vocabulary as V
-from test_search_last_frame_host import HISTO_LENGTH, compute_three_maxima, rot_bin
+from test_search_last_frame_host import HISTO_LENGTH, ROTATION_CULL, compute_three_maxima, rot_bin, rotation_cull_expected
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -465,6 +465,18 @@ CONSTRUCTED = {
     "an angle difference that rounds to bin 30": (sides([0, 0, 0], [3, 3, 3], kf_node=[0, 1, 2], f_node=[0, 1, 2], kf_angle=[900, 5, 1200], f_angle=[0, 0, 0]),
                                                   default_params(), [0, 1, -1], 2),
 }
+# the rotation check's edges (ROTATION_CULL): every keyframe keypoint in a node of its own with the frame keypoint it matches.  "eleven_and_one" and
+# "outside_360" are "a match culled by orientation" and "an angle difference that rounds to bin 30" above.
+ROTATION_KEPT = {"a match culled by orientation": (0, -1, -1), "the same without check_orientation": (-1, -1, -1),
+                 "an angle difference that rounds to bin 30": (0, -1, -1)}
+for _name, _on in (("four_equal_bins", 1), ("ten_and_one", 1), ("four_equal_bins", 0)):
+    _rots = ROTATION_CULL[_name]
+    _n = len(_rots)
+    _ind, _kept = rotation_cull_expected(_rots, _on)
+    _key = "rotation %s%s" % (_name, "" if _on else " without check_orientation")
+    CONSTRUCTED[_key] = (sides([0] * _n, [3] * _n, kf_node=range(_n), f_node=range(_n), kf_angle=_rots, f_angle=[0] * _n),
+                         default_params(check_orientation=_on), [i if _kept[i] else -1 for i in range(_n)], int(_kept.sum()))
+    ROTATION_KEPT[_key] = _ind
 
 
 @pytest.mark.parametrize("name", sorted(CONSTRUCTED))
@@ -472,6 +484,7 @@ def test_constructed_matcher_cases(name):
     (KF, F), prm, want, count = CONSTRUCTED[name]
     ref = both_searches(KF, F, prm)
     assert list(ref[0]) == want and ref[1] == count, (name, ref[0], ref[1])
+    assert name not in ROTATION_KEPT or tuple(ref[2]["ind"]) == ROTATION_KEPT[name]
 
 
 def single_node_case(n=360, seed=4):
@@ -586,8 +599,10 @@ def test_header_binding_and_build_declare_the_new_entry_points(orb):
     assert "track_reference_keyframe" in jb.EXAMPLES and jb.VARIANTS["tiny_bow_sort"] == (["-DBW_SORT_LDS=64"], ["k_bow.hip"])
     assert orb.bow_build_caps() == (BW_NODE_REGS, BW_SORT_LDS)
     ksrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "k_bow.hip")).read()
-    for name, val in (("BW_NODE_REGS", BW_NODE_REGS), ("BW_LANES", BW_LANES), ("BW_POS", BW_POS), ("BW_IDX", BW_IDX), ("BW_SORT_LDS", BW_SORT_LDS)):
-        assert re.search(r"#define %s %d\b" % (name, val), ksrc), name
+    csrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "k_search_common.h")).read()      # the key layout k_bow.hip and k_triangulate.hip share
+    for name, val, text in (("BW_NODE_REGS", BW_NODE_REGS, ksrc), ("BW_LANES", BW_LANES, ksrc), ("BW_POS", BW_POS, ksrc), ("BW_IDX", BW_IDX, csrc),
+                            ("BW_SORT_LDS", BW_SORT_LDS, ksrc)):
+        assert re.search(r"#define %s %d\b" % (name, val), text), name
     shim = open(os.path.join(ROOT, "include", "jsorb_compat.hpp")).read()
     assert re.search(r"inline int SearchByBoW\(", shim) and re.search(r"inline void ComputeBoW\(", shim) and re.search(r"class Vocabulary \{", shim)
 

@@ -10,7 +10,7 @@ import pytest
 
 from jetson_slam_amd import vocabulary as V
 from jetson_slam_amd.synth import synth_stereo_pair
-from test_bow_host import (CONSTRUCTED, REAL_SEED, agree, both_transforms, chain_and_shallow_tree, default_params, flip_bits, frame_side, sampled_voc,
+from test_bow_host import (ROTATION_KEPT, CONSTRUCTED, REAL_SEED, agree, both_transforms, chain_and_shallow_tree, default_params, flip_bits, frame_side, sampled_voc,
                            search_by_bow_reference, search_by_bow_restated, single_node_case, tied_tree)
 from test_gpu_search_local import _dev, _mk
 
@@ -223,6 +223,7 @@ def test_constructed_cases_through_the_device(orb, configs):
         for sync in (False, True):
             h = check_search(orb, g, [KF], Fp, prm, sync=sync)
             assert list(h[0][0][:len(want)]) == want and h[0][1] == count, name
+            assert name not in ROTATION_KEPT or g.search_by_bow_stats()[3] == ROTATION_KEPT[name], name      # the rotation check's edges: kept_bins
 
 
 @pytest.mark.parametrize("variant", [None, "tiny_bow_wave"])

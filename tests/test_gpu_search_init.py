@@ -152,6 +152,44 @@ def test_window_over_the_whole_grid(orb, configs):
     assert len(F2["kx"]) > SI_CAP and h[4][2] >= int((F1["octave"] < 0).sum()) > 0
 
 
+# ---- the rotation check at its edges: four equal bins, a lone match at and below a tenth, an angle outside [0, 360), the check off ----
+def test_rotation_cull_cases(orb, configs):
+    from test_gpu_search_kf import constructed_on_device
+    from test_search_kf_host import lattice_case
+    from test_search_last_frame_host import ROTATION_CULL, rotation_cull_expected
+    for name, rots in sorted(ROTATION_CULL.items()):
+        F0, _, _ = lattice_case(rots)
+        g, F2 = constructed_on_device(orb, configs["c1"], F0)
+        n, own = len(rots), np.arange(len(rots))
+        F1 = dict(octave=np.zeros(n, np.int32), angle=np.asarray(rots, np.float32), desc=F0["desc"].copy())
+        prev = np.stack([F0["kx"], F0["ky"]]).astype(np.float32)
+        for on in (1, 0):
+            ind, kept = rotation_cull_expected(rots, on)
+            h = check_raw(orb, g, F1, F2, prev, default_params(window=f32(5), check_orientation=on))
+            assert np.array_equal(h[0], np.where(kept, own, -1)) and h[2] == kept.sum() and tuple(h[4][4]) == ind, (name, on)
+
+
+# ---- the shared compaction at a group's width and at the list's end: 15, 16, 17 and (on the small build) cap + 1 survivors in one window, the points
+# in the first and last group of a wave, the first of the next wave and the last of the block ----
+@pytest.mark.parametrize("variant", [None, "tiny_init_cap"])
+def test_survivor_counts_at_the_group_and_list_edges(orb, configs, monkeypatch, variant):
+    from jetson_slam_amd import build as jb
+    from test_gpu_search_kf import constructed_on_device
+    from test_search_kf_host import COMPACTION_AT, compaction_case
+    if variant:
+        monkeypatch.setattr(orb, "_lib", orb.load_library(jb.build_variant(variant, *jb.VARIANTS[variant])))
+    cap = 2 if variant else SI_CAP
+    F0, Pk, _ = compaction_case()
+    g, F2 = constructed_on_device(orb, configs["c1"], F0)
+    u = [40.0 if i in (0, 15) else 120.0 if i == 3 else 200.0 if i == 4 else 280.0 for i in range(16)]
+    v = [140.0 if i == 15 else 40.0 if i in COMPACTION_AT else 100.0 for i in range(16)]
+    F1 = dict(octave=np.zeros(16, np.int32), angle=np.zeros(16, np.float32), desc=np.zeros((16, 32), np.uint8))
+    h = check_raw(orb, g, F1, F2, np.array([u, v], np.float32), default_params(window=f32(5)), cap=cap)
+    rounds, n_cand, n_over = h[4][:3]
+    assert n_cand == sum(COMPACTION_AT.values()) and n_over == sum(k > cap for k in COMPACTION_AT.values()) == (4 if variant else 0)
+    assert h[2] == 4 and sorted(np.nonzero(h[0] >= 0)[0]) == sorted(COMPACTION_AT)
+
+
 # ---- the build with 2 candidates per point: most points take the resolver's rescan of the grid ----
 def test_candidate_overflow_build(orb, configs, monkeypatch):
     from jetson_slam_amd import build as jb

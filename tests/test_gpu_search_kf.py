@@ -16,8 +16,9 @@ from test_gpu_bow import check_search, side_of
 from test_gpu_call_order import world  # noqa: F401  (the module-scoped fixture)
 from test_gpu_search_last_frame import last_frame_of
 from test_gpu_search_local import EUROC, _dev, _mk
-from test_search_kf_host import (camera_centre, chain_case, culled_keypoint_case, distance_ranges, make_frame, search_by_projection_kf,
-                                 search_kf_restated)
+from test_search_kf_host import (COMPACTION_AT, camera_centre, chain_case, compaction_case, culled_keypoint_case, distance_ranges, lattice_case,
+                                 make_frame, search_by_projection_kf, search_kf_restated)
+from test_search_last_frame_host import ROTATION_CULL, rotation_cull_expected
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,6 +213,36 @@ def test_culled_keypoint_stays_hidden_on_the_device(po, orb, configs):
     prm = dict(prm, max_x=f32(c["w"]), max_y=f32(c["h"]))
     m, km, cnt, (_, _, _, ind) = check(po, orb, g, F, P, prm)
     assert m[12] == 12 and m[13] == 13 and km[12] == -1 and cnt == 13 and ind == (0, -1, -1)
+
+
+# ---- the rotation check at its edges: four equal bins, a lone match at and below a tenth, an angle outside [0, 360), the check off ----
+def test_rotation_cull_cases(po, orb, configs):
+    c = configs["c1"]
+    for name, rots in sorted(ROTATION_CULL.items()):
+        F0, P, prm = lattice_case(rots)
+        g, F = constructed_on_device(orb, c, F0)
+        n, own = len(rots), np.arange(len(rots))
+        for on in (1, 0):
+            ind, kept = rotation_cull_expected(rots, on)
+            m, km, cnt, st = check(po, orb, g, F, P, dict(prm, max_x=f32(c["w"]), max_y=f32(c["h"]), check_orientation=on))
+            assert np.array_equal(m, own) and np.array_equal(km[:n], np.where(kept, own, -1)) and (km[n:] == -1).all(), (name, on)
+            assert cnt == kept.sum() and st[3] == ind, (name, on)
+
+
+# ---- the shared compaction at a group's width and at the list's end: 15, 16, 17 and (on the small build) cap + 1 survivors in one window, the points
+# in the first and last group of a wave, the first of the next wave and the last of the block ----
+@pytest.mark.parametrize("variant", [None, "tiny_kf_cap"])
+def test_survivor_counts_at_the_group_and_list_edges(po, orb, configs, monkeypatch, variant):
+    from jetson_slam_amd import build as jb
+    if variant:
+        monkeypatch.setattr(orb, "_lib", orb.load_library(jb.build_variant(variant, *jb.VARIANTS[variant])))
+    cap = orb.search_kf_build_caps()[0]
+    assert cap == (2 if variant else 128)
+    F0, P, prm = compaction_case()
+    g, F = constructed_on_device(orb, configs["c1"], F0)
+    m, km, cnt, (rounds, n_cand, n_over, _) = check(po, orb, g, F, P, dict(prm, max_x=f32(configs["c1"]["w"]), max_y=f32(configs["c1"]["h"])))
+    assert n_cand == sum(COMPACTION_AT.values()) and n_over == sum(v > cap for v in COMPACTION_AT.values()) == (4 if variant else 0)
+    assert cnt == 4 and sorted(np.nonzero(m >= 0)[0]) == sorted(COMPACTION_AT)
 
 
 # ---- a 1 x 1 grid and a window over the whole image: one point sees every keypoint (more than the shipped list holds: the resolver walks again) ----

@@ -10,7 +10,8 @@ import pytest
 
 from jetson_slam_amd.synth import synth_stereo_pair
 from test_gpu_search_local import EUROC, _dev, _from_device_ptr, _mk, _stereo, frame_of
-from test_search_last_frame_host import HISTO_LENGTH, rot_bin, search_by_projection_last, search_last_restated, track_with_motion_model
+from test_search_last_frame_host import (HISTO_LENGTH, ROTATION_CULL, rot_bin, rotation_cull_expected, search_by_projection_last, search_last_restated,
+                                         track_with_motion_model)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -170,6 +171,26 @@ def test_retry(po, orb, configs):
     # retry off: one pass however few
     _, _, _, passes, _ = check(po, orb, gl, F, Pf, prm0, ur_t)
     assert passes == 1
+
+
+# ---- the rotation check at its edges: four equal bins, a lone match at and below a tenth, an angle outside [0, 360), the check off ----
+def test_rotation_cull_cases(po, orb, configs):
+    from test_gpu_search_kf import constructed_on_device
+    from test_search_kf_host import lattice_case
+    c = configs["c1"]
+    for name, rots in sorted(ROTATION_CULL.items()):
+        F0, Pk, pk = lattice_case(rots)
+        g, Fk = constructed_on_device(orb, c, F0)
+        F = dict(Fk, mbf=f32(c["bf"]), u_right=None)
+        n, own = len(rots), np.arange(len(rots))
+        P = dict(Px=Pk["Px"], Py=Pk["Py"], Pz=Pk["Pz"], octave=np.zeros(n, np.int32), angle=Pk["angle"], desc=Pk["desc"])
+        prm = dict(th=f32(5), th_high=100, direction=0, retry_below=0, fx=pk["fx"], fy=pk["fy"], cx=pk["cx"], cy=pk["cy"], min_x=f32(0), max_x=f32(c["w"]),
+                   min_y=f32(0), max_y=f32(c["h"]), Rcw=pk["Rcw"], tcw=pk["tcw"])
+        for on in (1, 0):
+            ind, kept = rotation_cull_expected(rots, on)
+            m, km, cnt, passes, got = check(po, orb, g, F, P, dict(prm, check_orientation=on))
+            assert np.array_equal(m, own) and np.array_equal(km[:n], np.where(kept, own, -1)) and (km[n:] == -1).all(), (name, on)
+            assert cnt == kept.sum() and got == ind and passes == 1, (name, on)
 
 
 # ---- edges, validation, kernel timing ----

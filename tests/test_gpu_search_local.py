@@ -176,6 +176,31 @@ def test_th5_and_candidate_overflow(orb, configs, monkeypatch):
     assert cnt2 == cnt and n_cand2 == n_cand and n_over2 > len(P["u"]) // 2
 
 
+# ---- the shared compaction at a group's width and at the list's end: 15, 16, 17 and (on the small build) cap + 1 survivors in one window, the points
+# in the first and last group of a wave, the first of the next wave and the last of the block ----
+@pytest.mark.parametrize("variant", [None, "tiny_local_cap"])
+def test_survivor_counts_at_the_group_and_list_edges(orb, configs, monkeypatch, variant):
+    from jetson_slam_amd import build as jb
+    from test_gpu_search_kf import constructed_on_device
+    from test_search_kf_host import COMPACTION_AT, compaction_case
+    from test_search_local_host import candidate_lists
+    if variant:
+        monkeypatch.setattr(orb, "_lib", orb.load_library(jb.build_variant(variant, *jb.VARIANTS[variant])))
+    cap = 2 if variant else 128
+    c = configs["c1"]
+    F0, _, _ = compaction_case()
+    g, Fk = constructed_on_device(orb, c, F0)
+    F = dict(Fk, mbf=f32(c["bf"]), u_right=None)
+    u = [40.0 if i in (0, 15) else 120.0 if i == 3 else 200.0 if i == 4 else 280.0 for i in range(16)]
+    v = [140.0 if i == 15 else 40.0 if i in COMPACTION_AT else 100.0 for i in range(16)]
+    P = dict(u=np.array(u, np.float32), v=np.array(v, np.float32), invz=np.ones(16, np.float32), level=np.zeros(16, np.int32),
+             view_cos=np.ones(16, np.float32), in_frustum=np.ones(16, np.uint8), desc=np.zeros((16, 32), np.uint8))
+    assert [len(l) for l in candidate_lists(F, P, 2.0)] == [COMPACTION_AT.get(i, 0) for i in range(16)]      # radius 2.5 * th = 5
+    cnt, (rounds, n_cand, n_over) = check(g, F, P, 2.0)
+    assert n_cand == sum(COMPACTION_AT.values()) and n_over == sum(k > cap for k in COMPACTION_AT.values()) == (4 if variant else 0)
+    assert cnt == 4
+
+
 # ---- a claim chain: every point at the same spot with the same descriptor; point i takes the i-th keypoint of the shared order ----
 def test_claim_chain_needs_many_rounds(orb, configs):
     c = configs["c2"]

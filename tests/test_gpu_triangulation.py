@@ -12,7 +12,7 @@ import pytest
 from jetson_slam_amd.synth import synth_stereo_pair
 from test_bow_host import REAL_SEED, both_transforms, frame_side, sampled_voc
 from test_gpu_search_local import _dev, _mk
-from test_triangulation_host import (CONSTRUCTED, F_LINE, FAR, TR_KF_CHUNK, agree, default_params, geometry, random_case, scale_tables,
+from test_triangulation_host import (ROTATION_KEPT, CONSTRUCTED, F_LINE, FAR, TR_KF_CHUNK, agree, default_params, geometry, random_case, scale_tables,
                                      search_for_triangulation_reference, search_for_triangulation_restated, sides)
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +99,7 @@ def test_constructed_cases_through_the_device(orb, matcher):
         for sync in (False, True):
             h = check_search(orb, matcher, KF1, [KF2], [geom], prm, sync=sync)
             assert list(h[0][0]) == want and h[0][1] == count, name
+            assert name not in ROTATION_KEPT or matcher.stats()[4] == ROTATION_KEPT[name], name      # the rotation check's edges: kept_bins
 
 
 # ---- the group, wave and workgroup edges: KF2 node runs of 1, 15, 16, 17 and 33 entries, KF1 of 1, 15, 16, 17 and 257 sorted positions ----

@@ -69,6 +69,33 @@ def compute_three_maxima(sizes):
     return ind1, ind2, ind3
 
 
+# The rotation check at its edges, the same inputs through every matcher that has one (the GPU tests of each): the rotations (angle of the point's
+# side - angle of the frame's keypoint, the latter 0) of up to 40 matches, in match order.
+ROTATION_CULL = {
+    "four_equal_bins": [33.0] * 10 + [63.0] * 10 + [93.0] * 10 + [123.0] * 10,      # bins 1..4, ten each: the three earliest stay, the fourth goes
+    "ten_and_one": [3.0] * 10 + [153.0],                                            # (float)1 < 0.1f * 10 is false: the lone one stays
+    "eleven_and_one": [3.0] * 11 + [153.0],                                         # 1 < 0.1f * 11: it goes
+    "outside_360": [3.0] * 5 + [1000.0],                                            # bin 33 -> HISTO_LENGTH: never kept
+}
+
+
+def rotation_cull_expected(rots, check_orientation=1):
+    """(kept_bins, which of the matches stay) from rot_bin and compute_three_maxima"""
+    bins = [rot_bin(r, 0.0) for r in rots]
+    if not check_orientation:
+        return (-1, -1, -1), np.ones(len(rots), bool)
+    ind = compute_three_maxima(np.bincount(bins, minlength=HISTO_LENGTH + 1))
+    return ind, np.array([b in ind for b in bins])
+
+
+def test_rotation_cull_cases_are_what_they_say():
+    want = {"four_equal_bins": ((1, 2, 3), 30), "ten_and_one": ((0, 5, -1), 11), "eleven_and_one": ((0, -1, -1), 11), "outside_360": ((0, -1, -1), 5)}
+    for name, rots in ROTATION_CULL.items():
+        ind, kept = rotation_cull_expected(rots)
+        assert (ind, int(kept.sum())) == want[name] and len(rots) <= 40, name
+        assert rotation_cull_expected(rots, 0)[1].all()
+
+
 # ---- the yardstick: a literal transcription of the GPU branch, sequential, float32 ----
 def get_features_in_area_invz(F, x, y, invzc, r, min_level, max_level):
     """Frame::GetFeaturesInArea(x, y, invzc, r, indices, minLevel, maxLevel) (Frame.cpp:569-639) with mvpMapPoints all NULL"""

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from test_bow_host import as_ints, dist, feature_vector, flip_bits, sort_keys
-from test_search_last_frame_host import HISTO_LENGTH, compute_three_maxima, rot_bin
+from test_search_last_frame_host import HISTO_LENGTH, ROTATION_CULL, compute_three_maxima, rot_bin, rotation_cull_expected
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -411,6 +411,9 @@ def threshold_cases():
     return found
 
 
+ROTATION_KEPT = {"rotation_cull_removes_a_match": (0, -1, -1), "angle_outside_360_never_kept": (0, -1, -1)}      # case -> kept_bins
+
+
 def _constructed():
     c = {}
     g = geometry(F_LINE, *FAR)
@@ -473,6 +476,16 @@ def _constructed():
     c["rotation_cull_removes_a_match"] = (*sides([10] * n, kf1_n=n, node1=list(range(n)), node2=list(range(n)), angle1=[0] * (n - 1) + [300]), g, pr,
                                          list(range(n - 1)) + [-1], n - 1)
     c["angle_outside_360_never_kept"] = (*sides([10, 10], kf1_n=2, node1=[0, 1], node2=[0, 1], angle1=[0, 1000]), g, pr, [0, -1], 1)
+    # the rotation check's edges (ROTATION_CULL; its "eleven_and_one" and "outside_360" are the two cases above): four equal bins, ten and one, and
+    # the check switched off
+    for name, on in (("four_equal_bins", 1), ("ten_and_one", 1), ("four_equal_bins", 0)):
+        rots = ROTATION_CULL[name]
+        n = len(rots)
+        ind, kept = rotation_cull_expected(rots, on)
+        key = "rotation_%s%s" % (name, "" if on else "_check_off")
+        c[key] = (*sides([10] * n, kf1_n=n, node1=list(range(n)), node2=list(range(n)), angle1=rots), g, default_params(check_orientation=on),
+                  [i if kept[i] else -1 for i in range(n)], int(kept.sum()))
+        ROTATION_KEPT[key] = ind
     # the double threshold: dsqr on either side of 3.84 * (double)sigma2, the lower one equal to the float product 3.84f * sigma2
     th = threshold_cases()
     for name, want in (("below", [0]), ("above", [-1])):
@@ -490,6 +503,7 @@ def test_constructed_cases(name):
     KF1, KF2, geom, prm, want, count = CONSTRUCTED[name]
     ref = both_searches(KF1, KF2, geom, prm)
     assert list(ref[0]) == want and ref[1] == count, (name, list(ref[0]), ref[1])
+    assert name not in ROTATION_KEPT or tuple(ref[3]["ind"]) == ROTATION_KEPT[name]
     both_searches(KF1, KF2, geom, prm, network=True)
 
 
@@ -541,7 +555,8 @@ def test_header_binding_and_build_declare_the_new_entry_points(orb):
     assert "k_triangulate.hip" in jb.SOURCES and "jsorb_keyframes.hip" in jb.SOURCES and "create_new_map_points" in jb.EXAMPLES
     ksrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "k_triangulate.hip")).read()
     lsrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "jsorb_launch.h")).read()
-    for name, val, text in (("TR_LANES", TR_LANES, ksrc), ("TR_IDX", TR_IDX, ksrc), ("TR_KF_CHUNK", TR_KF_CHUNK, lsrc)):
+    csrc = open(os.path.join(ROOT, "jetson_slam_amd", "csrc", "k_search_common.h")).read()      # k_bow_group's key layout, shared with k_bow.hip
+    for name, val, text in (("TR_LANES", TR_LANES, ksrc), ("BW_IDX", TR_IDX, csrc), ("TR_KF_CHUNK", TR_KF_CHUNK, lsrc)):
         assert re.search(r"#define %s %d\b" % (name, val), text), name
     assert "fma" not in re.sub(r"//.*", "", ksrc)                        # the contract's arithmetic has no fused multiply-add
     shim = open(os.path.join(ROOT, "include", "jsorb_compat.hpp")).read()
