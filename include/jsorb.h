@@ -713,6 +713,93 @@ int jsorb_search_for_triangulation(jsorb_keyframe_matcher *m, const jsorb_triang
 int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *n_line_tests, int *largest_node,
                                          int kept_bins[3]);
 
+/* ---- fusing map points into keyframes: ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th)
+ * (src/ORBmatcher.cpp:812-962) and its loop-closing overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:964-1087), with
+ * KeyFrame::GetFeaturesInArea and KeyFrame::IsInImage (src/KeyFrame.cpp:573-617), as LocalMapping::SearchInNeighbors calls it
+ * (src/LocalMapping.cpp:460-540): once per target keyframe with the current keyframe's map points (10 neighbours plus up to 5 second neighbours each
+ * with a stereo sensor, 20 plus up to 5 each with a monocular one), then once into the current keyframe with every map point of all those keyframes -
+ * each direction in ONE call of the keyframe matcher above, on its stream ----
+ * What runs here is the search, :839-936: per (keyframe, point) the keypoint bestIdx and its distance bestDist, a pure function of the arrays as
+ * they are before the call - there is no claim rule and no rotation check.  What touches the map stays with the caller: the head test
+ * `!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)` (:833-837) and the tail :938-958 (Replace, AddObservation, AddMapPoint).  The caller walks the
+ * keyframes and points in the reference's order, evaluates the head test on the LIVE map and applies the tail to best_idx.  That replay equals the
+ * sequential loop, for three reasons:
+ *   - nothing the tail mutates feeds the search: Replace and AddObservation change neither the position, the normal, the distance range nor the
+ *     descriptor of a point (those change in UpdateNormalAndDepth / ComputeDistinctiveDescriptors, which SearchInNeighbors calls after all fusing);
+ *   - vpMapPointMatches is a copy taken before the loop, so the point list of a call does not change under it;
+ *   - the head test only ever goes from pass to skip while the loops run: isBad never reverts, and a point leaves a keyframe only by becoming bad.
+ *     So a pair the device searched and the replay skips costs work, never a result; `skip` lets the caller leave out what is known before the call.
+ * Inputs, DEVICE arrays unless said otherwise.  Points i = 0 .. n_points-1: Px, Py, Pz (GetWorldPos), Nx, Ny, Nz (GetNormal), max_distance
+ * (mfMaxDistance), min_dist_inv / max_dist_inv (GetMinDistanceInvariance / GetMaxDistanceInvariance) float[n_points]; desc n_points x 32 bytes
+ * (GetDescriptor), 16-byte aligned.  The keyframes are concatenated: keyframe k is the entries kf_start[k] .. kf_start[k + 1] (HOST array of
+ * n_keyframes + 1 ascending offsets) of x, y (mvKeysUn), octave int32, uright (mvuRight; NULL: every keyframe is monocular, as uright < 0
+ * everywhere) and kf_desc.  Per keyframe, HOST arrays copied into the launch arguments like F12 and epipole above: Rcw[9 k ..] row-major, tcw[3 k ..],
+ * Ow[3 k ..] (GetRotation, GetTranslation, GetCameraCenter; the loop-closing overload passes the rotation, translation and centre it derives from
+ * Scw, :967-974).  skip: NULL or n_keyframes x n_points bytes; a nonzero byte gives -1 with no work done and no statistics.
+ * The reference computes the projection, the distance and the level through cv::Mat products, cv::norm, cv::Mat::dot and the host's log, whose
+ * rounding nothing in its tree pins; as for jsorb_search_by_projection_kf this library defines them as the arithmetic of the reference's own device
+ * kernels where one exists.  Per (keyframe, point), all in float unless said otherwise:
+ *   1. projection with K14's arithmetic (jsorb_project_points): Pc = tcw + Rcw P per row as fma(z,R2,fma(x,R0,y*R1)) + t, invz = 1.0f/Pcz,
+ *      u = fma(Pcx*fx, invz, cx), v likewise.  No candidate unless Pcz > 0 (in the reference's text Pcz == 0 reaches an infinite invz and fails
+ *      IsInImage; a NaN fails too)
+ *   2. KeyFrame::IsInImage's own gate, half open: u >= min_x && u < max_x && v >= min_y && v < max_y; a NaN fails.  (Not K14's closed gate)
+ *   3. ur = u - bf*invz: the product rounded, then the difference rounded - no fma
+ *   4. distance gate with K16's arithmetic (jsorb_is_in_frustum): o = P - Ow, dist = sqrtf(fma(oz,oz,fma(ox,ox,oy*oy))); no candidate when
+ *      dist < min_dist_inv[i] || dist > max_dist_inv[i] (written so: a NaN passes, as in the reference's comparison)
+ *   5. viewing angle: dot = fma(oz,nz,fma(ox,nx,oy*ny)) (K16's chain); no candidate when dot < 0.5f*dist (a NaN passes)
+ *   6. L = clamp(cvt_rzi_s32(ceilf(logf(max_distance[i] / dist) / log_scale_factor)), 0, n_levels-1) with K16's logf and the device's float -> int
+ *      rule: MapPoint::PredictScale with mfMaxDistance itself
+ *   7. radius = th * scale_factor[L] (one float product); cells, early returns and walk order of KeyFrame::GetFeaturesInArea as for
+ *      jsorb_search_local_points (ix outer, iy inner, a cell's keypoints ascending) over the grid PosInGrid builds from x, y with roundf
+ *   8. per keypoint k of the window, in walk order, from bestDist = 256:
+ *        window: fabsf(x[k] - u) < radius && fabsf(y[k] - v) < radius
+ *        level: octave[k] in [L-1, L]; an octave outside [0, n_levels) is never a candidate (at L = 0 the reference would read
+ *          mvInvLevelSigma2[-1] there)
+ *        with check_reprojection: ex = u - x[k], ey = v - y[k]; when uright[k] >= 0: er = ur - uright[k], e2 = ex*ex + ey*ey + er*er, dropped when
+ *          (double)(e2 * inv_level_sigma2[octave]) > 7.8; otherwise e2 = ex*ex + ey*ey, dropped when (double)(e2 * inv_level_sigma2[octave]) > 5.99.
+ *          Every product and sum rounded to float on its own, left to right; the comparison in DOUBLE, as the C++ promotes it; a NaN passes
+ *        d = popcount Hamming distance; strict < updates bestDist, bestIdx: the first in walk order wins a tie
+ *   9. nothing in 3 and 8 is contracted into an fma (the kernel writes them with __fmul_rn / __fadd_rn / __fsub_rn)
+ *  10. a match iff bestDist <= th_low: best_idx = bestIdx (the keypoint's index WITHIN its keyframe), best_dist = bestDist; otherwise both -1
+ * Outputs (DEVICE): best_idx, best_dist int32[n_keyframes x n_points] (row k: keyframe k; every entry is written), n_matched_dev[n_keyframes] = the
+ * matches of each keyframe (nFused before the replay's head test).  Enqueued on the matcher's stream, no host decision after the argument checks,
+ * capturable once the scratch has its size: k_fuse_grids (one workgroup per keyframe), k_fuse_match (32 keyframes per launch).
+ * Limits: n_keyframes in [0, 256]; the keypoints of all keyframes of a call below 2^18 = 262144; cols * rows <= 4096 (what k_fuse_grids holds in
+ * LDS); JSORB_ERR_INVALID for these, a NULL required pointer, descending or negative kf_start, th_low outside [0, 255], n_levels outside
+ * [1, JSORB_MAX_LEVELS], descriptors not 16-byte aligned, a negative n_points.  n_points == 0 or n_keyframes == 0 is a valid call: the counts are
+ * cleared, nothing else runs.  The statistics words and the "done" mark of a fuse are its own: a fuse leaves
+ * jsorb_search_for_triangulation_stats as it was, and a triangulation leaves jsorb_fuse_stats as it was. */
+typedef struct jsorb_fuse_params {
+    float th;                        /* 3 in LocalMapping::SearchInNeighbors (the default), 4 in loop closing */
+    int th_low;                      /* ORBmatcher::TH_LOW = 50; [0, 255] */
+    int check_reprojection;          /* 1: Fuse(pKF, vpMapPoints, th) (:812); 0: the loop-closing overload (:964), which has no chi-square gate */
+    float fx, fy, cx, cy, bf;        /* pKF->fx .. cy, mbf */
+    float min_x, max_x, min_y, max_y; /* KeyFrame::mnMinX, mnMaxX, mnMinY, mnMaxY: IsInImage's bounds and the grid origin */
+    float inv_w, inv_h;              /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* mnGridCols, mnGridRows */
+    float log_scale_factor;          /* KeyFrame::mfLogScaleFactor */
+    int n_levels;                    /* mnScaleLevels, [1, JSORB_MAX_LEVELS] */
+    float scale_factor[JSORB_MAX_LEVELS];        /* mvScaleFactors */
+    float inv_level_sigma2[JSORB_MAX_LEVELS];    /* mvInvLevelSigma2 */
+} jsorb_fuse_params;
+int jsorb_fuse_async(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n_points, const float *Px, const float *Py, const float *Pz,
+                     const float *Nx, const float *Ny, const float *Nz, const float *max_distance, const float *min_dist_inv,
+                     const float *max_dist_inv, const uint8_t *desc, int n_keyframes, const int32_t *kf_start, const float *x, const float *y,
+                     const int32_t *octave, const float *uright, const uint8_t *kf_desc, const float *Rcw, const float *tcw, const float *Ow,
+                     const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, int32_t *n_matched_dev);
+/* Synchronous: the same into buffers of the matcher; best_idx_host, best_dist_host [n_keyframes x n_points] and n_matched_host[n_keyframes] (host),
+ * one copy back.  JSORB_ERR_UNSUPPORTED when n_keyframes x n_points exceeds INT_MAX - 256. */
+int jsorb_fuse(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n_points, const float *Px, const float *Py, const float *Pz,
+               const float *Nx, const float *Ny, const float *Nz, const float *max_distance, const float *min_dist_inv, const float *max_dist_inv,
+               const uint8_t *desc, int n_keyframes, const int32_t *kf_start, const float *x, const float *y, const int32_t *octave,
+               const float *uright, const uint8_t *kf_desc, const float *Rcw, const float *tcw, const float *Ow, const uint8_t *skip,
+               int32_t *best_idx_host, int32_t *best_dist_host, int *n_matched_host);
+/* Diagnostics of the last fuse (waits for it): n_windows = (keyframe, point) pairs that reached a window (passed steps 1-6 and the early returns
+ * of step 7); n_walked = keypoints of those windows' cells; n_distances = Hamming distances computed (step 8's survivors); largest_window = the
+ * most keypoints in the cells of one window.  A skipped pair and a keyframe without keypoints count nothing.  JSORB_ERR_STATE before the first fuse.
+ * Any pointer may be NULL. */
+int jsorb_fuse_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window);
+
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates
  * pinned-host + device buffer pairs and moves data with cudaMemcpy(Async) on a private stream; these calls are the HIP side of

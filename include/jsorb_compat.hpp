@@ -531,6 +531,25 @@ struct KeyframeSide {
     const float *angle = nullptr;
     const unsigned char *descriptors = nullptr;
 };
+// The sides of Fuse as DEVICE arrays.  FusePoints: n map points - GetWorldPos, GetNormal, mfMaxDistance, GetMinDistanceInvariance,
+// GetMaxDistanceInvariance and GetDescriptor (32 bytes each).  FuseKeyframes: the target keyframes one after the other - mvKeysUn as x / y /
+// octave, mvuRight (nullptr: all monocular) and mDescriptors.  FusePoses: HOST arrays, per keyframe 9 floats of GetRotation (row-major), 3 of
+// GetTranslation and 3 of GetCameraCenter.
+struct FusePoints {
+    int n = 0;
+    const float *Px = nullptr, *Py = nullptr, *Pz = nullptr, *Nx = nullptr, *Ny = nullptr, *Nz = nullptr;
+    const float *max_distance = nullptr, *min_dist_inv = nullptr, *max_dist_inv = nullptr;
+    const unsigned char *descriptors = nullptr;
+};
+struct FuseKeyframes {
+    const float *x = nullptr, *y = nullptr;
+    const int32_t *octave = nullptr;
+    const float *uright = nullptr;
+    const unsigned char *descriptors = nullptr;
+};
+struct FusePoses {
+    const float *Rcw = nullptr, *tcw = nullptr, *Ow = nullptr;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -787,6 +806,32 @@ inline std::vector<int> SearchForTriangulation(jsorb::KeyframeMatcher &matcher, 
             if (match12[i * kf1.n + k] >= 0) vMatchedPairs[i].push_back(std::make_pair((size_t)k, (size_t)match12[i * kf1.n + k]));
     }
     return counts;
+}
+
+// The search of matcher.Fuse(pKFi, vpMapPointMatches) (ORBmatcher.cpp:812-936; with params.check_reprojection = 0 the loop-closing overload
+// :964-1087) for ALL n_kf target keyframes of LocalMapping::SearchInNeighbors' loops (LocalMapping.cpp:460-540) in one call: keyframes holds the
+// targets concatenated, target k at kf_start[k] .. kf_start[k + 1].  skip_gpu: nullptr or one byte per (keyframe, point) on the device, nonzero
+// where the caller already knows the head test fails (!pMP, isBad, IsInKeyFrame).  best_idx / best_dist [k * points.n + i] = bestIdx (within
+// keyframe k) and bestDist of point i, -1 where the reference finds none within TH_LOW.  The caller replays the head test and the tail :938-958
+// over them, keyframes and points in the reference's order.  Returns the number of matches over all keyframes.
+inline int Fuse(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &params, const jsorb::FusePoints &points, int n_kf, const int32_t *kf_start,
+                const jsorb::FuseKeyframes &keyframes, const jsorb::FusePoses &poses, const unsigned char *skip_gpu, std::vector<int32_t> &best_idx,
+                std::vector<int32_t> &best_dist)
+{
+    const size_t rows = (size_t)(n_kf > 0 ? n_kf : 0) * (points.n > 0 ? points.n : 0);
+    best_idx.assign(rows + 1, -1);
+    best_dist.assign(rows + 1, -1);
+    std::vector<int> counts(n_kf > 0 ? n_kf : 1, 0);
+    if (jsorb_fuse(matcher.handle(), &params, points.n, points.Px, points.Py, points.Pz, points.Nx, points.Ny, points.Nz, points.max_distance,
+                   points.min_dist_inv, points.max_dist_inv, points.descriptors, n_kf, kf_start, keyframes.x, keyframes.y, keyframes.octave,
+                   keyframes.uright, keyframes.descriptors, poses.Rcw, poses.tcw, poses.Ow, skip_gpu, best_idx.data(), best_dist.data(),
+                   counts.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_fuse: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    best_idx.resize(rows);
+    best_dist.resize(rows);
+    int total = 0;
+    for (int k = 0; k < n_kf; k++) total += counts[k];
+    return total;
 }
 
 // Relocalization's matcher2.SearchByProjection(mCurrentFrame, vpCandidateKFs[i], sFound, th, ORBdist) (Tracking.cpp:2065 with (10, 100), :2079 with

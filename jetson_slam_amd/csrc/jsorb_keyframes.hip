@@ -1,6 +1,6 @@
-// jsorb_keyframes.hip - host side of the keyframe-to-keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*).
+// jsorb_keyframes.hip - host side of the keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*, jsorb_fuse*).
 // The matcher belongs to no extractor handle: it owns its stream and scratch, so LocalMapping's thread never enqueues on Tracking's handles.  The
-// kernels are in k_triangulate.hip; the grouping is k_bow.hip's k_bow_group with KF1 as the frame side.
+// kernels are in k_triangulate.hip (the grouping is k_bow.hip's k_bow_group with KF1 as the frame side) and k_fuse.hip.
 #include "jsorb_handle.h"
 
 struct jsorb_keyframe_matcher {
@@ -13,12 +13,20 @@ struct jsorb_keyframe_matcher {
     int32_t *out = nullptr;                                     // synchronous call: counts (256), then match12 (out_cap)
     int out_cap = 0;
     bool done = false;
+    // jsorb_fuse*: its own statistics and "done" mark, the keyframes' grid CSRs (grown only) and the synchronous form's outputs
+    int *fuse_stats = nullptr;                                  // FUSE_STATS words of the last fuse
+    int32_t *grid_start = nullptr, *grid_items = nullptr;       // n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
+    int grid_cap = 0, items_cap = 0;
+    int32_t *fuse_out = nullptr;                                // counts (256), then best_idx and best_dist (fuse_out_cap each)
+    int fuse_out_cap = 0;
+    bool fuse_done = false;
     std::string err;
 };
 
 namespace {
 
 #define TRI_STATS 8
+#define FUSE_STATS 4
 
 int tri_fail(jsorb_keyframe_matcher *m, const std::string &msg, int rc = JSORB_ERR_INVALID)
 {
@@ -56,7 +64,7 @@ void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
-    free_device(m->sort1, m->sort2, m->stats, m->out);
+    free_device(m->sort1, m->sort2, m->stats, m->out, m->fuse_stats, m->grid_start, m->grid_items, m->fuse_out);
     destroy_event(m->ev_switch);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
@@ -66,7 +74,7 @@ int jsorb_keyframe_matcher_set_stream(jsorb_keyframe_matcher *m, void *hip_strea
 {
     if (!m) return JSORB_ERR_INVALID;
     hipStream_t ns = hip_stream ? (hipStream_t)hip_stream : m->own_stream;
-    if (ns != m->stream && m->done) {               // the new stream continues after what the old one still carries (it reads the same scratch)
+    if (ns != m->stream && (m->done || m->fuse_done)) {               // the new stream continues after what the old one still carries (it reads the same scratch)
         HIPCHK(m, hipSetDevice(m->device));
         HIPCHK(m, hipEventRecord(m->ev_switch, m->stream));
         HIPCHK(m, hipStreamWaitEvent(ns, m->ev_switch, 0));
@@ -170,6 +178,104 @@ int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_
     if (n_line_tests) *n_line_tests = s[2];
     if (largest_node) *largest_node = s[3];
     if (kept_bins) for (int b = 0; b < 3; b++) kept_bins[b] = s[4 + b] - 1;
+    return JSORB_OK;
+}
+
+int jsorb_fuse_async(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n_points, const float *Px, const float *Py, const float *Pz,
+                     const float *Nx, const float *Ny, const float *Nz, const float *max_distance, const float *min_dist_inv,
+                     const float *max_dist_inv, const uint8_t *desc, int n_keyframes, const int32_t *kf_start, const float *x, const float *y,
+                     const int32_t *octave, const float *uright, const uint8_t *kf_desc, const float *Rcw, const float *tcw, const float *Ow,
+                     const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, int32_t *n_matched_dev)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    if (!params) return tri_fail(m, "fuse: NULL params");
+    if (params->n_levels < 1 || params->n_levels > JSORB_MAX_LEVELS) return tri_fail(m, "fuse: n_levels out of range");
+    if (params->th_low < 0 || params->th_low > 255) return tri_fail(m, "fuse: th_low must be in [0, 255]");
+    if (params->cols < 1 || params->rows < 1 || (long long)params->cols * params->rows > FUSE_MAX_CELLS) return tri_fail(m, "fuse: grid size out of range (cols*rows <= 4096)");
+    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "fuse: n_keyframes must be in [0, 256]");
+    if (n_points < 0) return tri_fail(m, "fuse: n_points must not be negative");
+    if (n_keyframes > 0 && (!kf_start || !n_matched_dev || !Rcw || !tcw || !Ow)) return tri_fail(m, "fuse: NULL kf_start, Rcw, tcw, Ow or n_matched");
+    FuseGridArgs g{};
+    int base = 0, total = 0, rc = 0;
+    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, g.kf_start, &base, &total, &rc)) return tri_fail(m, std::string("fuse: ") + bad);
+    if (total >= (1 << 18)) return tri_fail(m, "fuse: the keyframes of a call must hold fewer than 262144 keypoints");
+    if ((long long)n_keyframes * n_points > (long long)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "fuse: n_keyframes x n_points too large", JSORB_ERR_UNSUPPORTED);
+    if (n_points > 0 && (!Px || !Py || !Pz || !Nx || !Ny || !Nz || !max_distance || !min_dist_inv || !max_dist_inv || !desc)) return tri_fail(m, "fuse: NULL point array");
+    if (total > 0 && (!x || !y || !octave || !kf_desc)) return tri_fail(m, "fuse: NULL keyframe array");
+    if ((uintptr_t)desc % 16 || (uintptr_t)kf_desc % 16) return tri_fail(m, "fuse: descriptors must be 16-byte aligned");
+    if (n_keyframes > 0 && n_points > 0 && (!best_idx || !best_dist)) return tri_fail(m, "fuse: NULL best_idx or best_dist");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int n_cells = params->cols * params->rows;
+    const int want_grid = std::max(n_keyframes, 1) * (n_cells + 1);
+    RCCHK(reserve_device(m, m->fuse_stats, FUSE_STATS * sizeof(int)));
+    RCCHK(reserve_device(m, m->grid_start, (size_t)want_grid * sizeof(int32_t), &m->grid_cap, want_grid));
+    RCCHK(reserve_device(m, m->grid_items, (size_t)std::max(total, 1) * sizeof(int32_t), &m->items_cap, std::max(total, 1)));
+    hipStream_t st = m->stream;
+    HIPCHK(m, hipMemsetAsync(m->fuse_stats, 0, FUSE_STATS * sizeof(int), st));
+    m->fuse_done = true;
+    if (n_keyframes == 0) return JSORB_OK;
+    HIPCHK(m, hipMemsetAsync(n_matched_dev, 0, (size_t)n_keyframes * sizeof(int32_t), st));
+    if (n_points == 0) return JSORB_OK;
+    g.x = x + base; g.y = y + base;
+    g.min_x = params->min_x; g.min_y = params->min_y; g.inv_w = params->inv_w; g.inv_h = params->inv_h; g.cols = params->cols; g.rows = params->rows;
+    g.cell_start = m->grid_start; g.cell_items = m->grid_items;
+    launch_fuse_grids(g, n_keyframes, st);
+    HIPCHK(m, hipGetLastError());
+    FuseArgs a{};
+    a.p = *params;
+    a.n_points = n_points;
+    a.Px = Px; a.Py = Py; a.Pz = Pz; a.Nx = Nx; a.Ny = Ny; a.Nz = Nz;
+    a.max_distance = max_distance; a.min_dist_inv = min_dist_inv; a.max_dist_inv = max_dist_inv; a.mp_desc = desc;
+    a.x = g.x; a.y = g.y; a.uright = uright ? uright + base : nullptr; a.octave = octave + base; a.kf_desc = kf_desc + (size_t)32 * base;
+    a.skip = skip;
+    a.cell_start = m->grid_start; a.cell_items = m->grid_items;
+    a.best_idx = best_idx; a.best_dist = best_dist; a.n_matched = n_matched_dev; a.stats = m->fuse_stats;
+    for (int k0 = 0; k0 < n_keyframes; k0 += FUSE_KF_CHUNK) {
+        FusePose q{};
+        q.kf0 = k0; q.n = std::min(FUSE_KF_CHUNK, n_keyframes - k0);
+        for (int i = 0; i <= q.n; i++) q.start[i] = g.kf_start[k0 + i];
+        for (int i = 0; i < q.n; i++) {
+            memcpy(q.pose[i], Rcw + 9 * (size_t)(k0 + i), 9 * sizeof(float));
+            memcpy(q.pose[i] + 9, tcw + 3 * (size_t)(k0 + i), 3 * sizeof(float));
+            memcpy(q.pose[i] + 12, Ow + 3 * (size_t)(k0 + i), 3 * sizeof(float));
+        }
+        launch_fuse_match(a, q, st);
+        HIPCHK(m, hipGetLastError());
+    }
+    return JSORB_OK;
+}
+
+int jsorb_fuse(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n_points, const float *Px, const float *Py, const float *Pz,
+               const float *Nx, const float *Ny, const float *Nz, const float *max_distance, const float *min_dist_inv, const float *max_dist_inv,
+               const uint8_t *desc, int n_keyframes, const int32_t *kf_start, const float *x, const float *y, const int32_t *octave,
+               const float *uright, const uint8_t *kf_desc, const float *Rcw, const float *tcw, const float *Ow, const uint8_t *skip,
+               int32_t *best_idx_host, int32_t *best_dist_host, int *n_matched_host)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "fuse: n_keyframes must be in [0, 256]");
+    if (n_points < 0) return tri_fail(m, "fuse: n_points must not be negative");
+    if (n_keyframes > 0 && (!n_matched_host || (n_points > 0 && (!best_idx_host || !best_dist_host)))) return tri_fail(m, "fuse: NULL host output");
+    HIPCHK(m, hipSetDevice(m->device));
+    const size_t rows = (size_t)n_keyframes * n_points;
+    if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return tri_fail(m, "fuse: n_keyframes x n_points too large", JSORB_ERR_UNSUPPORTED);
+    const int want = (int)std::max(rows, (size_t)1);
+    RCCHK(reserve_device(m, m->fuse_out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + 2 * (size_t)want) * sizeof(int32_t), &m->fuse_out_cap, want));
+    int32_t *cnt = m->fuse_out, *bi = cnt + JSORB_BOW_MAX_KEYFRAMES, *bd = bi + want;
+    RCCHK(jsorb_fuse_async(m, params, n_points, Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv, desc, n_keyframes, kf_start, x, y,
+                           octave, uright, kf_desc, Rcw, tcw, Ow, skip, bi, bd, cnt));
+    if (rows > 0) HIPCHK(m, hipMemcpyAsync(best_dist_host, bd, rows * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    return copy_kf_results(m, n_keyframes, rows, cnt, bi, best_idx_host, n_matched_host);
+}
+
+int jsorb_fuse_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    int32_t s[FUSE_STATS] = {0};
+    RCCHK(read_stats(m, m->fuse_done, "fuse_stats before jsorb_fuse", m->fuse_stats, s, FUSE_STATS));
+    if (n_windows) *n_windows = s[0];
+    if (n_walked) *n_walked = s[1];
+    if (n_distances) *n_distances = s[2];
+    if (largest_window) *largest_window = s[3];
     return JSORB_OK;
 }
 

@@ -255,6 +255,39 @@ struct TriGeom {
 };
 void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s);
 void launch_tri_resolve(const TriArgs &a, hipStream_t s);
+// k_fuse_grids / k_fuse_match (k_fuse.hip): ORBmatcher::Fuse(pKF, vpMapPoints, th) and its loop-closing overload for several keyframes in one call
+#define FUSE_MAX_CELLS 4096                      // cols * rows k_fuse_grids holds in LDS (counts and cursors of every cell, 1024 scan words)
+struct FuseGridArgs {
+    const float *x, *y;                          // mvKeysUn of the keyframes, concatenated
+    float min_x, min_y, inv_w, inv_h;
+    int cols, rows;
+    int32_t *cell_start, *cell_items;            // per keyframe cols * rows + 1 starts (relative to the keyframe); items at the keyframe's offset
+    int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
+};
+struct FuseArgs {
+    jsorb_fuse_params p;
+    // the map points, in the caller's order
+    int n_points;
+    const float *Px, *Py, *Pz, *Nx, *Ny, *Nz, *max_distance, *min_dist_inv, *max_dist_inv;
+    const uint8_t *mp_desc;
+    // the keyframes, concatenated (the launch's FusePose has their offsets)
+    const float *x, *y, *uright;                 // uright NULL: every keyframe monocular
+    const int32_t *octave;
+    const uint8_t *kf_desc;
+    const uint8_t *skip;                         // n_kf x n_points or NULL
+    const int32_t *cell_start, *cell_items;      // k_fuse_grids' CSRs
+    // outputs
+    int32_t *best_idx, *best_dist, *n_matched;   // n_kf x n_points each (every entry written), n_kf (cleared to 0)
+    int *stats;                                  // pairs with a window, keypoints walked, distances, largest window (cleared to 0)
+};
+#define FUSE_KF_CHUNK 32                        // keyframes whose pose and offsets one k_fuse_match launch carries in its arguments
+struct FusePose {
+    int kf0, n;                                  // the launch's keyframes kf0 .. kf0 + n
+    int start[FUSE_KF_CHUNK + 1];                // their kf_start
+    float pose[FUSE_KF_CHUNK][15];               // Rcw row-major, tcw, Ow
+};
+void launch_fuse_grids(const FuseGridArgs &g, int n_kf, hipStream_t s);
+void launch_fuse_match(const FuseArgs &a, const FusePose &g, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

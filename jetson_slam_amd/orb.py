@@ -64,7 +64,7 @@ EXPORTS = [
     "jsorb_search_by_projection_kf_async", "jsorb_search_by_projection_kf", "jsorb_search_by_projection_kf_stats", "jsorb_search_kf_build_caps",
     "jsorb_keyframe_matcher_create", "jsorb_keyframe_matcher_destroy", "jsorb_keyframe_matcher_set_stream", "jsorb_keyframe_matcher_get_stream",
     "jsorb_keyframe_matcher_last_error", "jsorb_search_for_triangulation_async", "jsorb_search_for_triangulation",
-    "jsorb_search_for_triangulation_stats",
+    "jsorb_search_for_triangulation_stats", "jsorb_fuse_async", "jsorb_fuse", "jsorb_fuse_stats",
 ]
 
 
@@ -166,6 +166,30 @@ def make_triangulation_params(scale_factor, level_sigma2=None, th_low=TH_LOW, ch
     for l in range(min(len(sf), MAX_LEVELS)):
         p.scale_factor[l] = sf[l]
         p.level_sigma2[l] = s2[l]
+    return p
+
+
+class JsorbFuseParams(C.Structure):
+    _fields_ = [("th", C.c_float), ("th_low", C.c_int), ("check_reprojection", C.c_int)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")] + \
+               [("cols", C.c_int), ("rows", C.c_int), ("log_scale_factor", C.c_float), ("n_levels", C.c_int),
+                ("scale_factor", C.c_float * MAX_LEVELS), ("inv_level_sigma2", C.c_float * MAX_LEVELS)]
+
+
+def make_fuse_params(camera, bounds, grid, log_scale_factor, scale_factor, inv_level_sigma2=None, th=3.0, th_low=TH_LOW, check_reprojection=True,
+                     bf=0.0, cols=64, rows=48):
+    """jsorb_fuse_params: camera = (fx, fy, cx, cy) and bf = mbf of the keyframes, bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), grid =
+    (mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows, log_scale_factor = mfLogScaleFactor, scale_factor / inv_level_sigma2 the float
+    tables mvScaleFactors / mvInvLevelSigma2 (None: 1.0f / (scale_factor squared) in float32, ORBextractor.cpp:43-71).  th = 3 and
+    check_reprojection = True are LocalMapping::SearchInNeighbors' Fuse (ORBmatcher.cpp:812); th = 4 and False the loop-closing overload (:964)"""
+    sf = np.ascontiguousarray(scale_factor, np.float32).ravel()
+    i2 = (np.float32(1) / (sf * sf).astype(np.float32)).astype(np.float32) if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32).ravel()
+    if len(i2) != len(sf):
+        raise JsorbError("make_fuse_params: scale_factor and inv_level_sigma2 must have one entry per level")
+    p = JsorbFuseParams(th, int(th_low), int(check_reprojection), *camera, bf, *bounds, *grid, cols, rows, log_scale_factor, len(sf))
+    for l in range(min(len(sf), MAX_LEVELS)):
+        p.scale_factor[l] = sf[l]
+        p.inv_level_sigma2[l] = i2[l]
     return p
 
 
@@ -315,6 +339,9 @@ def load_library(path=None):
         "jsorb_search_for_triangulation_async": (I, [P, C.POINTER(JsorbTriangulationParams), I] + [P] * 7 + [I] + [P] * 13),
         "jsorb_search_for_triangulation": (I, [P, C.POINTER(JsorbTriangulationParams), I] + [P] * 7 + [I] + [P] * 13),
         "jsorb_search_for_triangulation_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_fuse_async": (I, [P, C.POINTER(JsorbFuseParams), I] + [P] * 10 + [I] + [P] * 13),
+        "jsorb_fuse": (I, [P, C.POINTER(JsorbFuseParams), I] + [P] * 10 + [I] + [P] * 13),
+        "jsorb_fuse_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -608,6 +635,87 @@ class KeyframeMatcher:
         p, d, l, m, b = C.c_int(), C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
         self._chk(self._lib.jsorb_search_for_triangulation_stats(self._m, C.byref(p), C.byref(d), C.byref(l), C.byref(m), b))
         return p.value, d.value, l.value, m.value, tuple(b)
+
+
+    POINT_KEYS = ("Px", "Py", "Pz", "Nx", "Ny", "Nz", "max_distance", "min_dist_inv", "max_dist_inv", "desc")
+    FUSE_KF_KEYS = ("x", "y", "octave", "uright", "desc")
+
+    def _fuse_args(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip):
+        import torch
+        what = "fuse"
+        if not isinstance(params, JsorbFuseParams):
+            raise JsorbError("%s: params must come from make_fuse_params" % what)
+        ks = np.ascontiguousarray(kf_start, np.int32)
+        if ks.ndim != 1 or len(ks) < 1:
+            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
+        nk, total = len(ks) - 1, int(ks[-1])
+        R, t, O = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (Rcw, tcw, Ow))
+        if len(R) != 9 * nk or len(t) != 3 * nk or len(O) != 3 * nk:
+            raise JsorbError("%s: Rcw must hold 9, tcw 3 and Ow 3 floats per keyframe" % what)
+        dt = dict(octave=torch.int32, desc=torch.uint8)
+
+        def side(d, keys, name, n):
+            ptrs = []
+            for k in keys:
+                t_ = d.get(k)
+                if t_ is None and k == "uright":
+                    ptrs.append(None)
+                    continue
+                if not hasattr(t_, "data_ptr") or not getattr(t_, "is_cuda", False):
+                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
+                shape = (n, 32) if k == "desc" else (n,)
+                if t_.dtype != dt.get(k, torch.float32) or tuple(t_.shape) != shape or not t_.is_contiguous():
+                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, dt.get(k, torch.float32), shape))
+                ptrs.append(t_.data_ptr() if n else None)
+            if n and d["desc"].data_ptr() % 16:
+                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
+            return ptrs
+
+        n = int(points["Px"].shape[0])
+        pp, pk = side(points, self.POINT_KEYS, "points", n), side(keyframes, self.FUSE_KF_KEYS, "keyframes", total)
+        sp = None
+        if skip is not None:
+            if not getattr(skip, "is_cuda", False) or skip.dtype not in (torch.uint8, torch.bool) or skip.numel() != nk * n or not skip.is_contiguous():
+                raise JsorbError("%s: skip must be a contiguous uint8 / bool device tensor of n_keyframes x n_points entries" % what)
+            sp = skip.data_ptr() if nk * n else None
+        return n, nk, (ks, R, t, O), [C.byref(params), n] + pp + [nk, ks.ctypes.data] + pk + [R.ctypes.data, t.ctypes.data, O.ctypes.data, sp]
+
+    def fuse(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip=None, wait=True):
+        """jsorb_fuse_async: the n map points (dict of device tensors: Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv float32[n],
+        desc uint8[n, 32]) against the len(kf_start) - 1 concatenated keyframes (dict: x, y float32, octave int32, desc uint8[., 32] and uright float32 or
+        None / absent: monocular; kf_start: HOST int32 offsets; Rcw host float32[n_keyframes, 9] row-major, tcw and Ow host float32[n_keyframes, 3]).
+        skip: uint8 / bool device tensor [n_keyframes, n] or None.  Returns (best_idx, best_dist int32[n_keyframes, n], n_matched
+        int32[n_keyframes]) as device tensors; wait= as in search_for_triangulation, with the same rule for the returned tensors' lifetime."""
+        import torch
+        n, nk, keep, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
+        dev = points["Px"].device
+        best_idx = torch.full((max(nk, 1), max(n, 1)), -7, dtype=torch.int32, device=dev)
+        best_dist = torch.full((max(nk, 1), max(n, 1)), -7, dtype=torch.int32, device=dev)
+        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_fuse_async(self._m, *args, best_idx.data_ptr(), best_dist.data_ptr(), count.data_ptr()))
+        if wait:
+            self.sync()
+        return best_idx.reshape(-1)[:nk * n].reshape(nk, n), best_dist.reshape(-1)[:nk * n].reshape(nk, n), count[:nk]
+
+    def fuse_host(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip=None):
+        """jsorb_fuse, the synchronous form: the same inputs, (best_idx, best_dist int32[n_keyframes, n], n_matched int32[n_keyframes]) on the host
+        with one copy back"""
+        import torch
+        n, nk, keep, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
+        best_idx = np.full(max(nk * n, 1), -7, np.int32)
+        best_dist = np.full(max(nk * n, 1), -7, np.int32)
+        count = np.full(max(nk, 1), -7, np.int32)
+        torch.cuda.current_stream(points["Px"].device).synchronize()
+        self._chk(self._lib.jsorb_fuse(self._m, *args, best_idx.ctypes.data, best_dist.ctypes.data, count.ctypes.data))
+        return best_idx[:nk * n].reshape(nk, n), best_dist[:nk * n].reshape(nk, n), count[:nk]
+
+    def fuse_stats(self):
+        """((keyframe, point) pairs that reached a window, keypoints walked, Hamming distances, the largest window) of the last fuse"""
+        w, k, d, l = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._chk(self._lib.jsorb_fuse_stats(self._m, C.byref(w), C.byref(k), C.byref(d), C.byref(l)))
+        return w.value, k.value, d.value, l.value
 
 
 def matched_pairs(match12_row):
