@@ -800,6 +800,114 @@ int jsorb_fuse(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n
  * Any pointer may be NULL. */
 int jsorb_fuse_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window);
 
+/* ---- loop-closure candidates by BoW: ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12)
+ * (src/ORBmatcher.cpp:509-642) with ComputeThreeMaxima (:2097-2138), as LoopClosing::ComputeSim3 calls it once per consistent loop candidate with
+ * ORBmatcher matcher(0.75, true) (src/LoopClosing.cpp:244, :270) - the current keyframe against ALL candidates in one call of the keyframe matcher
+ * above (LoopClosing is a thread of its own and creates its own matcher) ----
+ * This is not jsorb_search_by_bow with other arguments: there the many-keyframe side is the ordered outer walk and the single frame is claimed;
+ * here the single side (KF1) is the ordered outer walk and each candidate is claimed (vbMatched2), and the threshold comparison is strict.
+ * Inputs, DEVICE arrays unless said otherwise.  KF1, the current keyframe, n1 entries: node1 int32 (the FeatureVector node of the keypoint or -1),
+ * valid1 uint8 (pMP1 && !pMP1->isBad()), angle1 float (mvKeysUn[].angle), desc1 n1 x 32 bytes, 16-byte aligned.  The candidates are concatenated:
+ * candidate i is the entries kf_start[i] .. kf_start[i + 1] (HOST array of n_keyframes + 1 ascending offsets; kf_start[0] need not be 0) of node2,
+ * valid2, angle2, desc2.  params: jsorb_bow_params; ComputeSim3 uses nn_ratio 0.75, th_low 50, check_orientation 1.
+ * Per candidate, with j local to the candidate:
+ *   1. match12[k] = -1 for all k < n1, matched2[j] = false, nmatches = 0 (:521-522)
+ *   2. the two facts of jsorb_search_by_bow_async hold: ascending indices within a node, every keypoint in at most one node - so nodes are
+ *      independent.  For every node on both sides the KF1 keypoints idx1 of the node are walked in ascending order (:541); skip when !valid1[idx1]
+ *   3. walk the candidate's keypoints idx2 of the node in ascending order: skip when matched2[idx2] || !valid2[idx2] (:563-567); from
+ *      bestDist1 = bestDist2 = 256, bestIdx2 = -1 the two-smallest rule of :573-582 - a tie with the best lowers the second, the index is the first
+ *      in walk order with the minimum
+ *   4. claim iff bestDist1 < th_low AND (float)bestDist1 < nn_ratio * (float)bestDist2: the first comparison is STRICT (:585), unlike the <= of
+ *      SearchByBoW(KeyFrame*, Frame&) at :215; the second is one float product.  On a claim match12[idx1] = bestIdx2, matched2[bestIdx2] = true,
+ *      nmatches++, and with check_orientation idx1 goes into the bin of rot = angle1[idx1] - angle2[bestIdx2] (the arithmetic of
+ *      jsorb_search_last_frame).  No entry below 256 (bestIdx2 = -1): no claim, whatever th_low
+ *   5. with check_orientation: ComputeThreeMaxima, then every idx1 of every other bin: match12[idx1] = -1, nmatches--.  A bin outside [0, 30) is
+ *      never kept.  matched2 is not undone - it is read only inside the loop
+ * Outputs (DEVICE): match12 n_keyframes x n1 (row i: candidate i, values local to the candidate), n_matches_dev[n_keyframes].  Enqueued on the
+ * matcher's stream, no host decision after the argument checks, no allocation after the first call of a size: k_bow_group (KF1 as the frame
+ * side), k_loop_bow_match (one wave per candidate and node), k_tri_resolve.
+ * Limits and errors as for jsorb_search_for_triangulation_async: at most 256 candidates, n1 and every candidate below 2^18; JSORB_ERR_INVALID for
+ * NULL required pointers, a bad kf_start or misaligned descriptors.  Empty sides write -1 / 0 and launch nothing that reads.  The statistics
+ * words and the "done" mark are the call's own: it leaves the triangulation and fuse statistics as they were, and the reverse. */
+int jsorb_search_by_bow_kf_async(jsorb_keyframe_matcher *m, const jsorb_bow_params *params, int n1, const int32_t *node1, const uint8_t *valid1,
+                                 const float *angle1, const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2,
+                                 const uint8_t *valid2, const float *angle2, const uint8_t *desc2, int32_t *match12, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the matcher; match12_host[n_keyframes x n1] and n_matches_host[n_keyframes] (host), one copy back. */
+int jsorb_search_by_bow_kf(jsorb_keyframe_matcher *m, const jsorb_bow_params *params, int n1, const int32_t *node1, const uint8_t *valid1,
+                           const float *angle1, const uint8_t *desc1, int n_keyframes, const int32_t *kf_start, const int32_t *node2,
+                           const uint8_t *valid2, const float *angle2, const uint8_t *desc2, int32_t *match12_host, int *n_matches_host);
+/* Diagnostics of the last call (waits for it): n_node_pairs = (candidate, node) pairs present on both sides; n_distances = the Hamming distances
+ * step 3 computes; largest_node = the most candidate keypoints in a node of such a pair; kept_bins = candidate 0's ComputeThreeMaxima ind1..3
+ * (-1: none, all -1 without check_orientation).  JSORB_ERR_STATE before the first call.  Any pointer may be NULL. */
+int jsorb_search_by_bow_kf_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *largest_node, int kept_bins[3]);
+/* The compile-time cap of this build's k_loop.hip (no device needed): candidate entries of a node a lane of k_loop_bow_match keeps in registers (2;
+ * the entries beyond 64 x that are read again for every KF1 keypoint).  A test build lowers it (jetson_slam_amd/build.py VARIANTS). */
+int jsorb_loop_build_caps(int *node_regs);
+
+/* ---- loop-closure matches by projection: ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cpp:1089-1313), as
+ * LoopClosing::ComputeSim3 calls it after a successful Sim3Solver (src/LoopClosing.cpp:328, th = 7.5): the map points of each keyframe projected
+ * into the other one, a best keypoint per point, and the pairs on which both directions agree ----
+ * Both keyframes share the camera and the grid, as in the reference (fx .. cy of pKF1 serve both directions, :1092-1095).  Per side s in {1, 2},
+ * n entries aligned with the keyframe's keypoints, slot i = keypoint i and map point vpMapPoints_s[i], DEVICE arrays: x, y (mvKeysUn), octave
+ * int32, kp_desc n x 32 bytes; Px, Py, Pz (GetWorldPos), max_distance (mfMaxDistance), min_dist_inv / max_dist_inv (GetMinDistanceInvariance /
+ * GetMaxDistanceInvariance), mp_desc n x 32 bytes (GetDescriptor); search uint8 = pMP && !vbAlreadyMatched_s[i] && !pMP->isBad() (:1116-1129,
+ * :1139-1143), which the caller evaluates, GetIndexInKeyFrame included, because that is map state.  Both descriptor arrays 16-byte aligned.  In
+ * the side struct itself, HOST values copied into the launch arguments: the keyframe's own Rw[9] row-major and tw[3], and the similarity into the
+ * OTHER camera sR[9], t[3] (side 1: sR21, t21; side 2: sR12, t12) - the caller computes them from cv::Mat as :1106-1108 does; the library does not
+ * redo cv::Mat products whose rounding nothing pins (the rule stated for F12 above).
+ * Per searched slot of side 1 into keyframe 2, and symmetrically, in the arithmetic jsorb_fuse_async defines:
+ *   1. Pc_own = tw + Rw P, then Pc = t + sR Pc_own, every row in K14's form fma(z,R2,fma(x,R0,y*R1)) + t
+ *   2. no candidate unless Pc.z > 0.  That equals the reference, whose own test is z < 0: z == 0 reaches an infinite invz and fails IsInImage, and
+ *      so does a NaN
+ *   3. invz = 1.0f / Pc.z, u = fma(Pc.x*fx, invz, cx), v likewise
+ *   4. KeyFrame::IsInImage, half open: u >= min_x && u < max_x && v >= min_y && v < max_y
+ *   5. dist3D = sqrtf(fma(z,z,fma(x,x,y*y))) of Pc: K16's chain with a zero centre
+ *   6. no candidate when dist3D < min_dist_inv || dist3D > max_dist_inv (a NaN passes, as written).  There is NO viewing-angle test
+ *   7. L = the predicted level of jsorb_fuse_async item 6
+ *   8. radius = th * scale_factor[L], one float product
+ *   9. KeyFrame::GetFeaturesInArea over the other keyframe's grid: cells, early returns and walk order as jsorb_fuse_async item 7; kept when
+ *      |x-u| < radius && |y-v| < radius and octave in [L-1, L] - a plain integer comparison as in :1194, no table is indexed by the octave
+ *  10. d = popcount Hamming distance of mp_desc against kp_desc; strict < best in walk order
+ *  11. vnMatch = bestIdx iff bestDist <= th_high, else -1 (the reference starts at INT_MAX; for th_high <= 255 that equals starting at 256)
+ * Agreement (:1294-1310): match12[i1] = idx2 iff vnMatch1[i1] == idx2 >= 0 && vnMatch2[idx2] == i1, else -1; n_found = their count.  The caller
+ * writes vpMatches12[i1] = vpMapPoints2[idx2] where match12[i1] >= 0 and leaves the rest of vpMatches12 alone.
+ * Outputs (DEVICE): match1[n1], match2[n2] (the two vnMatch arrays; every entry is written), match12[n1], *n_found_dev.  Enqueued on the matcher's
+ * stream, no host decision after the argument checks: k_fuse_grids per keyframe, k_sim3_match (both directions in one launch), k_sim3_agree.
+ * Limits: n1 + n2 < 2^18; cols * rows <= 4096; th_high in [0, 255]; n_levels in [1, JSORB_MAX_LEVELS]; JSORB_ERR_INVALID for these, a NULL required
+ * pointer or misaligned descriptors.  n1 == 0 or n2 == 0 is valid: everything is -1 / 0.  Statistics and "done" mark are the call's own. */
+typedef struct jsorb_sim3_params {
+    float th;                        /* 7.5 in LoopClosing::ComputeSim3 */
+    int th_high;                     /* ORBmatcher::TH_HIGH = 100; [0, 255] */
+    float fx, fy, cx, cy;            /* pKF1->fx .. cy */
+    float min_x, max_x, min_y, max_y; /* KeyFrame::mnMinX, mnMaxX, mnMinY, mnMaxY: IsInImage's bounds and the grid origin */
+    float inv_w, inv_h;              /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* mnGridCols, mnGridRows */
+    float log_scale_factor;          /* KeyFrame::mfLogScaleFactor */
+    int n_levels;                    /* mnScaleLevels, [1, JSORB_MAX_LEVELS] */
+    float scale_factor[JSORB_MAX_LEVELS];        /* mvScaleFactors */
+} jsorb_sim3_params;
+typedef struct jsorb_sim3_side {
+    int n;                           /* keypoints (= map point slots) of the keyframe */
+    const float *x, *y;              /* DEVICE from here ... */
+    const int32_t *octave;
+    const uint8_t *kp_desc;
+    const float *Px, *Py, *Pz, *max_distance, *min_dist_inv, *max_dist_inv;
+    const uint8_t *mp_desc;
+    const uint8_t *search;           /* ... to here */
+    float Rw[9], tw[3];              /* HOST: the keyframe's GetRotation (row-major), GetTranslation */
+    float sR[9], t[3];               /* HOST: the similarity into the other camera */
+} jsorb_sim3_side;
+int jsorb_search_by_sim3_async(jsorb_keyframe_matcher *m, const jsorb_sim3_params *params, const jsorb_sim3_side *side1, const jsorb_sim3_side *side2,
+                               int32_t *match1, int32_t *match2, int32_t *match12, int32_t *n_found_dev);
+/* Synchronous: the same into buffers of the matcher; match1_host[n1], match2_host[n2] (either may be NULL), match12_host[n1] and *n_found (host),
+ * one copy back. */
+int jsorb_search_by_sim3(jsorb_keyframe_matcher *m, const jsorb_sim3_params *params, const jsorb_sim3_side *side1, const jsorb_sim3_side *side2,
+                         int32_t *match1_host, int32_t *match2_host, int32_t *match12_host, int *n_found);
+/* Diagnostics of the last call (waits for it): those of jsorb_fuse_stats summed over both directions (slots that reached a window, keypoints of
+ * those windows' cells, Hamming distances, the most keypoints in the cells of one window) and n_agree = the agreements.  JSORB_ERR_STATE before
+ * the first call.  Any pointer may be NULL. */
+int jsorb_search_by_sim3_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window, int *n_agree);
+
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates
  * pinned-host + device buffer pairs and moves data with cudaMemcpy(Async) on a private stream; these calls are the HIP side of

@@ -550,6 +550,21 @@ struct FuseKeyframes {
 struct FusePoses {
     const float *Rcw = nullptr, *tcw = nullptr, *Ow = nullptr;
 };
+// One side of the loop-closing SearchByBoW(pKF1, pKF2, vpMatches12) as DEVICE arrays: n keypoints; node = the FeatureVector node per keypoint (-1:
+// none), valid = pMP && !pMP->isBad() of GetMapPointMatches()[i], angle = mvKeysUn[i].angle, descriptors 32 bytes each.  The candidate side holds all
+// loop candidates one after the other.
+struct BowKeyframeSide {
+    int n = 0;
+    const int32_t *node = nullptr;
+    const unsigned char *valid = nullptr;
+    const float *angle = nullptr;
+    const unsigned char *descriptors = nullptr;
+};
+// One side of SearchBySim3: jsorb_sim3_side (include/jsorb.h) with everything cleared - n slots aligned with the keyframe's keypoints as DEVICE
+// arrays, and on the HOST the keyframe's own Rw / tw and the similarity sR / t into the other camera (side 1: sR21, t21; side 2: sR12, t12).
+struct Sim3Side : jsorb_sim3_side {
+    Sim3Side() : jsorb_sim3_side() {}
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -832,6 +847,46 @@ inline int Fuse(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &params
     int total = 0;
     for (int k = 0; k < n_kf; k++) total += counts[k];
     return total;
+}
+
+// matcher.SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) (ORBmatcher.cpp:509-642) for ALL n_kf consistent candidates of
+// LoopClosing::ComputeSim3's loop (LoopClosing.cpp:255-285) in one call: candidates holds them concatenated, candidate i at kf_start[i] ..
+// kf_start[i + 1].  match12[i][idx1] = the keypoint of candidate i (local to it) whose map point the reference puts into
+// vvpMapPointMatches[i][idx1], or -1: the caller writes vpMatches12[idx1] = pKF->GetMapPointMatches()[match12[i][idx1]].  Returns the reference's
+// return value per candidate.
+inline std::vector<int> SearchByBoW(jsorb::KeyframeMatcher &matcher, const jsorb_bow_params &params, const jsorb::BowKeyframeSide &kf1, int n_kf,
+                                    const int32_t *kf_start, const jsorb::BowKeyframeSide &candidates, std::vector<std::vector<int>> &match12)
+{
+    const size_t n1 = kf1.n > 0 ? kf1.n : 0;
+    std::vector<int32_t> rows((size_t)(n_kf > 0 ? n_kf : 0) * n1 + 1, -1);
+    std::vector<int> counts(n_kf > 0 ? n_kf : 1, 0);
+    if (jsorb_search_by_bow_kf(matcher.handle(), &params, kf1.n, kf1.node, kf1.valid, kf1.angle, kf1.descriptors, n_kf, kf_start, candidates.node,
+                               candidates.valid, candidates.angle, candidates.descriptors, rows.data(), counts.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_by_bow_kf: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    counts.resize(n_kf > 0 ? n_kf : 0);
+    match12.assign(counts.size(), {});
+    for (size_t i = 0; i < counts.size(); i++) match12[i].assign(rows.begin() + i * n1, rows.begin() + (i + 1) * n1);
+    return counts;
+}
+
+// matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5) (ORBmatcher.cpp:1089-1313, LoopClosing.cpp:328): side1 / side2 are the two
+// keyframes' slots; the caller fills their `search` flags from vpMatches12 as :1116-1129 does and computes sR21, t21, sR12 from cv::Mat as
+// :1106-1108 does.  match12[i1] = idx2 where both directions agree, else -1: the caller writes vpMatches12[i1] = vpMapPoints2[idx2] there and leaves
+// the rest alone.  Returns nFound.
+inline int SearchBySim3(jsorb::KeyframeMatcher &matcher, const jsorb_sim3_params &params, const jsorb::Sim3Side &side1, const jsorb::Sim3Side &side2,
+                        std::vector<int> &match12, std::vector<int> *vnMatch1 = nullptr, std::vector<int> *vnMatch2 = nullptr)
+{
+    match12.assign((side1.n > 0 ? side1.n : 0) + 1, -1);
+    if (vnMatch1) vnMatch1->assign((side1.n > 0 ? side1.n : 0) + 1, -1);
+    if (vnMatch2) vnMatch2->assign((side2.n > 0 ? side2.n : 0) + 1, -1);
+    int found = 0;
+    if (jsorb_search_by_sim3(matcher.handle(), &params, &side1, &side2, vnMatch1 ? vnMatch1->data() : nullptr, vnMatch2 ? vnMatch2->data() : nullptr,
+                             match12.data(), &found) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_search_by_sim3: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    match12.resize(side1.n > 0 ? side1.n : 0);
+    if (vnMatch1) vnMatch1->resize(match12.size());
+    if (vnMatch2) vnMatch2->resize(side2.n > 0 ? side2.n : 0);
+    return found;
 }
 
 // Relocalization's matcher2.SearchByProjection(mCurrentFrame, vpCandidateKFs[i], sFound, th, ORBdist) (Tracking.cpp:2065 with (10, 100), :2079 with

@@ -1,7 +1,7 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
 // stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid; jsorb_search.hip: the four grid matchers; jsorb_bow.hip:
-// vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip: the keyframe matcher, which shares the helpers that take any owner).
+// vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip and jsorb_loop.hip: the keyframe matcher, which shares the helpers that take any owner).
 // include/jsorb.h only forward-declares the handle, so its layout is free to change.
 #pragma once
 
@@ -288,6 +288,40 @@ struct jsorb_extractor {
         double h2d = 0, enq = 0, wait = 0, st_enq = 0, st_wait = 0;
         long n = 0, st_n = 0;
     } trace;
+};
+
+// The keyframe matcher of LocalMapping and LoopClosing (jsorb_keyframes.hip: create, destroy, streams, triangulation, fuse; jsorb_loop.hip: the
+// loop-closing matchers).  It belongs to no extractor handle.
+struct jsorb_keyframe_matcher {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev_switch = nullptr;                             // orders a new stream behind the old one (jsorb_keyframe_matcher_set_stream)
+    unsigned long long *sort1 = nullptr, *sort2 = nullptr;      // sorted keys of KF1 (cap1) and of the KF2s (cap2): grown only
+    int cap1 = 0, cap2 = 0;
+    int *stats = nullptr;                                       // TRI_STATS statistics words of the last search
+    int32_t *out = nullptr;                                     // synchronous call: counts (256), then match12 (out_cap)
+    int out_cap = 0;
+    bool done = false;
+    // jsorb_fuse*: its own statistics and "done" mark, the keyframes' grid CSRs (grown only) and the synchronous form's outputs
+    int *fuse_stats = nullptr;                                  // FUSE_STATS words of the last fuse
+    int32_t *grid_start = nullptr, *grid_items = nullptr;       // n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
+    int grid_cap = 0, items_cap = 0;
+    int32_t *fuse_out = nullptr;                                // counts (256), then best_idx and best_dist (fuse_out_cap each)
+    int fuse_out_cap = 0;
+    bool fuse_done = false;
+    // jsorb_search_by_bow_kf* (jsorb_loop.hip): its own statistics and "done" mark, vbMatched2 of the candidates (grown only) and the synchronous form's outputs
+    int *loop_stats = nullptr;                                  // LOOP_STATS words of the last search
+    uint8_t *matched2 = nullptr;                                // one byte per candidate keypoint (matched2_cap)
+    int matched2_cap = 0;
+    int32_t *loop_out = nullptr;                                // counts (256), then match12 (loop_out_cap)
+    int loop_out_cap = 0;
+    bool loop_done = false;
+    // jsorb_search_by_sim3* (jsorb_loop.hip): the grids are grid_start / grid_items above
+    int *sim3_stats = nullptr;                                  // SIM3_STATS words of the last search
+    int32_t *sim3_out = nullptr;                                // the count, then match1, match2 and match12 (sim3_out_cap entries in all)
+    int sim3_out_cap = 0;
+    bool sim3_done = false;
+    std::string err;
 };
 
 #define HIPCHK(e, call)                                                                                   \

@@ -1,27 +1,8 @@
-// jsorb_keyframes.hip - host side of the keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*, jsorb_fuse*).
+// jsorb_keyframes.hip - host side of the keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*, jsorb_fuse*);
+// LoopClosing's calls on the same kind of matcher are in jsorb_loop.hip.
 // The matcher belongs to no extractor handle: it owns its stream and scratch, so LocalMapping's thread never enqueues on Tracking's handles.  The
 // kernels are in k_triangulate.hip (the grouping is k_bow.hip's k_bow_group with KF1 as the frame side) and k_fuse.hip.
-#include "jsorb_handle.h"
-
-struct jsorb_keyframe_matcher {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev_switch = nullptr;                             // orders a new stream behind the old one (jsorb_keyframe_matcher_set_stream)
-    unsigned long long *sort1 = nullptr, *sort2 = nullptr;      // sorted keys of KF1 (cap1) and of the KF2s (cap2): grown only
-    int cap1 = 0, cap2 = 0;
-    int *stats = nullptr;                                       // TRI_STATS statistics words of the last search
-    int32_t *out = nullptr;                                     // synchronous call: counts (256), then match12 (out_cap)
-    int out_cap = 0;
-    bool done = false;
-    // jsorb_fuse*: its own statistics and "done" mark, the keyframes' grid CSRs (grown only) and the synchronous form's outputs
-    int *fuse_stats = nullptr;                                  // FUSE_STATS words of the last fuse
-    int32_t *grid_start = nullptr, *grid_items = nullptr;       // n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
-    int grid_cap = 0, items_cap = 0;
-    int32_t *fuse_out = nullptr;                                // counts (256), then best_idx and best_dist (fuse_out_cap each)
-    int fuse_out_cap = 0;
-    bool fuse_done = false;
-    std::string err;
-};
+#include "jsorb_handle.h"      // struct jsorb_keyframe_matcher: shared with jsorb_loop.hip
 
 namespace {
 
@@ -65,6 +46,7 @@ void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m)
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
     free_device(m->sort1, m->sort2, m->stats, m->out, m->fuse_stats, m->grid_start, m->grid_items, m->fuse_out);
+    free_device(m->loop_stats, m->matched2, m->loop_out, m->sim3_stats, m->sim3_out);
     destroy_event(m->ev_switch);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
@@ -74,7 +56,7 @@ int jsorb_keyframe_matcher_set_stream(jsorb_keyframe_matcher *m, void *hip_strea
 {
     if (!m) return JSORB_ERR_INVALID;
     hipStream_t ns = hip_stream ? (hipStream_t)hip_stream : m->own_stream;
-    if (ns != m->stream && (m->done || m->fuse_done)) {               // the new stream continues after what the old one still carries (it reads the same scratch)
+    if (ns != m->stream && (m->done || m->fuse_done || m->loop_done || m->sim3_done)) {               // the new stream continues after what the old one still carries (it reads the same scratch)
         HIPCHK(m, hipSetDevice(m->device));
         HIPCHK(m, hipEventRecord(m->ev_switch, m->stream));
         HIPCHK(m, hipStreamWaitEvent(ns, m->ev_switch, 0));

@@ -288,6 +288,47 @@ struct FusePose {
 };
 void launch_fuse_grids(const FuseGridArgs &g, int n_kf, hipStream_t s);
 void launch_fuse_match(const FuseArgs &a, const FusePose &g, hipStream_t s);
+// k_loop_bow_match (k_loop.hip): ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) for several candidates KF2 of LoopClosing::ComputeSim3; the grouping
+// is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over a TriArgs with the same rows
+struct LoopBowArgs {
+    // KF1: n1 keypoints
+    int n1;
+    const uint8_t *valid1;
+    const uint8_t *desc1;
+    // the candidates, concatenated; candidate i is kf_start[i] .. kf_start[i + 1] (relative to the pointers below)
+    int n_kf;
+    const uint8_t *valid2;
+    const uint8_t *desc2;
+    jsorb_bow_params p;
+    // workspace and outputs
+    const unsigned long long *sorted1, *sorted2; // k_bow_group's keys
+    uint8_t *matched2;                           // vbMatched2 of the entries beyond the register cap: one byte per candidate keypoint (cleared to 0)
+    int32_t *match12;                            // n_kf x n1 (cleared to -1)
+    int *stats;                                  // node pairs, distances, ., largest candidate node of a pair, ind1 + 1, ind2 + 1, ind3 + 1 of candidate 0 (k_tri_resolve's layout)
+    int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
+};
+int loop_node_regs();                           // the compile-time cap of k_loop.hip (jsorb_loop_build_caps)
+void launch_loop_bow_match(const LoopBowArgs &a, hipStream_t s);
+// k_sim3_match / k_sim3_agree (k_loop.hip): ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th); the grids are launch_fuse_grids'
+struct Sim3Side {
+    int n;
+    const float *x, *y;                          // mvKeysUn
+    const int32_t *octave;
+    const uint8_t *kp_desc;
+    const float *Px, *Py, *Pz, *max_distance, *min_dist_inv, *max_dist_inv;
+    const uint8_t *mp_desc, *search;
+    float T[24];                                 // Rw row-major, tw, then sR row-major, t into the OTHER camera
+    const int32_t *cell_start, *cell_items;      // this keyframe's grid CSR
+    int32_t *match;                              // vnMatch of this side: n entries, every one written
+};
+struct Sim3Args {
+    jsorb_sim3_params p;
+    Sim3Side s[2];
+    int32_t *match12, *n_found;                  // n1 entries (every one written), one count (cleared to 0)
+    int *stats;                                  // slots with a window, keypoints walked, distances, largest window, agreements (cleared to 0)
+};
+void launch_sim3_match(const Sim3Args &a, hipStream_t s);
+void launch_sim3_agree(const Sim3Args &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

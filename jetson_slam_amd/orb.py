@@ -65,6 +65,8 @@ EXPORTS = [
     "jsorb_keyframe_matcher_create", "jsorb_keyframe_matcher_destroy", "jsorb_keyframe_matcher_set_stream", "jsorb_keyframe_matcher_get_stream",
     "jsorb_keyframe_matcher_last_error", "jsorb_search_for_triangulation_async", "jsorb_search_for_triangulation",
     "jsorb_search_for_triangulation_stats", "jsorb_fuse_async", "jsorb_fuse", "jsorb_fuse_stats",
+    "jsorb_search_by_bow_kf_async", "jsorb_search_by_bow_kf", "jsorb_search_by_bow_kf_stats", "jsorb_loop_build_caps",
+    "jsorb_search_by_sim3_async", "jsorb_search_by_sim3", "jsorb_search_by_sim3_stats",
 ]
 
 
@@ -190,6 +192,29 @@ def make_fuse_params(camera, bounds, grid, log_scale_factor, scale_factor, inv_l
     for l in range(min(len(sf), MAX_LEVELS)):
         p.scale_factor[l] = sf[l]
         p.inv_level_sigma2[l] = i2[l]
+    return p
+
+
+class JsorbSim3Params(C.Structure):
+    _fields_ = [("th", C.c_float), ("th_high", C.c_int)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")] + \
+               [("cols", C.c_int), ("rows", C.c_int), ("log_scale_factor", C.c_float), ("n_levels", C.c_int), ("scale_factor", C.c_float * MAX_LEVELS)]
+
+
+class JsorbSim3Side(C.Structure):
+    _fields_ = [("n", C.c_int)] + [(k, C.c_void_p) for k in ("x", "y", "octave", "kp_desc", "Px", "Py", "Pz", "max_distance", "min_dist_inv",
+                                                             "max_dist_inv", "mp_desc", "search")] + \
+               [("Rw", C.c_float * 9), ("tw", C.c_float * 3), ("sR", C.c_float * 9), ("t", C.c_float * 3)]
+
+
+def make_sim3_params(camera, bounds, grid, log_scale_factor, scale_factor, th=7.5, th_high=TH_HIGH, cols=64, rows=48):
+    """jsorb_sim3_params of LoopClosing::ComputeSim3's SearchBySim3 (th = 7.5, ORBmatcher.cpp:1089): camera = (fx, fy, cx, cy) of pKF1 (it serves
+    both directions), bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), grid = (mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows,
+    log_scale_factor = mfLogScaleFactor, scale_factor the float table mvScaleFactors"""
+    sf = np.ascontiguousarray(scale_factor, np.float32).ravel()
+    p = JsorbSim3Params(th, int(th_high), *camera, *bounds, *grid, cols, rows, log_scale_factor, len(sf))
+    for l in range(min(len(sf), MAX_LEVELS)):
+        p.scale_factor[l] = sf[l]
     return p
 
 
@@ -342,6 +367,13 @@ def load_library(path=None):
         "jsorb_fuse_async": (I, [P, C.POINTER(JsorbFuseParams), I] + [P] * 10 + [I] + [P] * 13),
         "jsorb_fuse": (I, [P, C.POINTER(JsorbFuseParams), I] + [P] * 10 + [I] + [P] * 13),
         "jsorb_fuse_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+        "jsorb_search_by_bow_kf_async": (I, [P, C.POINTER(JsorbBowParams), I] + [P] * 4 + [I] + [P] * 7),
+        "jsorb_search_by_bow_kf": (I, [P, C.POINTER(JsorbBowParams), I] + [P] * 4 + [I] + [P] * 7),
+        "jsorb_search_by_bow_kf_stats": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_loop_build_caps": (I, [C.POINTER(I)]),
+        "jsorb_search_by_sim3_async": (I, [P, C.POINTER(JsorbSim3Params), C.POINTER(JsorbSim3Side), C.POINTER(JsorbSim3Side)] + [P] * 4),
+        "jsorb_search_by_sim3": (I, [P, C.POINTER(JsorbSim3Params), C.POINTER(JsorbSim3Side), C.POINTER(JsorbSim3Side)] + [P] * 3 + [C.POINTER(I)]),
+        "jsorb_search_by_sim3_stats": (I, [P] + [C.POINTER(I)] * 5),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -493,6 +525,13 @@ def search_kf_build_caps():
     c, l = C.c_int(), C.c_int()
     load_library().jsorb_search_kf_build_caps(C.byref(c), C.byref(l))
     return c.value, l.value
+
+
+def loop_build_caps():
+    """jsorb_loop_build_caps of the loaded library: candidate entries of a node a lane of k_loop_bow_match keeps in registers"""
+    r = C.c_int()
+    load_library().jsorb_loop_build_caps(C.byref(r))
+    return r.value
 
 
 def bow_transform_descriptors(voc, descriptors):
@@ -716,6 +755,145 @@ class KeyframeMatcher:
         w, k, d, l = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         self._chk(self._lib.jsorb_fuse_stats(self._m, C.byref(w), C.byref(k), C.byref(d), C.byref(l)))
         return w.value, k.value, d.value, l.value
+
+
+    # ---- LoopClosing::ComputeSim3: SearchByBoW(KF, KF) for all candidates, SearchBySim3 ----
+    BOW_KF_KEYS = ("node", "valid", "angle", "desc")
+
+    def _bow_kf_args(self, kf1, kf_start, candidates, params):
+        import torch
+        what = "search_by_bow_kf"
+        if not isinstance(params, JsorbBowParams):
+            raise JsorbError("%s: params must come from make_bow_params" % what)
+        ks = np.ascontiguousarray(kf_start, np.int32)
+        if ks.ndim != 1 or len(ks) < 1:
+            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
+        nk, total = len(ks) - 1, int(ks[-1])
+        dt = dict(node=(torch.int32,), valid=(torch.uint8, torch.bool), angle=(torch.float32,), desc=(torch.uint8,))
+
+        def side(kf, name, n):
+            ptrs = []
+            for k in self.BOW_KF_KEYS:
+                t = kf[k]
+                if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
+                shape = (n, 32) if k == "desc" else (n,)
+                if t.dtype not in dt[k] or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(d) for d in dt[k]), shape))
+                ptrs.append(t.data_ptr() if n else None)
+            if n and kf["desc"].data_ptr() % 16:
+                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
+            return ptrs
+
+        n1 = int(kf1["node"].shape[0])
+        p1, p2 = side(kf1, "kf1", n1), side(candidates, "candidates", total)
+        return n1, nk, ks, [C.byref(params), n1] + p1 + [nk, ks.ctypes.data] + p2
+
+    def search_by_bow_kf(self, kf1, kf_start, candidates, params, wait=True):
+        """jsorb_search_by_bow_kf_async: the current keyframe (dict of device tensors: node int32[n1], valid uint8 / bool [n1], angle float32[n1],
+        desc uint8[n1, 32]) against the len(kf_start) - 1 concatenated loop candidates (the same keys; kf_start: HOST int32 offsets into them, the
+        arrays hold kf_start[-1] entries).  Returns (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) as device tensors; wait= as in
+        search_for_triangulation, with the same rule for the returned tensors' lifetime."""
+        import torch
+        n1, nk, ks, args = self._bow_kf_args(kf1, kf_start, candidates, params)
+        dev = kf1["node"].device
+        match12 = torch.full((max(nk, 1), max(n1, 1)), -7, dtype=torch.int32, device=dev)
+        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_by_bow_kf_async(self._m, *args, match12.data_ptr(), count.data_ptr()))
+        if wait:
+            self.sync()
+        return match12.reshape(-1)[:nk * n1].reshape(nk, n1), count[:nk]
+
+    def search_by_bow_kf_host(self, kf1, kf_start, candidates, params):
+        """jsorb_search_by_bow_kf, the synchronous form: the same inputs, (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) on the host
+        with one copy back"""
+        import torch
+        n1, nk, ks, args = self._bow_kf_args(kf1, kf_start, candidates, params)
+        match12 = np.full(max(nk * n1, 1), -7, np.int32)
+        count = np.full(max(nk, 1), -7, np.int32)
+        torch.cuda.current_stream(kf1["node"].device).synchronize()
+        self._chk(self._lib.jsorb_search_by_bow_kf(self._m, *args, match12.ctypes.data, count.ctypes.data))
+        return match12[:nk * n1].reshape(nk, n1), count[:nk]
+
+    def search_by_bow_kf_stats(self):
+        """((candidate, node) pairs on both sides, Hamming distances, most candidate keypoints in such a node, candidate 0's (ind1, ind2, ind3)) of
+        the last search_by_bow_kf"""
+        p, d, m, b = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 3)()
+        self._chk(self._lib.jsorb_search_by_bow_kf_stats(self._m, C.byref(p), C.byref(d), C.byref(m), b))
+        return p.value, d.value, m.value, tuple(b)
+
+    SIM3_KEYS = ("x", "y", "octave", "kp_desc", "Px", "Py", "Pz", "max_distance", "min_dist_inv", "max_dist_inv", "mp_desc", "search")
+    SIM3_POSE = (("Rw", 9), ("tw", 3), ("sR", 9), ("t", 3))
+
+    def _sim3_side(self, d, name):
+        import torch
+        what = "search_by_sim3"
+        n = int(d["x"].shape[0])
+        dt = dict(octave=(torch.int32,), kp_desc=(torch.uint8,), mp_desc=(torch.uint8,), search=(torch.uint8, torch.bool))
+        s = JsorbSim3Side(n)
+        for k in self.SIM3_KEYS:
+            t = d[k]
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
+            shape = (n, 32) if k.endswith("desc") else (n,)
+            ok = dt.get(k, (torch.float32,))
+            if t.dtype not in ok or tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(x) for x in ok), shape))
+            if n and k.endswith("desc") and t.data_ptr() % 16:
+                raise JsorbError("%s: %s[%r] must be 16-byte aligned" % (what, name, k))
+            setattr(s, k, t.data_ptr() if n else None)
+        for k, size in self.SIM3_POSE:
+            v = np.ascontiguousarray(d[k], np.float32).reshape(-1)
+            if len(v) != size:
+                raise JsorbError("%s: %s[%r] must hold %d floats" % (what, name, k, size))
+            setattr(s, k, (C.c_float * size)(*v.tolist()))
+        return s
+
+    def _sim3_args(self, side1, side2, params):
+        if not isinstance(params, JsorbSim3Params):
+            raise JsorbError("search_by_sim3: params must come from make_sim3_params")
+        s1, s2 = self._sim3_side(side1, "side1"), self._sim3_side(side2, "side2")
+        return s1, s2, [C.byref(params), C.byref(s1), C.byref(s2)]
+
+    def search_by_sim3(self, side1, side2, params, wait=True):
+        """jsorb_search_by_sim3_async: each side a dict of device tensors aligned with the keyframe's keypoints (x, y float32, octave int32, kp_desc
+        uint8[n, 32]; Px, Py, Pz, max_distance, min_dist_inv, max_dist_inv float32, mp_desc uint8[n, 32], search uint8 / bool) and of HOST float32
+        arrays: Rw (9, row-major), tw (3) of the keyframe itself, sR (9), t (3) into the OTHER camera (side 1: sR21, t21; side 2: sR12, t12).
+        Returns (match1 int32[n1], match2 int32[n2], match12 int32[n1], n_found int32[1]) as device tensors; wait= as in
+        search_for_triangulation, with the same rule for the returned tensors' lifetime."""
+        import torch
+        s1, s2, args = self._sim3_args(side1, side2, params)
+        dev = side1["x"].device
+        m1 = torch.full((max(s1.n, 1),), -7, dtype=torch.int32, device=dev)
+        m2 = torch.full((max(s2.n, 1),), -7, dtype=torch.int32, device=dev)
+        m12 = torch.full((max(s1.n, 1),), -7, dtype=torch.int32, device=dev)
+        found = torch.full((1,), -7, dtype=torch.int32, device=dev)
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_search_by_sim3_async(self._m, *args, m1.data_ptr(), m2.data_ptr(), m12.data_ptr(), found.data_ptr()))
+        if wait:
+            self.sync()
+        return m1[:s1.n], m2[:s2.n], m12[:s1.n], found
+
+    def search_by_sim3_host(self, side1, side2, params):
+        """jsorb_search_by_sim3, the synchronous form: the same inputs, (match1 int32[n1], match2 int32[n2], match12 int32[n1], n_found) on the host
+        with one copy back"""
+        import torch
+        s1, s2, args = self._sim3_args(side1, side2, params)
+        m1, m2, m12 = np.full(max(s1.n, 1), -7, np.int32), np.full(max(s2.n, 1), -7, np.int32), np.full(max(s1.n, 1), -7, np.int32)
+        found = C.c_int(-7)
+        torch.cuda.current_stream(side1["x"].device).synchronize()
+        self._chk(self._lib.jsorb_search_by_sim3(self._m, *args, m1.ctypes.data, m2.ctypes.data, m12.ctypes.data, C.byref(found)))
+        return m1[:s1.n], m2[:s2.n], m12[:s1.n], found.value
+
+    def search_by_sim3_stats(self):
+        """(slots that reached a window, keypoints walked, Hamming distances, the largest window, agreements) of the last search_by_sim3, both
+        directions together"""
+        v = [C.c_int() for _ in range(5)]
+        self._chk(self._lib.jsorb_search_by_sim3_stats(self._m, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 def matched_pairs(match12_row):
