@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from frame_builders import last_frame_of, params, points_of  # noqa: F401  (other GPU tests import them from here)
 from jetson_slam_amd.synth import synth_stereo_pair
 from test_gpu_search_local import EUROC, _dev, _from_device_ptr, _mk, _stereo, frame_of
 from test_search_last_frame_host import (HISTO_LENGTH, ROTATION_CULL, rot_bin, rotation_cull_expected, search_by_projection_last, search_last_restated,
@@ -17,44 +18,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 INT_MIN = -2 ** 31
-
-
-def last_frame_of(g, c, u_right=None, bounds=None):
-    F = frame_of(g, c, u_right=u_right, bounds=bounds)
-    kp = g.keypoints(0)
-    N = len(kp) // 6
-    F["angle"] = kp[3 * N:4 * N].astype(np.int32).view(np.float32)
-    return F
-
-
-def params(c, F, th, direction=0, bounds=None, cam=None, retry_below=20, check_orientation=1, seed=0):
-    """a current pose a little off the one the points were made with (points_of): K14 lands them next to their keypoints"""
-    rng = np.random.default_rng(seed)
-    a = rng.normal(0, 0.002, 3)
-    R = np.array([[1, -a[2], a[1]], [a[2], 1, -a[0]], [-a[1], a[0], 1]], np.float32)
-    t = rng.normal(0, 0.01, 3).astype(np.float32)
-    fx, fy, cx, cy = cam if cam is not None else (f32(c["fx"]), f32(c["fx"]), f32(c["w"] / 2), f32(c["h"] / 2))
-    b = bounds if bounds is not None else (f32(0), f32(c["w"]), f32(0), f32(c["h"]))
-    return dict(th=f32(th), th_high=100, check_orientation=check_orientation, direction=direction, retry_below=retry_below, fx=f32(fx), fy=f32(fy),
-                cx=f32(cx), cy=f32(cy), min_x=f32(b[0]), max_x=f32(b[1]), min_y=f32(b[2]), max_y=f32(b[3]), Rcw=R, tcw=t)
-
-
-def points_of(rng, F, prm, n, n_levels, outliers=0.3):
-    """the last frame's map points: keypoints of this frame back-projected through the slightly perturbed pose of prm (sources drawn with
-    replacement: keypoints chosen twice), descriptors a few bits off, octaves +-0..2, angles offset by one rotation plus ~30 % outliers"""
-    N = len(F["kx"])
-    src = rng.integers(0, N, n)
-    z = rng.uniform(1.0, 15.0, n)
-    Pc = np.stack([(F["kx"][src] + rng.normal(0, 1.0, n) - prm["cx"]) * z / prm["fx"], (F["ky"][src] + rng.normal(0, 1.0, n) - prm["cy"]) * z / prm["fy"], z])
-    Pw = np.linalg.solve(prm["Rcw"].astype(np.float64), Pc - prm["tcw"].astype(np.float64)[:, None]).astype(np.float32)
-    desc = F["desc"][src].copy()
-    flip = rng.random((n, 32)) < 0.03
-    desc[flip] ^= rng.integers(1, 256, int(flip.sum()), dtype=np.uint8)
-    octave = np.clip(F["octave"][src] + rng.integers(-2, 3, n), 0, n_levels - 1).astype(np.int32)
-    octave[rng.random(n) < 0.1] = 0
-    off = np.where(rng.random(n) < outliers, rng.uniform(0, 360, n), f32(12.0)).astype(np.float32)
-    angle = np.mod(F["angle"][src] + off, f32(360)).astype(np.float32)
-    return dict(Px=Pw[0].copy(), Py=Pw[1].copy(), Pz=Pw[2].copy(), octave=octave, angle=angle, desc=desc), src
 
 
 def run_device(orb, g, F, P, prm, u_right_t=None, image=0):

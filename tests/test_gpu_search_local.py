@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from jetson_slam_amd.synth import synth_stereo_pair
+from frame_builders import frame_of, points_near_keypoints
 from test_search_local_host import build_grid, search_by_projection, search_local_restated
 
 pytestmark = pytest.mark.gpu
@@ -32,38 +33,6 @@ def _from_device_ptr(orb, ptr, n):
     t = torch.empty(max(n, 1), dtype=torch.float32, device="cuda")
     assert ptr and orb.load_library().jsorb_mem_d2d(ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(ptr), ctypes.c_size_t(4 * n)) == 0
     return t[:n]
-
-
-def frame_of(g, c, u_right=None, blocked=None, cols=64, rows=48, bounds=None):
-    kp = g.keypoints(0)
-    n = len(kp) // 6
-    xu, yu = g.keypoints_undistorted(0)
-    min_x, max_x, min_y, max_y = bounds if bounds is not None else (f32(0), f32(c["w"]), f32(0), f32(c["h"]))
-    inv_w, inv_h = f32(cols) / f32(max_x - min_x), f32(rows) / f32(max_y - min_y)
-    grid, start, items = build_grid(xu, yu, min_x, min_y, inv_w, inv_h, cols, rows)
-    return dict(kx=xu, ky=yu, octave=kp[4 * n:5 * n].astype(np.int64), desc=g.descriptors(0), grid=grid, start=start, items=items, cols=cols,
-                rows=rows, min_x=f32(min_x), min_y=f32(min_y), inv_w=inv_w, inv_h=inv_h, scale=g.get_scale_factors(), mbf=f32(c["bf"]),
-                u_right=u_right, blocked=blocked)
-
-
-def points_near_keypoints(rng, F, n, n_levels, noise=2.0, desc_noise=0.06):
-    """map points projected next to keypoints, with their descriptors a few bits off: most have a match, some conflict"""
-    N = len(F["kx"])
-    src = rng.integers(0, N, n)
-    u = (F["kx"][src] + rng.normal(0, noise, n)).astype(np.float32)
-    v = (F["ky"][src] + rng.normal(0, noise, n)).astype(np.float32)
-    level = np.clip(F["octave"][src] + rng.integers(0, 2, n), 0, n_levels - 1).astype(np.int32)
-    desc = F["desc"][src].copy()
-    flip = rng.random((n, 32)) < desc_noise
-    desc[flip] ^= rng.integers(1, 256, int(flip.sum()), dtype=np.uint8)
-    view_cos = rng.choice(np.array([0.3, 0.99799996, 0.998, 0.9980001, 1.0], np.float32), n)
-    if F["u_right"] is not None:
-        ur = F["u_right"][src]
-        invz = np.where(ur > 0, (u - ur) / F["mbf"], rng.uniform(0.05, 0.5, n)).astype(np.float32) + rng.normal(0, 0.01, n).astype(np.float32)
-    else:
-        invz = rng.uniform(0.05, 0.5, n).astype(np.float32)
-    return dict(u=u, v=v, invz=invz.astype(np.float32), level=level, view_cos=view_cos, in_frustum=(rng.random(n) < 0.95).astype(np.uint8),
-                desc=desc), src
 
 
 def run_device(g, F, P, th, u_right_t=None, nn_ratio=0.8, th_high=100):
