@@ -15,7 +15,8 @@
 //   * no LDS tile, no barrier: lanes are independent, a workgroup is just 256 consecutive (strip, band) items of one level, so small
 //     levels fill their waves (round 3's 64 x 128 tiles covered 1.3x the ROI: 23 % of the lanes idle);
 //   * certificate as before (below): A + 49152 rounded toward -inf leaves floor(256 A) in the mantissa; undecided pixels are flagged in
-//     a per-lane byte mask in LDS, listed per wave after the band and recomputed with the reference's 49-FMA chain, one pixel per lane.
+//     a per-lane row mask in LDS (with the side of the integer A sits on), listed per wave after the band and recomputed with the reference's
+//     49-FMA chain, one pixel per lane; the exact byte is stored only where it differs from the one the fast pass stored (k_blur_body.h).
 #include "jsorb_launch.h"
 #include "k_blur_body.h"
 #include "k_compact_body.h"

@@ -46,7 +46,7 @@ static_assert(BLUR_RB_TALL <= BLUR_RB_MAX && BLUR_RB_BATCH <= BLUR_RB_MAX, "band
 #ifndef BLUR_X_LEAD
 #define BLUR_X_LEAD 4
 #endif
-static_assert(BLUR_RB_MAX % 16 == 0 && BLUR_RB_MAX <= 32, "the per-lane row masks are read back as 16-byte units; list entries hold 5 bits of row");
+static_assert(BLUR_RB_MAX % 8 == 0 && BLUR_RB_MAX <= 32, "the per-lane row masks (two bytes per row) are read back as 16-byte units; list entries hold 5 bits of row");
 #ifndef BLUR_BOUSTRO
 #define BLUR_BOUSTRO 1         // odd bands walk bottom-up (see blur_workgroup)
 #endif
@@ -68,6 +68,12 @@ static_assert(BLUR_RB_MAX % 16 == 0 && BLUR_RB_MAX <= 32, "the per-lane row mask
 // marks the pixel as undecided.  Those (~0.8 % of natural pixels; every pixel of an exactly flat window, whose C lies within 1e-4 of
 // an integer) are recomputed with the exact chain; a wave with too many of them recomputes its bands densely with the same exact
 // code.  The output is bit-identical to the chain in every case.
+// The exact pass stores a byte only where it CHANGES the one the fast pass stored.  It runs at the end of the band, long after the fast pass wrote the
+// full rows: each of its one-byte stores reaches memory as a partial write of its own, and for all but ~0.2 % of the undecided pixels of a textured image (an exactly
+// flat window changes for 68 of the 256 grey levels) the byte is the one already there.  The stored byte is not recomputed (an A' that differed from A in the last bit would
+// go wrong only where the two straddle an integer): the flag carries the pixel's SIDE, a bit of the fraction byte - 0: A just above an integer
+// (fraction 0), 1: just below one (fraction 255).  A is within 2^-8 of that integer and C within 1e-3 of A, so the integer is m = rint(C) and the fast
+// pass stored m - side; the exact lane stores trunc(C) only if it differs (tests/test_fixup_rule_host.py).
 #define BLUR_BAND 0.00390625f
 
 // separable factors: gv[j] = exp(-j^2/200) and gh[k] = exp(-k^2/200) / 47.092777252197266 (the reference's f32 weight sum 0x423C5F01),
@@ -77,12 +83,13 @@ static __constant__ float c_sep_h[4] = {(float)(1.0 / 47.092777252197266), (floa
                                  (float)(0.98019867330675525 / 47.092777252197266), (float)(0.95599748183309996 / 47.092777252197266)};
 
 typedef unsigned blur_u4 __attribute__((ext_vector_type(4)));
+typedef blur_u4 __attribute__((may_alias)) blur_u4_alias;      // reads the 16-bit row masks back, eight rows at a time
 
 // one workgroup of k_blur: image b, workgroup blk of the image's g.blur_blocks
 __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc &src, const uint8_t *slab, uint8_t *blur_slab, const uint32_t *__restrict__ ctab, int b, int blk)
 {
-    __shared__ __align__(16) unsigned char s_mask[BLUR_THREADS * BLUR_RB_MAX];      // per lane: one byte per output row, bit k = pixel k undecided
-    __shared__ unsigned short s_list[BLUR_THREADS / 64][BLUR_AMB_CAP];
+    __shared__ __align__(16) unsigned short s_mask[BLUR_THREADS * BLUR_RB_MAX];     // per lane: two bytes per output row; byte q = pixels 4 q .. 4 q + 3: bit 4 + t = pixel undecided, bit t = its side
+    static_assert(BLUR_AMB_CAP <= 64 * BLUR_RB_MAX, "a wave's list of undecided pixels is built in place of its row masks");
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform_i32(tid >> 6);
     const unsigned wd = ctab_load(ctab, ctab_blur(g) + blk);      // level | workgroup of the level << 4
     const int lvl = (int)(wd & 15u), wb = (int)(wd >> 4);
@@ -129,7 +136,11 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
         asm volatile("" : "+v"(gh[k]), "+v"(gv[k]));
     }
     const float magic = 49152.0f;
-    unsigned char *const my_mask = s_mask + tid * BLUR_RB_MAX;
+    // byte masks of the lane's pixels inside the ROI: for its 8-byte store, and as the weights that gather the flag bits of a row (see the fast pass)
+    const unsigned long long keep = ((px_mask & 1u) ? 0xFFull : 0) | ((px_mask & 2u) ? 0xFF00ull : 0) | ((px_mask & 4u) ? 0xFF0000ull : 0) | ((px_mask & 8u) ? 0xFF000000ull : 0) |
+                                    ((px_mask & 16u) ? 0xFF00000000ull : 0) | ((px_mask & 32u) ? 0xFF0000000000ull : 0) | ((px_mask & 64u) ? 0xFF000000000000ull : 0) | ((px_mask & 128u) ? 0xFF00000000000000ull : 0);
+    const unsigned dot_w[2] = {0x08040201u & (unsigned)keep, 0x08040201u & (unsigned)(keep >> 32)};
+    unsigned short *const my_mask = s_mask + tid * BLUR_RB_MAX;
 
     // ---- fast pass: stream down the band ----
     const int NR = RB + 6;                                                          // input rows ya - 3 .. ya + RB + 2 (wave-uniform count)
@@ -205,7 +216,7 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
                          "s_nop 1\n\ts_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0"
                          : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]), "=&v"(r[4]), "=&v"(r[5]), "=&v"(r[6]), "=&v"(r[7])
                          : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), "v"(magic));
-            unsigned ow[2], ambm = 0;
+            unsigned ow[2], fs[2];
 #pragma unroll
             for (int wi = 0; wi < 2; wi++) {
                 const unsigned a01 = __builtin_amdgcn_perm(__float_as_uint(r[4 * wi + 1]), __float_as_uint(r[4 * wi]), 0x04000501u);
@@ -216,12 +227,16 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
                 // y set (and possibly that of a byte of value 1 above one, which only sends a decided pixel through the exact code as well)
                 const unsigned y = (fr ^ (fr << 1)) & 0xFEFEFEFEu;
                 const unsigned z = (~y & (y - 0x01010101u)) & 0x80808080u;
-                // bit 8t + 7 -> bit 4 wi + t: bytes of z are 0 or 128, one v_dot4_u32_u8 with the byte weights 1, 2, 4, 8 (16 .. 128 for the second dword) adds up
-                // 128 x the nibble.  (Round 6: the 32-bit multiply this replaces - (z >> 7) * 0x01020408 >> 24 - is a quarter-rate instruction, two of them per
-                // row of 8 pixels were a tenth of the kernel's issue time.)
-                ambm = __builtin_amdgcn_udot4(z, wi ? 0x80402010u : 0x08040201u, ambm, false);
+                // The SIDE of a flagged pixel is any bit of its fraction byte (0 or 255: bit 3 is bit 7); it rides in bit 3 of the pixel's byte, under the
+                // flag in bit 7.  One v_dot4_u32_u8 with the byte weights 1, 2, 4, 8 then adds up 128 x the nibble of flags + 8 x the nibble of sides:
+                // every term lands on a bit of its own, so the stray side bits of unflagged pixels disturb nothing (they are never read).  The
+                // weights of pixels outside the ROI are 0 (dot_w: per lane, set up once), which spares masking the sum.  (Round 6: the 32-bit multiply
+                // the dot product replaces - (z >> 7) * 0x01020408 >> 24 - is a quarter-rate instruction, two of them per row of 8 pixels were a
+                // tenth of the kernel's issue time.  A second dot product for the sides, of fr & z, cost k_blur 1.2 %; this form is one AND-OR per dword.)
+                fs[wi] = __builtin_amdgcn_udot4((fr & 0x08080808u) | z, dot_w[wi], 0u, false);
             }
-            ambm >>= 7;
+            // row mask: byte wi = pixels 4 wi .. 4 wi + 3, flags in its high nibble, sides in its low nibble
+            const unsigned rowm = (fs[0] >> 3) | (fs[1] << 5);
             const unsigned dst_off = dst_row_off;                                    // byte offset of this output row's 8 pixels from out_base (a running sum: no 64-bit multiply per row)
             dst_row_off += out_step;
             const int orow = o_real;
@@ -230,8 +245,6 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
                 uint8_t *dst = out_base + dst_off;
                 if (BLUR_X_LEAD) {
                     // whole 8-byte units, zeros outside the ROI (the row's pitch has room for the last strip: pitch >= W rounded up to 64)
-                    const unsigned long long keep = ((px_mask & 1u) ? 0xFFull : 0) | ((px_mask & 2u) ? 0xFF00ull : 0) | ((px_mask & 4u) ? 0xFF0000ull : 0) | ((px_mask & 8u) ? 0xFF000000ull : 0) |
-                                                    ((px_mask & 16u) ? 0xFF00000000ull : 0) | ((px_mask & 32u) ? 0xFF0000000000ull : 0) | ((px_mask & 64u) ? 0xFF000000000000ull : 0) | ((px_mask & 128u) ? 0xFF00000000000000ull : 0);
                     *reinterpret_cast<unsigned long long *>(dst) = (((unsigned long long)ow[1] << 32) | ow[0]) & keep;
                 } else if (n_valid >= BLUR_SW) { reinterpret_cast<unsigned *>(dst)[0] = ow[0]; reinterpret_cast<unsigned *>(dst)[1] = ow[1]; }
                 else {
@@ -239,9 +252,8 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
                     for (int k = 0; k < BLUR_SW; k++)
                         if (k < n_valid) dst[k] = (uint8_t)((ow[k >> 2] >> (8 * (k & 3))) & 0xFFu);
                 }
-                ambm &= px_mask;
-                my_mask[orow] = (unsigned char)ambm;
-                n_amb_lane += __popc(ambm);
+                my_mask[orow] = (unsigned short)rowm;
+                n_amb_lane += __popc(rowm & 0xF0F0u);
             }
         }
     }
@@ -251,7 +263,8 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
     const int total = __builtin_amdgcn_readlane(incl, 63);
     if (total == 0) return;
     // exact value of pixel (x, y): acc = fma(w[r][c], I, acc) in raster order, taps from the level plane (16 bytes from the dword below x - 3 per row)
-    auto exact_pixel = [&](int x, int y) {
+    // and stored only where it differs from the byte the fast pass stored, rint(acc) - side (see the certificate's comment)
+    auto exact_pixel = [&](int x, int y, unsigned side) {
         const int sh = (x - 3) & 3;
         const int o16 = (y - 3) * pitch + ((x - 3) & ~3);
         blur_u4 v[7];
@@ -270,27 +283,34 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
             acc = __builtin_fmaf(g2, (float)((w1 >> 8) & 0xFFu), acc);
             acc = __builtin_fmaf(g3, (float)((w1 >> 16) & 0xFFu), acc);
         }
-        out_base[(size_t)y * out_pitch + x] = (uint8_t)((unsigned)acc & 0xFFu);      // cvt.rzi.u32.f32 + st.u8
+        const unsigned exact = (unsigned)acc, stored = (unsigned)__builtin_rintf(acc) - side;
+        if (exact != stored) out_base[(size_t)y * out_pitch + x] = (uint8_t)(exact & 0xFFu);      // cvt.rzi.u32.f32 + st.u8
     };
     if (total <= BLUR_AMB_CAP) {
-        unsigned short *my_list = s_list[wave];
+        // The list takes the place of the wave's own row masks (BLUR_AMB_CAP entries fit into them): every lane reads its masks into registers
+        // first - LDS operations of one wave execute in order, so all 64 lanes hold theirs before the first entry is written.  (A list of its
+        // own next to the 16-bit masks is 14 KB of static LDS: with the bucket counters of k_blur_compact a 720-row image kept 3 workgroups per CU, not 4.)
+        unsigned short *my_list = s_mask + 64 * wave * BLUR_RB_MAX;
         int pos = incl - (int)n_amb_lane;
-        if (n_amb_lane) {
-            // the lane's mask bytes as dwords (rows the lane never wrote - beyond n_out - are skipped): bit 8 (o & 3) + k of dword o >> 2 = pixel k of row o
-            const blur_u4 *mq = reinterpret_cast<const blur_u4 *>(my_mask);
+        blur_u4 mv[BLUR_RB_MAX / 8];
 #pragma unroll
-            for (int q = 0; q < BLUR_RB_MAX / 16; q++) {
-                const blur_u4 mv = mq[q];
-                const unsigned md[4] = {mv.x, mv.y, mv.z, mv.w};
+        for (int q = 0; q < BLUR_RB_MAX / 8; q++) mv[q] = reinterpret_cast<const blur_u4_alias *>(my_mask)[q];
+        if (n_amb_lane) {
+            // the lane's row masks as dwords of two rows (rows the lane never wrote - beyond n_out - are skipped): row o in the half o & 1 of dword o >> 1, the
+            // flag of pixel k in bit 4 + (k & 3) + 8 (k >> 2) of the half, its side 4 bits below.  List entry: side << 14 | lane << 8 | row << 3 | pixel
+#pragma unroll
+            for (int q = 0; q < BLUR_RB_MAX / 8; q++) {
+                const unsigned md[4] = {mv[q].x, mv[q].y, mv[q].z, mv[q].w};
 #pragma unroll
                 for (int d4 = 0; d4 < 4; d4++) {
-                    const int o0 = 16 * q + 4 * d4;
-                    unsigned m = md[d4];
-                    if (o0 + 4 > n_out) m &= o0 >= n_out ? 0u : (0xFFFFFFFFu >> (8 * (o0 + 4 - n_out)));
+                    const int o0 = 8 * q + 2 * d4;
+                    unsigned m = md[d4] & 0xF0F0F0F0u;
+                    if (o0 + 2 > n_out) m &= o0 >= n_out ? 0u : 0xFFFFu;
                     while (m) {
                         const int bit = __builtin_ctz(m);
                         m &= m - 1;
-                        my_list[pos++] = (unsigned short)((lane << 8) | (o0 << 3) | bit);      // (o0 + bit / 8) << 3 | bit % 8
+                        const unsigned side = (md[d4] >> (bit - 4)) & 1u;
+                        my_list[pos++] = (unsigned short)((side << 14) | (lane << 8) | ((o0 + (bit >> 4)) << 3) | ((bit & 8) >> 1) | (bit & 3));
                     }
                 }
             }
@@ -300,15 +320,20 @@ __device__ __forceinline__ void blur_workgroup(const Geometry &g, const ImageSrc
         for (int i = lane; i < total; i += 64) {
             const int e = my_list[i];
             int ex0, eya;
-            item_geometry(item0 + (e >> 8), ex0, eya);
-            exact_pixel(ex0 + (e & 7), eya + ((e >> 3) & 31));
+            item_geometry(item0 + ((e >> 8) & 63), ex0, eya);
+            exact_pixel(ex0 + (e & 7), eya + ((e >> 3) & 31), (unsigned)e >> 14);
         }
         return;
     }
-    // ---- dense exact path (bands of mostly flat windows): every pixel of the lane's strip through the reference's chain ----
-    for (int o = 0; o < n_out; o++)
-        for (int k = 0; k < n_valid; k++)
-            if ((px_mask >> k) & 1u) exact_pixel(x0 + k, ya + o);
+    // ---- dense exact path (bands of mostly flat windows): every lane takes the flagged pixels of its own strip through the reference's chain.  The
+    // unflagged ones are decided by the certificate: what the fast pass stored is the chain's byte ----
+    for (int o = 0; o < n_out; o++) {
+        const unsigned w = my_mask[o];
+        for (unsigned m = w & 0xF0F0u; m; m &= m - 1) {
+            const int bit = __builtin_ctz(m);
+            exact_pixel(x0 + (((bit & 8) >> 1) | (bit & 3)), ya + o, (w >> (bit - 4)) & 1u);
+        }
+    }
 }
 
 } // namespace jsorb
