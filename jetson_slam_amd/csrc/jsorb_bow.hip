@@ -1,5 +1,5 @@
 // jsorb_bow.hip - host side of the bag-of-words features: the device vocabulary (jsorb_vocabulary_*), the transform of a frame's descriptors
-// (jsorb_bow_transform*) and the keyframe-to-frame matcher (jsorb_search_by_bow*).  The kernels are in k_bow.hip; the handle's part is `bow`
+// (jsorb_bow_transform*) and the keyframe-to-frame matcher (jsorb_search_by_bow*, over jsorb_handle.h's kf_* frames).  The kernels are in k_bow.hip; the handle's part is `bow`
 // (jsorb_handle.h), reset by every extract and released in jsorb_destroy.
 #include "jsorb_handle.h"
 
@@ -17,13 +17,13 @@ void bow_after_extract(jsorb_extractor *e)
 {
     std::fill(e->bow.have.begin(), e->bow.have.end(), 0);
 }
-void bow_release(jsorb_extractor *e) { free_device(e->bow.ids, e->bow.fsort, e->bow.ksort, e->bow.stats, e->bow.out); }
+void bow_release(jsorb_extractor *e) { free_device(e->bow.ids, e->bow.fsort, e->bow.ksort, e->bow.search.stats, e->bow.search.out); }
 
 } // namespace jsorb_host
 
 namespace {
 
-#define BOW_STATS 8
+const char *const BOW = "search_by_bow";
 
 // the tree rooted at 0: every child id in [1, n) exactly once, every node reached, leaves with a word; its depth and widest node
 bool vocabulary_check(int n, const int32_t *child_start, const int32_t *children, const int32_t *word_id, int *depth, int *max_children, int *n_words)
@@ -205,48 +205,45 @@ int jsorb_search_by_bow_async(jsorb_extractor *e, int image, const jsorb_bow_par
                               const uint8_t *kf_descriptors, int32_t *match_kf, int32_t *n_matches_dev)
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!check_image(e, image)) { e->err = "search_by_bow: no extract result for this image"; return JSORB_ERR_STATE; }
-    if (!params) { e->err = "search_by_bow: NULL params"; return JSORB_ERR_INVALID; }
-    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) { e->err = "search_by_bow: n_keyframes must be in [0, 256]"; return JSORB_ERR_INVALID; }
-    if (n_keyframes > 0 && (!kf_start || !n_matches_dev)) { e->err = "search_by_bow: NULL kf_start or n_matches"; return JSORB_ERR_INVALID; }
+    if (!check_image(e, image)) return kf_fail(e, BOW, "no extract result for this image", JSORB_ERR_STATE);
+    if (!params) return kf_fail(e, BOW, "NULL params");
+    RCCHK(kf_check_sizes(e, BOW, n_keyframes, 0, 0, nullptr));
+    if (n_keyframes > 0 && (!kf_start || !n_matches_dev)) return kf_fail(e, BOW, "NULL kf_start or n_matches");
     const int N = jsorb_n_keypoints(e, image);
-    if (N >= (1 << 18)) { e->err = "search_by_bow: more than 262143 keypoints"; return JSORB_ERR_UNSUPPORTED; }
-    BowMatchArgs a{};
-    int base = 0, total = 0, rc = 0;
-    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, a.kf_start, &base, &total, &rc)) { e->err = std::string("search_by_bow: ") + bad; return rc; }
-    if (total > 0 && (!kf_node || !kf_valid || !kf_angle || !kf_descriptors)) { e->err = "search_by_bow: NULL keyframe array"; return JSORB_ERR_INVALID; }
-    if ((uintptr_t)kf_descriptors % 16) { e->err = "search_by_bow: kf_descriptors must be 16-byte aligned"; return JSORB_ERR_INVALID; }
-    if (n_keyframes > 0 && N > 0 && !match_kf) { e->err = "search_by_bow: NULL match_kf"; return JSORB_ERR_INVALID; }
+    if (N >= (1 << 18)) return kf_fail(e, BOW, "more than 262143 keypoints", JSORB_ERR_UNSUPPORTED);
+    int rel[JSORB_BOW_MAX_KEYFRAMES + 1] = {0}, base = 0, total = 0;
+    RCCHK(kf_rebase(e, BOW, kf_start, n_keyframes, rel, &base, &total, true));
+    if (total > 0 && (!kf_node || !kf_valid || !kf_angle || !kf_descriptors)) return kf_fail(e, BOW, "NULL keyframe array");
+    if ((uintptr_t)kf_descriptors % 16) return kf_fail(e, BOW, "kf_descriptors must be 16-byte aligned");
+    if (n_keyframes > 0 && N > 0 && !match_kf) return kf_fail(e, BOW, "NULL match_kf");
     if (!f_node && N > 0 && n_keyframes > 0) {
-        if (!bow_have(e, image)) { e->err = "search_by_bow: f_node is NULL and this image has no jsorb_bow_transform_async since the last extract"; return JSORB_ERR_STATE; }
+        if (!bow_have(e, image)) return kf_fail(e, BOW, "f_node is NULL and this image has no jsorb_bow_transform_async since the last extract", JSORB_ERR_STATE);
         f_node = bow_nodes(e, image);
     }
     HIPCHK(e, hipSetDevice(e->device));
-    RCCHK(reserve_device(e, e->bow.stats, BOW_STATS * sizeof(int)));
     RCCHK(reserve_device(e, e->bow.fsort, (size_t)std::max(e->g.T, 1) * sizeof(unsigned long long)));
     RCCHK(reserve_device(e, e->bow.ksort, (size_t)std::max(total, 1) * sizeof(unsigned long long), &e->bow.kf_cap, std::max(total, 1)));
     hipStream_t st = e->stream;
     RCCHK(wait_lanes(e, st, e));       // the frame may come from the lanes of a batch
     mark_main_stream(e);
+    KfCall &c = e->bow.search;
     bool run = false;
-    RCCHK(clear_kf_outputs(e, st, e->bow.stats, BOW_STATS, n_keyframes, N, total, n_matches_dev, match_kf, &run));
-    e->bow.done = true;
+    RCCHK(kf_clear(e, c, st, n_keyframes, N, total, n_matches_dev, match_kf, &run));
     if (!run) return JSORB_OK;
-    a.soa = jsorb_keypoints_device(e, image);
+    BowMatchArgs a = bow_group_args(rel, f_node, N, n_keyframes, kf_node + base, e->bow.fsort, e->bow.ksort);
     a.desc = jsorb_descriptors_device(e, image);
-    a.f_node = f_node;
-    a.N = N;
-    a.n_kf = n_keyframes;
-    a.kf_node = kf_node + base; a.kf_valid = kf_valid + base; a.kf_angle = kf_angle + base; a.kf_desc = kf_descriptors + (size_t)32 * base;
+    a.kf_valid = kf_valid + base; a.kf_desc = kf_descriptors + (size_t)32 * base;
     a.p = *params;
-    a.f_sorted = e->bow.fsort; a.kf_sorted = e->bow.ksort;
-    a.match_kf = match_kf; a.n_matches = n_matches_dev;
-    a.stats = e->bow.stats;
+    a.match_kf = match_kf;
+    a.stats = c.stats;
     TIMED(e, JSORB_K_BOW_GROUP, launch_bow_group(a, st));
     HIPCHK(e, hipGetLastError());
     TIMED(e, JSORB_K_BOW_MATCH, launch_bow_match(a, st));
     HIPCHK(e, hipGetLastError());
-    TIMED(e, JSORB_K_BOW_RESOLVE, launch_bow_resolve(a, st));
+    // the rotation check: the keyframe's angle against the frame keypoint's (the angle plane of the keypoint SoA), the kept bins behind the three match words
+    const float *f_angle = reinterpret_cast<const float *>(jsorb_keypoints_device(e, image) + 3 * (size_t)N);
+    TIMED(e, JSORB_K_BOW_RESOLVE, launch_bow_resolve(row_resolve_args(rel, n_keyframes, N, f_angle, kf_angle + base, params->check_orientation, match_kf,
+                                                                      n_matches_dev, c.stats + 3), st));
     HIPCHK(e, hipGetLastError());
     return JSORB_OK;
 }
@@ -256,25 +253,20 @@ int jsorb_search_by_bow(jsorb_extractor *e, int image, const jsorb_bow_params *p
                         const uint8_t *kf_descriptors, int32_t *match_kf_host, int *n_matches_host)
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!check_image(e, image)) { e->err = "search_by_bow: no extract result for this image"; return JSORB_ERR_STATE; }
-    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) { e->err = "search_by_bow: n_keyframes must be in [0, 256]"; return JSORB_ERR_INVALID; }
+    if (!check_image(e, image)) return kf_fail(e, BOW, "no extract result for this image", JSORB_ERR_STATE);      // (before n_keyframes: kept as it is)
+    RCCHK(kf_check_sizes(e, BOW, n_keyframes, 0, 0, nullptr));
     const int N = jsorb_n_keypoints(e, image);
-    if (n_keyframes > 0 && (!n_matches_host || (N > 0 && !match_kf_host))) { e->err = "search_by_bow: NULL host output"; return JSORB_ERR_INVALID; }
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t rows = (size_t)n_keyframes * std::max(N, 0);
-    if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) { e->err = "search_by_bow: n_keyframes x N too large"; return JSORB_ERR_UNSUPPORTED; }
-    const int want = (int)std::max(rows, (size_t)1);
-    RCCHK(reserve_device(e, e->bow.out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &e->bow.out_cap, want));
-    int32_t *cnt = e->bow.out, *mk = cnt + JSORB_BOW_MAX_KEYFRAMES;
-    RCCHK(jsorb_search_by_bow_async(e, image, params, f_node, n_keyframes, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors, mk, cnt));
-    return copy_kf_results(e, n_keyframes, rows, cnt, mk, match_kf_host, n_matches_host);
+    return kf_sync(e, BOW, e->bow.search, n_keyframes, N, "N", !n_matches_host || (N > 0 && !match_kf_host), 1, match_kf_host, nullptr, n_matches_host,
+                   [&](int32_t *cnt, int32_t *mk, int32_t *) {
+                       return jsorb_search_by_bow_async(e, image, params, f_node, n_keyframes, kf_start, kf_node, kf_valid, kf_angle, kf_descriptors, mk, cnt);
+                   });
 }
 
 int jsorb_search_by_bow_stats(jsorb_extractor *e, int *n_node_pairs, int *n_distances, int *largest_node, int kept_bins[3])
 {
     if (!e) return JSORB_ERR_INVALID;
-    int32_t s[BOW_STATS] = {0};
-    RCCHK(read_stats(e, e->bow.done, "search_by_bow_stats before jsorb_search_by_bow", e->bow.stats, s, BOW_STATS));
+    int32_t s[KF_STATS] = {0};
+    RCCHK(kf_stats(e, e->bow.search, "search_by_bow_stats before jsorb_search_by_bow", s));
     if (n_node_pairs) *n_node_pairs = s[0];
     if (n_distances) *n_distances = s[1];
     if (largest_node) *largest_node = s[2];

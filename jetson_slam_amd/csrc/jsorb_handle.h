@@ -52,6 +52,15 @@ struct jsorb_spec_state {
 
 // The handle: the core (geometry, buffers of the extract pipeline, main stream) directly, then one plain struct per feature.  Each feature's
 // fields are allocated, reset after an extract and released in the translation unit that holds its entry points.
+// The state of one kind of matcher call over keyframe sets, on an extractor (jsorb_search_by_bow*) or a keyframe matcher: allocated on first use
+struct KfCall {
+    int *stats = nullptr;                  // KF_STATS statistics words of the last call (device)
+    int32_t *out = nullptr;                // the synchronous form's outputs (device), grown with the rows
+    int out_cap = 0;
+    bool done = false;                     // a call has run: the statistics can be read
+};
+#define KF_STATS 8
+
 struct jsorb_extractor {
     // ---- core buffers and geometry (jsorb_api.hip: jsorb_create_masked / jsorb_destroy) ----
     jsorb_params p{};
@@ -267,10 +276,8 @@ struct jsorb_extractor {
         std::vector<char> have;            // per image: transformed since the last extract
         unsigned long long *fsort = nullptr, *ksort = nullptr;      // sorted keys of the frame (T) and of the keyframes (kf_cap)
         int kf_cap = 0;
-        int *stats = nullptr;              // 8 statistics words of the last search
-        int32_t *out = nullptr;            // synchronous call: counts (256), then match_kf (out_cap)
-        int out_cap = 0;
-        bool done = false, transformed = false;
+        KfCall search;                     // jsorb_search_by_bow*: 8 statistics words; synchronous call: counts (256), then match_kf (out_cap)
+        bool transformed = false;
     } bow;
 
     // ---- per-kernel timing (jsorb_api.hip) ----
@@ -298,29 +305,14 @@ struct jsorb_keyframe_matcher {
     hipEvent_t ev_switch = nullptr;                             // orders a new stream behind the old one (jsorb_keyframe_matcher_set_stream)
     unsigned long long *sort1 = nullptr, *sort2 = nullptr;      // sorted keys of KF1 (cap1) and of the KF2s (cap2): grown only
     int cap1 = 0, cap2 = 0;
-    int *stats = nullptr;                                       // TRI_STATS statistics words of the last search
-    int32_t *out = nullptr;                                     // synchronous call: counts (256), then match12 (out_cap)
-    int out_cap = 0;
-    bool done = false;
-    // jsorb_fuse*: its own statistics and "done" mark, the keyframes' grid CSRs (grown only) and the synchronous form's outputs
-    int *fuse_stats = nullptr;                                  // FUSE_STATS words of the last fuse
-    int32_t *grid_start = nullptr, *grid_items = nullptr;       // n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
+    // one state per kind of call, each with statistics and a "done" mark of its own.  The synchronous forms' buffers: counts (256), then match12
+    // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, N_CALLS };
+    KfCall call[N_CALLS];
+    int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
-    int32_t *fuse_out = nullptr;                                // counts (256), then best_idx and best_dist (fuse_out_cap each)
-    int fuse_out_cap = 0;
-    bool fuse_done = false;
-    // jsorb_search_by_bow_kf* (jsorb_loop.hip): its own statistics and "done" mark, vbMatched2 of the candidates (grown only) and the synchronous form's outputs
-    int *loop_stats = nullptr;                                  // LOOP_STATS words of the last search
-    uint8_t *matched2 = nullptr;                                // one byte per candidate keypoint (matched2_cap)
+    uint8_t *matched2 = nullptr;                                // BoW: vbMatched2, one byte per candidate keypoint (matched2_cap)
     int matched2_cap = 0;
-    int32_t *loop_out = nullptr;                                // counts (256), then match12 (loop_out_cap)
-    int loop_out_cap = 0;
-    bool loop_done = false;
-    // jsorb_search_by_sim3* (jsorb_loop.hip): the grids are grid_start / grid_items above
-    int *sim3_stats = nullptr;                                  // SIM3_STATS words of the last search
-    int32_t *sim3_out = nullptr;                                // the count, then match1, match2 and match12 (sim3_out_cap entries in all)
-    int sim3_out_cap = 0;
-    bool sim3_done = false;
     std::string err;
 };
 
@@ -483,6 +475,108 @@ template <class H> int copy_kf_results(H *h, int n_kf, size_t rows, const int32_
     for (int i = 0; i < n_kf; i++) n_matches_host[i] = c[i];
     return JSORB_OK;
 }
+// ---- the frames of the keyframe-set entry points, in the manner of jsorb_search.hip's search_check / search_begin /
+// search_sync.  The owner H is a handle or a keyframe matcher; `name` is the feature's name in front of every error text.  An entry point's own
+// checks (parameters, NULL arrays, alignment) stay written out between these, where they fire. ----
+template <class H> int kf_fail(H *h, const char *name, const std::string &what, int rc = JSORB_ERR_INVALID)
+{
+    h->err = std::string(name) + ": " + what;
+    return rc;
+}
+
+// The sizes, the first shared check of both forms: n_keyframes, then the single side's n against [0, n_limit) (n_limit 0: no upper bound) with
+// the entry point's text for it (NULL: it has no such check - the frame of jsorb_search_by_bow).
+template <class H> int kf_check_sizes(H *h, const char *name, int n_keyframes, int n, int n_limit, const char *n_text)
+{
+    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return kf_fail(h, name, "n_keyframes must be in [0, 256]");
+    if (n_text && (n < 0 || (n_limit && n >= n_limit))) return kf_fail(h, name, n_text);
+    return JSORB_OK;
+}
+
+// rebase_kf_start as a check.  keep_rc: the error's own code (a keyframe of more than 262143 keypoints is JSORB_ERR_UNSUPPORTED for
+// jsorb_search_by_bow_async); the keyframe matcher's entry points answer JSORB_ERR_INVALID for both - kept as it is.
+template <class H> int kf_rebase(H *h, const char *name, const int32_t *kf_start, int n_keyframes, int *rel, int *base, int *total, bool keep_rc = false)
+{
+    int rc = 0;
+    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, rel, base, total, &rc)) return kf_fail(h, name, bad, keep_rc ? rc : JSORB_ERR_INVALID);
+    return JSORB_OK;
+}
+
+// The start of a call's device work: its statistics words on first use, then clear_kf_outputs and the "done" mark
+template <class H> int kf_clear(H *h, KfCall &c, hipStream_t st, int n_kf, int n, int total, int32_t *n_matches, int32_t *match, bool *run)
+{
+    RCCHK(reserve_device(h, c.stats, KF_STATS * sizeof(int)));
+    RCCHK(clear_kf_outputs(h, st, c.stats, KF_STATS, n_kf, n, total, n_matches, match, run));
+    c.done = true;
+    return JSORB_OK;
+}
+
+// The synchronous form behind kf_check_sizes: the call's buffer as counts (256), then `arrays` (1 or 2) arrays of n_keyframes x n entries;
+// run(cnt, a0, a1) is the asynchronous form.  The counts and a0 come back through copy_kf_results, a1 (when there is one) into host1.
+template <class H, class Run>
+int kf_sync(H *h, const char *name, KfCall &c, int n_keyframes, int n, const char *n_name, bool null_host, int arrays, int32_t *host0, int32_t *host1,
+            int *n_matches_host, Run run)
+{
+    if (n_keyframes > 0 && null_host) return kf_fail(h, name, "NULL host output");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t rows = (size_t)n_keyframes * std::max(n, 0);
+    if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return kf_fail(h, name, std::string("n_keyframes x ") + n_name + " too large", JSORB_ERR_UNSUPPORTED);
+    const int want = (int)std::max(rows, (size_t)1);
+    RCCHK(reserve_device(h, c.out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + arrays * (size_t)want) * sizeof(int32_t), &c.out_cap, want));
+    int32_t *cnt = c.out, *a0 = cnt + JSORB_BOW_MAX_KEYFRAMES, *a1 = a0 + want;
+    RCCHK(run(cnt, a0, a1));
+    if (arrays > 1 && rows > 0) HIPCHK(h, hipMemcpyAsync(host1, a1, rows * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    return copy_kf_results(h, n_keyframes, rows, cnt, a0, host0, n_matches_host);
+}
+
+// The statistics words of a call's last run into s[KF_STATS] (read_stats; `before`: the error when none has run)
+template <class H> int kf_stats(H *h, const KfCall &c, const char *before, int32_t *s) { return read_stats(h, c.done, before, c.stats, s, KF_STATS); }
+
+// k_bow_group's launch arguments: the single side (f_node, N) and the concatenated keyframes (kf_node at the rebased offsets `rel`)
+inline BowMatchArgs bow_group_args(const int *rel, const int32_t *f_node, int N, int n_kf, const int32_t *kf_node, unsigned long long *f_sorted,
+                                   unsigned long long *kf_sorted)
+{
+    BowMatchArgs b{};
+    memcpy(b.kf_start, rel, sizeof(b.kf_start));
+    b.f_node = f_node; b.N = N; b.n_kf = n_kf; b.kf_node = kf_node;
+    b.f_sorted = f_sorted; b.kf_sorted = kf_sorted;
+    return b;
+}
+
+// k_bow_resolve's / k_tri_resolve's launch arguments: the rows `match` (n_kf x n) over the rebased offsets `rel`, the three kept-bin words
+inline RowResolveArgs row_resolve_args(const int *rel, int n_kf, int n, const float *row_angle, const float *kf_angle, int check_orientation, int32_t *match,
+                                       int32_t *n_matches, int *kept)
+{
+    RowResolveArgs r{};
+    memcpy(r.kf_start, rel, sizeof(r.kf_start));
+    r.n_kf = n_kf; r.n = n; r.row_angle = row_angle; r.kf_angle = kf_angle; r.check_orientation = check_orientation;
+    r.match = match; r.n_matches = n_matches; r.kept = kept;
+    return r;
+}
+
+// the keyframe matcher's grown-only scratch: k_bow_group's keys of both sides; the grid CSRs of n_grids keyframes with `total` keypoints in all
+inline int reserve_sort_keys(jsorb_keyframe_matcher *m, int n1, int total)
+{
+    RCCHK(reserve_device(m, m->sort1, (size_t)std::max(n1, 1) * sizeof(unsigned long long), &m->cap1, std::max(n1, 1)));
+    return reserve_device(m, m->sort2, (size_t)std::max(total, 1) * sizeof(unsigned long long), &m->cap2, std::max(total, 1));
+}
+inline int reserve_grids(jsorb_keyframe_matcher *m, int n_grids, int n_cells, int total)
+{
+    const int want = n_grids * (n_cells + 1);
+    RCCHK(reserve_device(m, m->grid_start, (size_t)want * sizeof(int32_t), &m->grid_cap, want));
+    return reserve_device(m, m->grid_items, (size_t)std::max(total, 1) * sizeof(int32_t), &m->items_cap, std::max(total, 1));
+}
+
+// k_fuse_grids' launch arguments from any parameter struct with min_x ... rows; the caller fills kf_start
+template <class P> FuseGridArgs fuse_grid_args(const P &p, const float *x, const float *y, int32_t *cell_start, int32_t *cell_items)
+{
+    FuseGridArgs g{};
+    g.x = x; g.y = y;
+    g.min_x = p.min_x; g.min_y = p.min_y; g.inv_w = p.inv_w; g.inv_h = p.inv_h; g.cols = p.cols; g.rows = p.rows;
+    g.cell_start = cell_start; g.cell_items = cell_items;
+    return g;
+}
+
 template <class T> int reserve_pinned(jsorb_extractor *e, T *&p, size_t bytes) { if (!p) HIPCHK(e, hipHostMalloc(&p, bytes)); return JSORB_OK; }
 // release functions: free (and forget) what a feature allocated
 template <class... T> void free_device(T *&...p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }

@@ -200,8 +200,7 @@ struct BowVocab {
 };
 #define JSORB_BOW_MAX_KEYFRAMES 256
 struct BowMatchArgs {
-    // the frame: keypoint SoA (6N), descriptors, node per keypoint (-1: in none)
-    const int32_t *soa;
+    // the frame: descriptors, node per keypoint (-1: in none)
     const uint8_t *desc;
     const int32_t *f_node;
     int N;
@@ -209,13 +208,12 @@ struct BowMatchArgs {
     int n_kf;
     const int32_t *kf_node;
     const uint8_t *kf_valid;
-    const float *kf_angle;
     const uint8_t *kf_desc;
     jsorb_bow_params p;
     // workspace and outputs
     unsigned long long *f_sorted, *kf_sorted;    // keys node << 18 | index, ascending; keypoints in no node last
-    int32_t *match_kf, *n_matches;               // n_kf x N (cleared to -1), n_kf (cleared to 0)
-    int *stats;                                  // node pairs, distances, largest frame node of a pair, ind1 + 1, ind2 + 1, ind3 + 1 of keyframe 0 (cleared to 0)
+    int32_t *match_kf;                           // n_kf x N (cleared to -1)
+    int *stats;                                  // node pairs, distances, largest frame node of a pair; then k_bow_resolve's kept bins (cleared to 0)
     int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
 };
 int bow_node_regs();                            // the compile-time caps of k_bow.hip (jsorb_bow_build_caps)
@@ -224,28 +222,39 @@ void launch_bow_transform(const BowVocab &v, const uint8_t *desc, size_t desc_st
                           int32_t *node, size_t out_stride, int *n_shallow, int n_images, hipStream_t s);      // counts NULL: n descriptors; else a grid for n, counts[img * counts_stride] of them per image
 void launch_bow_group(const BowMatchArgs &a, hipStream_t s);
 void launch_bow_match(const BowMatchArgs &a, hipStream_t s);
-void launch_bow_resolve(const BowMatchArgs &a, hipStream_t s);
+// k_bow_resolve (k_bow.hip) and k_tri_resolve (k_triangulate.hip): the rotation check over rows of matches (k_search_common.h: row_resolve).  Row kf is
+// match[kf * n .. + n); entry k holds j relative to kf_start[kf], or -1
+struct RowResolveArgs {
+    int n_kf, n;                                 // rows, entries of a row
+    const float *row_angle;                      // the angle of row position k (n of them)
+    const float *kf_angle;                       // the angle of entry kf_start[kf] + j of the concatenated side
+    int check_orientation;
+    int32_t *match, *n_matches;                  // n_kf x n (culled in place), n_kf (every non-empty keyframe's count written)
+    int *kept;                                   // three statistics words: ind1 + 1, ind2 + 1, ind3 + 1 of keyframe 0 (cleared to 0)
+    int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
+};
+void launch_bow_resolve(const RowResolveArgs &a, hipStream_t s);      // rot_bin(kf_angle, row_angle): SearchByBoW(KeyFrame*, Frame&)
 // k_tri_match / k_tri_resolve (k_triangulate.hip): ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) for several KF2;
 // the grouping is launch_bow_group over a BowMatchArgs whose frame side is KF1
 struct TriArgs {
     // KF1: n1 keypoints
     int n1;
     const uint8_t *free1, *stereo1;
-    const float *x1, *y1, *angle1;
+    const float *x1, *y1;
     const uint8_t *desc1;
     // the KF2s, concatenated; keyframe i is kf_start[i] .. kf_start[i + 1] (relative to the pointers below)
     int n_kf;
     const uint8_t *free2, *stereo2;
-    const float *x2, *y2, *angle2;
+    const float *x2, *y2;
     const int32_t *octave2;
     const uint8_t *desc2;
-    int th_low, check_orientation, only_stereo, n_levels;
+    int th_low, only_stereo, n_levels;
     float gate[JSORB_MAX_LEVELS];                // 100.0f * mvScaleFactors[l]: the epipole gate's right side
     double line[JSORB_MAX_LEVELS];               // 3.84 * (double)mvLevelSigma2[l]: the line test's right side
     // workspace and outputs
     const unsigned long long *sorted1, *sorted2; // k_bow_group's keys
-    int32_t *match12, *n_matches;                // n_kf x n1 (cleared to -1), n_kf (cleared to 0)
-    int *stats;                                  // node pairs, distances, line tests, largest KF2 node of a pair, ind1 + 1, ind2 + 1, ind3 + 1 of keyframe 0 (cleared to 0)
+    int32_t *match12;                            // n_kf x n1 (cleared to -1)
+    int *stats;                                  // node pairs, distances, line tests, largest KF2 node of a pair; then k_tri_resolve's kept bins (cleared to 0)
     int kf_start[JSORB_BOW_MAX_KEYFRAMES + 1];
 };
 #define TR_KF_CHUNK 32                          // keyframes whose geometry one k_tri_match launch carries in its arguments
@@ -254,7 +263,7 @@ struct TriGeom {
     float f[TR_KF_CHUNK][11];                    // F12 row-major, ex, ey
 };
 void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s);
-void launch_tri_resolve(const TriArgs &a, hipStream_t s);
+void launch_tri_resolve(const RowResolveArgs &a, hipStream_t s);      // rot_bin(row_angle, kf_angle): SearchForTriangulation, SearchByBoW(KF, KF)
 // k_fuse_grids / k_fuse_match (k_fuse.hip): ORBmatcher::Fuse(pKF, vpMapPoints, th) and its loop-closing overload for several keyframes in one call
 #define FUSE_MAX_CELLS 4096                      // cols * rows k_fuse_grids holds in LDS (counts and cursors of every cell, 1024 scan words)
 struct FuseGridArgs {
@@ -289,7 +298,7 @@ struct FusePose {
 void launch_fuse_grids(const FuseGridArgs &g, int n_kf, hipStream_t s);
 void launch_fuse_match(const FuseArgs &a, const FusePose &g, hipStream_t s);
 // k_loop_bow_match (k_loop.hip): ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) for several candidates KF2 of LoopClosing::ComputeSim3; the grouping
-// is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over a TriArgs with the same rows
+// is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over the same rows
 struct LoopBowArgs {
     // KF1: n1 keypoints
     int n1;

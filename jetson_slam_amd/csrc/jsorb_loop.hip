@@ -1,32 +1,28 @@
 // jsorb_loop.hip - host side of the keyframe matcher's loop-closing calls (jsorb_search_by_bow_kf*, jsorb_search_by_sim3*): the matchers of
 // LoopClosing::ComputeSim3.  They run on the jsorb_keyframe_matcher of jsorb_keyframes.hip (LoopClosing is a thread of its own and creates its own),
-// with statistics and "done" marks of their own.  The kernels are in k_loop.hip; the grouping is k_bow.hip's k_bow_group with KF1 as the frame side,
+// each with a call state of its own (KfCall).  The kernels are in k_loop.hip; the grouping is k_bow.hip's k_bow_group with KF1 as the frame side,
 // the rotation check k_triangulate.hip's k_tri_resolve, the grids k_fuse.hip's k_fuse_grids.
 #include "jsorb_handle.h"
 
 namespace {
 
-#define LOOP_STATS 8                            // k_tri_resolve's layout: node pairs, distances, ., largest node, ind1 + 1, ind2 + 1, ind3 + 1
-#define SIM3_STATS 8                            // windows, walked, distances, largest window, agreements
-
-int loop_fail(jsorb_keyframe_matcher *m, const std::string &msg, int rc = JSORB_ERR_INVALID)
-{
-    m->err = msg;
-    return rc;
-}
+// The calls' statistics words (KF_STATS each).  search_by_bow_kf: node pairs, distances, ., largest node, ind1 + 1, ind2 + 1, ind3 + 1 (the triangulation
+// matcher's layout, k_tri_resolve's kept bins).  search_by_sim3: windows, walked, distances, largest window, agreements.
+// The feature names and texts the shared frames (jsorb_handle.h: kf_*) put into the refusals:
+const char *const BOW_KF = "search_by_bow_kf", *const BOW_KF_N1 = "n1 must be in [0, 262143]", *const SIM3 = "search_by_sim3";
 
 int sim3_check(jsorb_keyframe_matcher *m, const jsorb_sim3_params *p, const jsorb_sim3_side *s1, const jsorb_sim3_side *s2)
 {
-    if (!p || !s1 || !s2) return loop_fail(m, "search_by_sim3: NULL params or side");
-    if (p->n_levels < 1 || p->n_levels > JSORB_MAX_LEVELS) return loop_fail(m, "search_by_sim3: n_levels out of range");
-    if (p->th_high < 0 || p->th_high > 255) return loop_fail(m, "search_by_sim3: th_high must be in [0, 255]");
-    if (p->cols < 1 || p->rows < 1 || (long long)p->cols * p->rows > FUSE_MAX_CELLS) return loop_fail(m, "search_by_sim3: grid size out of range (cols*rows <= 4096)");
-    if (s1->n < 0 || s2->n < 0 || (long long)s1->n + s2->n >= (1 << 18)) return loop_fail(m, "search_by_sim3: n1 + n2 must be in [0, 262143]");
+    if (!p || !s1 || !s2) return kf_fail(m, SIM3, "NULL params or side");
+    if (p->n_levels < 1 || p->n_levels > JSORB_MAX_LEVELS) return kf_fail(m, SIM3, "n_levels out of range");
+    if (p->th_high < 0 || p->th_high > 255) return kf_fail(m, SIM3, "th_high must be in [0, 255]");
+    if (p->cols < 1 || p->rows < 1 || (long long)p->cols * p->rows > FUSE_MAX_CELLS) return kf_fail(m, SIM3, "grid size out of range (cols*rows <= 4096)");
+    if (s1->n < 0 || s2->n < 0 || (long long)s1->n + s2->n >= (1 << 18)) return kf_fail(m, SIM3, "n1 + n2 must be in [0, 262143]");
     for (const jsorb_sim3_side *s : {s1, s2}) {
         if (s->n > 0 && (!s->x || !s->y || !s->octave || !s->kp_desc || !s->Px || !s->Py || !s->Pz || !s->max_distance || !s->min_dist_inv || !s->max_dist_inv ||
                          !s->mp_desc || !s->search))
-            return loop_fail(m, "search_by_sim3: NULL side array");
-        if (s->n > 0 && ((uintptr_t)s->kp_desc % 16 || (uintptr_t)s->mp_desc % 16)) return loop_fail(m, "search_by_sim3: descriptors must be 16-byte aligned");
+            return kf_fail(m, SIM3, "NULL side array");
+        if (s->n > 0 && ((uintptr_t)s->kp_desc % 16 || (uintptr_t)s->mp_desc % 16)) return kf_fail(m, SIM3, "descriptors must be 16-byte aligned");
     }
     return JSORB_OK;
 }
@@ -46,48 +42,37 @@ int jsorb_search_by_bow_kf_async(jsorb_keyframe_matcher *m, const jsorb_bow_para
                                  const uint8_t *valid2, const float *angle2, const uint8_t *desc2, int32_t *match12, int32_t *n_matches_dev)
 {
     if (!m) return JSORB_ERR_INVALID;
-    if (!params) return loop_fail(m, "search_by_bow_kf: NULL params");
-    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return loop_fail(m, "search_by_bow_kf: n_keyframes must be in [0, 256]");
-    if (n1 < 0 || n1 >= (1 << 18)) return loop_fail(m, "search_by_bow_kf: n1 must be in [0, 262143]");
-    if (n_keyframes > 0 && (!kf_start || !n_matches_dev)) return loop_fail(m, "search_by_bow_kf: NULL kf_start or n_matches");
+    if (!params) return kf_fail(m, BOW_KF, "NULL params");
+    RCCHK(kf_check_sizes(m, BOW_KF, n_keyframes, n1, 1 << 18, BOW_KF_N1));
+    if (n_keyframes > 0 && (!kf_start || !n_matches_dev)) return kf_fail(m, BOW_KF, "NULL kf_start or n_matches");
     LoopBowArgs a{};
-    int base = 0, total = 0, rc = 0;
-    if (const char *bad = rebase_kf_start(kf_start, n_keyframes, a.kf_start, &base, &total, &rc)) return loop_fail(m, std::string("search_by_bow_kf: ") + bad);
-    if (n1 > 0 && (!node1 || !valid1 || !angle1 || !desc1)) return loop_fail(m, "search_by_bow_kf: NULL KF1 array");
-    if (total > 0 && (!node2 || !valid2 || !angle2 || !desc2)) return loop_fail(m, "search_by_bow_kf: NULL candidate array");
-    if ((uintptr_t)desc1 % 16 || (uintptr_t)desc2 % 16) return loop_fail(m, "search_by_bow_kf: descriptors must be 16-byte aligned");
-    if (n_keyframes > 0 && n1 > 0 && !match12) return loop_fail(m, "search_by_bow_kf: NULL match12");
+    int base = 0, total = 0;
+    RCCHK(kf_rebase(m, BOW_KF, kf_start, n_keyframes, a.kf_start, &base, &total));
+    if (n1 > 0 && (!node1 || !valid1 || !angle1 || !desc1)) return kf_fail(m, BOW_KF, "NULL KF1 array");
+    if (total > 0 && (!node2 || !valid2 || !angle2 || !desc2)) return kf_fail(m, BOW_KF, "NULL candidate array");
+    if ((uintptr_t)desc1 % 16 || (uintptr_t)desc2 % 16) return kf_fail(m, BOW_KF, "descriptors must be 16-byte aligned");
+    if (n_keyframes > 0 && n1 > 0 && !match12) return kf_fail(m, BOW_KF, "NULL match12");
     HIPCHK(m, hipSetDevice(m->device));
-    RCCHK(reserve_device(m, m->loop_stats, LOOP_STATS * sizeof(int)));
-    RCCHK(reserve_device(m, m->sort1, (size_t)std::max(n1, 1) * sizeof(unsigned long long), &m->cap1, std::max(n1, 1)));
-    RCCHK(reserve_device(m, m->sort2, (size_t)std::max(total, 1) * sizeof(unsigned long long), &m->cap2, std::max(total, 1)));
+    RCCHK(reserve_sort_keys(m, n1, total));
     RCCHK(reserve_device(m, m->matched2, (size_t)std::max(total, 1), &m->matched2_cap, std::max(total, 1)));
+    KfCall &c = m->call[jsorb_keyframe_matcher::BOW_KF];
     hipStream_t st = m->stream;
     bool run = false;
-    RCCHK(clear_kf_outputs(m, st, m->loop_stats, LOOP_STATS, n_keyframes, n1, total, n_matches_dev, match12, &run));
-    m->loop_done = true;
+    RCCHK(kf_clear(m, c, st, n_keyframes, n1, total, n_matches_dev, match12, &run));
     if (!run) return JSORB_OK;
     HIPCHK(m, hipMemsetAsync(m->matched2, 0, (size_t)total, st));
-    // the grouping: KF1 as the frame side of k_bow_group, the candidates as its keyframes
-    BowMatchArgs b{};
-    memcpy(b.kf_start, a.kf_start, sizeof(b.kf_start));
-    b.f_node = node1; b.N = n1; b.n_kf = n_keyframes; b.kf_node = node2 + base;
-    b.f_sorted = m->sort1; b.kf_sorted = m->sort2;
     a.n1 = n1; a.valid1 = valid1; a.desc1 = desc1;
     a.n_kf = n_keyframes; a.valid2 = valid2 + base; a.desc2 = desc2 + (size_t)32 * base;
     a.p = *params;
     a.sorted1 = m->sort1; a.sorted2 = m->sort2; a.matched2 = m->matched2;
-    a.match12 = match12; a.stats = m->loop_stats;
-    // the rotation check: k_tri_resolve over the same rows (angle1[idx1] - angle2[match12[idx1]]), its kept bins in the same statistics words
-    TriArgs r{};
-    memcpy(r.kf_start, a.kf_start, sizeof(r.kf_start));
-    r.n1 = n1; r.angle1 = angle1; r.n_kf = n_keyframes; r.angle2 = angle2 + base; r.check_orientation = params->check_orientation;
-    r.match12 = match12; r.n_matches = n_matches_dev; r.stats = m->loop_stats;
-    launch_bow_group(b, st);
+    a.match12 = match12; a.stats = c.stats;
+    // the grouping: KF1 as the frame side of k_bow_group, the candidates as its keyframes
+    launch_bow_group(bow_group_args(a.kf_start, node1, n1, n_keyframes, node2 + base, m->sort1, m->sort2), st);
     HIPCHK(m, hipGetLastError());
     launch_loop_bow_match(a, st);
     HIPCHK(m, hipGetLastError());
-    launch_tri_resolve(r, st);
+    // the rotation check: k_tri_resolve over the same rows (angle1[idx1] - angle2[match12[idx1]]), its kept bins in the same statistics words
+    launch_tri_resolve(row_resolve_args(a.kf_start, n_keyframes, n1, angle1, angle2 + base, params->check_orientation, match12, n_matches_dev, c.stats + 4), st);
     HIPCHK(m, hipGetLastError());
     return JSORB_OK;
 }
@@ -97,24 +82,18 @@ int jsorb_search_by_bow_kf(jsorb_keyframe_matcher *m, const jsorb_bow_params *pa
                            const uint8_t *valid2, const float *angle2, const uint8_t *desc2, int32_t *match12_host, int *n_matches_host)
 {
     if (!m) return JSORB_ERR_INVALID;
-    if (n_keyframes < 0 || n_keyframes > JSORB_BOW_MAX_KEYFRAMES) return loop_fail(m, "search_by_bow_kf: n_keyframes must be in [0, 256]");
-    if (n1 < 0 || n1 >= (1 << 18)) return loop_fail(m, "search_by_bow_kf: n1 must be in [0, 262143]");
-    if (n_keyframes > 0 && (!n_matches_host || (n1 > 0 && !match12_host))) return loop_fail(m, "search_by_bow_kf: NULL host output");
-    HIPCHK(m, hipSetDevice(m->device));
-    const size_t rows = (size_t)n_keyframes * n1;
-    if (rows > (size_t)INT_MAX - JSORB_BOW_MAX_KEYFRAMES) return loop_fail(m, "search_by_bow_kf: n_keyframes x n1 too large", JSORB_ERR_UNSUPPORTED);
-    const int want = (int)std::max(rows, (size_t)1);
-    RCCHK(reserve_device(m, m->loop_out, ((size_t)JSORB_BOW_MAX_KEYFRAMES + want) * sizeof(int32_t), &m->loop_out_cap, want));
-    int32_t *cnt = m->loop_out, *mk = cnt + JSORB_BOW_MAX_KEYFRAMES;
-    RCCHK(jsorb_search_by_bow_kf_async(m, params, n1, node1, valid1, angle1, desc1, n_keyframes, kf_start, node2, valid2, angle2, desc2, mk, cnt));
-    return copy_kf_results(m, n_keyframes, rows, cnt, mk, match12_host, n_matches_host);
+    RCCHK(kf_check_sizes(m, BOW_KF, n_keyframes, n1, 1 << 18, BOW_KF_N1));
+    return kf_sync(m, BOW_KF, m->call[jsorb_keyframe_matcher::BOW_KF], n_keyframes, n1, "n1", !n_matches_host || (n1 > 0 && !match12_host), 1, match12_host, nullptr,
+                   n_matches_host, [&](int32_t *cnt, int32_t *mk, int32_t *) {
+                       return jsorb_search_by_bow_kf_async(m, params, n1, node1, valid1, angle1, desc1, n_keyframes, kf_start, node2, valid2, angle2, desc2, mk, cnt);
+                   });
 }
 
 int jsorb_search_by_bow_kf_stats(jsorb_keyframe_matcher *m, int *n_node_pairs, int *n_distances, int *largest_node, int kept_bins[3])
 {
     if (!m) return JSORB_ERR_INVALID;
-    int32_t s[LOOP_STATS] = {0};
-    RCCHK(read_stats(m, m->loop_done, "search_by_bow_kf_stats before jsorb_search_by_bow_kf", m->loop_stats, s, LOOP_STATS));
+    int32_t s[KF_STATS] = {0};
+    RCCHK(kf_stats(m, m->call[jsorb_keyframe_matcher::BOW_KF], "search_by_bow_kf_stats before jsorb_search_by_bow_kf", s));
     if (n_node_pairs) *n_node_pairs = s[0];
     if (n_distances) *n_distances = s[1];
     if (largest_node) *largest_node = s[3];
@@ -128,16 +107,14 @@ int jsorb_search_by_sim3_async(jsorb_keyframe_matcher *m, const jsorb_sim3_param
     if (!m) return JSORB_ERR_INVALID;
     RCCHK(sim3_check(m, params, side1, side2));
     const int n1 = side1->n, n2 = side2->n;
-    if (!n_found_dev || (n1 > 0 && (!match1 || !match12)) || (n2 > 0 && !match2)) return loop_fail(m, "search_by_sim3: NULL output");
+    if (!n_found_dev || (n1 > 0 && (!match1 || !match12)) || (n2 > 0 && !match2)) return kf_fail(m, SIM3, "NULL output");
     HIPCHK(m, hipSetDevice(m->device));
-    const int n_cells = params->cols * params->rows, want_grid = 2 * (n_cells + 1), total = std::max(n1 + n2, 1);
-    RCCHK(reserve_device(m, m->sim3_stats, SIM3_STATS * sizeof(int)));
-    RCCHK(reserve_device(m, m->grid_start, (size_t)want_grid * sizeof(int32_t), &m->grid_cap, want_grid));
-    RCCHK(reserve_device(m, m->grid_items, (size_t)total * sizeof(int32_t), &m->items_cap, total));
+    const int n_cells = params->cols * params->rows;
+    RCCHK(reserve_grids(m, 2, n_cells, n1 + n2));
+    KfCall &c = m->call[jsorb_keyframe_matcher::SIM3];
     hipStream_t st = m->stream;
-    HIPCHK(m, hipMemsetAsync(m->sim3_stats, 0, SIM3_STATS * sizeof(int), st));
-    HIPCHK(m, hipMemsetAsync(n_found_dev, 0, sizeof(int32_t), st));
-    m->sim3_done = true;
+    bool run = false;
+    RCCHK(kf_clear(m, c, st, 1, 0, 0, n_found_dev, nullptr, &run));      // the statistics and the one count; the three arrays are written below
     if (n1 == 0 || n2 == 0) {                       // nothing to search in, or nothing to search: everything is -1 / 0
         if (n1 > 0) {
             HIPCHK(m, hipMemsetAsync(match1, 0xff, (size_t)n1 * sizeof(int32_t), st));
@@ -162,15 +139,12 @@ int jsorb_search_by_sim3_async(jsorb_keyframe_matcher *m, const jsorb_sim3_param
         k.cell_items = m->grid_items + (d ? n1 : 0);
         k.match = out[d];
         // the keyframe's grid: k_fuse_grids over one keyframe, its CSR behind the other one's in the matcher's grid scratch
-        FuseGridArgs g{};
-        g.kf_start[0] = 0; g.kf_start[1] = s.n;
-        g.x = s.x; g.y = s.y;
-        g.min_x = params->min_x; g.min_y = params->min_y; g.inv_w = params->inv_w; g.inv_h = params->inv_h; g.cols = params->cols; g.rows = params->rows;
-        g.cell_start = m->grid_start + (size_t)d * (n_cells + 1); g.cell_items = m->grid_items + (d ? n1 : 0);
+        FuseGridArgs g = fuse_grid_args(*params, s.x, s.y, m->grid_start + (size_t)d * (n_cells + 1), m->grid_items + (d ? n1 : 0));      // (the two addresses again: k's fields are pointers to const, the grid kernel writes)
+        g.kf_start[1] = s.n;
         launch_fuse_grids(g, 1, st);
         HIPCHK(m, hipGetLastError());
     }
-    a.match12 = match12; a.n_found = n_found_dev; a.stats = m->sim3_stats;
+    a.match12 = match12; a.n_found = n_found_dev; a.stats = c.stats;
     launch_sim3_match(a, st);
     HIPCHK(m, hipGetLastError());
     launch_sim3_agree(a, st);
@@ -178,17 +152,19 @@ int jsorb_search_by_sim3_async(jsorb_keyframe_matcher *m, const jsorb_sim3_param
     return JSORB_OK;
 }
 
+// The synchronous form is its own, not kf_sync's: a different layout (one count, three arrays of two lengths) that comes back in one copy
 int jsorb_search_by_sim3(jsorb_keyframe_matcher *m, const jsorb_sim3_params *params, const jsorb_sim3_side *side1, const jsorb_sim3_side *side2,
                          int32_t *match1_host, int32_t *match2_host, int32_t *match12_host, int *n_found)
 {
     if (!m) return JSORB_ERR_INVALID;
     RCCHK(sim3_check(m, params, side1, side2));
     const int n1 = side1->n, n2 = side2->n;
-    if (!n_found || (n1 > 0 && !match12_host)) return loop_fail(m, "search_by_sim3: NULL host output");
+    if (!n_found || (n1 > 0 && !match12_host)) return kf_fail(m, SIM3, "NULL host output");
     HIPCHK(m, hipSetDevice(m->device));
     const int want = 2 * n1 + n2 + 1;
-    RCCHK(reserve_device(m, m->sim3_out, (size_t)want * sizeof(int32_t), &m->sim3_out_cap, want));
-    int32_t *cnt = m->sim3_out, *m1 = cnt + 1, *m2 = m1 + n1, *m12 = m2 + n2;
+    KfCall &c = m->call[jsorb_keyframe_matcher::SIM3];
+    RCCHK(reserve_device(m, c.out, (size_t)want * sizeof(int32_t), &c.out_cap, want));
+    int32_t *cnt = c.out, *m1 = cnt + 1, *m2 = m1 + n1, *m12 = m2 + n2;
     RCCHK(jsorb_search_by_sim3_async(m, params, side1, side2, m1, m2, m12, cnt));
     std::vector<int32_t> h((size_t)want);            // the count and the three arrays lie next to each other: one copy
     HIPCHK(m, hipMemcpyAsync(h.data(), cnt, (size_t)want * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
@@ -203,8 +179,8 @@ int jsorb_search_by_sim3(jsorb_keyframe_matcher *m, const jsorb_sim3_params *par
 int jsorb_search_by_sim3_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window, int *n_agree)
 {
     if (!m) return JSORB_ERR_INVALID;
-    int32_t s[SIM3_STATS] = {0};
-    RCCHK(read_stats(m, m->sim3_done, "search_by_sim3_stats before jsorb_search_by_sim3", m->sim3_stats, s, SIM3_STATS));
+    int32_t s[KF_STATS] = {0};
+    RCCHK(kf_stats(m, m->call[jsorb_keyframe_matcher::SIM3], "search_by_sim3_stats before jsorb_search_by_sim3", s));
     if (n_windows) *n_windows = s[0];
     if (n_walked) *n_walked = s[1];
     if (n_distances) *n_distances = s[2];

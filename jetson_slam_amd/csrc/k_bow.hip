@@ -13,13 +13,14 @@
 //                  above n never moves and is never stored): a node's keypoints are one run of the array, in ascending index.  In LDS up to
 //                  BW_SORT_LDS keys, in place in global memory above.
 // k_bow_match      one wave per (keyframe, node present on both sides): the wave at the first position of a keyframe's run finds the frame's run of
-//                  the same node by bisection.  Lane l owns the frame entries l, l + 64, ...: the first BW_NODE_REGS of them with their descriptor
-//                  and claimed flag in registers, the rest read again for every keyframe keypoint (their claimed flag is match_kf itself, written
-//                  by the owning lane).  The keyframe's keypoints of the node are taken in turn (:174-238); the wave reduces to (bestDist1, first
-//                  position with it, bestDist2) and the owner of the winning entry claims it.  Every keypoint is in at most one node, so no two
-//                  waves touch the same entry of match_kf and no order of nodes can change a result.
-// k_bow_resolve    one workgroup per keyframe: the rotation histogram of the claims, ComputeThreeMaxima, the culling and the count (:254-272).
-// The rotation check, the key layout and the bisection are k_search_common.h's (rot_bin, rot_keep; BW_IDX, bw_lower_bound).
+//                  the same node by bisection.  The search itself is k_search_common.h's node_walk, shared with k_loop_bow_match: the frame's run
+//                  is the claimed side (the first BW_NODE_REGS entries of a lane in registers; past them the claimed flag is match_kf itself,
+//                  written by the owning lane), the keyframe's keypoints of the node are the outer walk (:174-238), accepted at bestDist1 <=
+//                  th_low.  Every keypoint is in at most one node, so no two waves touch the same entry of match_kf and no order of nodes can
+//                  change a result.
+// k_bow_resolve    one workgroup per keyframe: the rotation histogram of the claims, ComputeThreeMaxima, the culling and the count (:254-272):
+//                  k_search_common.h's row_resolve, shared with k_tri_resolve, with the keyframe's angle first.
+// The key layout and the bisection are k_search_common.h's too (BW_IDX, bw_lower_bound).
 // The contract (include/jsorb.h, jsorb_bow_transform_async / jsorb_search_by_bow_async) is restated in numpy in tests/test_bow_host.py.
 #include <climits>
 
@@ -155,64 +156,28 @@ __global__ __launch_bounds__(256) void k_bow_match(BowMatchArgs a)
     const int pe = bw_lower_bound(ks, len, (v + 1) << BW_IDX);
     const unsigned long long *fs = a.f_sorted + fb;
     int32_t *row = a.match_kf + (size_t)kf * a.N;
-    // the lane's first entries: index, descriptor, claimed flag
-    int kreg[BW_NODE_REGS];
-    uint4 rlo[BW_NODE_REGS], rhi[BW_NODE_REGS];
-    unsigned claimed = 0;
-#pragma unroll
-    for (int r = 0; r < BW_NODE_REGS; r++) {
-        const int t = lane + 64 * r;
-        kreg[r] = t < m ? (int)(fs[t] & BW_IDX_MASK) : -1;
-        if (t < m) sl_load_desc(a.desc + 32 * (size_t)kreg[r], rlo[r], rhi[r]);
-        else { rlo[r] = make_uint4(0, 0, 0, 0); rhi[r] = rlo[r]; }
-    }
-    const float ratio = a.p.nn_ratio;
-    int n_dist = 0;
-    for (int q = p; q < pe; q++) {                   // vIndicesKF in ascending index (:174)
-        const int j = (int)(ks[q] & BW_IDX_MASK);
-        if (!a.kf_valid[off + j]) continue;          // !pMP || pMP->isBad() (:178-184)
-        uint4 klo, khi;
-        sl_load_desc(a.kf_desc + 32 * (size_t)(off + j), klo, khi);
-        // bestDist1 / bestDist2 from 256 over the entries not yet matched (:188-213): the two smallest of the multiset, the first position with the smallest
-        int d1 = 256, d2 = 256;
-        unsigned best = ~0u;
-        auto take = [&](int d, int t) {
-            n_dist++;
-            if (d < d1) {                            // a lane meets its entries in ascending position: a tie never replaces
-                d2 = d1; d1 = d;
-                best = (unsigned)d << BW_IDX | (unsigned)t;
-            } else if (d < d2) {
-                d2 = d;
-            }
-        };
-#pragma unroll
-        for (int r = 0; r < BW_NODE_REGS; r++)
-            if (kreg[r] >= 0 && !(claimed >> r & 1)) take(SL_HAMMING(rlo[r], rhi[r], klo, khi), lane + 64 * r);
-        for (int t = lane + 64 * BW_NODE_REGS; t < m; t += 64) {
-            const int k = (int)(fs[t] & BW_IDX_MASK);
-            if (row[k] >= 0) continue;               // vpMapPointMatches[realIdxF] (:196): written by this lane, if at all
-            uint4 lo, hi;
-            sl_load_desc(a.desc + 32 * (size_t)k, lo, hi);
-            take(SL_HAMMING(lo, hi, klo, khi), t);
+    // the frame's run is the claimed side (vpMapPointMatches[realIdxF], :196 - match_kf itself past the register cap), the keyframe's keypoints of
+    // the node the outer walk (vIndicesKF in ascending index, :174)
+    struct {
+        const BowMatchArgs &a;
+        const unsigned long long *fs, *ks;
+        int32_t *row;
+        int off;
+        __device__ int index(int t) const { return (int)(fs[t] & BW_IDX_MASK); }
+        __device__ const uint8_t *desc(int k) const { return a.desc + 32 * (size_t)k; }
+        __device__ bool hidden_at_load(int) const { return false; }
+        __device__ bool hidden_late(int k) const { return row[k] >= 0; }
+        __device__ bool outer(int q, int &j, uint4 &lo, uint4 &hi) const
+        {
+            j = (int)(ks[q] & BW_IDX_MASK);
+            if (!a.kf_valid[off + j]) return false;  // !pMP || pMP->isBad() (:178-184)
+            sl_load_desc(a.kf_desc + 32 * (size_t)(off + j), lo, hi);
+            return true;
         }
-        for (int s = 32; s > 0; s >>= 1) {
-            const unsigned ob = (unsigned)__shfl_xor((int)best, s);
-            const int o1 = __shfl_xor(d1, s), o2 = __shfl_xor(d2, s);
-            d2 = min(max(d1, o1), min(d2, o2));
-            d1 = min(d1, o1);
-            best = min(best, ob);
-        }
-        if (best == ~0u || d1 > a.p.th_low || !((float)d1 < ratio * (float)d2)) continue;      // :215-217 (no entry below 256: bestIdxF = -1)
-        const int t = (int)(best & BW_IDX_MASK);
-        if (t % 64 == lane) {                        // the owner of the entry: vpMapPointMatches[bestIdxF] = pMP
-            int k = -1;
-#pragma unroll
-            for (int r = 0; r < BW_NODE_REGS; r++)
-                if (t == lane + 64 * r) { k = kreg[r]; claimed |= 1u << r; }
-            if (k < 0) k = (int)(fs[t] & BW_IDX_MASK);
-            row[k] = j;
-        }
-    }
+        __device__ bool accept(int d1) const { return d1 <= a.p.th_low; }      // :215
+        __device__ void claim(int k, int j, bool) const { row[k] = j; }        // vpMapPointMatches[bestIdxF] = pMP
+    } w{a, fs, ks, row, off};
+    int n_dist = node_walk<BW_NODE_REGS>(w, lane, m, p, pe, a.p.nn_ratio);
     for (int s = 32; s > 0; s >>= 1) n_dist += __shfl_xor(n_dist, s);
     if (lane == 0) {
         atomicAdd(&a.stats[0], 1);
@@ -221,45 +186,10 @@ __global__ __launch_bounds__(256) void k_bow_match(BowMatchArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void k_bow_resolve(BowMatchArgs a)
+__global__ __launch_bounds__(256) void k_bow_resolve(RowResolveArgs a)
 {
-    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_claims, s_culled;
-    const int kf = blockIdx.x, tid = threadIdx.x, N = a.N;
-    const int off = a.kf_start[kf];
-    if (a.kf_start[kf + 1] - off <= 0) return;       // an empty keyframe: its row and count were cleared with the others
-    int32_t *row = a.match_kf + (size_t)kf * N;
-    const bool rot = a.p.check_orientation != 0;
-    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
-    if (tid == 0) { s_claims = 0; s_culled = 0; }
-    __syncthreads();
-    int claims = 0;
-    for (int k = tid; k < N; k += 256) {
-        const int j = row[k];
-        if (j < 0) continue;
-        claims++;
-        if (rot) atomicAdd(&s_hist[rot_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))], 1);
-    }
-    atomicAdd(&s_claims, claims);
-    __syncthreads();
-    if (tid == 0) {
-        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);
-        if (kf == 0) { a.stats[3] = t.ind1 + 1; a.stats[4] = t.ind2 + 1; a.stats[5] = t.ind3 + 1; }      // (0: none - the cleared state)
-    }
-    __syncthreads();
-    if (rot) {
-        int culled = 0;
-        for (int k = tid; k < N; k += 256) {
-            const int j = row[k];
-            if (j < 0) continue;
-            if (!s_keep[rot_bin(a.kf_angle[off + j], __int_as_float(a.soa[3 * (size_t)N + k]))]) {
-                row[k] = -1;                         // :268-269
-                culled++;
-            }
-        }
-        atomicAdd(&s_culled, culled);
-        __syncthreads();
-    }
-    if (tid == 0) a.n_matches[kf] = s_claims - s_culled;
+    // :254-272; the keyframe's angle comes first (rot = kf angle - frame angle)
+    row_resolve(a, [&](int k, int j) { return rot_bin(a.kf_angle[j], a.row_angle[k]); }, a.kept, a.n);
 }
 
 void launch_bow_transform(const BowVocab &v, const uint8_t *desc, size_t desc_stride, const int *counts, int counts_stride, int n, int32_t *word,
@@ -281,6 +211,6 @@ void launch_bow_match(const BowMatchArgs &a, hipStream_t s)
     hipLaunchKernelGGL(k_bow_match, dim3((longest + 3) / 4, a.n_kf), dim3(256), 0, s, a);
 }
 
-void launch_bow_resolve(const BowMatchArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_bow_resolve, dim3(a.n_kf), dim3(256), 0, s, a); }
+void launch_bow_resolve(const RowResolveArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_bow_resolve, dim3(a.n_kf), dim3(256), 0, s, a); }
 
 } // namespace jsorb

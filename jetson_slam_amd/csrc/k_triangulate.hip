@@ -13,7 +13,8 @@
 //              the minimum over the lanes is the reference's winner.  An entry whose distance lies above the lane's best so far cannot win and
 //              skips the line test, as :725 does in walk order.  No LDS, no barrier; the per-keyframe geometry (F12, epipole) comes in the launch
 //              arguments, TR_KF_CHUNK keyframes per launch.
-// k_tri_resolve one workgroup per keyframe: the rotation histogram over idx1, ComputeThreeMaxima, the culling and the count (:778-797).
+// k_tri_resolve one workgroup per keyframe: the rotation histogram over idx1, ComputeThreeMaxima, the culling and the count (:778-797):
+//              k_search_common.h's row_resolve, shared with k_bow_resolve, with KF1's angle first.  It also resolves k_loop_bow_match's rows.
 // The contract (include/jsorb.h, jsorb_search_for_triangulation_async) is restated in numpy in tests/test_triangulation_host.py.
 #include "jsorb_launch.h"
 #include "k_search_common.h"
@@ -100,45 +101,10 @@ __global__ __launch_bounds__(256) void k_tri_match(TriArgs a, TriGeom g)
     }
 }
 
-__global__ __launch_bounds__(256) void k_tri_resolve(TriArgs a)
+__global__ __launch_bounds__(256) void k_tri_resolve(RowResolveArgs a)
 {
-    __shared__ int s_hist[HISTO_LENGTH + 1], s_keep[HISTO_LENGTH + 1], s_found, s_culled;
-    const int kf = blockIdx.x, tid = threadIdx.x, n1 = a.n1;
-    const int off = a.kf_start[kf];
-    if (a.kf_start[kf + 1] - off <= 0) return;       // an empty keyframe: its row and count were cleared with the others
-    int32_t *row = a.match12 + (size_t)kf * n1;
-    const bool rot = a.check_orientation != 0;
-    if (tid <= HISTO_LENGTH) s_hist[tid] = 0;
-    if (tid == 0) { s_found = 0; s_culled = 0; }
-    __syncthreads();
-    int found = 0;
-    for (int k = tid; k < n1; k += 256) {
-        const int j = row[k];
-        if (j < 0) continue;
-        found++;
-        if (rot) atomicAdd(&s_hist[rot_bin(a.angle1[k], a.angle2[off + j])], 1);      // :753-760
-    }
-    atomicAdd(&s_found, found);
-    __syncthreads();
-    if (tid == 0) {
-        const ThreeMaxima t = rot_keep(s_hist, s_keep, rot);      // (bin HISTO_LENGTH, outside [0, 30), is never kept)
-        if (kf == 0) { a.stats[4] = t.ind1 + 1; a.stats[5] = t.ind2 + 1; a.stats[6] = t.ind3 + 1; }      // (0: none - the cleared state)
-    }
-    __syncthreads();
-    if (rot) {
-        int culled = 0;
-        for (int k = tid; k < n1; k += 256) {
-            const int j = row[k];
-            if (j < 0) continue;
-            if (!s_keep[rot_bin(a.angle1[k], a.angle2[off + j])]) {
-                row[k] = -1;                         // :792-793
-                culled++;
-            }
-        }
-        atomicAdd(&s_culled, culled);
-        __syncthreads();
-    }
-    if (tid == 0) a.n_matches[kf] = s_found - s_culled;
+    // :753-760 and :778-797; KF1's angle comes first (rot = angle1[idx1] - angle2[idx2])
+    row_resolve(a, [&](int k, int j) { return rot_bin(a.row_angle[k], a.kf_angle[j]); }, a.kept, a.n);
 }
 
 void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s)
@@ -148,6 +114,6 @@ void launch_tri_match(const TriArgs &a, const TriGeom &g, hipStream_t s)
     hipLaunchKernelGGL(k_tri_match, dim3((a.n1 + per_block - 1) / per_block, g.n), dim3(256), 0, s, a, g);
 }
 
-void launch_tri_resolve(const TriArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_tri_resolve, dim3(a.n_kf), dim3(256), 0, s, a); }
+void launch_tri_resolve(const RowResolveArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_tri_resolve, dim3(a.n_kf), dim3(256), 0, s, a); }
 
 } // namespace jsorb

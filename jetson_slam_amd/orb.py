@@ -603,39 +603,80 @@ class KeyframeMatcher:
         if rc != 0:
             raise JsorbError("KeyframeMatcher.sync: jsorb_mem_stream_sync rc=%d" % rc)
 
+    # ---- the argument builders' shared parts: one side checker, one kf_start reader, one runner per call form ----
+    @staticmethod
+    def _side(what, d, keys, dtypes, name, n, optional=None):
+        """the pointers of one side of a call (NULL when n is 0): d[k] for every key a contiguous device tensor of shape (n,), or (n, 32) and
+        16-byte aligned for a descriptor key (*desc); dtypes: the dtypes a key may have (float32 when absent).  optional: the keys that may be
+        None or absent (a NULL pointer) - a side that has some is read with .get, so that a missing key is "not a device tensor" there"""
+        import torch
+        ptrs = []
+        for k in keys:
+            t = d[k] if optional is None else d.get(k)
+            if t is None and optional and k in optional:
+                ptrs.append(None)
+                continue
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
+            shape = (n, 32) if k.endswith("desc") else (n,)
+            ok = dtypes.get(k, (torch.float32,))
+            if t.dtype not in ok or tuple(t.shape) != shape or not t.is_contiguous():
+                raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(x) for x in ok), shape))
+            if n and k.endswith("desc") and t.data_ptr() % 16:
+                raise JsorbError("%s: %s[%r] must be 16-byte aligned" % (what, name, k))
+            ptrs.append(t.data_ptr() if n else None)
+        return ptrs
+
+    @staticmethod
+    def _kf_start(what, kf_start):
+        """kf_start as a host int32 array -> (the array, n_keyframes, the keypoints of all keyframes)"""
+        ks = np.ascontiguousarray(kf_start, np.int32)
+        if ks.ndim != 1 or len(ks) < 1:
+            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
+        return ks, len(ks) - 1, int(ks[-1])
+
+    @staticmethod
+    def _c_args(args):
+        """a builder's arguments as the C call takes them.  The converted host arrays (kf_start, the per-keyframe geometry) stand in `args` as
+        numpy arrays and give their address only here: whoever holds `args` across the call keeps them alive - np.ascontiguousarray copies a
+        list, another dtype or a strided array, and an address taken from such a copy inside the builder would outlive it"""
+        return [a.ctypes.data if isinstance(a, np.ndarray) else a for a in args]
+
+    def _enqueue(self, name, args, dev, shapes, wait):
+        """the asynchronous form `name`: the outputs (int32 device tensors of `shapes`, allocated -7-filled with no dimension below 1) behind
+        `args`; wait as in search_for_triangulation.  Returns the outputs cut to their shapes."""
+        import torch
+        outs = [torch.full([max(s, 1) for s in shape], -7, dtype=torch.int32, device=dev) for shape in shapes]
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(getattr(self._lib, name)(self._m, *self._c_args(args), *[o.data_ptr() for o in outs]))
+        if wait:
+            self.sync()
+        return tuple(o.reshape(-1)[:int(np.prod(shape))].reshape(shape) for o, shape in zip(outs, shapes))
+
+    def _call_host(self, name, args, dev, shapes):
+        """the synchronous form `name`: the same with host arrays; a shape () is one int, returned as a number"""
+        import torch
+        outs = [C.c_int(-7) if shape == () else np.full(max(int(np.prod(shape)), 1), -7, np.int32) for shape in shapes]
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(getattr(self._lib, name)(self._m, *self._c_args(args), *[C.byref(o) if shape == () else o.ctypes.data for o, shape in zip(outs, shapes)]))
+        return tuple(o.value if shape == () else o[:int(np.prod(shape))].reshape(shape) for o, shape in zip(outs, shapes))
+
     def _args(self, kf1, kf_start, kf2, F12, epipole, params):
+        """-> (device, output shapes, arguments) of jsorb_search_for_triangulation*"""
         import torch
         what = "search_for_triangulation"
         if not isinstance(params, JsorbTriangulationParams):
             raise JsorbError("%s: params must come from make_triangulation_params" % what)
-        ks = np.ascontiguousarray(kf_start, np.int32)
-        if ks.ndim != 1 or len(ks) < 1:
-            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
-        nk, total = len(ks) - 1, int(ks[-1])
+        ks, nk, total = self._kf_start(what, kf_start)
         F = np.ascontiguousarray(F12, np.float32).reshape(-1)
         E = np.ascontiguousarray(epipole, np.float32).reshape(-1)
         if len(F) != 9 * nk or len(E) != 2 * nk:
             raise JsorbError("%s: F12 must hold 9 and epipole 2 floats per keyframe" % what)
-        dt = dict(node=(torch.int32,), octave=(torch.int32,), free=(torch.uint8, torch.bool), stereo=(torch.uint8, torch.bool), x=(torch.float32,),
-                  y=(torch.float32,), angle=(torch.float32,), desc=(torch.uint8,))
-
-        def side(kf, keys, name, n):
-            ptrs = []
-            for k in keys:
-                t = kf[k]
-                if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
-                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
-                shape = (n, 32) if k == "desc" else (n,)
-                if t.dtype not in dt[k] or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(d) for d in dt[k]), shape))
-                ptrs.append(t.data_ptr() if n else None)
-            if n and kf["desc"].data_ptr() % 16:
-                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
-            return ptrs
-
+        dt = dict(node=(torch.int32,), octave=(torch.int32,), free=(torch.uint8, torch.bool), stereo=(torch.uint8, torch.bool), desc=(torch.uint8,))
         n1 = int(kf1["node"].shape[0])
-        p1, p2 = side(kf1, self.KF1_KEYS, "kf1", n1), side(kf2, self.KF2_KEYS, "kf2", total)
-        return n1, nk, ks, F, E, [C.byref(params), n1] + p1 + [nk, ks.ctypes.data] + p2 + [F.ctypes.data, E.ctypes.data]
+        p1, p2 = self._side(what, kf1, self.KF1_KEYS, dt, "kf1", n1), self._side(what, kf2, self.KF2_KEYS, dt, "kf2", total)
+        return kf1["node"].device, [(nk, n1), (nk,)], [C.byref(params), n1] + p1 + [nk, ks] + p2 + [F, E]
 
     def search_for_triangulation(self, kf1, kf_start, kf2, F12, epipole, params, wait=True):
         """jsorb_search_for_triangulation_async: KF1 against the len(kf_start) - 1 concatenated KF2s (kf_start: HOST int32 offsets; F12 host
@@ -645,28 +686,14 @@ class KeyframeMatcher:
         wait=False the returned tensors come from torch's caching allocator on the CURRENT torch stream but are written on the matcher's stream:
         keep them alive until the matcher's stream has finished (or make that stream the current torch stream, as set_stream with
         torch.cuda.current_stream().cuda_stream does), or the allocator may hand their memory out again while the kernels still write it."""
-        import torch
-        n1, nk, ks, F, E, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
-        dev = kf1["node"].device
-        match12 = torch.full((max(nk, 1), max(n1, 1)), -7, dtype=torch.int32, device=dev)
-        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
-        if wait:
-            torch.cuda.current_stream(dev).synchronize()
-        self._chk(self._lib.jsorb_search_for_triangulation_async(self._m, *args, match12.data_ptr(), count.data_ptr()))
-        if wait:
-            self.sync()
-        return match12.reshape(-1)[:nk * n1].reshape(nk, n1), count[:nk]
+        dev, shapes, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
+        return self._enqueue("jsorb_search_for_triangulation_async", args, dev, shapes, wait)
 
     def search_for_triangulation_host(self, kf1, kf_start, kf2, F12, epipole, params):
         """jsorb_search_for_triangulation, the synchronous form: the same inputs, (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) on
         the host with one copy back"""
-        import torch
-        n1, nk, ks, F, E, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
-        match12 = np.full(max(nk * n1, 1), -7, np.int32)
-        count = np.full(max(nk, 1), -7, np.int32)
-        torch.cuda.current_stream(kf1["node"].device).synchronize()
-        self._chk(self._lib.jsorb_search_for_triangulation(self._m, *args, match12.ctypes.data, count.ctypes.data))
-        return match12[:nk * n1].reshape(nk, n1), count[:nk]
+        dev, shapes, args = self._args(kf1, kf_start, kf2, F12, epipole, params)
+        return self._call_host("jsorb_search_for_triangulation", args, dev, shapes)
 
     def stats(self):
         """((keyframe, node) pairs on both sides, Hamming distances, candidates at the line test, most KF2 keypoints in such a node, keyframe 0's
@@ -680,44 +707,26 @@ class KeyframeMatcher:
     FUSE_KF_KEYS = ("x", "y", "octave", "uright", "desc")
 
     def _fuse_args(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip):
+        """-> (device, output shapes, arguments) of jsorb_fuse*"""
         import torch
         what = "fuse"
         if not isinstance(params, JsorbFuseParams):
             raise JsorbError("%s: params must come from make_fuse_params" % what)
-        ks = np.ascontiguousarray(kf_start, np.int32)
-        if ks.ndim != 1 or len(ks) < 1:
-            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
-        nk, total = len(ks) - 1, int(ks[-1])
+        ks, nk, total = self._kf_start(what, kf_start)
         R, t, O = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (Rcw, tcw, Ow))
         if len(R) != 9 * nk or len(t) != 3 * nk or len(O) != 3 * nk:
             raise JsorbError("%s: Rcw must hold 9, tcw 3 and Ow 3 floats per keyframe" % what)
-        dt = dict(octave=torch.int32, desc=torch.uint8)
-
-        def side(d, keys, name, n):
-            ptrs = []
-            for k in keys:
-                t_ = d.get(k)
-                if t_ is None and k == "uright":
-                    ptrs.append(None)
-                    continue
-                if not hasattr(t_, "data_ptr") or not getattr(t_, "is_cuda", False):
-                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
-                shape = (n, 32) if k == "desc" else (n,)
-                if t_.dtype != dt.get(k, torch.float32) or tuple(t_.shape) != shape or not t_.is_contiguous():
-                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, dt.get(k, torch.float32), shape))
-                ptrs.append(t_.data_ptr() if n else None)
-            if n and d["desc"].data_ptr() % 16:
-                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
-            return ptrs
-
+        dt = dict(octave=(torch.int32,), desc=(torch.uint8,))
         n = int(points["Px"].shape[0])
-        pp, pk = side(points, self.POINT_KEYS, "points", n), side(keyframes, self.FUSE_KF_KEYS, "keyframes", total)
+        pp = self._side(what, points, self.POINT_KEYS, dt, "points", n, optional=())
+        pk = self._side(what, keyframes, self.FUSE_KF_KEYS, dt, "keyframes", total, optional=("uright",))
         sp = None
         if skip is not None:
             if not getattr(skip, "is_cuda", False) or skip.dtype not in (torch.uint8, torch.bool) or skip.numel() != nk * n or not skip.is_contiguous():
                 raise JsorbError("%s: skip must be a contiguous uint8 / bool device tensor of n_keyframes x n_points entries" % what)
             sp = skip.data_ptr() if nk * n else None
-        return n, nk, (ks, R, t, O), [C.byref(params), n] + pp + [nk, ks.ctypes.data] + pk + [R.ctypes.data, t.ctypes.data, O.ctypes.data, sp]
+        return points["Px"].device, [(nk, n), (nk, n), (nk,)], \
+            [C.byref(params), n] + pp + [nk, ks] + pk + [R, t, O, sp]
 
     def fuse(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip=None, wait=True):
         """jsorb_fuse_async: the n map points (dict of device tensors: Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv float32[n],
@@ -725,30 +734,14 @@ class KeyframeMatcher:
         None / absent: monocular; kf_start: HOST int32 offsets; Rcw host float32[n_keyframes, 9] row-major, tcw and Ow host float32[n_keyframes, 3]).
         skip: uint8 / bool device tensor [n_keyframes, n] or None.  Returns (best_idx, best_dist int32[n_keyframes, n], n_matched
         int32[n_keyframes]) as device tensors; wait= as in search_for_triangulation, with the same rule for the returned tensors' lifetime."""
-        import torch
-        n, nk, keep, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
-        dev = points["Px"].device
-        best_idx = torch.full((max(nk, 1), max(n, 1)), -7, dtype=torch.int32, device=dev)
-        best_dist = torch.full((max(nk, 1), max(n, 1)), -7, dtype=torch.int32, device=dev)
-        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
-        if wait:
-            torch.cuda.current_stream(dev).synchronize()
-        self._chk(self._lib.jsorb_fuse_async(self._m, *args, best_idx.data_ptr(), best_dist.data_ptr(), count.data_ptr()))
-        if wait:
-            self.sync()
-        return best_idx.reshape(-1)[:nk * n].reshape(nk, n), best_dist.reshape(-1)[:nk * n].reshape(nk, n), count[:nk]
+        dev, shapes, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
+        return self._enqueue("jsorb_fuse_async", args, dev, shapes, wait)
 
     def fuse_host(self, points, kf_start, keyframes, Rcw, tcw, Ow, params, skip=None):
         """jsorb_fuse, the synchronous form: the same inputs, (best_idx, best_dist int32[n_keyframes, n], n_matched int32[n_keyframes]) on the host
         with one copy back"""
-        import torch
-        n, nk, keep, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
-        best_idx = np.full(max(nk * n, 1), -7, np.int32)
-        best_dist = np.full(max(nk * n, 1), -7, np.int32)
-        count = np.full(max(nk, 1), -7, np.int32)
-        torch.cuda.current_stream(points["Px"].device).synchronize()
-        self._chk(self._lib.jsorb_fuse(self._m, *args, best_idx.ctypes.data, best_dist.ctypes.data, count.ctypes.data))
-        return best_idx[:nk * n].reshape(nk, n), best_dist[:nk * n].reshape(nk, n), count[:nk]
+        dev, shapes, args = self._fuse_args(points, kf_start, keyframes, Rcw, tcw, Ow, params, skip)
+        return self._call_host("jsorb_fuse", args, dev, shapes)
 
     def fuse_stats(self):
         """((keyframe, point) pairs that reached a window, keypoints walked, Hamming distances, the largest window) of the last fuse"""
@@ -761,61 +754,30 @@ class KeyframeMatcher:
     BOW_KF_KEYS = ("node", "valid", "angle", "desc")
 
     def _bow_kf_args(self, kf1, kf_start, candidates, params):
+        """-> (device, output shapes, arguments) of jsorb_search_by_bow_kf*"""
         import torch
         what = "search_by_bow_kf"
         if not isinstance(params, JsorbBowParams):
             raise JsorbError("%s: params must come from make_bow_params" % what)
-        ks = np.ascontiguousarray(kf_start, np.int32)
-        if ks.ndim != 1 or len(ks) < 1:
-            raise JsorbError("%s: kf_start must be a host array of n_keyframes + 1 offsets" % what)
-        nk, total = len(ks) - 1, int(ks[-1])
-        dt = dict(node=(torch.int32,), valid=(torch.uint8, torch.bool), angle=(torch.float32,), desc=(torch.uint8,))
-
-        def side(kf, name, n):
-            ptrs = []
-            for k in self.BOW_KF_KEYS:
-                t = kf[k]
-                if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
-                    raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
-                shape = (n, 32) if k == "desc" else (n,)
-                if t.dtype not in dt[k] or tuple(t.shape) != shape or not t.is_contiguous():
-                    raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(d) for d in dt[k]), shape))
-                ptrs.append(t.data_ptr() if n else None)
-            if n and kf["desc"].data_ptr() % 16:
-                raise JsorbError("%s: %s['desc'] must be 16-byte aligned" % (what, name))
-            return ptrs
-
+        ks, nk, total = self._kf_start(what, kf_start)
+        dt = dict(node=(torch.int32,), valid=(torch.uint8, torch.bool), desc=(torch.uint8,))
         n1 = int(kf1["node"].shape[0])
-        p1, p2 = side(kf1, "kf1", n1), side(candidates, "candidates", total)
-        return n1, nk, ks, [C.byref(params), n1] + p1 + [nk, ks.ctypes.data] + p2
+        p1, p2 = self._side(what, kf1, self.BOW_KF_KEYS, dt, "kf1", n1), self._side(what, candidates, self.BOW_KF_KEYS, dt, "candidates", total)
+        return kf1["node"].device, [(nk, n1), (nk,)], [C.byref(params), n1] + p1 + [nk, ks] + p2
 
     def search_by_bow_kf(self, kf1, kf_start, candidates, params, wait=True):
         """jsorb_search_by_bow_kf_async: the current keyframe (dict of device tensors: node int32[n1], valid uint8 / bool [n1], angle float32[n1],
         desc uint8[n1, 32]) against the len(kf_start) - 1 concatenated loop candidates (the same keys; kf_start: HOST int32 offsets into them, the
         arrays hold kf_start[-1] entries).  Returns (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) as device tensors; wait= as in
         search_for_triangulation, with the same rule for the returned tensors' lifetime."""
-        import torch
-        n1, nk, ks, args = self._bow_kf_args(kf1, kf_start, candidates, params)
-        dev = kf1["node"].device
-        match12 = torch.full((max(nk, 1), max(n1, 1)), -7, dtype=torch.int32, device=dev)
-        count = torch.full((max(nk, 1),), -7, dtype=torch.int32, device=dev)
-        if wait:
-            torch.cuda.current_stream(dev).synchronize()
-        self._chk(self._lib.jsorb_search_by_bow_kf_async(self._m, *args, match12.data_ptr(), count.data_ptr()))
-        if wait:
-            self.sync()
-        return match12.reshape(-1)[:nk * n1].reshape(nk, n1), count[:nk]
+        dev, shapes, args = self._bow_kf_args(kf1, kf_start, candidates, params)
+        return self._enqueue("jsorb_search_by_bow_kf_async", args, dev, shapes, wait)
 
     def search_by_bow_kf_host(self, kf1, kf_start, candidates, params):
         """jsorb_search_by_bow_kf, the synchronous form: the same inputs, (match12 int32[n_keyframes, n1], n_matches int32[n_keyframes]) on the host
         with one copy back"""
-        import torch
-        n1, nk, ks, args = self._bow_kf_args(kf1, kf_start, candidates, params)
-        match12 = np.full(max(nk * n1, 1), -7, np.int32)
-        count = np.full(max(nk, 1), -7, np.int32)
-        torch.cuda.current_stream(kf1["node"].device).synchronize()
-        self._chk(self._lib.jsorb_search_by_bow_kf(self._m, *args, match12.ctypes.data, count.ctypes.data))
-        return match12[:nk * n1].reshape(nk, n1), count[:nk]
+        dev, shapes, args = self._bow_kf_args(kf1, kf_start, candidates, params)
+        return self._call_host("jsorb_search_by_bow_kf", args, dev, shapes)
 
     def search_by_bow_kf_stats(self):
         """((candidate, node) pairs on both sides, Hamming distances, most candidate keypoints in such a node, candidate 0's (ind1, ind2, ind3)) of
@@ -827,35 +789,25 @@ class KeyframeMatcher:
     SIM3_KEYS = ("x", "y", "octave", "kp_desc", "Px", "Py", "Pz", "max_distance", "min_dist_inv", "max_dist_inv", "mp_desc", "search")
     SIM3_POSE = (("Rw", 9), ("tw", 3), ("sR", 9), ("t", 3))
 
-    def _sim3_side(self, d, name):
-        import torch
-        what = "search_by_sim3"
-        n = int(d["x"].shape[0])
-        dt = dict(octave=(torch.int32,), kp_desc=(torch.uint8,), mp_desc=(torch.uint8,), search=(torch.uint8, torch.bool))
-        s = JsorbSim3Side(n)
-        for k in self.SIM3_KEYS:
-            t = d[k]
-            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
-                raise JsorbError("%s: %s[%r] must be a device tensor" % (what, name, k))
-            shape = (n, 32) if k.endswith("desc") else (n,)
-            ok = dt.get(k, (torch.float32,))
-            if t.dtype not in ok or tuple(t.shape) != shape or not t.is_contiguous():
-                raise JsorbError("%s: %s[%r] must be a contiguous %s tensor of shape %s" % (what, name, k, " / ".join(str(x) for x in ok), shape))
-            if n and k.endswith("desc") and t.data_ptr() % 16:
-                raise JsorbError("%s: %s[%r] must be 16-byte aligned" % (what, name, k))
-            setattr(s, k, t.data_ptr() if n else None)
-        for k, size in self.SIM3_POSE:
-            v = np.ascontiguousarray(d[k], np.float32).reshape(-1)
-            if len(v) != size:
-                raise JsorbError("%s: %s[%r] must hold %d floats" % (what, name, k, size))
-            setattr(s, k, (C.c_float * size)(*v.tolist()))
-        return s
-
     def _sim3_args(self, side1, side2, params):
+        """-> (jsorb_sim3_side of side1, of side2, arguments) of jsorb_search_by_sim3* (nothing of `self` is read)"""
+        import torch
+        what, K = "search_by_sim3", KeyframeMatcher
         if not isinstance(params, JsorbSim3Params):
-            raise JsorbError("search_by_sim3: params must come from make_sim3_params")
-        s1, s2 = self._sim3_side(side1, "side1"), self._sim3_side(side2, "side2")
-        return s1, s2, [C.byref(params), C.byref(s1), C.byref(s2)]
+            raise JsorbError("%s: params must come from make_sim3_params" % what)
+        dt = dict(octave=(torch.int32,), kp_desc=(torch.uint8,), mp_desc=(torch.uint8,), search=(torch.uint8, torch.bool))
+        sides = []
+        for d, name in ((side1, "side1"), (side2, "side2")):
+            s = JsorbSim3Side(int(d["x"].shape[0]))
+            for k, ptr in zip(K.SIM3_KEYS, K._side(what, d, K.SIM3_KEYS, dt, name, s.n)):
+                setattr(s, k, ptr)
+            for k, size in K.SIM3_POSE:
+                v = np.ascontiguousarray(d[k], np.float32).reshape(-1)
+                if len(v) != size:
+                    raise JsorbError("%s: %s[%r] must hold %d floats" % (what, name, k, size))
+                setattr(s, k, (C.c_float * size)(*v.tolist()))
+            sides.append(s)
+        return sides[0], sides[1], [C.byref(params), C.byref(sides[0]), C.byref(sides[1])]
 
     def search_by_sim3(self, side1, side2, params, wait=True):
         """jsorb_search_by_sim3_async: each side a dict of device tensors aligned with the keyframe's keypoints (x, y float32, octave int32, kp_desc
@@ -863,30 +815,14 @@ class KeyframeMatcher:
         arrays: Rw (9, row-major), tw (3) of the keyframe itself, sR (9), t (3) into the OTHER camera (side 1: sR21, t21; side 2: sR12, t12).
         Returns (match1 int32[n1], match2 int32[n2], match12 int32[n1], n_found int32[1]) as device tensors; wait= as in
         search_for_triangulation, with the same rule for the returned tensors' lifetime."""
-        import torch
         s1, s2, args = self._sim3_args(side1, side2, params)
-        dev = side1["x"].device
-        m1 = torch.full((max(s1.n, 1),), -7, dtype=torch.int32, device=dev)
-        m2 = torch.full((max(s2.n, 1),), -7, dtype=torch.int32, device=dev)
-        m12 = torch.full((max(s1.n, 1),), -7, dtype=torch.int32, device=dev)
-        found = torch.full((1,), -7, dtype=torch.int32, device=dev)
-        if wait:
-            torch.cuda.current_stream(dev).synchronize()
-        self._chk(self._lib.jsorb_search_by_sim3_async(self._m, *args, m1.data_ptr(), m2.data_ptr(), m12.data_ptr(), found.data_ptr()))
-        if wait:
-            self.sync()
-        return m1[:s1.n], m2[:s2.n], m12[:s1.n], found
+        return self._enqueue("jsorb_search_by_sim3_async", args, side1["x"].device, [(s1.n,), (s2.n,), (s1.n,), (1,)], wait)
 
     def search_by_sim3_host(self, side1, side2, params):
         """jsorb_search_by_sim3, the synchronous form: the same inputs, (match1 int32[n1], match2 int32[n2], match12 int32[n1], n_found) on the host
         with one copy back"""
-        import torch
         s1, s2, args = self._sim3_args(side1, side2, params)
-        m1, m2, m12 = np.full(max(s1.n, 1), -7, np.int32), np.full(max(s2.n, 1), -7, np.int32), np.full(max(s1.n, 1), -7, np.int32)
-        found = C.c_int(-7)
-        torch.cuda.current_stream(side1["x"].device).synchronize()
-        self._chk(self._lib.jsorb_search_by_sim3(self._m, *args, m1.ctypes.data, m2.ctypes.data, m12.ctypes.data, C.byref(found)))
-        return m1[:s1.n], m2[:s2.n], m12[:s1.n], found.value
+        return self._call_host("jsorb_search_by_sim3", args, side1["x"].device, [(s1.n,), (s2.n,), (s1.n,), ()])
 
     def search_by_sim3_stats(self):
         """(slots that reached a window, keypoints walked, Hamming distances, the largest window, agreements) of the last search_by_sim3, both
