@@ -722,13 +722,22 @@ int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_
  * What runs here is the search, :839-936: per (keyframe, point) the keypoint bestIdx and its distance bestDist, a pure function of the arrays as
  * they are before the call - there is no claim rule and no rotation check.  What touches the map stays with the caller: the head test
  * `!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)` (:833-837) and the tail :938-958 (Replace, AddObservation, AddMapPoint).  The caller walks the
- * keyframes and points in the reference's order, evaluates the head test on the LIVE map and applies the tail to best_idx.  That replay equals the
- * sequential loop, for three reasons:
- *   - nothing the tail mutates feeds the search: Replace and AddObservation change neither the position, the normal, the distance range nor the
- *     descriptor of a point (those change in UpdateNormalAndDepth / ComputeDistinctiveDescriptors, which SearchInNeighbors calls after all fusing);
+ * keyframes and points in the reference's order, evaluates the head test on the LIVE map and applies the tail to best_idx.  ONE THING THE TAIL
+ * MUTATES FEEDS THE SEARCH, and the caller has to follow it:
+ *   - MapPoint::Replace ends with ComputeDistinctiveDescriptors() on the surviving point (src/MapPoint.cpp:243), which picks mDescriptor again
+ *     from all the observations the survivor has just inherited (:273-338); SearchInNeighbors (LocalMapping.cpp:490-496) and SearchAndFuse
+ *     (LoopClosing.cpp:596-617) search that point in the NEXT keyframe with the new descriptor.  Position, normal and distance range do not change
+ *     (UpdateNormalAndDepth runs after all fusing).  So, after replaying keyframe k, every point of the list that is still good and whose 32
+ *     descriptor bytes differ from those it was last searched with is searched again - one more call of this function over those points and the
+ *     keyframes k+1.., `skip` set where the head test fails - and its best_idx / best_dist for those keyframes are replaced.  Within keyframe k
+ *     nothing is searched again: the survivor of a Replace is either the point at hand, whose search there is over, or the point in the
+ *     keyframe's slot, which the head test skips there.  Without this step the replay differs from the reference's loop (run against the
+ *     reference's own ORBmatcher.cpp: tests/fuse_replay.py, tests/test_ref_matcher.py).
+ * With it the replay equals the sequential loop, because
  *   - vpMapPointMatches is a copy taken before the loop, so the point list of a call does not change under it;
- *   - the head test only ever goes from pass to skip while the loops run: isBad never reverts, and a point leaves a keyframe only by becoming bad.
- *     So a pair the device searched and the replay skips costs work, never a result; `skip` lets the caller leave out what is known before the call.
+ *   - the head test only ever goes from pass to skip while the loops run: isBad never reverts, and in a map whose slots and observations agree a
+ *     point leaves a keyframe only by becoming bad.  So a pair the device searched and the replay skips costs work, never a result; `skip` lets
+ *     the caller leave out what is known before the call.
  * Inputs, DEVICE arrays unless said otherwise.  Points i = 0 .. n_points-1: Px, Py, Pz (GetWorldPos), Nx, Ny, Nz (GetNormal), max_distance
  * (mfMaxDistance), min_dist_inv / max_dist_inv (GetMinDistanceInvariance / GetMaxDistanceInvariance) float[n_points]; desc n_points x 32 bytes
  * (GetDescriptor), 16-byte aligned.  The keyframes are concatenated: keyframe k is the entries kf_start[k] .. kf_start[k + 1] (HOST array of

@@ -828,7 +828,9 @@ inline std::vector<int> SearchForTriangulation(jsorb::KeyframeMatcher &matcher, 
 // targets concatenated, target k at kf_start[k] .. kf_start[k + 1].  skip_gpu: nullptr or one byte per (keyframe, point) on the device, nonzero
 // where the caller already knows the head test fails (!pMP, isBad, IsInKeyFrame).  best_idx / best_dist [k * points.n + i] = bestIdx (within
 // keyframe k) and bestDist of point i, -1 where the reference finds none within TH_LOW.  The caller replays the head test and the tail :938-958
-// over them, keyframes and points in the reference's order.  Returns the number of matches over all keyframes.
+// over them, keyframes and points in the reference's order, and calls this again - for the keyframes not yet replayed - for every point whose
+// descriptor a Replace changed (MapPoint.cpp:243 recomputes the survivor's; include/jsorb.h).  Returns the number of matches over
+// all keyframes.
 inline int Fuse(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &params, const jsorb::FusePoints &points, int n_kf, const int32_t *kf_start,
                 const jsorb::FuseKeyframes &keyframes, const jsorb::FusePoses &poses, const unsigned char *skip_gpu, std::vector<int32_t> &best_idx,
                 std::vector<int32_t> &best_dist)

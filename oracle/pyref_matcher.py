@@ -28,7 +28,8 @@ _libs = {}
 def lib(fused=False):
     if fused not in _libs:
         l = ctypes.CDLL(lib_path(fused))
-        assert l.rm_abi_version() == 1
+        assert l.rm_abi_version() == 2
+        l.rm_fuse.restype = l.rm_fuse_sim3.restype = l.rm_log_sizes.restype = l.rm_log_copy.restype = None
         _libs[fused] = l
     return _libs[fused]
 
@@ -161,7 +162,100 @@ def _tri(l, c):
     return dict(pairs=pairs[:n_pairs.value].copy(), nmatches=np.int32(cnt))
 
 
-DRIVERS = {"search_local": _local, "search_last_frame": _last, "search_init": _init, "search_by_bow": _bow, "search_by_bow_kf": _bow_kf,
+def logs(l):
+    """the event log [E, 4], the descriptors of its descriptor events [D, 32] and the probe log [P, 5] of the last logging driver"""
+    sizes = (c_i * 3)()
+    l.rm_log_sizes(sizes)
+    ev, de, pr = np.zeros((sizes[0], 4), np.int32), np.zeros((sizes[1], 32), np.uint8), np.zeros((sizes[2], 5), np.float32)
+    l.rm_log_copy(c_p(ev.ctypes.data if ev.size else None), c_p(de.ctypes.data if de.size else None), c_p(pr.ctypes.data if pr.size else None))
+    return ev, de, pr
+
+
+def _map_args(k, c):
+    """the live map of a fuse case as build_map of harness.cpp takes it; returns (arguments, keyframe sizes, number of points)"""
+    KF, P, prm = c["KF"], c["P"], c["prm"]
+    views = (View * len(KF))()
+    for i, K in enumerate(KF):
+        side = dict(K, u_right=K["uright"], scale=prm["scale"], inv_sigma2=prm["inv_sigma2"], start=K["_start"], items=K["_items"],
+                    **{a: prm[a] for a in ("cols", "rows", "min_x", "min_y", "inv_w", "inv_h")})      # (_start, _items: the grid's CSR, built by the caller)
+        views[i] = view(k, side, len(K["x"]), x="x", y="y", max_x=float(prm["max_x"]), max_y=float(prm["max_y"]), log_scale=float(prm["log_sf"]),
+                        fx=float(prm["fx"]), fy=float(prm["fy"]), cx=float(prm["cx"]), cy=float(prm["cy"]), mbf=float(prm["bf"]))
+    sizes = [len(K["x"]) for K in KF]
+    mps = np.concatenate([np.asarray(K["mps"], np.int32) for K in KF] + [np.zeros(0, np.int32)])
+    n = len(P["Px"])
+    pos = np.stack([P["Px"], P["Py"], P["Pz"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    nrm = np.stack([P["Nx"], P["Ny"], P["Nz"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    obs = np.asarray(c["obs"], np.int32).reshape(-1, 3)
+    args = [len(KF), views, c_p(k.arr(mps, np.int32)), n, c_p(k.arr(pos, np.float32)), c_p(k.arr(nrm, np.float32)), c_p(k.arr(P["maxd"], np.float32)),
+            c_p(k.arr(P["mind"], np.float32)), c_p(k.arr(P["desc"], np.uint8)), c_p(k.arr(P["bad"], np.uint8)), len(obs), c_p(k.arr(obs, np.int32)),
+            len(c["targets"]), c_p(k.arr(c["targets"], np.int32))]
+    return args, sizes, n
+
+
+def _map_outs(l, sizes, n):
+    mps_out, state, desc = np.full(max(sum(sizes), 1), -1, np.int32), np.zeros((max(n, 1), 3), np.int32), np.zeros((max(n, 1), 32), np.uint8)
+    return (mps_out, state, desc), lambda: dict(kf_mps=mps_out[:sum(sizes)].copy(), pt_bad=state[:n, 0].astype(np.uint8), pt_replaced=state[:n, 1].copy(),
+                                                pt_nobs=state[:n, 2].copy(), pt_desc=desc[:n].copy(), **dict(zip(("events", "ev_desc", "probe"), logs(l))))
+
+
+def _fuse(l, c):
+    k = _Keep()
+    args, sizes, n = _map_args(k, c)
+    lst = np.asarray(c["list"], np.int32)
+    nf = np.zeros(max(len(c["targets"]), 1), np.int32)
+    (mps_out, state, desc), outs = _map_outs(l, sizes, n)
+    l.rm_fuse(*args, len(lst), c_p(k.arr(lst, np.int32)), c_f(c["prm"]["th"]), c_p(nf.ctypes.data), c_p(mps_out.ctypes.data), c_p(state.ctypes.data),
+              c_p(desc.ctypes.data))
+    return dict(outs(), nfused=nf[:len(c["targets"])].copy(), nmatches=np.int32(nf[:len(c["targets"])].sum()))
+
+
+def _fuse_sim3(l, c):
+    k = _Keep()
+    args, sizes, n = _map_args(k, c)
+    lst = np.asarray(c["list"], np.int32)
+    nt = len(c["targets"])
+    nf, rep = np.zeros(max(nt, 1), np.int32), np.full((max(nt, 1), max(len(lst), 1)), -1, np.int32)
+    (mps_out, state, desc), outs = _map_outs(l, sizes, n)
+    l.rm_fuse_sim3(*args, c_p(k.arr(c["Scw"], np.float32)), int(c["replace_loop"]), len(lst), c_p(k.arr(lst, np.int32)), c_f(c["prm"]["th"]),
+                   c_p(nf.ctypes.data), c_p(rep.ctypes.data), c_p(mps_out.ctypes.data), c_p(state.ctypes.data), c_p(desc.ctypes.data))
+    return dict(outs(), nfused=nf[:nt].copy(), nmatches=np.int32(nf[:nt].sum()), replace=rep[:nt, :len(lst)].copy())
+
+
+def _sim3(l, c):
+    k = _Keep()
+    prm, P = c["prm"], c["P"]
+    views = (View * 2)()
+    for i, K in enumerate(c["KF"]):
+        side = dict(K, scale=prm["scale"], start=K["_start"], items=K["_items"], **{a: prm[a] for a in ("cols", "rows", "min_x", "min_y", "inv_w", "inv_h")})
+        views[i] = view(k, side, len(K["x"]), x="x", y="y", max_x=float(prm["max_x"]), max_y=float(prm["max_y"]), log_scale=float(prm["log_sf"]),
+                        fx=float(prm["fx"]), fy=float(prm["fy"]), cx=float(prm["cx"]), cy=float(prm["cy"]))
+    n, n1 = len(P["Px"]), len(c["KF"][0]["x"])
+    pos = np.stack([P["Px"], P["Py"], P["Pz"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    obs = np.asarray(c["obs"], np.int32).reshape(-1, 3)
+    m12 = np.full(max(n1, 1), -1, np.int32)
+    m12[:n1] = c["matches12"]
+    cnt = l.rm_search_by_sim3(views, c_p(k.arr(c["KF"][0]["mps"], np.int32)), c_p(k.arr(c["KF"][1]["mps"], np.int32)), n, c_p(k.arr(pos, np.float32)),
+                              c_p(k.arr(P["maxd"], np.float32)), c_p(k.arr(P["mind"], np.float32)), c_p(k.arr(P["desc"], np.uint8)),
+                              c_p(k.arr(P["bad"], np.uint8)), len(obs), c_p(k.arr(obs, np.int32)), c_f(c["s12"]), c_p(k.arr(c["R12"], np.float32)),
+                              c_p(k.arr(c["t12"], np.float32)), c_f(prm["th"]), c_p(m12.ctypes.data))
+    return dict(matches12=m12[:n1].copy(), nmatches=np.int32(cnt), probe=logs(l)[2])
+
+
+def _kf(l, c):
+    F, P, prm = c["F"], c["P"], c["prm"]
+    k = _Keep()
+    N, n = len(F["kx"]), len(P["Px"])
+    v = view(k, F, N, Rcw=k.arr(prm["Rcw"], np.float32), tcw=k.arr(prm["tcw"], np.float32), log_scale=float(prm["log_sf"]),
+             **{a: float(prm[a]) for a in ("fx", "fy", "cx", "cy", "max_x", "max_y")})
+    pos = np.stack([P["Px"], P["Py"], P["Pz"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    out = np.full(max(N, 1), -1, np.int32)
+    cnt = l.rm_search_kf(ctypes.byref(v), c_p(k.arr(F["blocked"], np.uint8)), n, c_p(k.arr(P["state"], np.uint8)), c_p(k.arr(pos, np.float32)),
+                         c_p(k.arr(P["maxd"], np.float32)), c_p(k.arr(P["mind"], np.float32)), c_p(k.arr(P["desc"], np.uint8)),
+                         c_p(k.arr(P["angle"], np.float32)), c_f(prm["th"]), int(prm["orb_dist"]), int(prm["check_orientation"]), c_p(out.ctypes.data))
+    return dict(kp_match=out[:N].copy(), nmatches=np.int32(cnt), probe=logs(l)[2])
+
+
+DRIVERS = {"search_kf": _kf, "fuse": _fuse, "fuse_sim3": _fuse_sim3, "search_by_sim3": _sim3, "search_local": _local, "search_last_frame": _last, "search_init": _init, "search_by_bow": _bow, "search_by_bow_kf": _bow_kf,
            "search_for_triangulation": _tri}
 
 

@@ -23,6 +23,9 @@ public:
     std::set<MapPoint *> GetMapPoints();
     MapPoint *GetMapPoint(const size_t &idx);
     void AddMapPoint(MapPoint *pMP, const size_t &idx);
+    void ReplaceMapPointMatch(const size_t &idx, MapPoint *pMP);
+    void EraseMapPointMatch(const size_t &idx);
+    bool isBad();
 
     std::vector<size_t> GetFeaturesInArea(const float &x, const float &y, const float &r) const;
     bool IsInImage(const float &x, const float &y) const;

@@ -36,6 +36,7 @@ public:
     int GetIndexInKeyFrame(KeyFrame *pKF);
     void AddObservation(KeyFrame *pKF, size_t idx);
     void Replace(MapPoint *pMP);
+    void ComputeDistinctiveDescriptors();
 
     float GetMinDistanceInvariance();
     float GetMaxDistanceInvariance();

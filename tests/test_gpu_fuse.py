@@ -430,4 +430,4 @@ def test_search_in_neighbors_example(po, orb, configs, tmp_path, matcher, check)
         assert np.array_equal(bi[found], h[0][found]) and np.array_equal(bd[found], h[1][found])
         total += int(found.sum())
     assert pos[0] == len(blob) and total >= 15 and fusedA >= 15 and fusedB >= 0
-    assert ("fused=%d,%d" % (fusedA, fusedB)) in out.stdout and "host_sequential_us=" in out.stdout
+    assert ("fused=%d,%d" % (fusedA, fusedB)) in out.stdout and "host_sequential_us=" in out.stdout and "researched=" in out.stdout

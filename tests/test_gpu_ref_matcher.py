@@ -11,18 +11,23 @@ The other entry points of a frame handle match against the frame the handle extr
 ("real": 484 keypoints, 500 - 800 points a case) run against that extraction: the test extracts the same synthetic image (ref_matcher_cases.SYNTH)
 and requires the stored frame.  Every other case - the generators' random blocks and the constructed chains - is stored as a handle can hold it
 (ref_matcher_cases.on_handle: integer coordinates, padded to the keypoint count of the POKE handle) and is written over that handle's keypoints
-(tests/test_gpu_search_kf.py: poke_keypoints); the grid comes from the caller's parameters.  No case of any file is left out."""
+(tests/test_gpu_search_kf.py: poke_keypoints); the grid comes from the caller's parameters.  No case of any file is left out.
+The two Fuse overloads return bestIdx / bestDist per (keyframe, point) and leave the map to the caller: their files hold the reference's run on a
+live map (event log, final map, nFused per keyframe), and the device's results go through the caller's replay of tests/fuse_replay.py - the first
+call in the stored shape, then the follow-up calls for points whose descriptor a Replace changed - before they are compared."""
 import numpy as np
 import pytest
 
+import fuse_replay
 import ref_matcher_cases as cases
 from oracle import pyref_matcher as rm
 from jetson_slam_amd.synth import synth_stereo_pair
 from test_bow_host import REAL_SEED
 from test_gpu_bow import bow_params, concat as concat_bow, padded, poke_frame
-from test_gpu_loop import bow_prm, dev_bow
+from test_gpu_fuse import concat as concat_fuse, dev_keyframes, dev_points, fuse_params, pose_arrays
+from test_gpu_loop import bow_prm, dev_bow, dev_sim3, sim3_prm
 from test_gpu_search_init import init_params
-from test_gpu_search_kf import poke_keypoints
+from test_gpu_search_kf import POINT_KEYS as KF_POINT_KEYS, c_params as kf_c_params, poke_keypoints
 from test_gpu_search_last_frame import run_device as run_last_frame
 from test_gpu_search_local import _dev, _mk, run_device as run_local
 from test_gpu_triangulation import KF1_DT, KF2_DT, concat, dev_side, tri_params
@@ -111,6 +116,75 @@ def test_search_for_triangulation(orb, matcher):
             names = [n for n, _ in call]
             assert mk.shape == want.shape and np.array_equal(mk, want) and np.array_equal(np.asarray(cnt).ravel(), count), (names, sync)
             assert matcher.stats() == stats, (names, matcher.stats(), stats)
+
+
+# ---- the two Fuse overloads: the device's best_idx / best_dist through the caller's replay, against the reference's run on a live map ----
+def device_fuse_search(orb, matcher, c, sync):
+    """fuse_replay's search on the device: one jsorb_fuse call per search, over the target keyframes and list points asked for, in the stored call
+    shape (all keyframes of a case in the first call), with the descriptors the map holds at that moment"""
+    prm = fuse_params(orb, cases.fuse_prm(c))
+
+    def search(ts, idxs, desc, skip):
+        sides = [cases.kf_side(c, int(c["targets"][t])) for t in ts]
+        start, cat = concat_fuse([K for K, _ in sides])
+        R, t, O = pose_arrays([pose for _, pose in sides])
+        dp, dk = dev_points(cases.list_points(c, idxs, desc)), dev_keyframes(cat)
+        if sync:
+            bi, bd, cnt = matcher.fuse_host(dp, start, dk, R, t, O, prm, skip=_dev(skip))
+        else:
+            bi, bd, cnt = matcher.fuse(dp, start, dk, R, t, O, prm, skip=_dev(skip))
+            bi, bd, cnt = bi.cpu().numpy(), bd.cpu().numpy(), cnt.cpu().numpy()
+        assert np.array_equal(np.asarray(cnt).ravel(), (bi >= 0).sum(1))
+        return bi, bd, matcher.fuse_stats()
+    return search
+
+
+@pytest.mark.parametrize("name", ["fuse", "fuse_sim3"])
+def test_fuse_through_the_replay(orb, matcher, name):
+    """every case of the file, check_reprojection 1 (Fuse(pKF, vpMapPoints, th)) and 0 (the overload with Scw): the events, the final map and nFused
+    per keyframe that the caller's replay makes of the device's results are the stored reference's, and the statistics of every device call - the
+    first over all target keyframes, then one per keyframe after which a descriptor changed - are the transcription's"""
+    golden = rm.load_golden(name)
+    m = cases.MATCHERS[name]
+    fused = n_calls = 0
+    for cname, c in golden.items():
+        c = m.prepare(c)
+        assert int(c["prm"]["check"]) == (name == "fuse")
+        for sync in (False, True):
+            got, calls, _ = fuse_replay.replay(c, device_fuse_search(orb, matcher, c, sync), "research")
+            try:
+                fuse_replay.same_map(got, c["out"])
+            except AssertionError as e:
+                raise AssertionError("%s / %s (sync %s): the replay of the device's result is not the reference's run" % (name, cname, sync)) from e
+            assert np.array_equal(np.asarray(calls, np.int64).reshape(-1, 4), c["counters"]["calls"]), (cname, sync, calls)
+        fused += int(c["out"]["nmatches"])
+        n_calls += len(calls)
+    assert fused > 500 and n_calls > len(golden)                   # not vacuous: the reference fused, and descriptors changed between keyframes
+    assert max(len(c["targets"]) for c in golden.values()) == 33   # one call crosses FUSE_KF_CHUNK
+
+
+def test_search_by_sim3(orb, matcher):
+    """every case, both call forms: the new entries of vpMatches12 (as keypoints of keyframe 2; the reference leaves the pre-filled ones as they
+    were), nFound and the statistics tuple"""
+    golden = rm.load_golden("search_by_sim3")
+    m = cases.MATCHERS["search_by_sim3"]
+    total = 0
+    for cname, c in golden.items():
+        c = m.prepare(c)
+        S1, S2 = cases.sim3_sides(c)
+        want, found, ctr = m.expected_m12(c), int(c["out"]["nmatches"]), c["counters"]
+        stats = tuple(int(ctr[k]) for k in ("windows", "walked", "distances", "largest")) + (found,)
+        for sync in (False, True):
+            d1, d2 = dev_sim3(S1), dev_sim3(S2)
+            if sync:
+                m1, m2, m12, n = matcher.search_by_sim3_host(d1, d2, sim3_prm(orb, cases.fuse_prm_sim3(c)))
+            else:
+                m1, m2, m12, n = matcher.search_by_sim3(d1, d2, sim3_prm(orb, cases.fuse_prm_sim3(c)))
+                m12, n = m12.cpu().numpy(), int(n.cpu()[0])
+            assert np.array_equal(m12, want) and int(n) == found, (cname, sync)
+            assert matcher.search_by_sim3_stats() == stats, (cname, matcher.search_by_sim3_stats(), stats)
+        total += found
+    assert total > 100
 
 
 # ---- the entry points of a frame handle ----
@@ -221,6 +295,43 @@ def test_search_for_initialization(orb, frame, poked):
         assert (st[0], st[1], st[2], st[3], tuple(st[4])) == want, (name, st, want)
         total += int(cnt.item())
     assert total > 500
+
+
+def test_search_by_projection_kf(orb, frame, poked):
+    """every case through handle_cases (the extracted frames and the POKE handle), both call forms: kp_match as slot numbers, the count and the
+    statistics.  The device gets the slots the caller would hand it (a live point that is not already found).  A stated difference
+    (ref_matcher_cases.STATED_DIFFERENCES) is asserted at the contract's value."""
+    import torch
+    m = cases.MATCHERS["search_kf"]
+    total = 0
+    for name, c, g in handle_cases(orb, "search_kf", frame, poked, angle=True):
+        F, prm = cases.kf_frame(c), cases.kf_prm(c)
+        P, idx = cases.kf_live(c)
+        blocked = _dev(np.asarray(F["blocked"], np.uint8))
+        stated = cases.STATED_DIFFERENCES.get(("search_kf", name), {})
+        want = np.where(c["out"]["kp_match"] == -2, -1, c["out"]["kp_match"])
+        count = int(c["out"]["nmatches"])
+        if "contract" in stated:
+            k = len(stated["contract"]["kp_match"])
+            want = np.concatenate([stated["contract"]["kp_match"], np.full(len(want) - k, -1)])
+            count = stated["contract"]["nmatches"]
+        ctr = c["counters"]
+        for sync in (False, True):
+            args = [_dev(P[k]) for k in KF_POINT_KEYS]
+            if sync:
+                km, cnt = g.search_by_projection_kf_host(*args, kf_c_params(orb, F, prm), blocked=blocked)
+            else:
+                mk, md, km, cnt = g.search_by_projection_kf(*args, kf_c_params(orb, F, prm), blocked=blocked)
+                torch.cuda.synchronize()
+                km, cnt = km.cpu().numpy(), int(cnt.cpu().numpy()[0])
+            km = np.asarray(km, np.int64)
+            slots = np.where(km >= 0, idx[np.maximum(km, 0)] if len(idx) else -1, -1)
+            assert np.array_equal(slots, want) and cnt == count, (name, sync)
+            st = g.search_by_projection_kf_stats()
+            assert st == (int(ctr["rounds"]), int(ctr["candidates"]), int(ctr["overflow"]), tuple(int(v) for v in ctr["ind"])), (name, st)
+        assert cnt > 100 or not cases.is_real(name), name
+        total += cnt
+    assert total > 1000
 
 
 def test_search_by_bow(orb, configs):

@@ -12,6 +12,13 @@ What the reference cannot be given is changed in the INPUT, never left out of a 
  - the device holds integer keypoint coordinates and a fixed keypoint count: the generators' frames of the three frame-handle matchers are
    stored with rounded coordinates, padded to the count of the handle they are written over (tests/ref_matcher_cases.py: on_handle);
  - an angle difference outside [0, 360) makes it index outside its histogram: such angles are folded into [0, 360).
+ - the projecting matchers (both Fuse overloads, SearchBySim3, SearchByProjection(Frame, KeyFrame)) compute pixel, distance and level on the device with K14 / K16's fused steps and in
+   the reference with separate float products and sums: their cases are built on inputs for which every such step is exact in float32 (rotations
+   that are signed permutations, power-of-two depths and scales, fx = fy = 256, a quarter-pixel grid), and the tool PROVES it per case
+   (ref_matcher_cases.prove_exact*), requires that no level depends on the logf in use, and that the reference's own u, v, dist3D, level and radius
+   (the harness's probe log) equal the contract's bit for bit, before it writes the case (Matcher.verify).
+ - where the library's contract differs from the reference's text on purpose (a depth of zero or below), the file stores the reference's output
+   and ref_matcher_cases.STATED_DIFFERENCES holds both sides.
 
 Usage: python tools/ref_matcher_goldens.py [name ...]      (no name: all)"""
 import os
@@ -37,8 +44,9 @@ def main(names):
         m = cases.MATCHERS[name]
         out, blocks = {}, {}
         for cname, case in m.build(po).items():
-            case = dict(case)
+            case = cases.named(m.prepare(dict(case)), m.driver, cname)
             case["out"] = rm.run(m.driver, case)
+            m.verify(po, case)
             case["counters"] = {k: np.asarray(v, np.int64) for k, v in m.counters(po, case, m.transcription(po, case)).items()}
             out[cname] = case
             if cases.block_of(cname):
