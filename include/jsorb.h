@@ -917,6 +917,77 @@ int jsorb_search_by_sim3(jsorb_keyframe_matcher *m, const jsorb_sim3_params *par
  * the first call.  Any pointer may be NULL. */
 int jsorb_search_by_sim3_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window, int *n_agree);
 
+/* ---- the loop's acceptance test: ORBmatcher::SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints,
+ * vector<MapPoint*> &vpMatched, int th) (src/ORBmatcher.cpp:277-390), as LoopClosing::ComputeSim3 calls it on the accepted candidate with the map
+ * points of the loop keyframe and its neighbours (src/LoopClosing.cpp:380, th = 10) before it counts nTotalMatches against 40 ----
+ * The search of one point is that of Fuse(pKF, Scw, ...) (:964-1087, jsorb_fuse_async with check_reprojection = 0).  What is new is state: a
+ * keypoint with vpMatched[idx] != NULL is hidden (:362), and a point that matches sets vpMatched[bestIdx] (:383) and so hides that keypoint from
+ * every LATER point of the call.  The result is that of the sequential loop.
+ * params->th is a float; the reference's is an int converted to float before its one product (:347), so whole numbers behave the same.  Rcw[9]
+ * (row-major), tcw[3] and Ow[3] are HOST values in the struct: the caller decomposes Scw as :286-290 does; the library does not redo cv::Mat
+ * products whose rounding nothing pins (the rule stated for F12 and for Fuse above).
+ * Inputs, DEVICE arrays.  Points i = 0 .. n_points-1 are the points the reference would search, in vpPoints order: the caller drops isBad() points
+ * and members of spAlreadyFound (:293-305), which are map state; dropping them changes no order.  Per point Px, Py, Pz (GetWorldPos), Nx, Ny, Nz
+ * (GetNormal), max_distance (mfMaxDistance), min_dist_inv / max_dist_inv (GetMinDistanceInvariance / GetMaxDistanceInvariance) float[n_points];
+ * desc n_points x 32 bytes (GetDescriptor), 16-byte aligned.  The keyframe, n_keypoints = N entries: x, y (mvKeysUn), octave int32, kf_desc N x 32
+ * bytes, 16-byte aligned; blocked uint8[N] = vpMatched[k] != NULL before the call (NULL: nothing is blocked).
+ * Per point, in index order, in the arithmetic jsorb_fuse_async defines (its item numbers):
+ *   items 1 and 2: K14's projection, no candidate unless Pcz > 0 (the reference's own test is Pcz < 0: Pcz == 0 reaches an infinite invz and fails
+ *     IsInImage, and so does a NaN), and KeyFrame::IsInImage, half open
+ *   items 4 and 5: K16's distance gate with Ow, and the viewing angle dot < 0.5f*dist; a NaN passes, as written
+ *   items 6 and 7: the predicted level, radius = th * scale_factor[L], cells and walk order
+ *   there is no ur (item 3) and no chi-square gate
+ * then per keypoint k of the window, in walk order, from bestDist = 256:
+ *   k is hidden when blocked[k] is set, or when an EARLIER point of this call matched k (:362)
+ *   window: that of item 8, fabsf(x[k] - u) < radius && fabsf(y[k] - v) < radius
+ *   level: octave[k] in [L-1, L], a plain integer comparison (:367); no table is indexed by the octave
+ *   d = popcount Hamming distance; strict < updates bestDist, bestIdx: the first in walk order wins a tie (:374)
+ * The point matches iff bestDist <= th_low (:381).  Only a matching point hides its keypoint: one whose best lies above th_low claims nothing.
+ * Outputs (DEVICE, every entry written): match_kp[n_points] = the keypoint or -1; match_dist[n_points] = bestDist of a match or -1;
+ * kp_match[N] = the point that holds keypoint k after the call or -1 - keypoints blocked before the call stay -1; the caller writes
+ * vpMatched[k] = vpPoints[kp_match[k]] where it is >= 0 and leaves the rest alone; *n_matches_dev = the return value.
+ * Enqueued on the matcher's stream, no host decision after the argument checks, capturable once the scratch has its size: k_fuse_grids over the
+ * one keyframe, k_scw_candidates (per point the keys distance << 18 | walk position of the candidates at or below th_low - no other key can
+ * become a match, whatever is hidden), k_scw_resolve (one workgroup: the claim rule as a fixed point).
+ * Limits: N < 2^18 = 262144; cols * rows <= 4096; n_levels in [1, JSORB_MAX_LEVELS]; th_low in [0, 255]; JSORB_ERR_INVALID for these, a NULL
+ * required pointer, descriptors not 16-byte aligned, a negative n_points.  n_points == 0 or N == 0 is a valid call: it writes -1 / 0 and launches
+ * nothing that reads.  The statistics words and the "done" mark are the call's own: the other calls of the keyframe matcher leave them alone, and
+ * this one leaves theirs. */
+typedef struct jsorb_scw_params {
+    float th;                        /* 10 in LoopClosing::ComputeSim3 */
+    int th_low;                      /* ORBmatcher::TH_LOW = 50; [0, 255] */
+    float fx, fy, cx, cy;            /* pKF->fx .. cy */
+    float min_x, max_x, min_y, max_y; /* KeyFrame::mnMinX, mnMaxX, mnMinY, mnMaxY: IsInImage's bounds and the grid origin */
+    float inv_w, inv_h;              /* mfGridElementWidthInv, mfGridElementHeightInv */
+    int cols, rows;                  /* mnGridCols, mnGridRows */
+    float log_scale_factor;          /* KeyFrame::mfLogScaleFactor */
+    int n_levels;                    /* mnScaleLevels, [1, JSORB_MAX_LEVELS] */
+    float scale_factor[JSORB_MAX_LEVELS];        /* mvScaleFactors */
+    float Rcw[9], tcw[3], Ow[3];     /* HOST: Scw decomposed as :286-290 - sRcw / scw row-major, Scw's translation / scw, -Rcw^T tcw */
+} jsorb_scw_params;
+int jsorb_search_by_projection_sim3_async(jsorb_keyframe_matcher *m, const jsorb_scw_params *params, int n_points, const float *Px, const float *Py,
+                                          const float *Pz, const float *Nx, const float *Ny, const float *Nz, const float *max_distance,
+                                          const float *min_dist_inv, const float *max_dist_inv, const uint8_t *desc, int n_keypoints, const float *x,
+                                          const float *y, const int32_t *octave, const uint8_t *kf_desc, const uint8_t *blocked, int32_t *match_kp,
+                                          int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev);
+/* Synchronous: the same into buffers of the matcher; match_kp_host[n_points], match_dist_host[n_points] and kp_match_host[N] (the last two may be
+ * NULL) and *n_matches (host), one copy back. */
+int jsorb_search_by_projection_sim3(jsorb_keyframe_matcher *m, const jsorb_scw_params *params, int n_points, const float *Px, const float *Py,
+                                    const float *Pz, const float *Nx, const float *Ny, const float *Nz, const float *max_distance,
+                                    const float *min_dist_inv, const float *max_dist_inv, const uint8_t *desc, int n_keypoints, const float *x,
+                                    const float *y, const int32_t *octave, const uint8_t *kf_desc, const uint8_t *blocked, int32_t *match_kp_host,
+                                    int32_t *match_dist_host, int32_t *kp_match_host, int *n_matches);
+/* Diagnostics of the last call (waits for it): rounds = the rounds of the fixed point (at most n_points + 1); n_kept = the keys kept over all
+ * points (candidates that passed the window, blocked and level filters with a distance <= th_low); n_overflow = points with more kept keys than the
+ * build's list cap, which walk their window again; n_windows = points that reached a window; n_distances = Hamming distances k_scw_candidates
+ * computed (the filters' survivors, kept or not); largest_window = the most keypoints in the cells of one window.  JSORB_ERR_STATE before the
+ * first call.  Any pointer may be NULL. */
+int jsorb_search_by_projection_sim3_stats(jsorb_keyframe_matcher *m, int *rounds, int *n_kept, int *n_overflow, int *n_windows, int *n_distances,
+                                          int *largest_window);
+/* The compile-time caps of this build's k_scw.hip (no device needed): keys k_scw_candidates keeps per point (32), keypoints up to which
+ * k_scw_resolve keeps its claims in LDS (16384).  A test build lowers both (jetson_slam_amd/build.py VARIANTS). */
+int jsorb_scw_build_caps(int *cap, int *lds_claims);
+
 /* ---- memory: what orb_cuda::SyncedMem<T> needs (include/cuda/synced_mem_holder.hpp:10-65, src/cuda/synced_mem_holder.cpp:8-199) ----
  * The reference's untouched host code (ORBmatcher.cpp:1673-1877, Tracking.cpp:1427-1600, orb_stereo_match.cu statics) allocates
  * pinned-host + device buffer pairs and moves data with cudaMemcpy(Async) on a private stream; these calls are the HIP side of

@@ -18,9 +18,11 @@
 #define JSORB_COMPAT_HPP
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <type_traits>
 #include <utility>
@@ -565,6 +567,21 @@ struct BowKeyframeSide {
 struct Sim3Side : jsorb_sim3_side {
     Sim3Side() : jsorb_sim3_side() {}
 };
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): a map point as that call reads it, HOST values - GetWorldPos, GetNormal, mfMaxDistance,
+// GetMinDistanceInvariance, GetMaxDistanceInvariance, GetDescriptor and isBad() - and the keyframe's mvKeysUn (x / y / octave) and mDescriptors
+// as DEVICE arrays, which a loop-closing thread keeps from SearchByBoW(KF, KF) and SearchBySim3.
+struct ScwPoint {
+    float pos[3] = {0, 0, 0}, normal[3] = {0, 0, 0};
+    float max_distance = 0, min_dist_inv = 0, max_dist_inv = 0;
+    unsigned char descriptor[32] = {};
+    bool bad = false;
+};
+struct ScwKeyframe {
+    int n = 0;
+    const float *x = nullptr, *y = nullptr;
+    const int32_t *octave = nullptr;
+    const unsigned char *descriptors = nullptr;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -888,6 +905,63 @@ inline int SearchBySim3(jsorb::KeyframeMatcher &matcher, const jsorb_sim3_params
     match12.resize(side1.n > 0 ? side1.n : 0);
     if (vnMatch1) vnMatch1->resize(match12.size());
     if (vnMatch2) vnMatch2->resize(side2.n > 0 ? side2.n : 0);
+    return found;
+}
+
+// matcher.SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10) (ORBmatcher.cpp:277-390, LoopClosing.cpp:380) in the
+// reference's argument shape: Scw 4 x 4 row-major, vpPoints the loop points, vpMatched[k] the point keypoint k holds (nullptr: none; resized to the
+// keyframe's keypoints).  Here, as the reference does: Scw decomposed (:286-290), bad points and members of spAlreadyFound dropped (:293-305), and
+// vpMatched[bestIdx] = pMP written for every match (:383).  The dropped points are map state, which is why this is host code; the points that
+// remain go to the device in one upload and the matches come back in one copy.  params: camera, bounds, grid and levels of the keyframe (th and
+// the pose are set here).  Returns nmatches.  (Build the caller without floating-point contraction if Scw is not a scaled rigid motion of
+// dyadic numbers: the decomposition is the reference's, term for term, only when no product is fused into a sum.)
+inline int SearchByProjection(jsorb::KeyframeMatcher &matcher, jsorb_scw_params params, const jsorb::ScwKeyframe &kf, const float *Scw,
+                              const std::vector<const jsorb::ScwPoint *> &vpPoints, std::vector<const jsorb::ScwPoint *> &vpMatched, int th)
+{
+    const int N = kf.n > 0 ? kf.n : 0;
+    vpMatched.resize((size_t)N, nullptr);
+    // :286-290
+    const float scw = std::sqrt(Scw[0] * Scw[0] + Scw[1] * Scw[1] + Scw[2] * Scw[2]);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) params.Rcw[3 * r + c] = Scw[4 * r + c] / scw;
+        params.tcw[r] = Scw[4 * r + 3] / scw;
+    }
+    for (int c = 0; c < 3; c++) params.Ow[c] = -(params.Rcw[c] * params.tcw[0] + params.Rcw[3 + c] * params.tcw[1] + params.Rcw[6 + c] * params.tcw[2]);
+    params.th = (float)th;
+    // :293-305
+    std::set<const jsorb::ScwPoint *> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+    spAlreadyFound.erase(nullptr);
+    std::vector<const jsorb::ScwPoint *> searched;
+    for (const jsorb::ScwPoint *pMP : vpPoints)
+        if (pMP && !pMP->bad && !spAlreadyFound.count(pMP)) searched.push_back(pMP);
+    const int n = (int)searched.size();
+    // one upload: nine float arrays of n, the descriptors (16-byte aligned), blocked
+    const size_t nf = ((size_t)n + 3) / 4 * 4, fl = 9 * nf * sizeof(float), bytes = fl + 32 * (size_t)n + (size_t)N + 16;
+    std::vector<unsigned char> host(bytes, 0);
+    float *f = reinterpret_cast<float *>(host.data());
+    for (int i = 0; i < n; i++) {
+        const jsorb::ScwPoint &p = *searched[(size_t)i];
+        for (int a = 0; a < 3; a++) { f[a * nf + i] = p.pos[a]; f[(3 + a) * nf + i] = p.normal[a]; }
+        f[6 * nf + i] = p.max_distance; f[7 * nf + i] = p.min_dist_inv; f[8 * nf + i] = p.max_dist_inv;
+        std::memcpy(host.data() + fl + 32 * (size_t)i, p.descriptor, 32);
+    }
+    for (int k = 0; k < N; k++) host[fl + 32 * (size_t)n + k] = vpMatched[(size_t)k] != nullptr;
+    void *dev = nullptr;
+    if (jsorb_mem_alloc_device(bytes, &dev) != JSORB_OK || jsorb_mem_h2d(dev, host.data(), bytes) != JSORB_OK) {
+        if (dev) jsorb_mem_free_device(dev);
+        throw std::runtime_error(std::string("SearchByProjection: ") + jsorb_mem_last_error());
+    }
+    const float *d = static_cast<const float *>(dev);
+    const unsigned char *db = static_cast<const unsigned char *>(dev) + fl;
+    std::vector<int32_t> match_kp((size_t)n + 1, -1), kp_match((size_t)N + 1, -1);
+    int found = 0;
+    const int rc = jsorb_search_by_projection_sim3(matcher.handle(), &params, n, d, d + nf, d + 2 * nf, d + 3 * nf, d + 4 * nf, d + 5 * nf, d + 6 * nf,
+                                                   d + 7 * nf, d + 8 * nf, db, N, kf.x, kf.y, kf.octave, kf.descriptors, db + 32 * (size_t)n,
+                                                   match_kp.data(), nullptr, kp_match.data(), &found);
+    jsorb_mem_free_device(dev);
+    if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_search_by_projection_sim3: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    for (int k = 0; k < N; k++)
+        if (kp_match[(size_t)k] >= 0) vpMatched[(size_t)k] = searched[(size_t)kp_match[(size_t)k]];      // :383
     return found;
 }
 

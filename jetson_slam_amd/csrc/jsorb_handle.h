@@ -298,7 +298,7 @@ struct jsorb_extractor {
 };
 
 // The keyframe matcher of LocalMapping and LoopClosing (jsorb_keyframes.hip: create, destroy, streams, triangulation, fuse; jsorb_loop.hip: the
-// loop-closing matchers).  It belongs to no extractor handle.
+// loop-closing matchers, SearchByProjection(pKF, Scw, ...) among them).  It belongs to no extractor handle.
 struct jsorb_keyframe_matcher {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -306,13 +306,18 @@ struct jsorb_keyframe_matcher {
     unsigned long long *sort1 = nullptr, *sort2 = nullptr;      // sorted keys of KF1 (cap1) and of the KF2s (cap2): grown only
     int cap1 = 0, cap2 = 0;
     // one state per kind of call, each with statistics and a "done" mark of its own.  The synchronous forms' buffers: counts (256), then match12
-    // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all
-    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, N_CALLS };
+    // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all;
+    // scw: the count, then match_kp, match_dist and kp_match, out_cap in all
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, N_CALLS };
     KfCall call[N_CALLS];
     int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
     uint8_t *matched2 = nullptr;                                // BoW: vbMatched2, one byte per candidate keypoint (matched2_cap)
     int matched2_cap = 0;
+    struct {                                                    // jsorb_search_by_projection_sim3* (jsorb_loop.hip): k_scw_candidates' lists, grown only
+        int *cand = nullptr, *cand_n = nullptr;                 // cand_cap x scw_cap() kept keys, cand_n_cap counts
+        int cand_cap = 0, cand_n_cap = 0;
+    } scw;
     std::string err;
 };
 

@@ -338,6 +338,29 @@ struct Sim3Args {
 };
 void launch_sim3_match(const Sim3Args &a, hipStream_t s);
 void launch_sim3_agree(const Sim3Args &a, hipStream_t s);
+// k_scw_candidates / k_scw_resolve (k_scw.hip): ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th); the grid is launch_fuse_grids'
+struct ScwArgs {
+    jsorb_scw_params p;                          // window, threshold, camera, bounds, grid, levels, pose
+    // the loop points, in vpPoints order
+    int n_points;
+    const float *Px, *Py, *Pz, *Nx, *Ny, *Nz, *max_distance, *min_dist_inv, *max_dist_inv;
+    const uint8_t *mp_desc;
+    // the keyframe
+    int n_kp;
+    const float *x, *y;                          // mvKeysUn
+    const int32_t *octave;
+    const uint8_t *kf_desc;
+    const uint8_t *blocked;                      // vpMatched[k] != NULL before the call (NULL: none)
+    const int32_t *cell_start, *cell_items;      // k_fuse_grids' CSR
+    // workspace and outputs
+    int *cand, *cand_n;                          // n_points x scw_cap() kept keys (distance << 18 | CSR position, distance <= th_low) in walk order, n_points counts
+    int32_t *match_kp, *match_dist, *kp_match, *n_matches;
+    int *stats;                                  // rounds, keys kept, points over the capacity, points with a window, distances, largest window (cleared to 0)
+};
+int scw_cap();                                  // the compile-time caps of k_scw.hip (jsorb_scw_build_caps)
+int scw_lds_claims();
+void launch_scw_candidates(const ScwArgs &a, hipStream_t s);
+void launch_scw_resolve(const ScwArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

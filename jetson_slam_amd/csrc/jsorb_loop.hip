@@ -1,15 +1,17 @@
-// jsorb_loop.hip - host side of the keyframe matcher's loop-closing calls (jsorb_search_by_bow_kf*, jsorb_search_by_sim3*): the matchers of
-// LoopClosing::ComputeSim3.  They run on the jsorb_keyframe_matcher of jsorb_keyframes.hip (LoopClosing is a thread of its own and creates its own),
+// jsorb_loop.hip - host side of the keyframe matcher's loop-closing calls (jsorb_search_by_bow_kf*, jsorb_search_by_sim3*,
+// jsorb_search_by_projection_sim3*): the matchers of LoopClosing::ComputeSim3.  They run on the jsorb_keyframe_matcher of jsorb_keyframes.hip (LoopClosing is a thread of its own and creates its own),
 // each with a call state of its own (KfCall).  The kernels are in k_loop.hip; the grouping is k_bow.hip's k_bow_group with KF1 as the frame side,
-// the rotation check k_triangulate.hip's k_tri_resolve, the grids k_fuse.hip's k_fuse_grids.
+// the rotation check k_triangulate.hip's k_tri_resolve, the grids k_fuse.hip's k_fuse_grids; SearchByProjection(pKF, Scw, ...)'s are in k_scw.hip.
 #include "jsorb_handle.h"
 
 namespace {
 
 // The calls' statistics words (KF_STATS each).  search_by_bow_kf: node pairs, distances, ., largest node, ind1 + 1, ind2 + 1, ind3 + 1 (the triangulation
 // matcher's layout, k_tri_resolve's kept bins).  search_by_sim3: windows, walked, distances, largest window, agreements.
+// search_by_projection_sim3: rounds, keys kept, points over the cap (claim_resolve's three), windows, distances, largest window.
 // The feature names and texts the shared frames (jsorb_handle.h: kf_*) put into the refusals:
 const char *const BOW_KF = "search_by_bow_kf", *const BOW_KF_N1 = "n1 must be in [0, 262143]", *const SIM3 = "search_by_sim3";
+const char *const SCW = "search_by_projection_sim3";
 
 int sim3_check(jsorb_keyframe_matcher *m, const jsorb_sim3_params *p, const jsorb_sim3_side *s1, const jsorb_sim3_side *s2)
 {
@@ -24,6 +26,24 @@ int sim3_check(jsorb_keyframe_matcher *m, const jsorb_sim3_params *p, const jsor
             return kf_fail(m, SIM3, "NULL side array");
         if (s->n > 0 && ((uintptr_t)s->kp_desc % 16 || (uintptr_t)s->mp_desc % 16)) return kf_fail(m, SIM3, "descriptors must be 16-byte aligned");
     }
+    return JSORB_OK;
+}
+
+// the argument checks both forms of jsorb_search_by_projection_sim3 share (the outputs are each form's own)
+int scw_check(jsorb_keyframe_matcher *m, const jsorb_scw_params *p, int n_points, const float *Px, const float *Py, const float *Pz, const float *Nx,
+              const float *Ny, const float *Nz, const float *max_distance, const float *min_dist_inv, const float *max_dist_inv, const uint8_t *desc,
+              int n_keypoints, const float *x, const float *y, const int32_t *octave, const uint8_t *kf_desc)
+{
+    if (!p) return kf_fail(m, SCW, "NULL params");
+    if (p->n_levels < 1 || p->n_levels > JSORB_MAX_LEVELS) return kf_fail(m, SCW, "n_levels out of range");
+    if (p->th_low < 0 || p->th_low > 255) return kf_fail(m, SCW, "th_low must be in [0, 255]");
+    if (p->cols < 1 || p->rows < 1 || (long long)p->cols * p->rows > FUSE_MAX_CELLS) return kf_fail(m, SCW, "grid size out of range (cols*rows <= 4096)");
+    if (n_points < 0) return kf_fail(m, SCW, "n_points must not be negative");
+    if (n_keypoints < 0 || n_keypoints >= (1 << 18)) return kf_fail(m, SCW, "n_keypoints must be in [0, 262143]");
+    if (n_points > 0 && (!Px || !Py || !Pz || !Nx || !Ny || !Nz || !max_distance || !min_dist_inv || !max_dist_inv || !desc))
+        return kf_fail(m, SCW, "NULL point array");
+    if (n_keypoints > 0 && (!x || !y || !octave || !kf_desc)) return kf_fail(m, SCW, "NULL keyframe array");
+    if ((n_points > 0 && (uintptr_t)desc % 16) || (n_keypoints > 0 && (uintptr_t)kf_desc % 16)) return kf_fail(m, SCW, "descriptors must be 16-byte aligned");
     return JSORB_OK;
 }
 
@@ -186,6 +206,99 @@ int jsorb_search_by_sim3_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n
     if (n_distances) *n_distances = s[2];
     if (largest_window) *largest_window = s[3];
     if (n_agree) *n_agree = s[4];
+    return JSORB_OK;
+}
+
+int jsorb_scw_build_caps(int *cap, int *lds_claims)
+{
+    if (cap) *cap = scw_cap();
+    if (lds_claims) *lds_claims = scw_lds_claims();
+    return JSORB_OK;
+}
+
+int jsorb_search_by_projection_sim3_async(jsorb_keyframe_matcher *m, const jsorb_scw_params *params, int n_points, const float *Px, const float *Py,
+                                          const float *Pz, const float *Nx, const float *Ny, const float *Nz, const float *max_distance,
+                                          const float *min_dist_inv, const float *max_dist_inv, const uint8_t *desc, int n_keypoints, const float *x,
+                                          const float *y, const int32_t *octave, const uint8_t *kf_desc, const uint8_t *blocked, int32_t *match_kp,
+                                          int32_t *match_dist, int32_t *kp_match, int32_t *n_matches_dev)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    RCCHK(scw_check(m, params, n_points, Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv, desc, n_keypoints, x, y, octave, kf_desc));
+    if (!n_matches_dev || (n_points > 0 && (!match_kp || !match_dist)) || (n_keypoints > 0 && !kp_match)) return kf_fail(m, SCW, "NULL output");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int n_cells = params->cols * params->rows;
+    RCCHK(reserve_grids(m, 1, n_cells, n_keypoints));
+    const int want = std::max(n_points, 1);
+    RCCHK(reserve_device(m, m->scw.cand, (size_t)want * scw_cap() * sizeof(int), &m->scw.cand_cap, want));
+    RCCHK(reserve_device(m, m->scw.cand_n, (size_t)want * sizeof(int), &m->scw.cand_n_cap, want));
+    KfCall &c = m->call[jsorb_keyframe_matcher::SCW];
+    hipStream_t st = m->stream;
+    bool run = false;
+    RCCHK(kf_clear(m, c, st, 1, 0, 0, n_matches_dev, nullptr, &run));      // the statistics and the one count; the three arrays are written below
+    if (n_points == 0 || n_keypoints == 0) {        // nothing to search, or nothing to search in: everything is -1 / 0
+        if (n_points > 0) {
+            HIPCHK(m, hipMemsetAsync(match_kp, 0xff, (size_t)n_points * sizeof(int32_t), st));
+            HIPCHK(m, hipMemsetAsync(match_dist, 0xff, (size_t)n_points * sizeof(int32_t), st));
+        }
+        if (n_keypoints > 0) HIPCHK(m, hipMemsetAsync(kp_match, 0xff, (size_t)n_keypoints * sizeof(int32_t), st));
+        return JSORB_OK;
+    }
+    // the keyframe's grid: k_fuse_grids over one keyframe
+    FuseGridArgs g = fuse_grid_args(*params, x, y, m->grid_start, m->grid_items);
+    g.kf_start[1] = n_keypoints;
+    launch_fuse_grids(g, 1, st);
+    HIPCHK(m, hipGetLastError());
+    ScwArgs a{};
+    a.p = *params;
+    a.n_points = n_points; a.Px = Px; a.Py = Py; a.Pz = Pz; a.Nx = Nx; a.Ny = Ny; a.Nz = Nz;
+    a.max_distance = max_distance; a.min_dist_inv = min_dist_inv; a.max_dist_inv = max_dist_inv; a.mp_desc = desc;
+    a.n_kp = n_keypoints; a.x = x; a.y = y; a.octave = octave; a.kf_desc = kf_desc; a.blocked = blocked;
+    a.cell_start = m->grid_start; a.cell_items = m->grid_items;
+    a.cand = m->scw.cand; a.cand_n = m->scw.cand_n;
+    a.match_kp = match_kp; a.match_dist = match_dist; a.kp_match = kp_match; a.n_matches = n_matches_dev; a.stats = c.stats;
+    launch_scw_candidates(a, st);
+    HIPCHK(m, hipGetLastError());
+    launch_scw_resolve(a, st);
+    HIPCHK(m, hipGetLastError());
+    return JSORB_OK;
+}
+
+// The synchronous form, in the manner of jsorb_search_by_sim3: one count and three arrays of two lengths that come back in one copy
+int jsorb_search_by_projection_sim3(jsorb_keyframe_matcher *m, const jsorb_scw_params *params, int n_points, const float *Px, const float *Py,
+                                    const float *Pz, const float *Nx, const float *Ny, const float *Nz, const float *max_distance,
+                                    const float *min_dist_inv, const float *max_dist_inv, const uint8_t *desc, int n_keypoints, const float *x,
+                                    const float *y, const int32_t *octave, const uint8_t *kf_desc, const uint8_t *blocked, int32_t *match_kp_host,
+                                    int32_t *match_dist_host, int32_t *kp_match_host, int *n_matches)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    RCCHK(scw_check(m, params, n_points, Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv, desc, n_keypoints, x, y, octave, kf_desc));
+    if (!n_matches || (n_points > 0 && !match_kp_host)) return kf_fail(m, SCW, "NULL host output");
+    HIPCHK(m, hipSetDevice(m->device));
+    const int want = 2 * n_points + n_keypoints + 1;
+    KfCall &c = m->call[jsorb_keyframe_matcher::SCW];
+    RCCHK(reserve_device(m, c.out, (size_t)want * sizeof(int32_t), &c.out_cap, want));
+    int32_t *cnt = c.out, *mk = cnt + 1, *md = mk + n_points, *km = md + n_points;
+    RCCHK(jsorb_search_by_projection_sim3_async(m, params, n_points, Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv, desc, n_keypoints, x,
+                                                y, octave, kf_desc, blocked, mk, md, km, cnt));
+    std::vector<int32_t> h((size_t)want);            // the count and the three arrays lie next to each other: one copy
+    HIPCHK(m, hipMemcpyAsync(h.data(), cnt, (size_t)want * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(m, hipStreamSynchronize(m->stream));
+    *n_matches = h[0];
+    if (n_points > 0) memcpy(match_kp_host, h.data() + 1, (size_t)n_points * sizeof(int32_t));
+    if (n_points > 0 && match_dist_host) memcpy(match_dist_host, h.data() + 1 + n_points, (size_t)n_points * sizeof(int32_t));
+    if (n_keypoints > 0 && kp_match_host) memcpy(kp_match_host, h.data() + 1 + 2 * n_points, (size_t)n_keypoints * sizeof(int32_t));
+    return JSORB_OK;
+}
+
+int jsorb_search_by_projection_sim3_stats(jsorb_keyframe_matcher *m, int *rounds, int *n_kept, int *n_overflow, int *n_windows, int *n_distances,
+                                          int *largest_window)
+{
+    if (!m) return JSORB_ERR_INVALID;
+    int32_t s[KF_STATS] = {0};
+    RCCHK(kf_stats(m, m->call[jsorb_keyframe_matcher::SCW], "search_by_projection_sim3_stats before jsorb_search_by_projection_sim3", s));
+    int *out[6] = {rounds, n_kept, n_overflow, n_windows, n_distances, largest_window};
+    for (int i = 0; i < 6; i++)
+        if (out[i]) *out[i] = s[i];
     return JSORB_OK;
 }
 

@@ -67,6 +67,7 @@ EXPORTS = [
     "jsorb_search_for_triangulation_stats", "jsorb_fuse_async", "jsorb_fuse", "jsorb_fuse_stats",
     "jsorb_search_by_bow_kf_async", "jsorb_search_by_bow_kf", "jsorb_search_by_bow_kf_stats", "jsorb_loop_build_caps",
     "jsorb_search_by_sim3_async", "jsorb_search_by_sim3", "jsorb_search_by_sim3_stats",
+    "jsorb_search_by_projection_sim3_async", "jsorb_search_by_projection_sim3", "jsorb_search_by_projection_sim3_stats", "jsorb_scw_build_caps",
 ]
 
 
@@ -215,6 +216,43 @@ def make_sim3_params(camera, bounds, grid, log_scale_factor, scale_factor, th=7.
     p = JsorbSim3Params(th, int(th_high), *camera, *bounds, *grid, cols, rows, log_scale_factor, len(sf))
     for l in range(min(len(sf), MAX_LEVELS)):
         p.scale_factor[l] = sf[l]
+    return p
+
+
+class JsorbScwParams(C.Structure):
+    _fields_ = [("th", C.c_float), ("th_low", C.c_int)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")] + \
+               [("cols", C.c_int), ("rows", C.c_int), ("log_scale_factor", C.c_float), ("n_levels", C.c_int), ("scale_factor", C.c_float * MAX_LEVELS),
+                ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)]
+
+
+def scw_from_pose(Scw):
+    """Scw (4 x 4) decomposed in float32, term for term as ORBmatcher.cpp:286-290 does: scw = sqrt(row 0 of sRcw . itself) with the products
+    summed left to right, Rcw = sRcw / scw, tcw = Scw's translation / scw, Ow = -Rcw^T tcw (each row: the products summed left to right, then the
+    sign).  -> (Rcw float32[9] row-major, tcw float32[3], Ow float32[3])"""
+    f = np.float32
+    S = np.asarray(Scw, np.float32).reshape(4, 4)
+    sR = S[:3, :3]
+    scw = f(np.sqrt(f(f(f(sR[0, 0] * sR[0, 0]) + f(sR[0, 1] * sR[0, 1])) + f(sR[0, 2] * sR[0, 2]))))
+    R = (sR / scw).astype(np.float32)
+    t = (S[:3, 3] / scw).astype(np.float32)
+    O = np.array([-f(f(f(R[0, c] * t[0]) + f(R[1, c] * t[1])) + f(R[2, c] * t[2])) for c in range(3)], np.float32)
+    return R.ravel(), t, O
+
+
+def scw_params(camera, bounds, grid, log_scale_factor, scale_factor, Rcw, tcw, Ow, th=10.0, th_low=TH_LOW, cols=64, rows=48):
+    """jsorb_scw_params of LoopClosing::ComputeSim3's SearchByProjection(pKF, Scw, vpPoints, vpMatched, 10) (ORBmatcher.cpp:277): camera = (fx, fy,
+    cx, cy) of pKF, bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), grid = (mfGridElementWidthInv, mfGridElementHeightInv) over cols x rows,
+    log_scale_factor = mfLogScaleFactor, scale_factor the float table mvScaleFactors; Rcw (9, row-major), tcw (3), Ow (3) as scw_from_pose gives them"""
+    sf = np.ascontiguousarray(scale_factor, np.float32).ravel()
+    p = JsorbScwParams(th, int(th_low), *camera, *bounds, *grid, cols, rows, log_scale_factor, len(sf))
+    for l in range(min(len(sf), MAX_LEVELS)):
+        p.scale_factor[l] = sf[l]
+    for name, v, size in (("Rcw", Rcw, 9), ("tcw", tcw, 3), ("Ow", Ow, 3)):
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        if len(v) != size:
+            raise JsorbError("scw_params: %s must hold %d floats" % (name, size))
+        setattr(p, name, (C.c_float * size)(*v.tolist()))
     return p
 
 
@@ -374,6 +412,10 @@ def load_library(path=None):
         "jsorb_search_by_sim3_async": (I, [P, C.POINTER(JsorbSim3Params), C.POINTER(JsorbSim3Side), C.POINTER(JsorbSim3Side)] + [P] * 4),
         "jsorb_search_by_sim3": (I, [P, C.POINTER(JsorbSim3Params), C.POINTER(JsorbSim3Side), C.POINTER(JsorbSim3Side)] + [P] * 3 + [C.POINTER(I)]),
         "jsorb_search_by_sim3_stats": (I, [P] + [C.POINTER(I)] * 5),
+        "jsorb_search_by_projection_sim3_async": (I, [P, C.POINTER(JsorbScwParams), I] + [P] * 10 + [I] + [P] * 9),
+        "jsorb_search_by_projection_sim3": (I, [P, C.POINTER(JsorbScwParams), I] + [P] * 10 + [I] + [P] * 8 + [C.POINTER(I)]),
+        "jsorb_search_by_projection_sim3_stats": (I, [P] + [C.POINTER(I)] * 6),
+        "jsorb_scw_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -532,6 +574,13 @@ def loop_build_caps():
     r = C.c_int()
     load_library().jsorb_loop_build_caps(C.byref(r))
     return r.value
+
+
+def scw_build_caps():
+    """jsorb_scw_build_caps of the loaded library: (keys k_scw_candidates keeps per point, keypoints up to which k_scw_resolve claims in LDS)"""
+    c, l = C.c_int(), C.c_int()
+    load_library().jsorb_scw_build_caps(C.byref(c), C.byref(l))
+    return c.value, l.value
 
 
 def bow_transform_descriptors(voc, descriptors):
@@ -829,6 +878,43 @@ class KeyframeMatcher:
         directions together"""
         v = [C.c_int() for _ in range(5)]
         self._chk(self._lib.jsorb_search_by_sim3_stats(self._m, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+    # ---- LoopClosing::ComputeSim3's acceptance test: SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) ----
+    SCW_KF_KEYS = ("x", "y", "octave", "desc", "blocked")
+
+    def _scw_args(self, points, keyframe, params):
+        """-> (device, n_points, N, arguments) of jsorb_search_by_projection_sim3* (nothing of `self` is read)"""
+        import torch
+        what, K = "search_by_projection_sim3", KeyframeMatcher
+        if not isinstance(params, JsorbScwParams):
+            raise JsorbError("%s: params must come from scw_params" % what)
+        dt = dict(octave=(torch.int32,), desc=(torch.uint8,), blocked=(torch.uint8, torch.bool))
+        if not hasattr(points.get("Px"), "shape") or not hasattr(keyframe.get("x"), "shape"):
+            raise JsorbError("%s: points['Px'] and keyframe['x'] must be device tensors" % what)
+        n, N = int(points["Px"].shape[0]), int(keyframe["x"].shape[0])
+        pp = K._side(what, points, K.POINT_KEYS, dt, "points", n, optional=())
+        pk = K._side(what, keyframe, K.SCW_KF_KEYS, dt, "keyframe", N, optional=("blocked",))
+        return points["Px"].device, n, N, [C.byref(params), n] + pp + [N] + pk
+
+    def search_by_projection_sim3(self, points, keyframe, params, sync=False, wait=True):
+        """jsorb_search_by_projection_sim3_async (sync=False) or jsorb_search_by_projection_sim3 (sync=True): the n loop points the reference would
+        search, in vpPoints order (dict of device tensors: Px, Py, Pz, Nx, Ny, Nz, max_distance, min_dist_inv, max_dist_inv float32[n], desc
+        uint8[n, 32]) against the keyframe (dict: x, y float32[N], octave int32[N], desc uint8[N, 32] and blocked uint8 / bool [N] or None / absent:
+        nothing blocked).  Returns (match_kp int32[n], match_dist int32[n], kp_match int32[N], n_matches): device tensors (n_matches int32[1]) with
+        sync=False - wait= as in search_for_triangulation, with the same rule for the returned tensors' lifetime - or host arrays and a number
+        with sync=True."""
+        dev, n, N, args = self._scw_args(points, keyframe, params)
+        if sync:
+            return self._call_host("jsorb_search_by_projection_sim3", args, dev, [(n,), (n,), (N,), ()])
+        return self._enqueue("jsorb_search_by_projection_sim3_async", args, dev, [(n,), (n,), (N,), (1,)], wait)
+
+    def search_by_projection_sim3_stats(self):
+        """(rounds of the fixed point, keys kept, points over the list cap, points that reached a window, Hamming distances, the largest window) of
+        the last search_by_projection_sim3"""
+        v = [C.c_int() for _ in range(6)]
+        self._chk(self._lib.jsorb_search_by_projection_sim3_stats(self._m, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 

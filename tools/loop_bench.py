@@ -1,9 +1,13 @@
-"""GPU time of the two matchers of LoopClosing::ComputeSim3 on a jsorb_keyframe_matcher: jsorb_search_by_bow_kf_async (k_bow_group +
-k_loop_bow_match + k_tri_resolve) for the current keyframe against 1, 3 and 10 loop candidates in one call, and jsorb_search_by_sim3_async
-(k_fuse_grids x 2 + k_sim3_match + k_sim3_agree) for one keyframe pair.  The current keyframe is the left view of a synthetic pair at C2 (752x480,
+"""GPU time of the three matchers of LoopClosing::ComputeSim3 on a jsorb_keyframe_matcher: jsorb_search_by_bow_kf_async (k_bow_group +
+k_loop_bow_match + k_tri_resolve) for the current keyframe against 1, 3 and 10 loop candidates in one call, jsorb_search_by_sim3_async
+(k_fuse_grids x 2 + k_sim3_match + k_sim3_agree) for one keyframe pair, and jsorb_search_by_projection_sim3_async (k_fuse_grids + k_scw_candidates +
+k_scw_resolve) for 2 000 and 8 000 loop points against the current keyframe, beside the sequential loop of examples/compute_sim3.cpp on the same
+inputs (-O2, one thread, this machine).  The current keyframe is the left view of a synthetic pair at C2 (752x480,
 8 levels, tile 30), the candidates are the right and left views in turn; the vocabulary is sampled from the left view's descriptors (10 children, 3
 levels, nodes one level above the words), nine keypoints in ten carry a map point.  For the Sim3 call the map points are the keypoints back-projected
-at depth 4, the right camera a baseline beside the left one and the similarity between them that baseline, slightly off.  Per case: median over --reps
+at depth 4, the right camera a baseline beside the left one and the similarity between them that baseline, slightly off.  The loop points are
+the keypoints of both views back-projected the same way, drawn with replacement, a fifth of them with a descriptor beyond TH_LOW; a quarter of the
+current keyframe's keypoints hold a point before the call.  Per case: median over --reps
 of the hipEvent span of the whole call on the matcher's stream.  Nobody has measured these calls before: there is no time to stand against.
 Prints one JSON line."""
 import argparse
@@ -68,7 +72,7 @@ def main():
         return {"median_us": round(float(np.median(out)), 2), "p10_us": round(float(np.percentile(out, 10)), 2), "p90_us": round(float(np.percentile(out, 90)), 2)}
 
     result = {"tool": "loop_bench", "reps": args.reps, "frame": "C2", "keypoints": [len(left["x"]), len(right["x"])], "node_regs": orb.loop_build_caps(),
-              "bow": [], "sim3": None}
+              "bow": [], "sim3": None, "scw": []}
     keys = orb.KeyframeMatcher.BOW_KF_KEYS
     n1 = len(left["x"])
     d1 = {k: dev(left[k]) for k in keys}
@@ -110,6 +114,54 @@ def main():
     windows, walked, dists, largest, agree = m.search_by_sim3_stats()
     row.update(windows=windows, walked=walked, distances=dists, largest_window=largest, found=agree)
     result["sim3"] = row
+    # the acceptance test: the loop points against the left view, Scw = the identity scaled by 1.02 (the points' world frame is the left camera's)
+    import subprocess
+    import tempfile
+    from jetson_slam_amd import build as jb
+    tmp = tempfile.mkdtemp()
+    exe = jb.build_example("compute_sim3", os.path.join(tmp, "compute_sim3"), ["-O2"])
+    S = np.eye(4, dtype=np.float32)
+    S[:3, :3] *= np.float32(1.02)
+    S[:3, 3] = np.float32(1.02) * np.array([0.002, -0.001, 0.0], np.float32)
+    cp = orb.scw_params((FX, FX, cx, cy), (0, c["w"], 0, c["h"]), (64 / c["w"], 48 / c["h"]), float(np.log(np.float32(1.2))), scale, *orb.scw_from_pose(S))
+    N = len(left["x"])
+    blocked = (rng.random(N) < 0.25).astype(np.uint8)
+    kf = dict(x=dev(left["x"]), y=dev(left["y"]), octave=dev(left["octave"]), desc=dev(left["desc"]), blocked=dev(blocked))
+    pool = []
+    for f, tw in ((left, [0, 0, 0]), (right, [-base, 0, 0])):
+        Pc = np.stack([(f["x"] - cx) * z / FX, (f["y"] - cy) * z / FX, np.full(len(f["x"]), z)])
+        Pw = Pc - np.asarray(tw, np.float64)[:, None]
+        o = Pw - (-np.asarray(tw, np.float64))[:, None]
+        dist = np.sqrt((o * o).sum(0))
+        maxd = (dist * scale[f["octave"]]).astype(np.float32)
+        pool.append(dict(pos=Pw.T.astype(np.float32), normal=(o / dist).T.astype(np.float32), maxd=maxd, mindi=(np.float32(0.8) * maxd / scale[-1]).astype(np.float32),
+                         maxdi=(np.float32(1.2) * maxd).astype(np.float32), desc=f["desc"]))
+    pool = {k: np.concatenate([q[k] for q in pool]) for k in pool[0]}
+    for n in (2000, 8000):
+        pick = rng.integers(0, len(pool["maxd"]), n)
+        P = {k: np.ascontiguousarray(v[pick]) for k, v in pool.items()}
+        far = rng.random(n) < 0.2
+        P["desc"][far] ^= rng.integers(0, 256, (int(far.sum()), 32), dtype=np.uint8)
+        pts = dict(Px=dev(P["pos"][:, 0]), Py=dev(P["pos"][:, 1]), Pz=dev(P["pos"][:, 2]), Nx=dev(P["normal"][:, 0]), Ny=dev(P["normal"][:, 1]),
+                   Nz=dev(P["normal"][:, 2]), max_distance=dev(P["maxd"]), min_dist_inv=dev(P["mindi"]), max_dist_inv=dev(P["maxdi"]), desc=dev(P["desc"]))
+        _, _, _, a = m._scw_args(pts, kf, cp)
+        out = [torch.empty(max(n, N), dtype=torch.int32, device="cuda") for _ in range(4)]
+        row = {"loop_points": n, "keypoints": N, "blocked": int(blocked.sum()), "caps": list(orb.scw_build_caps())}
+        row.update(spans(lambda: lib.jsorb_search_by_projection_sim3_async(m.handle, *m._c_args(a), *[o.data_ptr() for o in out])))
+        rounds, kept, over, windows, dists, largest = m.search_by_projection_sim3_stats()
+        row.update(matches=int(out[3].cpu()[0]), rounds=rounds, keys_kept=kept, over_cap=over, windows=windows, distances=dists, largest_window=largest)
+        path = os.path.join(tmp, "scw_%d.bin" % n)
+        with open(path, "wb") as fh:
+            fh.write(np.array([N, n], np.int32).tobytes() + bytes(cp))
+            for v in (left["x"], left["y"], left["octave"], left["desc"], blocked):
+                fh.write(np.ascontiguousarray(v).tobytes())
+            fh.write(np.concatenate([P["pos"], P["normal"], P["maxd"][:, None], P["mindi"][:, None], P["maxdi"][:, None]], 1).astype(np.float32).tobytes())
+            fh.write(P["desc"].tobytes())
+        host = subprocess.run([exe, "--scw-host-loop", path, "21"], capture_output=True, text=True, check=True).stdout.split()
+        hv = dict(kv.split("=") for kv in host[1:])
+        assert int(hv["nmatches"]) == row["matches"], (hv, row["matches"])      # the same loop on the same inputs
+        row["host_loop_median_us"] = float(hv["median_us"])
+        result["scw"].append(row)
     m.close()
     print(json.dumps(result), flush=True)
 
