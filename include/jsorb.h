@@ -809,6 +809,60 @@ int jsorb_fuse(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int n
  * Any pointer may be NULL. */
 int jsorb_fuse_stats(jsorb_keyframe_matcher *m, int *n_windows, int *n_walked, int *n_distances, int *largest_window);
 
+/* ---- the map points' descriptors between two matcher calls: MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cpp:273-338), as LocalMapping
+ * calls it for every map point it touches - ProcessNewKeyFrame (src/LocalMapping.cpp:158-159), CreateNewMapPoints (:448), SearchInNeighbors
+ * (:532) - and as MapPoint::Replace (MapPoint.cpp:243), LoopClosing (src/LoopClosing.cpp:537) and Tracking's map initialisations do, for MANY
+ * points in one call of the keyframe matcher above, on its stream ----
+ * The descriptor it picks is the `desc` input of jsorb_fuse, jsorb_search_local_points, jsorb_search_last_frame, jsorb_search_by_projection_kf and
+ * jsorb_search_by_projection_sim3; it is the recomputation the contract of jsorb_fuse_async asks for after the replay of keyframe k, and `changed`
+ * below is that contract's "32 descriptor bytes differ from those it was last searched with".  What touches the map stays with the caller: the
+ * reference walks mObservations, a std::map<KeyFrame*, size_t>, in pointer order and leaves out the keyframes that are bad (:292-298); the caller
+ * lists each point's observations in the order its own map iteration gives, the bad keyframes left out (dropping entries changes no order).
+ * For one point with the descriptors D[0 .. N-1] of its observations, in that order:
+ *   1. N == 0: nothing happens, mDescriptor stays what it was (:287, :300)
+ *   2. dist[i][j] = the popcount Hamming distance of D[i] and D[j] (ORBmatcher::DescriptorDistance), dist[i][i] = 0 (:306-316).  The reference
+ *      keeps them in a float array and reads them back into ints: exact for values up to 256
+ *   3. per row i the median is the element at index (size_t)(0.5*(N-1)) = (N-1)/2 of the ascending row (:323-325); the row INCLUDES the
+ *      self-distance 0.  So every median is 0 for N = 1 and 2, the smaller of the two real distances for N = 3, the LOWER middle for an even N
+ *   4. BestIdx is the FIRST i with the smallest median: strict < from INT_MAX, i ascending (:319-332).  The observations' order matters through
+ *      this rule alone
+ *   5. mDescriptor = D[BestIdx] (:336)
+ * Inputs: DEVICE arrays, the sizes host values.  obs_start int32[n_points + 1]: the CSR of the observations, point p has obs_start[p] ..
+ * obs_start[p + 1]; obs_row int32[n_obs]: each a row of kf_desc; kf_desc n_rows x 32 bytes, 16-byte aligned: the keyframes' descriptor matrices
+ * concatenated as for jsorb_fuse / jsorb_search_for_triangulation (the caller adds its kf_start[k] to the keypoint index).  out_row: NULL (point p
+ * writes row p) or int32[n_points], distinct rows of desc_out; read only with desc_out.
+ * Outputs (DEVICE), every entry of the first two written: best_obs int32[n_points] = BestIdx within the point's own list, -1 for an empty or
+ * invalid point; best_median int32[n_points] = the winning median, or -1.  desc_out (may be NULL) n_out_rows x 32 bytes, 16-byte aligned: the
+ * point's row is overwritten with the winner's 32 bytes ONLY when best_obs[p] >= 0 (rule 1: the old descriptor stays); it must not overlap kf_desc
+ * and may be the very `desc` array a following jsorb_fuse_async on the same matcher reads - the stream orders the two calls.  changed (may be NULL,
+ * needs desc_out) uint8[n_points]: 1 when the row was written with bytes that differ from what it held, else 0.
+ * Defined for every device input, nothing faults: a point is INVALID - -1 / -1, its row untouched, changed 0 - when obs_start[p] or
+ * obs_start[p + 1] lies outside [0, n_obs], obs_start descends at p, one of its obs_row entries lies outside [0, n_rows), or (with desc_out) its
+ * output row lies outside [0, n_out_rows).  The same row twice in one point is legal (distance 0), and so are points whose
+ * ranges overlap (each point alone is judged).  There is no limit on N.
+ * Enqueued on the matcher's stream, no host decision after the argument checks, launch shapes from the host sizes alone, capturable once the
+ * scratch has its size: k_distinct_plan (the checks, the points binned by N), k_distinct_lanes (16 lanes a point for N <= 16, a wave a point for
+ * N <= 64), k_distinct_block (a workgroup a point beyond, its descriptors in LDS up to 1024 of them) - jsorb_distinct_build_caps reports the three
+ * numbers of the library in use.  JSORB_ERR_INVALID for a NULL required pointer, a negative size, kf_desc or desc_out not 16-byte aligned, changed
+ * without desc_out.  n_points == 0 is a valid call that launches nothing.  The statistics words and the "done" mark are the call's own, as for fuse
+ * and triangulation. */
+int jsorb_distinctive_descriptors_async(jsorb_keyframe_matcher *m, int n_points, const int32_t *obs_start, int n_obs, const int32_t *obs_row,
+                                        const uint8_t *kf_desc, int n_rows, const int32_t *out_row, int n_out_rows, uint8_t *desc_out,
+                                        uint8_t *changed, int32_t *best_obs, int32_t *best_median);
+/* Synchronous: the same with best_obs_host, best_median_host [n_points] on the host, one copy back; desc_out and changed stay DEVICE arrays. */
+int jsorb_distinctive_descriptors(jsorb_keyframe_matcher *m, int n_points, const int32_t *obs_start, int n_obs, const int32_t *obs_row,
+                                  const uint8_t *kf_desc, int n_rows, const int32_t *out_row, int n_out_rows, uint8_t *desc_out, uint8_t *changed,
+                                  int32_t *best_obs_host, int32_t *best_median_host);
+/* Diagnostics of the last call (waits for it): n_group, n_wave, n_block = the points whose CSR entry is valid with N in [1, group_lanes],
+ * (group_lanes, wave_max], beyond; n_beyond_lds = those of n_block with more than lds_descriptors observations; n_empty = N == 0; n_invalid = the
+ * invalid points; n_changed = rows written with other bytes than they held; largest_n = the largest N of a point with a valid CSR entry.
+ * JSORB_ERR_STATE before the first call.  Any pointer may be NULL. */
+int jsorb_distinctive_descriptors_stats(jsorb_keyframe_matcher *m, int *n_group, int *n_wave, int *n_block, int *n_beyond_lds, int *n_empty,
+                                        int *n_invalid, int *n_changed, int *largest_n);
+/* The compile-time caps of the library in use: lanes per point of the group tier (16), the largest N of the wave tier (64), descriptors the block
+ * tier holds in LDS (1024).  Any pointer may be NULL. */
+int jsorb_distinct_build_caps(int *group_lanes, int *wave_max, int *lds_descriptors);
+
 /* ---- loop-closure candidates by BoW: ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12)
  * (src/ORBmatcher.cpp:509-642) with ComputeThreeMaxima (:2097-2138), as LoopClosing::ComputeSim3 calls it once per consistent loop candidate with
  * ORBmatcher matcher(0.75, true) (src/LoopClosing.cpp:244, :270) - the current keyframe against ALL candidates in one call of the keyframe matcher

@@ -576,6 +576,15 @@ struct ScwPoint {
     unsigned char descriptor[32] = {};
     bool bad = false;
 };
+// The observations of n map points as DEVICE arrays, flat: obs_start[n + 1] the CSR, obs_row[n_obs] each observation's row of the concatenated
+// keyframe descriptors kf_descriptors (n_rows x 32 bytes; the caller adds its kf_start[k] to the keypoint index) - per point in the order
+// GetObservations() iterates, the keyframes that are isBad() left out.  out_row: nullptr (point p owns row p of the table) or n rows of it.
+struct Observations {
+    int n = 0, n_obs = 0, n_rows = 0;
+    const int32_t *obs_start = nullptr, *obs_row = nullptr;
+    const unsigned char *kf_descriptors = nullptr;
+    const int32_t *out_row = nullptr;
+};
 struct ScwKeyframe {
     int n = 0;
     const float *x = nullptr, *y = nullptr;
@@ -866,6 +875,28 @@ inline int Fuse(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &params
     int total = 0;
     for (int k = 0; k < n_kf; k++) total += counts[k];
     return total;
+}
+
+// pMP->ComputeDistinctiveDescriptors() (MapPoint.cpp:273-338) for ALL the points LocalMapping touches at one place - ProcessNewKeyFrame
+// (LocalMapping.cpp:158-159), CreateNewMapPoints (:448), SearchInNeighbors (:532), the survivors of MapPoint::Replace (MapPoint.cpp:243) - in one
+// call.  table_gpu: nullptr or the device table of the map points' descriptors (n_table_rows x 32 bytes, the `desc` a following Fuse reads):
+// the row of every point with an observation is overwritten with the winner's bytes, the others keep theirs (:287, :300).  changed_gpu: nullptr
+// or obs.n bytes on the device, 1 where a row got other bytes than it held - the points to search again after a replay (include/jsorb.h).
+// best_obs[p] = BestIdx within the point's own list or -1, best_median[p] its median or -1.  Returns the number of points with a winner.
+inline int ComputeDistinctiveDescriptors(jsorb::KeyframeMatcher &matcher, const jsorb::Observations &obs, unsigned char *table_gpu, int n_table_rows,
+                                         unsigned char *changed_gpu, std::vector<int32_t> &best_obs, std::vector<int32_t> &best_median)
+{
+    const size_t n = obs.n > 0 ? obs.n : 0;
+    best_obs.assign(n + 1, -1);
+    best_median.assign(n + 1, -1);
+    if (jsorb_distinctive_descriptors(matcher.handle(), obs.n, obs.obs_start, obs.n_obs, obs.obs_row, obs.kf_descriptors, obs.n_rows, obs.out_row,
+                                      n_table_rows, table_gpu, changed_gpu, best_obs.data(), best_median.data()) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_distinctive_descriptors: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    best_obs.resize(n);
+    best_median.resize(n);
+    int found = 0;
+    for (size_t p = 0; p < n; p++) found += best_obs[p] >= 0;
+    return found;
 }
 
 // matcher.SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) (ORBmatcher.cpp:509-642) for ALL n_kf consistent candidates of

@@ -1,7 +1,7 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
 // stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid; jsorb_search.hip: the four grid matchers; jsorb_bow.hip:
-// vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip and jsorb_loop.hip: the keyframe matcher, which shares the helpers that take any owner).
+// vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip, jsorb_loop.hip and jsorb_mappoints.hip: the keyframe matcher, which shares the helpers that take any owner).
 // include/jsorb.h only forward-declares the handle, so its layout is free to change.
 #pragma once
 
@@ -298,7 +298,8 @@ struct jsorb_extractor {
 };
 
 // The keyframe matcher of LocalMapping and LoopClosing (jsorb_keyframes.hip: create, destroy, streams, triangulation, fuse; jsorb_loop.hip: the
-// loop-closing matchers, SearchByProjection(pKF, Scw, ...) among them).  It belongs to no extractor handle.
+// loop-closing matchers, SearchByProjection(pKF, Scw, ...) among them; jsorb_mappoints.hip: the map points' distinctive descriptors).  It belongs to
+// no extractor handle.
 struct jsorb_keyframe_matcher {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -308,7 +309,8 @@ struct jsorb_keyframe_matcher {
     // one state per kind of call, each with statistics and a "done" mark of its own.  The synchronous forms' buffers: counts (256), then match12
     // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all;
     // scw: the count, then match_kp, match_dist and kp_match, out_cap in all
-    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, N_CALLS };
+    // distinct: best_obs, then best_median, out_cap entries each
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, N_CALLS };
     KfCall call[N_CALLS];
     int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
@@ -318,6 +320,10 @@ struct jsorb_keyframe_matcher {
         int *cand = nullptr, *cand_n = nullptr;                 // cand_cap x scw_cap() kept keys, cand_n_cap counts
         int cand_cap = 0, cand_n_cap = 0;
     } scw;
+    struct {                                                    // jsorb_distinctive_descriptors* (jsorb_mappoints.hip): k_distinct_plan's tier lists, grown only
+        int *list = nullptr;                                    // 3 x list_cap points
+        int list_cap = 0;
+    } distinct;
     std::string err;
 };
 

@@ -1,5 +1,5 @@
 // jsorb_keyframes.hip - host side of the keyframe matcher of LocalMapping (jsorb_keyframe_matcher_*, jsorb_search_for_triangulation*, jsorb_fuse*);
-// LoopClosing's calls on the same kind of matcher are in jsorb_loop.hip.
+// LoopClosing's calls on the same kind of matcher are in jsorb_loop.hip, the map points' distinctive descriptors in jsorb_mappoints.hip.
 // The matcher belongs to no extractor handle: it owns its stream and scratch, so LocalMapping's thread never enqueues on Tracking's handles.  The
 // kernels are in k_triangulate.hip (the grouping is k_bow.hip's k_bow_group with KF1 as the frame side) and k_fuse.hip.  The checks on sizes and
 // kf_start, the start of the device work and the synchronous forms are jsorb_handle.h's frames (kf_check_sizes, kf_rebase, kf_clear, kf_sync).
@@ -40,7 +40,7 @@ void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
-    free_device(m->sort1, m->sort2, m->grid_start, m->grid_items, m->matched2, m->scw.cand, m->scw.cand_n);
+    free_device(m->sort1, m->sort2, m->grid_start, m->grid_items, m->matched2, m->scw.cand, m->scw.cand_n, m->distinct.list);
     for (KfCall &c : m->call) free_device(c.stats, c.out);
     destroy_event(m->ev_switch);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);

@@ -361,6 +361,22 @@ int scw_cap();                                  // the compile-time caps of k_sc
 int scw_lds_claims();
 void launch_scw_candidates(const ScwArgs &a, hipStream_t s);
 void launch_scw_resolve(const ScwArgs &a, hipStream_t s);
+// k_distinct_plan / k_distinct_lanes / k_distinct_block (k_distinct.hip): MapPoint::ComputeDistinctiveDescriptors for n_points map points
+struct DistinctArgs {
+    int n_points, n_obs, n_rows, n_out_rows;
+    const int32_t *obs_start, *obs_row;          // the observations' CSR (n_points + 1) and their rows of kf_desc (n_obs)
+    const uint8_t *kf_desc;                      // n_rows x 32 bytes
+    const int32_t *out_row;                      // NULL: point p writes row p
+    // workspace and outputs
+    int *list;                                   // 3 x n_points: the points of the group, wave and block tier (stats[0 .. 2] of them)
+    int32_t *best_obs, *best_median;             // n_points each, every entry written
+    uint8_t *desc_out, *changed;                 // n_out_rows x 32 bytes or NULL; n_points bytes or NULL
+    int *stats;                                  // points per tier (3), block-tier points beyond the LDS cap, empty, invalid, changed, largest N (cleared to 0)
+};
+int distinct_group_lanes();                     // the compile-time caps of k_distinct.hip (jsorb_distinct_build_caps)
+int distinct_wave_lanes();
+int distinct_lds_desc();
+void launch_distinct(const DistinctArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

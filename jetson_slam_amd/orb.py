@@ -68,6 +68,7 @@ EXPORTS = [
     "jsorb_search_by_bow_kf_async", "jsorb_search_by_bow_kf", "jsorb_search_by_bow_kf_stats", "jsorb_loop_build_caps",
     "jsorb_search_by_sim3_async", "jsorb_search_by_sim3", "jsorb_search_by_sim3_stats",
     "jsorb_search_by_projection_sim3_async", "jsorb_search_by_projection_sim3", "jsorb_search_by_projection_sim3_stats", "jsorb_scw_build_caps",
+    "jsorb_distinctive_descriptors_async", "jsorb_distinctive_descriptors", "jsorb_distinctive_descriptors_stats", "jsorb_distinct_build_caps",
 ]
 
 
@@ -416,6 +417,10 @@ def load_library(path=None):
         "jsorb_search_by_projection_sim3": (I, [P, C.POINTER(JsorbScwParams), I] + [P] * 10 + [I] + [P] * 8 + [C.POINTER(I)]),
         "jsorb_search_by_projection_sim3_stats": (I, [P] + [C.POINTER(I)] * 6),
         "jsorb_scw_build_caps": (I, [C.POINTER(I), C.POINTER(I)]),
+        "jsorb_distinctive_descriptors_async": (I, [P, I, P, I, P, P, I, P, I] + [P] * 4),
+        "jsorb_distinctive_descriptors": (I, [P, I, P, I, P, P, I, P, I] + [P] * 4),
+        "jsorb_distinctive_descriptors_stats": (I, [P] + [C.POINTER(I)] * 8),
+        "jsorb_distinct_build_caps": (I, [C.POINTER(I)] * 3),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -581,6 +586,14 @@ def scw_build_caps():
     c, l = C.c_int(), C.c_int()
     load_library().jsorb_scw_build_caps(C.byref(c), C.byref(l))
     return c.value, l.value
+
+
+def distinct_build_caps():
+    """jsorb_distinct_build_caps of the loaded library: (lanes per point of k_distinct's group tier, the largest N of its wave tier, descriptors its
+    block tier holds in LDS)"""
+    g, w, l = C.c_int(), C.c_int(), C.c_int()
+    load_library().jsorb_distinct_build_caps(C.byref(g), C.byref(w), C.byref(l))
+    return g.value, w.value, l.value
 
 
 def bow_transform_descriptors(voc, descriptors):
@@ -915,6 +928,52 @@ class KeyframeMatcher:
         the last search_by_projection_sim3"""
         v = [C.c_int() for _ in range(6)]
         self._chk(self._lib.jsorb_search_by_projection_sim3_stats(self._m, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+    # ---- between two matcher calls: MapPoint::ComputeDistinctiveDescriptors for many points ----
+    @staticmethod
+    def _distinct_args(obs_start, obs_row, kf_desc, out_row, desc_out, changed):
+        """-> (device, n_points, the `changed` tensor or None, arguments) of jsorb_distinctive_descriptors* (nothing of `self` is read)"""
+        import torch
+        what, K = "distinctive_descriptors", KeyframeMatcher
+        for name, t in (("obs_start", obs_start), ("obs_row", obs_row), ("kf_desc", kf_desc)):
+            if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False):
+                raise JsorbError("%s: %s must be a device tensor" % (what, name))
+        if obs_start.dtype != torch.int32 or len(obs_start.shape) != 1 or obs_start.shape[0] < 1 or not obs_start.is_contiguous():
+            raise JsorbError("%s: obs_start must be a contiguous torch.int32 tensor of n_points + 1 offsets" % what)
+        n, n_obs, n_rows = int(obs_start.shape[0]) - 1, int(obs_row.shape[0]), int(kf_desc.shape[0])
+        dt = dict(obs_row=(torch.int32,), out_row=(torch.int32,), kf_desc=(torch.uint8,), desc=(torch.uint8,))
+        (po,) = K._side(what, dict(obs_row=obs_row), ("obs_row",), dt, "observations", n_obs)
+        (pk,) = K._side(what, dict(kf_desc=kf_desc), ("kf_desc",), dt, "keyframes", n_rows)
+        n_out = 0 if desc_out is None else int(desc_out.shape[0]) if hasattr(desc_out, "shape") and len(desc_out.shape) else -1
+        (pd,) = K._side(what, dict(desc=desc_out), ("desc",), dt, "desc_out", n_out, optional=("desc",))
+        (pr,) = K._side(what, dict(out_row=out_row), ("out_row",), dt, "points", n, optional=("out_row",))
+        if changed and desc_out is None:
+            raise JsorbError("%s: changed needs desc_out" % what)
+        ch = torch.full((max(n, 1),), 7, dtype=torch.uint8, device=obs_start.device) if changed else None
+        return obs_start.device, n, ch, [n, obs_start.data_ptr(), n_obs, po, pk, n_rows, pr, n_out, pd, ch.data_ptr() if changed and pd else None]      # (no rows at all: no desc_out pointer, so none for changed)
+
+    def distinctive_descriptors(self, obs_start, obs_row, kf_desc, out_row=None, desc_out=None, changed=False, sync=False, wait=True):
+        """jsorb_distinctive_descriptors_async (sync=False) or jsorb_distinctive_descriptors (sync=True): MapPoint::ComputeDistinctiveDescriptors for
+        the len(obs_start) - 1 points whose observations are the CSR obs_start int32[n + 1] / obs_row int32[n_obs] into the rows of kf_desc
+        uint8[n_rows, 32] (device tensors, the observations of a point in the caller's map order with the bad keyframes left out).  desc_out: None
+        or a uint8[n_out_rows, 32] device tensor whose row out_row[p] (int32[n] device tensor; None: row p) is overwritten IN PLACE with the winner's
+        bytes; changed=True also returns a uint8[n] device tensor, 1 where a row was written with other bytes than it held.  Returns (best_obs
+        int32[n], best_median int32[n]) - device tensors with sync=False (wait= as in search_for_triangulation, with the same rule for the returned
+        tensors' lifetime), host arrays with sync=True - followed by the `changed` tensor when asked for."""
+        dev, n, ch, args = self._distinct_args(obs_start, obs_row, kf_desc, out_row, desc_out, changed)
+        if sync:
+            out = self._call_host("jsorb_distinctive_descriptors", args, dev, [(n,), (n,)])
+        else:
+            out = self._enqueue("jsorb_distinctive_descriptors_async", args, dev, [(n,), (n,)], wait)
+        return out + (ch[:n],) if changed else out
+
+    def distinctive_descriptors_stats(self):
+        """(points of the group tier, of the wave tier, of the block tier, those of the block tier beyond its LDS cap, empty points, invalid points,
+        rows changed, the largest N) of the last distinctive_descriptors"""
+        v = [C.c_int() for _ in range(8)]
+        self._chk(self._lib.jsorb_distinctive_descriptors_stats(self._m, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 
