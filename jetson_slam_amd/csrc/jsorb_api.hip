@@ -28,7 +28,9 @@ const char *k_names_kf[JSORB_K_ID_LAST - JSORB_K_KF_CANDIDATES] = {"k_kf_candida
 // holds up every other stream that shares its queue.  This library runs 4 lane streams + 1 upload stream + one main stream per handle;
 // on 4 queues which of them share is decided by creation order (measured with otherwise identical code, only the number of idle streams
 // created earlier differing: 85.7 k against 91.4 k pairs/s device-resident, 47 k against 71 k host-streamed).  Sixteen queues give every
-// stream of a few handle pairs its own (8 were not enough for bench.py, which keeps two sets of handles alive).  The variable is read when the HIP runtime initialises (its first API call), so this
+// stream of a few handle pairs its own (8 were not enough for bench.py, which keeps two sets of handles alive).  Where the user has set fewer, the
+// lane pool is created in the order that still gives the four lanes of the device-resident batch path a queue each (pool_create below).
+// The variable is read when the HIP runtime initialises (its first API call), so this
 // constructor - run when the library is loaded - is early enough for a process that links the library or imports the Python binding
 // before it touches the GPU; an explicit setting by the user wins.  ("Runtime environment")
 // JSORB_NO_ENV=1 forbids it: an integrator who does not want a library to touch the process environment sets the variable itself (or not).
@@ -229,6 +231,7 @@ struct LanePool {
     hipStream_t s[JSORB_MAX_LANES] = {};
     hipStream_t copy = nullptr;     // uploads of host batches, all handles: see pool_copy_stream
     std::vector<hipStream_t> idle_main;   // main streams of destroyed handles, handed to the next jsorb_create (see pool_main_stream)
+    int n_main = 0;                 // main streams created on this device so far (pool_create)
 };
 LanePool g_pool[16];
 
@@ -272,12 +275,44 @@ void arena_release(unsigned *data)
 // Main streams are recycled, never destroyed: which hardware queue HIP gives a new stream depends on every stream created and destroyed
 // before it, and a process that had closed one handle pair and opened another (same code, same sizes) measured 57 k instead of 68 k
 // pairs/s in the host-streamed regime.  With recycled streams the stream -> queue assignment of the process settles once.
+//
+// Which hardware queue a stream gets is decided when it is CREATED, so the device's first four lane streams are created here, with the device's first
+// handle that can run a multi-lane batch (max_batch > 1), in an order that leaves each of them a queue of its own even with four queues.  The runtime
+// gives a new stream a new queue until GPU_MAX_HW_QUEUES exist and from then on the queue with the fewest streams - among equals the one created LAST
+// (rocprofv3 queue ids, profiles/r09_overlap.txt).  The legacy stream holds the first queue (torch, hipMemset: touched below so that it does in every
+// process).  With four queues the next three streams therefore take the three new queues, and from the fourth stream on any FOUR CONSECUTIVE streams
+// land on four different queues (q4, q3, q2, q1, q4, ...).  So: three main streams first (those the device's handles have created already count; the
+// rest are kept for the next handles), then lanes 0-3 in a row.  Every lane then shares its queue with a main stream or with the legacy stream, which are
+// idle while a multi-lane batch runs; single frames and one-lane batches, which do run on a main stream, use no lane.  (Lanes created lazily in
+// run_pipeline, behind the legacy stream and TWO main streams: lanes 0 and 1 on ONE queue, never four kernels in flight, 118 k against 130 k pairs/s at
+// C2.)  With eight or more queues every stream of a handle pair has its own in any order.
+// A handle that takes single images only (max_batch = 1: the C++ shim's) never uses a lane and does not bring the pool up: in a process of such
+// handles the streams are what they were - with the pool's seven streams ahead of them the frame took 175 us instead of 133 (the shim's own streams
+// then share queues with the main streams).
+#ifndef JSORB_POOL_MAINS_AHEAD
+#define JSORB_POOL_MAINS_AHEAD 3
+#endif
+int pool_create(jsorb_extractor *e, LanePool &p)      // p.m is held
+{
+    if (p.s[0]) return JSORB_OK;
+    HIPCHK(e, hipStreamSynchronize(nullptr));      // (jsorb_create waits for the whole device at its end anyway)
+    for (; p.n_main < JSORB_POOL_MAINS_AHEAD; p.n_main++) {
+        hipStream_t s = nullptr;
+        HIPCHK(e, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        p.idle_main.insert(p.idle_main.begin(), s);      // handed out in creation order
+    }
+    for (int j = 0; j < std::min(4, JSORB_MAX_LANES); j++) HIPCHK(e, hipStreamCreateWithFlags(&p.s[j], hipStreamNonBlocking));
+    return JSORB_OK;
+}
+
 int pool_main_stream(jsorb_extractor *e, hipStream_t *out)
 {
     LanePool &p = g_pool[e->device & 15];
     std::lock_guard<std::mutex> lk(p.m);
+    if (e->B > 1) RCCHK(pool_create(e, p));
     if (!p.idle_main.empty()) { *out = p.idle_main.back(); p.idle_main.pop_back(); return JSORB_OK; }
     HIPCHK(e, hipStreamCreateWithFlags(out, hipStreamNonBlocking));
+    p.n_main++;
     return JSORB_OK;
 }
 void pool_return_main_stream(int device, hipStream_t s)
@@ -467,7 +502,7 @@ int jsorb_create_masked(const jsorb_params *params, const uint8_t *mask, int mas
     RCCHK(pool_main_stream(e, &e->own_stream));
     e->stream = e->own_stream;
     HIPCHK(e, hipEventCreateWithFlags(&e->lanes.ev_fork, hipEventDisableTiming));
-    for (int j = 0; j < JSORB_MAX_LANES; j++) {      // the extra lane STREAMS are created on first use (run_pipeline): a single-frame handle never needs them
+    for (int j = 0; j < JSORB_MAX_LANES; j++) {      // (the lane STREAMS belong to the device's pool: pool_create made the first four for a handle that takes batches, lanes 4-7 are created on first use)
         HIPCHK(e, hipEventCreateWithFlags(&e->lanes.done[j], hipEventDisableTiming));
         HIPCHK(e, hipEventCreateWithFlags(&e->lanes.readers_done[j], hipEventDisableTiming));
     }
