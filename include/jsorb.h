@@ -863,6 +863,88 @@ int jsorb_distinctive_descriptors_stats(jsorb_keyframe_matcher *m, int *n_group,
  * tier holds in LDS (1024).  Any pointer may be NULL. */
 int jsorb_distinct_build_caps(int *group_lanes, int *wave_max, int *lds_descriptors);
 
+/* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
+ * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF
+ * weights, L1 norm, L1 score.  An object of its own like the keyframe matcher: its stream, its scratch, its error text; whoever creates none
+ * allocates and launches nothing.  Everything is enqueued on the database's stream with no host decision between kernels (capturable); the
+ * calls of one database must not run concurrently on the host.
+ *   1. A BowVector on the device is three arrays: `word` int32 (distinct word ids ascending - std::map's order), `value` double, and a device
+ *      count.  Every reader clamps the count to [0, cap], the arrays' capacity (a host value).
+ *   2. jsorb_bow_vector_async: n word ids at a DEVICE pointer (for a frame: jsorb_bow_word_device; n known on the host) -> bow_word / bow_value of
+ *      capacity n and *bow_n_dev.  An id outside [0, n_words) or whose word_weight is not > 0 contributes nothing (:1157).  A word with c
+ *      occurrences has the value w added to itself c - 1 times in sequence (BowVector::addWeight; NOT c * w); BowVector::normalize(L1): norm =
+ *      the sequential double sum of fabs(value) in ascending word order from 0.0, and when norm > 0.0 every value becomes value / norm (IEEE
+ *      division).  The result has the host's bits.  n = 0 writes the count 0 and launches nothing that reads.
+ *   3. A keyframe is a caller-chosen slot in [0, max_keyframes).  add copies a device BowVector of at most `cap` entries into the database's own
+ *      pool (the count is read on the device), marks the slot present, gives it the next add sequence number and the KeyFrame constructor's query
+ *      state (KeyFrame.cpp:39): loop_query = reloc_query = 0, loop_words = reloc_words = 0 - and loop_score = reloc_score = 0.0f, which the
+ *      reference leaves uninitialised.  Adding to a present slot is JSORB_ERR_INVALID.  The pool may grow in add (which then waits for the
+ *      stream); no query allocates.  erase marks the slot absent (an absent slot: nothing); a later add of it is a new keyframe with fresh state
+ *      and a new sequence number.  clear empties all slots.  JSORB_ERR_UNSUPPORTED after 2^32 - 1 adds since the last clear.
+ *   4. No inverted file: the reference's lists are appended in add order and erase keeps the others' order, so a keyframe's position in
+ *      lKFsSharingWords is the ascending order of the key (its lowest word id in common with the query, its add sequence number).
+ *   5. score (the minScore loop, LoopClosing.cpp:129-143): for each entry of the DEVICE list `slots` that is present, score_f64 = L1Scoring::score:
+ *      over the words of both vectors in ascending word order s += fabs(vi - wi) - fabs(vi) - fabs(wi) from 0.0 in double, then -s / 2.0; score =
+ *      its cast to float; *min_score_dev = the minimum from 1.0f with `<`.  An absent (or out-of-range) slot is skipped like an isBad()
+ *      keyframe: its outputs are -1.  score_f64 may be NULL.
+ *   6. The two queries.  query_id is pKF->mnId / F->mnId.  neighbours: DEVICE int32 [max_keyframes x 10], row s = GetBestCovisibilityKeyFrames(10)
+ *      of slot s in its order; -1 pads and stands for a keyframe that is not in the database.  Loop form: connected = a DEVICE byte per slot
+ *      (spConnectedKeyFrames.count) or NULL; min_score is the host value unless min_score_dev, a DEVICE pointer, is given (5.'s output: no wait
+ *      in between).  candidates: DEVICE int32 of capacity max_keyframes, the slots in the reference's output order; *n_candidates_dev their count.
+ *      With c = a present slot's count of words in common with the query (c = 0: untouched):
+ *        loop (:90-108): loop_query != id and connected: loop_words = 1, not listed; loop_query != id otherwise: loop_query = id, loop_words = c,
+ *        listed; else loop_words += c, not listed.  reloc (:211-226): reloc_query != id: reloc_query = id, reloc_words = c, listed; else
+ *        reloc_words += c, not listed.
+ *      maxCommonWords over the listed slots; minCommonWords = (int)(maxCommonWords * 0.8f).  A listed slot with words > minCommonWords is scored
+ *      as in 5.: si = (float)score into loop_score / reloc_score (nothing else writes these); the loop form keeps si >= min_score.  Per kept
+ *      entry in list order: acc = best = si, best slot = the slot; for the neighbours in row order, skipping -1, absent and out-of-range
+ *      slots: loop counts a neighbour iff loop_query == id && loop_words > minCommonWords, reloc iff reloc_query == id (no words test: the
+ *      reloc_score an earlier query left is read); a counting neighbour adds its score in float and takes over the best slot when its score >
+ *      best.  bestAcc from min_score (loop) / 0 (reloc) rises on acc > bestAcc; the entries with acc > 0.75f * bestAcc output their best slot in
+ *      list order, a slot once, at its first occurrence.  Empty stages give zero candidates.
+ *      The one difference: the reference reads the fields of any KeyFrame* a neighbour list returns; a neighbour outside the database is skipped
+ *      here (it matters for query_id == 0, or an erased keyframe still listed as a neighbour, which SetBadFlag prevents).
+ *   7. JSORB_ERR_INVALID: a NULL required pointer, a negative size, a slot outside [0, max_keyframes), add to a present slot - with a text in
+ *      jsorb_keyframe_database_last_error and nothing launched. ---- */
+typedef struct jsorb_keyframe_database jsorb_keyframe_database;
+/* word_weight: a HOST array of the n_words leaf weights by word id (copied). */
+int jsorb_keyframe_database_create(int device_id, int max_keyframes, int n_words, const double *word_weight, jsorb_keyframe_database **out);
+void jsorb_keyframe_database_destroy(jsorb_keyframe_database *db);
+int jsorb_keyframe_database_set_stream(jsorb_keyframe_database *db, void *hip_stream);      /* NULL: the database's own */
+void *jsorb_keyframe_database_get_stream(const jsorb_keyframe_database *db);
+const char *jsorb_keyframe_database_last_error(const jsorb_keyframe_database *db);
+int jsorb_keyframe_database_size(const jsorb_keyframe_database *db);                         /* present slots */
+int jsorb_bow_vector_async(jsorb_keyframe_database *db, const int32_t *word_id, int n, int32_t *bow_word, double *bow_value, int32_t *bow_n_dev);
+int jsorb_keyframe_database_add_async(jsorb_keyframe_database *db, int slot, const int32_t *bow_word, const double *bow_value, int cap,
+                                      const int32_t *bow_n_dev);
+int jsorb_keyframe_database_erase(jsorb_keyframe_database *db, int slot);
+int jsorb_keyframe_database_clear(jsorb_keyframe_database *db);
+int jsorb_keyframe_database_score_async(jsorb_keyframe_database *db, const int32_t *q_word, const double *q_value, int q_cap, const int32_t *q_n_dev,
+                                        const int32_t *slots, int n_slots, float *score, double *score_f64, float *min_score_dev);
+int jsorb_detect_loop_candidates_async(jsorb_keyframe_database *db, const int32_t *q_word, const double *q_value, int q_cap, const int32_t *q_n_dev,
+                                       uint64_t query_id, const uint8_t *connected, const int32_t *neighbours, float min_score,
+                                       const float *min_score_dev, int32_t *candidates, int32_t *n_candidates_dev);
+int jsorb_detect_relocalization_candidates_async(jsorb_keyframe_database *db, const int32_t *q_word, const double *q_value, int q_cap,
+                                                 const int32_t *q_n_dev, uint64_t query_id, const int32_t *neighbours, int32_t *candidates,
+                                                 int32_t *n_candidates_dev);
+/* The synchronous forms: the same, then a wait; candidates_host (capacity max_keyframes) and *n_candidates_host are HOST outputs. */
+int jsorb_detect_loop_candidates(jsorb_keyframe_database *db, const int32_t *q_word, const double *q_value, int q_cap, const int32_t *q_n_dev,
+                                 uint64_t query_id, const uint8_t *connected, const int32_t *neighbours, float min_score, const float *min_score_dev,
+                                 int32_t *candidates_host, int *n_candidates_host);
+int jsorb_detect_relocalization_candidates(jsorb_keyframe_database *db, const int32_t *q_word, const double *q_value, int q_cap, const int32_t *q_n_dev,
+                                           uint64_t query_id, const int32_t *neighbours, int32_t *candidates_host, int *n_candidates_host);
+/* Diagnostics of the last query of either form (waits for it): keyframes sharing a word (lKFsSharingWords.size()), maxCommonWords, minCommonWords,
+ * keyframes scored (nscores), entries kept by minScore (lScoreAndMatch.size()), bestAccScore (its start value when nothing was kept) and the
+ * candidates.  JSORB_ERR_STATE before the first query.  Any pointer may be NULL. */
+int jsorb_detect_candidates_stats(jsorb_keyframe_database *db, int *n_sharing, int *max_common_words, int *min_common_words, int *n_scored, int *n_kept,
+                                  float *best_acc_score, int *n_candidates);
+/* The persistent per-slot state, max_keyframes entries each, into HOST arrays (waits for the stream).  Any pointer may be NULL. */
+int jsorb_keyframe_database_copy_state(jsorb_keyframe_database *db, int32_t *present, uint64_t *loop_query, uint64_t *reloc_query, int32_t *loop_words,
+                                       int32_t *reloc_words, float *loop_score, float *reloc_score);
+/* The compile-time caps of the library in use: query entries the kernels stage in LDS (4096; a longer query is searched in global memory), word
+ * ids jsorb_bow_vector_async sorts in LDS (8192).  Any pointer may be NULL. */
+int jsorb_kfdb_build_caps(int *query_lds, int *sort_lds);
+
 /* ---- loop-closure candidates by BoW: ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12)
  * (src/ORBmatcher.cpp:509-642) with ComputeThreeMaxima (:2097-2138), as LoopClosing::ComputeSim3 calls it once per consistent loop candidate with
  * ORBmatcher matcher(0.75, true) (src/LoopClosing.cpp:244, :270) - the current keyframe against ALL candidates in one call of the keyframe matcher

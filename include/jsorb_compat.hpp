@@ -591,6 +591,42 @@ struct ScwKeyframe {
     const int32_t *octave = nullptr;
     const unsigned char *descriptors = nullptr;
 };
+// A BowVector on the device (include/jsorb.h): `cap` entries of room in DEVICE arrays the caller owns, the count on the device.
+struct DeviceBowVector {
+    int32_t *word = nullptr;
+    double *value = nullptr;
+    int32_t *n = nullptr;
+    int cap = 0;
+};
+// KeyFrameDatabase on the device (jsorb_keyframe_database, include/jsorb.h): RAII over the C calls.  A keyframe is a slot in [0, max_keyframes) the
+// caller maps its KeyFrame* to; word_weight: the n_words leaf weights by word id, HOST.  It owns its stream and scratch.
+class KeyframeDatabase {
+public:
+    KeyframeDatabase(int max_keyframes, int n_words, const double *word_weight, int device_id = 0) : max_keyframes_(max_keyframes)
+    {
+        if (jsorb_keyframe_database_create(device_id, max_keyframes, n_words, word_weight, &d_) != JSORB_OK)
+            throw std::runtime_error("jsorb_keyframe_database_create failed");
+    }
+    KeyframeDatabase(const KeyframeDatabase &) = delete;
+    KeyframeDatabase &operator=(const KeyframeDatabase &) = delete;
+    ~KeyframeDatabase() { jsorb_keyframe_database_destroy(d_); }
+    jsorb_keyframe_database *handle() const { return d_; }
+    int max_keyframes() const { return max_keyframes_; }
+    void set_stream(void *hip_stream) { jsorb_keyframe_database_set_stream(d_, hip_stream); }
+    void *stream() const { return jsorb_keyframe_database_get_stream(d_); }
+    // KeyFrameDatabase::add / erase / clear (KeyFrameDatabase.cpp:44-77)
+    void add(int slot, const DeviceBowVector &v) { check(jsorb_keyframe_database_add_async(d_, slot, v.word, v.value, v.cap, v.n), "add"); }
+    void erase(int slot) { check(jsorb_keyframe_database_erase(d_, slot), "erase"); }
+    void clear() { check(jsorb_keyframe_database_clear(d_), "clear"); }
+    void check(int rc, const char *what) const
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_keyframe_database ") + what + ": " + jsorb_keyframe_database_last_error(d_));
+    }
+
+private:
+    jsorb_keyframe_database *d_ = nullptr;
+    int max_keyframes_ = 0;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -897,6 +933,49 @@ inline int ComputeDistinctiveDescriptors(jsorb::KeyframeMatcher &matcher, const 
     int found = 0;
     for (size_t p = 0; p < n; p++) found += best_obs[p] >= 0;
     return found;
+}
+
+// Frame::ComputeBoW / KeyFrame::ComputeBoW's mBowVec (Frame.cpp:393-401) from n word ids on the DEVICE (jsorb_bow_word_device of the frame, behind
+// jsorb_bow_transform_async), into `v` - enqueued on the database's stream, nothing waited for.
+inline void ComputeBowVector(jsorb::KeyframeDatabase &db, const int32_t *word_id_gpu, int n, const jsorb::DeviceBowVector &v)
+{
+    if (v.cap < n) throw std::invalid_argument("ComputeBowVector: the vector's capacity is below n");
+    db.check(jsorb_bow_vector_async(db.handle(), word_id_gpu, n, v.word, v.value, v.n), "bow_vector");
+}
+
+// mpKeyFrameDB->DetectLoopCandidates(mpCurrentKF, minScore) (KeyFrameDatabase.cpp:80-201) as slots in the reference's output order.
+// connected_gpu: a byte per slot (mpCurrentKF->GetConnectedKeyFrames()) or nullptr; neighbours_gpu: max_keyframes x 10 slots, row s =
+// GetBestCovisibilityKeyFrames(10) of slot s, -1 padding (both DEVICE, include/jsorb.h).  min_score_gpu: nullptr, or the device float
+// LoopMinScore left (then min_score is not read).
+inline std::vector<int> DetectLoopCandidates(jsorb::KeyframeDatabase &db, const jsorb::DeviceBowVector &bow, unsigned long long kf_id,
+                                             const unsigned char *connected_gpu, const int32_t *neighbours_gpu, float min_score,
+                                             const float *min_score_gpu = nullptr)
+{
+    std::vector<int32_t> out((size_t)db.max_keyframes());
+    int n = 0;
+    db.check(jsorb_detect_loop_candidates(db.handle(), bow.word, bow.value, bow.cap, bow.n, kf_id, connected_gpu, neighbours_gpu, min_score, min_score_gpu,
+                                          out.data(), &n), "detect_loop_candidates");
+    return std::vector<int>(out.begin(), out.begin() + n);
+}
+
+// The minScore loop of LoopClosing::DetectLoop (LoopClosing.cpp:129-143) over the covisible keyframes' slots (DEVICE, n_slots of them): the
+// minimum lands in *min_score_gpu, which DetectLoopCandidates reads with no wait in between.  score_gpu: n_slots floats.
+inline void LoopMinScore(jsorb::KeyframeDatabase &db, const jsorb::DeviceBowVector &bow, const int32_t *slots_gpu, int n_slots, float *score_gpu,
+                         float *min_score_gpu)
+{
+    db.check(jsorb_keyframe_database_score_async(db.handle(), bow.word, bow.value, bow.cap, bow.n, slots_gpu, n_slots, score_gpu, nullptr, min_score_gpu),
+             "score");
+}
+
+// mpKeyFrameDB->DetectRelocalizationCandidates(&mCurrentFrame) (KeyFrameDatabase.cpp:203-313, Tracking.cpp:1961) as slots in its output order
+inline std::vector<int> DetectRelocalizationCandidates(jsorb::KeyframeDatabase &db, const jsorb::DeviceBowVector &bow, unsigned long long frame_id,
+                                                       const int32_t *neighbours_gpu)
+{
+    std::vector<int32_t> out((size_t)db.max_keyframes());
+    int n = 0;
+    db.check(jsorb_detect_relocalization_candidates(db.handle(), bow.word, bow.value, bow.cap, bow.n, frame_id, neighbours_gpu, out.data(), &n),
+             "detect_relocalization_candidates");
+    return std::vector<int>(out.begin(), out.begin() + n);
 }
 
 // matcher.SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) (ORBmatcher.cpp:509-642) for ALL n_kf consistent candidates of

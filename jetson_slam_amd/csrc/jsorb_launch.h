@@ -377,6 +377,59 @@ int distinct_group_lanes();                     // the compile-time caps of k_di
 int distinct_wave_lanes();
 int distinct_lds_desc();
 void launch_distinct(const DistinctArgs &a, hipStream_t s);
+// k_kfdb.hip: the keyframe database (KeyFrameDatabase.cpp:44-313, DBoW2's BowVector / L1Scoring).  A BowVector is (word, value, n): sorted distinct
+// word ids, their L1-normalised values, the count on the device.
+struct KfdbVector {
+    const int32_t *word;
+    const double *value;
+    const int32_t *n;                            // device count, clamped to [0, cap] by every reader
+    int cap;
+};
+struct KfdbState {                               // per slot, `slots` of them; the BowVectors live in the pool at off[s] .. off[s] + len[s]
+    int slots;                                   // the slots the kernels walk: the highest slot ever added + 1
+    int32_t *present, *off, *len;
+    uint32_t *seq;                               // add sequence number
+    unsigned long long *loop_query, *reloc_query;
+    int32_t *loop_words, *reloc_words;
+    float *loop_score, *reloc_score;
+    int32_t *pool_word;
+    double *pool_value;
+};
+#define KFDB_CTRL 16                             // control words of a query, zeroed in front of it (see k_kfdb.hip)
+#define KFDB_NEIGHBOURS 10                       // GetBestCovisibilityKeyFrames(10)
+struct KfdbQueryArgs {
+    KfdbState st;
+    KfdbVector q;
+    unsigned long long id;
+    int reloc;                                   // 0: DetectLoopCandidates, 1: DetectRelocalizationCandidates
+    const uint8_t *connected;                    // loop: a byte per slot, or NULL
+    const int32_t *neighbours;                   // slots x KFDB_NEIGHBOURS
+    float min_score;                             // loop: the host value, unless ...
+    const float *min_score_dev;                  // ... this is not NULL
+    unsigned long long *key;                     // scratch per slot: the list key (lowest common word << 32 | seq), ~0 when not listed
+    float *tscore;                               // scratch per slot: (float)score of the slots with a common word
+    int32_t *first_pos;                          // scratch per slot: the first retained list position whose best slot it is
+    int32_t *list, *ent_flag, *ent_best;         // scratch per list position: the slot, kept, its best slot
+    float *ent_acc;                              // ... its accumulated score
+    int32_t *ctrl;                               // KFDB_CTRL words
+    int32_t *candidates, *n_candidates;          // outputs
+};
+struct KfdbScoreArgs {
+    KfdbState st;
+    KfdbVector q;
+    const int32_t *slot_list;
+    int n_slots;
+    float *score;
+    double *score_f64;                           // or NULL
+    float *min_score;
+};
+int kfdb_query_lds();                            // the compile-time caps of k_kfdb.hip (jsorb_kfdb_build_caps)
+int kfdb_sort_lds();
+void launch_kfdb_bow_vector(const int32_t *word_id, int n, const double *weight, int n_words, uint32_t *sort_scratch, int32_t *bow_word, double *bow_value,
+                            int32_t *bow_n, hipStream_t s);
+void launch_kfdb_add(const KfdbState &st, int slot, uint32_t seq, int off, const KfdbVector &v, hipStream_t s);
+void launch_kfdb_score(const KfdbScoreArgs &a, hipStream_t s);
+void launch_kfdb_query(const KfdbQueryArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -69,6 +69,11 @@ EXPORTS = [
     "jsorb_search_by_sim3_async", "jsorb_search_by_sim3", "jsorb_search_by_sim3_stats",
     "jsorb_search_by_projection_sim3_async", "jsorb_search_by_projection_sim3", "jsorb_search_by_projection_sim3_stats", "jsorb_scw_build_caps",
     "jsorb_distinctive_descriptors_async", "jsorb_distinctive_descriptors", "jsorb_distinctive_descriptors_stats", "jsorb_distinct_build_caps",
+    "jsorb_keyframe_database_create", "jsorb_keyframe_database_destroy", "jsorb_keyframe_database_set_stream", "jsorb_keyframe_database_get_stream",
+    "jsorb_keyframe_database_last_error", "jsorb_keyframe_database_size", "jsorb_bow_vector_async", "jsorb_keyframe_database_add_async",
+    "jsorb_keyframe_database_erase", "jsorb_keyframe_database_clear", "jsorb_keyframe_database_score_async", "jsorb_detect_loop_candidates_async",
+    "jsorb_detect_relocalization_candidates_async", "jsorb_detect_loop_candidates", "jsorb_detect_relocalization_candidates",
+    "jsorb_detect_candidates_stats", "jsorb_keyframe_database_copy_state", "jsorb_kfdb_build_caps",
 ]
 
 
@@ -421,6 +426,24 @@ def load_library(path=None):
         "jsorb_distinctive_descriptors": (I, [P, I, P, I, P, P, I, P, I] + [P] * 4),
         "jsorb_distinctive_descriptors_stats": (I, [P] + [C.POINTER(I)] * 8),
         "jsorb_distinct_build_caps": (I, [C.POINTER(I)] * 3),
+        "jsorb_keyframe_database_create": (I, [I, I, I, P, C.POINTER(P)]),
+        "jsorb_keyframe_database_destroy": (None, [P]),
+        "jsorb_keyframe_database_set_stream": (I, [P, P]),
+        "jsorb_keyframe_database_get_stream": (P, [P]),
+        "jsorb_keyframe_database_last_error": (C.c_char_p, [P]),
+        "jsorb_keyframe_database_size": (I, [P]),
+        "jsorb_bow_vector_async": (I, [P, P, I, P, P, P]),
+        "jsorb_keyframe_database_add_async": (I, [P, I, P, P, I, P]),
+        "jsorb_keyframe_database_erase": (I, [P, I]),
+        "jsorb_keyframe_database_clear": (I, [P]),
+        "jsorb_keyframe_database_score_async": (I, [P, P, P, I, P, P, I, P, P, P]),
+        "jsorb_detect_loop_candidates_async": (I, [P, P, P, I, P, C.c_uint64, P, P, F, P, P, P]),
+        "jsorb_detect_relocalization_candidates_async": (I, [P, P, P, I, P, C.c_uint64, P, P, P]),
+        "jsorb_detect_loop_candidates": (I, [P, P, P, I, P, C.c_uint64, P, P, F, P, P, C.POINTER(I)]),
+        "jsorb_detect_relocalization_candidates": (I, [P, P, P, I, P, C.c_uint64, P, P, C.POINTER(I)]),
+        "jsorb_detect_candidates_stats": (I, [P] + [C.POINTER(I)] * 5 + [C.POINTER(F), C.POINTER(I)]),
+        "jsorb_keyframe_database_copy_state": (I, [P] * 8),
+        "jsorb_kfdb_build_caps": (I, [C.POINTER(I)] * 2),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -535,6 +558,10 @@ class Vocabulary:
             self._v = C.c_void_p()
             raise JsorbError("jsorb_vocabulary_create rc=%d" % rc)
         self.levels_up = int(levels_up)
+        # the leaves' weights by word id, as double: what KeyframeDatabase folds BowVectors with (the device tree keeps one byte of them)
+        leaf = wi >= 0
+        self.word_weight = np.zeros(int(wi[leaf].max()) + 1 if leaf.any() else 0, np.float64)
+        self.word_weight[wi[leaf]] = we[leaf]
 
     def info(self):
         """dict(n_nodes, n_words, depth_L, levels_up, max_children)"""
@@ -975,6 +1002,188 @@ class KeyframeMatcher:
         v = [C.c_int() for _ in range(8)]
         self._chk(self._lib.jsorb_distinctive_descriptors_stats(self._m, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+
+def kfdb_build_caps():
+    """jsorb_kfdb_build_caps of the loaded library: (query entries k_kfdb stages in LDS, word ids jsorb_bow_vector_async sorts in LDS)"""
+    q, s = C.c_int(), C.c_int()
+    load_library().jsorb_kfdb_build_caps(C.byref(q), C.byref(s))
+    return q.value, s.value
+
+
+class KeyframeDatabase:
+    """jsorb_keyframe_database: KeyFrameDatabase's BoW queries on the device (include/jsorb.h), with a stream and scratch of its own.
+    word_weight: the leaves' weights by word id (a host array of double), or an orb.Vocabulary, whose word_weight is taken.  A BowVector is the
+    triple (word int32[cap], value float64[cap], count int32[1]) of device tensors bow_vector returns.  wait (every call): True waits for the
+    current torch stream before the call and for the database's stream after it; False only enqueues."""
+    STATE_KEYS = ("present", "loop_query", "reloc_query", "loop_words", "reloc_words", "loop_score", "reloc_score")
+    STATE_TYPES = (np.int32, np.uint64, np.uint64, np.int32, np.int32, np.float32, np.float32)
+
+    def __init__(self, word_weight, max_keyframes, device_id=0):
+        self._lib = load_library()
+        self._d = C.c_void_p()
+        w = np.ascontiguousarray(getattr(word_weight, "word_weight", word_weight), np.float64)
+        rc = self._lib.jsorb_keyframe_database_create(int(device_id), int(max_keyframes), len(w), w.ctypes.data, C.byref(self._d))
+        if rc != 0:
+            self._d = C.c_void_p()
+            raise JsorbError("jsorb_keyframe_database_create rc=%d" % rc)
+        self.device_id, self.max_keyframes, self.n_words = int(device_id), int(max_keyframes), len(w)
+
+    @property
+    def handle(self):
+        return self._d
+
+    def close(self):
+        if getattr(self, "_d", None):
+            self._lib.jsorb_keyframe_database_destroy(self._d)
+            self._d = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise JsorbError("libjsorb rc=%d: %s" % (rc, self._lib.jsorb_keyframe_database_last_error(self._d).decode()))
+
+    def set_stream(self, stream_ptr):
+        """use an external HIP stream (e.g. torch.cuda.current_stream().cuda_stream); None restores the database's own"""
+        self._chk(self._lib.jsorb_keyframe_database_set_stream(self._d, stream_ptr))
+
+    def get_stream(self):
+        return self._lib.jsorb_keyframe_database_get_stream(self._d) or 0
+
+    def sync(self):
+        rc = self._lib.jsorb_mem_stream_sync(C.c_void_p(self.get_stream()))
+        if rc != 0:
+            raise JsorbError("KeyframeDatabase.sync: jsorb_mem_stream_sync rc=%d" % rc)
+
+    def size(self):
+        return self._lib.jsorb_keyframe_database_size(self._d)
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.device_id)
+
+    def _run(self, wait, fn, *args):
+        import torch
+        if wait:
+            torch.cuda.current_stream(self._dev()).synchronize()
+        self._chk(fn(self._d, *args))
+        if wait:
+            self.sync()
+
+    @staticmethod
+    def _tensor(what, t, dtype, n=None):
+        import torch
+        if not hasattr(t, "data_ptr") or not getattr(t, "is_cuda", False) or t.dtype != dtype or not t.is_contiguous() or t.dim() != 1 or \
+                (n is not None and t.numel() != n):
+            raise JsorbError("KeyframeDatabase: %s must be a contiguous 1-d %s device tensor%s" % (what, dtype, "" if n is None else " of %d entries" % n))
+        return t
+
+    def _vec(self, vec):
+        import torch
+        word, value, count = vec
+        self._tensor("a BowVector's word", word, torch.int32)
+        self._tensor("a BowVector's value", value, torch.float64, word.numel())
+        self._tensor("a BowVector's count", count, torch.int32, 1)
+        cap = word.numel()
+        return [word.data_ptr() if cap else None, value.data_ptr() if cap else None, cap, count.data_ptr()]
+
+    def bow_vector(self, word_ids, n=None, wait=True):
+        """jsorb_bow_vector_async: word ids (an int32 device tensor; or a raw device pointer of n entries, e.g. ORBExtractor.bow_device_pointers'
+        first) -> (word, value, count)"""
+        import torch
+        if isinstance(word_ids, int):
+            ptr, n = word_ids, int(n)
+        else:
+            self._tensor("word_ids", word_ids, torch.int32)
+            ptr, n = word_ids.data_ptr(), word_ids.numel()
+        word = torch.full((n,), -7, dtype=torch.int32, device=self._dev())
+        value = torch.full((n,), -7.0, dtype=torch.float64, device=self._dev())
+        count = torch.full((1,), -7, dtype=torch.int32, device=self._dev())
+        self._run(wait, self._lib.jsorb_bow_vector_async, ptr if n else None, n, word.data_ptr() if n else None,
+                  value.data_ptr() if n else None, count.data_ptr())
+        return word, value, count
+
+    def add(self, slot, vec, wait=True):
+        self._run(wait, self._lib.jsorb_keyframe_database_add_async, int(slot), *self._vec(vec))
+
+    def erase(self, slot):
+        self._chk(self._lib.jsorb_keyframe_database_erase(self._d, int(slot)))
+
+    def clear(self):
+        self._chk(self._lib.jsorb_keyframe_database_clear(self._d))
+
+    def score(self, vec, slots, f64=True, wait=True):
+        """jsorb_keyframe_database_score_async over the int32 device tensor `slots` -> (score float32[n], score_f64 float64[n] or None,
+        min_score float32[1]) device tensors"""
+        import torch
+        self._tensor("slots", slots, torch.int32)
+        n = slots.numel()
+        score = torch.full((n,), -7.0, dtype=torch.float32, device=self._dev())
+        score64 = torch.full((n,), -7.0, dtype=torch.float64, device=self._dev()) if f64 else None
+        mn = torch.full((1,), -7.0, dtype=torch.float32, device=self._dev())
+        self._run(wait, self._lib.jsorb_keyframe_database_score_async, *self._vec(vec), slots.data_ptr() if n else None, n, score.data_ptr() if n else None,
+                  score64.data_ptr() if f64 and n else None, mn.data_ptr())
+        return score, score64, mn
+
+    def _neighbours(self, neighbours):
+        import torch
+        if not hasattr(neighbours, "data_ptr") or not getattr(neighbours, "is_cuda", False) or neighbours.dtype != torch.int32 or \
+                tuple(neighbours.shape) != (self.max_keyframes, 10) or not neighbours.is_contiguous():
+            raise JsorbError("KeyframeDatabase: neighbours must be a contiguous int32 device tensor of shape (%d, 10)" % self.max_keyframes)
+        return neighbours.data_ptr()
+
+    def _query(self, name, args, wait, sync):
+        import torch
+        if sync:
+            out, n = np.full(self.max_keyframes, -7, np.int32), C.c_int(-7)
+            torch.cuda.current_stream(self._dev()).synchronize()
+            self._chk(getattr(self._lib, name)(self._d, *args, out.ctypes.data, C.byref(n)))
+            return out[:n.value].copy()
+        cand = torch.full((self.max_keyframes,), -7, dtype=torch.int32, device=self._dev())
+        n = torch.full((1,), -7, dtype=torch.int32, device=self._dev())
+        self._run(wait, getattr(self._lib, name + "_async"), *args, cand.data_ptr(), n.data_ptr())
+        return cand, n
+
+    def detect_loop_candidates(self, vec, query_id, neighbours, min_score=0.0, connected=None, wait=True, sync=False):
+        """jsorb_detect_loop_candidates_async -> (candidates int32[max_keyframes], count int32[1]) device tensors; sync=True: the synchronous
+        form, a host array of the candidates.  min_score: a number, or a float32[1] device tensor (score()'s third output, no wait in between).
+        connected: a uint8 / bool device tensor of max_keyframes entries, or None."""
+        import torch
+        dev_min = hasattr(min_score, "data_ptr")
+        if dev_min:
+            self._tensor("min_score", min_score, torch.float32, 1)
+        if connected is not None:
+            if connected.dtype == torch.bool:
+                connected = connected.view(torch.uint8)
+            self._tensor("connected", connected, torch.uint8, self.max_keyframes)
+        args = self._vec(vec) + [C.c_uint64(int(query_id)), connected.data_ptr() if connected is not None else None, self._neighbours(neighbours),
+                                 0.0 if dev_min else float(min_score), min_score.data_ptr() if dev_min else None]
+        return self._query("jsorb_detect_loop_candidates", args, wait, sync)
+
+    def detect_relocalization_candidates(self, vec, query_id, neighbours, wait=True, sync=False):
+        """jsorb_detect_relocalization_candidates_async, as detect_loop_candidates"""
+        args = self._vec(vec) + [C.c_uint64(int(query_id)), self._neighbours(neighbours)]
+        return self._query("jsorb_detect_relocalization_candidates", args, wait, sync)
+
+    def stats(self):
+        """jsorb_detect_candidates_stats of the last query: dict(n_sharing, max_common, min_common, n_scored, n_kept, best_acc, n_candidates)"""
+        v = [C.c_int() for _ in range(5)]
+        best, n = C.c_float(), C.c_int()
+        self._chk(self._lib.jsorb_detect_candidates_stats(self._d, *[C.byref(t) for t in v], C.byref(best), C.byref(n)))
+        out = dict(zip(("n_sharing", "max_common", "min_common", "n_scored", "n_kept"), (t.value for t in v)))
+        out.update(best_acc=np.float32(best.value), n_candidates=n.value)
+        return out
+
+    def state(self):
+        """jsorb_keyframe_database_copy_state: dict of host arrays of max_keyframes entries (STATE_KEYS)"""
+        out = {k: np.zeros(self.max_keyframes, t) for k, t in zip(self.STATE_KEYS, self.STATE_TYPES)}
+        self._chk(self._lib.jsorb_keyframe_database_copy_state(self._d, *[out[k].ctypes.data for k in self.STATE_KEYS]))
+        return out
 
 
 def matched_pairs(match12_row):
