@@ -945,6 +945,65 @@ int jsorb_keyframe_database_copy_state(jsorb_keyframe_database *db, int32_t *pre
  * ids jsorb_bow_vector_async sorts in LDS (8192).  Any pointer may be NULL. */
 int jsorb_kfdb_build_caps(int *query_lds, int *sort_lds);
 
+/* ---- training a vocabulary: TemplatedVocabulary::create(training_features, k, L, weighting, scoring)
+ * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:557-996) with FORB::meanValue / FORB::distance (FORB.cpp:28-101) ----
+ * Hierarchical k-means++ and Lloyd iterations under the Hamming distance, on the device, one level of the tree at a time.  The result is the
+ * tree the reference returns - node order, word ids, weights - as the flat arrays jsorb_vocabulary_create takes.
+ * Input: `descriptors` n x 32 bytes at a DEVICE pointer, 16-byte aligned: DBoW2's `features` in the order of getFeatures (:620-637), the documents
+ *   concatenated.  doc_start: a HOST array of n_docs + 1 ascending offsets, doc_start[0] = 0, doc_start[n_docs] = n (document i is
+ *   training_features[i]; it matters only for the weights).  weighting: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY; scoring 0..5 (kept for the text file).
+ * JSORB_ERR_INVALID (nothing is launched): n = 0 (the reference leaves only the root, jsorb_vocabulary_create needs two nodes), n < 0 or
+ *   n > 2^30; k outside [2, 32]; depth_L outside [1, 16]; 1 + k + ... + k^depth_L beyond 2^31 - 1 (the reference's expected_nodes, :565);
+ *   weighting outside [0, 3], scoring outside [0, 5]; n_docs < 1, offsets that are not ascending from 0, doc_start[n_docs] != n; max_iterations < 0;
+ *   a NULL or misaligned pointer.
+ * One k-means run (HKmeansStep, :641-819) works on a node's descriptors, always a subsequence of the input in ascending input order (:749):
+ *   trivial (:660-670)  at most k descriptors: one cluster per descriptor, no draw
+ *   seeding (:832-913)  the first centre is RandomInt(0, size - 1); then, until k centres exist, min_dists is lowered by the last centre
+ *                       (:872-880), dist_sum is their sum - at 0 the seeding ends with fewer than k centres (:908) -, cut_d =
+ *                       RandomValue<double>(0, dist_sum) is drawn again while it is 0.0, and the next centre is the first index whose running sum is
+ *                       >= cut_d (the last feature when none is, :893-903).  The distances are integers and the sums stay below 2^53: every sum
+ *                       is exact in any order, and `running >= cut_d` is `running >= ceil(cut_d)` in integers
+ *   association (:732-751)  the nearest centre, the first of equals (strict <)
+ *   means (FORB::meanValue)  bit set iff its count >= N / 2 + N % 2; N = 1 copies the member.  N = 0 is undefined in the reference (the mean is
+ *                       released and the next distance reads through a null pointer): here the cluster keeps its previous centre
+ *   end (:755-779)      when a pass leaves every association as it was.  A converged run is a fixed point, so all runs of a level iterate
+ *                       together until none moves; the runs that had converged earlier stay what they were
+ * Random draws.  The reference calls rand() (seeded from the clock) in depth-first order; here the j-th 31-bit value a run consumes (j = 0, 1, ...,
+ *   the redraws included) is a function of the seed, the input index `first` of the run's first descriptor, the run's size and j:
+ *       mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31
+ *       r = mix(mix(seed ^ ((uint64)first << 32 | size)) + j) >> 33
+ *   with the reference's formulas and RAND_MAX = 2^31 - 1: RandomInt(0, size - 1) = int(((double)r / 2147483648.0) * size) (Random.cpp:47-50),
+ *   RandomValue<double>(0, s) = ((double)r / 2147483647.0) * s (Random.h:55-69).
+ * The tree.  A run's clusters become consecutive nodes (:785-793); the recursion goes on only below level depth_L and only into children with more
+ *   than one descriptor, in child order (:796-818): node ids are depth-first by blocks of siblings, word ids the leaves in id order (:917-938).
+ * Weights (:942-996).  Ni[w]: the documents with at least one descriptor whose transform (:1217-1259, jsorb_bow_transform_descriptors on the
+ *   finished tree) ends in word w - computed for every weighting.  TF_IDF and IDF: weight = log((double)n_docs / (double)Ni) with the host's libm,
+ *   0 where Ni = 0; TF and BINARY: 1.  Inner nodes: weight 0, Ni 0.
+ * max_iterations: the reference loops for ever when Lloyd cycles.  Here a level ends after max_iterations association passes (0: 1000); the runs a
+ *   descriptor of which moved in the last pass are counted in n_unconverged, their nodes are the centres that pass measured against, their
+ *   children's members that pass's association.  The status stays JSORB_OK.
+ * Synchronous: the work is enqueued on hip_stream (a hipStream_t on the device, NULL: the null stream) and waited for; the host reads one word
+ *   per association pass, and per level the centres and member counts of the level's runs.  Nothing faults on any content of `descriptors`.
+ * The result is a host object.  copy: parent int32[n_nodes] (parent[0] = -1), child_start int32[n_nodes + 1], children int32[n_nodes - 1],
+ *   descriptors uint8[n_nodes x 32] (row 0 zero), word_id int32[n_nodes] (-1 for inner nodes), weight double[n_nodes], Ni int32[n_nodes]; any
+ *   pointer may be NULL.  copy_assignment: per input descriptor the node its path of associations ended in (a leaf), int32[n].
+ * stats: k-means runs (the runs that seeded: more than k descriptors), draws consumed, clusters of those runs without a member in the last pass,
+ *   n_unconverged, and the association passes per level (lloyd_passes[16], 0 for a level without a seeded run). */
+typedef struct jsorb_vocab_train_result jsorb_vocab_train_result;
+int jsorb_vocabulary_train(int device_id, void *hip_stream, const uint8_t *descriptors, int n, const int32_t *doc_start, int n_docs, int k, int depth_L,
+                           int weighting, int scoring, uint64_t seed, int max_iterations, jsorb_vocab_train_result **out);
+const char *jsorb_vocabulary_train_last_error(void);                 /* text of the last failed jsorb_vocabulary_train of this thread */
+void jsorb_vocab_train_result_destroy(jsorb_vocab_train_result *r);
+int jsorb_vocab_train_result_info(const jsorb_vocab_train_result *r, int *n_nodes, int *n_words, int *n, int *k, int *depth_L, int *weighting, int *scoring);
+int jsorb_vocab_train_result_copy(const jsorb_vocab_train_result *r, int32_t *parent, int32_t *child_start, int32_t *children, uint8_t *descriptors,
+                                  int32_t *word_id, double *weight, int32_t *Ni);
+int jsorb_vocab_train_result_copy_assignment(const jsorb_vocab_train_result *r, int32_t *node_of_descriptor);
+int jsorb_vocab_train_stats(const jsorb_vocab_train_result *r, int *n_kmeans_runs, long long *n_draws, int *n_empty_clusters, int *n_unconverged,
+                            int *lloyd_passes);
+/* The compile-time caps of the library in use: positions per chunk of the kernels' chunk sums (1024), chunk sums the scan kernel takes per tile
+ * (1024).  Any pointer may be NULL. */
+int jsorb_vocab_train_build_caps(int *chunk, int *scan_threads);
+
 /* ---- loop-closure candidates by BoW: ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12)
  * (src/ORBmatcher.cpp:509-642) with ComputeThreeMaxima (:2097-2138), as LoopClosing::ComputeSim3 calls it once per consistent loop candidate with
  * ORBmatcher matcher(0.75, true) (src/LoopClosing.cpp:244, :270) - the current keyframe against ALL candidates in one call of the keyframe matcher

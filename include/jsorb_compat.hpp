@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <stdexcept>
@@ -503,6 +504,58 @@ public:
 private:
     jsorb_vocabulary *v_ = nullptr;
 };
+// A vocabulary trained on the device: what ORBVocabulary::create(training_features, k, L, weighting, scoring) leaves in m_nodes
+// (jsorb_vocabulary_train, include/jsorb.h), as flat host arrays - node 0 the root, DBoW2's node ids and word ids - with Ni per node and the
+// statistics of the run.
+struct TrainedVocabulary {
+    int n_nodes = 0, n_words = 0, k = 0, depth_L = 0, weighting = 0, scoring = 0;
+    std::vector<int32_t> parent, child_start, children, word_id, Ni;
+    std::vector<unsigned char> descriptors;      // n_nodes x 32
+    std::vector<double> weight;
+    int n_kmeans_runs = 0, n_empty_clusters = 0, n_unconverged = 0, lloyd_passes[16] = {0};
+    long long n_draws = 0;
+};
+// vocabulary.create(training_features, k, L, weighting, scoring) for n descriptors on the DEVICE (n x 32 bytes, the documents concatenated;
+// doc_start: the n_docs + 1 offsets of training_features[i]).  Waits for its work on hip_stream.
+inline TrainedVocabulary TrainVocabulary(const unsigned char *descriptors_gpu, int n, const std::vector<int32_t> &doc_start, int k, int L, int weighting = 0,
+                                         int scoring = 0, uint64_t seed = 0, int max_iterations = 0, void *hip_stream = nullptr, int device_id = 0)
+{
+    jsorb_vocab_train_result *r = nullptr;
+    const int rc = jsorb_vocabulary_train(device_id, hip_stream, descriptors_gpu, n, doc_start.data(), (int)doc_start.size() - 1, k, L, weighting, scoring,
+                                          seed, max_iterations, &r);
+    if (rc == JSORB_ERR_INVALID) throw std::invalid_argument(jsorb_vocabulary_train_last_error());
+    if (rc != JSORB_OK) throw std::runtime_error(jsorb_vocabulary_train_last_error());
+    TrainedVocabulary t;
+    jsorb_vocab_train_result_info(r, &t.n_nodes, &t.n_words, nullptr, &t.k, &t.depth_L, &t.weighting, &t.scoring);
+    const size_t nn = (size_t)t.n_nodes;
+    t.parent.resize(nn); t.child_start.resize(nn + 1); t.children.resize(nn - 1); t.word_id.resize(nn); t.Ni.resize(nn);
+    t.descriptors.resize(nn * 32); t.weight.resize(nn);
+    jsorb_vocab_train_result_copy(r, t.parent.data(), t.child_start.data(), t.children.data(), t.descriptors.data(), t.word_id.data(), t.weight.data(),
+                                  t.Ni.data());
+    jsorb_vocab_train_stats(r, &t.n_kmeans_runs, &t.n_draws, &t.n_empty_clusters, &t.n_unconverged, t.lloyd_passes);
+    jsorb_vocab_train_result_destroy(r);
+    return t;
+}
+// the device vocabulary of a trained tree (levels_up: the 4 of Frame::ComputeBoW)
+inline std::unique_ptr<Vocabulary> MakeVocabulary(const TrainedVocabulary &t, int levels_up = 4, int device_id = 0)
+{
+    return std::unique_ptr<Vocabulary>(new Vocabulary(t.n_nodes, t.depth_L, levels_up, t.child_start.data(), t.children.data(), t.descriptors.data(),
+                                                      t.word_id.data(), t.weight.data(), device_id));
+}
+// saveToTextFile (TemplatedVocabulary.h:1428-1457): `k L scoring weighting`, then per node `parent isLeaf b0 .. b31 weight` in node id order
+// (the weight with 17 significant digits: it reads back to the same double)
+inline bool SaveVocabularyText(const TrainedVocabulary &t, const std::string &path)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    fprintf(f, "%d %d %d %d\n", t.k, t.depth_L, t.scoring, t.weighting);
+    for (int i = 1; i < t.n_nodes; i++) {
+        fprintf(f, "%d %d ", t.parent[i], t.word_id[i] >= 0 ? 1 : 0);
+        for (int b = 0; b < 32; b++) fprintf(f, "%d ", (int)t.descriptors[(size_t)i * 32 + b]);
+        fprintf(f, "%.17g\n", t.weight[i]);
+    }
+    return fclose(f) == 0;
+}
 // The keyframe-to-keyframe matcher of LocalMapping (jsorb_keyframe_matcher, include/jsorb.h): RAII over the C calls.  It owns its stream and
 // scratch, so LocalMapping's thread never touches Tracking's extractors.  One object per thread.
 class KeyframeMatcher {

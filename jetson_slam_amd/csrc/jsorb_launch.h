@@ -430,6 +430,44 @@ void launch_kfdb_bow_vector(const int32_t *word_id, int n, const double *weight,
 void launch_kfdb_add(const KfdbState &st, int slot, uint32_t seq, int off, const KfdbVector &v, hipStream_t s);
 void launch_kfdb_score(const KfdbScoreArgs &a, hipStream_t s);
 void launch_kfdb_query(const KfdbQueryArgs &a, hipStream_t s);
+// k_vocab_train.hip: TemplatedVocabulary::create, one level of the tree at a time.  The nodes of a level are the S segments seg_start[s] ..
+// seg_start[s + 1] of the m positions; position p holds input descriptor perm[p], whose 32 bytes are rows[perm[p]].
+struct VocabTrainArgs {
+    int m, S, k;
+    unsigned long long seed;
+    const uint8_t *rows;                         // the caller's n x 32 bytes, read through perm
+    const int32_t *perm;                         // m
+    const int32_t *seg_start;                    // S + 1
+    const int32_t *cslot;                        // S: the segment's slot in `counters`, -1 for the trivial segments (size <= k)
+    int32_t *seg_of;                             // m
+    int32_t *seg_nc, *seg_j, *seg_changed;       // S: centres, draws consumed, the last pass that moved a descriptor
+    uint32_t *centres;                           // S x k x 8 dwords
+    uint32_t *cnt;                               // S x k members of the last pass
+    uint32_t *counters;                          // slots x k x 256 bit counts
+    uint8_t *assoc;                              // m
+    uint32_t *mind;                              // m: min_dists
+    uint32_t *chunk_sum;                         // chunks
+    unsigned long long *chunk_pre;               // chunks + 1
+    int32_t *level_word;                         // the last pass that moved any descriptor
+    // regrouping
+    uint32_t *hist, *hist_pre;                   // chunks x k, (chunks + 1) x k
+    uint32_t *seg_rank;                          // S x k: positions before the segment with each cluster index
+    const int32_t *dest_base;                    // S x k: the child's first position on the next level, -1 when it ends here
+    const int32_t *node_base;                    // S: the level-order node number of the segment's first child
+    int m_next;
+    int32_t *perm_out;                           // m_next
+    int32_t *leaf;                               // n: per input descriptor the level-order node its path ended in
+};
+int vocab_train_chunk();                        // the compile-time caps of k_vocab_train.hip (jsorb_vocab_train_build_caps)
+int vocab_train_scan_threads();
+inline int vocab_train_chunks(int m) { return (m + vocab_train_chunk() - 1) / vocab_train_chunk(); }
+void launch_vocab_train_iota(int32_t *perm, int n, hipStream_t s);
+void launch_vocab_train_seed(const VocabTrainArgs &a, hipStream_t s);             // seg_of, the first centre, then k - 1 kmeans++ steps
+void launch_vocab_train_assign(const VocabTrainArgs &a, int pass, hipStream_t s);
+void launch_vocab_train_means(const VocabTrainArgs &a, hipStream_t s);
+void launch_vocab_train_regroup(const VocabTrainArgs &a, hipStream_t s);
+void launch_vocab_train_doc_words(const int32_t *word_id, int i0, int i1, const int32_t *doc_start, int d0, int d1, int n_words, uint32_t *bitmap,
+                                  int32_t *ni, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -74,6 +74,8 @@ EXPORTS = [
     "jsorb_keyframe_database_erase", "jsorb_keyframe_database_clear", "jsorb_keyframe_database_score_async", "jsorb_detect_loop_candidates_async",
     "jsorb_detect_relocalization_candidates_async", "jsorb_detect_loop_candidates", "jsorb_detect_relocalization_candidates",
     "jsorb_detect_candidates_stats", "jsorb_keyframe_database_copy_state", "jsorb_kfdb_build_caps",
+    "jsorb_vocabulary_train", "jsorb_vocabulary_train_last_error", "jsorb_vocab_train_result_destroy", "jsorb_vocab_train_result_info",
+    "jsorb_vocab_train_result_copy", "jsorb_vocab_train_result_copy_assignment", "jsorb_vocab_train_stats", "jsorb_vocab_train_build_caps",
 ]
 
 
@@ -444,6 +446,14 @@ def load_library(path=None):
         "jsorb_detect_candidates_stats": (I, [P] + [C.POINTER(I)] * 5 + [C.POINTER(F), C.POINTER(I)]),
         "jsorb_keyframe_database_copy_state": (I, [P] * 8),
         "jsorb_kfdb_build_caps": (I, [C.POINTER(I)] * 2),
+        "jsorb_vocabulary_train": (I, [I, P, P, I, P, I, I, I, I, I, C.c_uint64, I, C.POINTER(P)]),
+        "jsorb_vocabulary_train_last_error": (C.c_char_p, []),
+        "jsorb_vocab_train_result_destroy": (None, [P]),
+        "jsorb_vocab_train_result_info": (I, [P] + [C.POINTER(I)] * 7),
+        "jsorb_vocab_train_result_copy": (I, [P] * 8),
+        "jsorb_vocab_train_result_copy_assignment": (I, [P, P]),
+        "jsorb_vocab_train_stats": (I, [P, C.POINTER(I), C.POINTER(C.c_longlong), C.POINTER(I), C.POINTER(I), P]),
+        "jsorb_vocab_train_build_caps": (I, [C.POINTER(I)] * 2),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1009,6 +1019,59 @@ def kfdb_build_caps():
     q, s = C.c_int(), C.c_int()
     load_library().jsorb_kfdb_build_caps(C.byref(q), C.byref(s))
     return q.value, s.value
+
+
+def vocab_train_build_caps():
+    """jsorb_vocab_train_build_caps of the loaded library: (positions per chunk of k_vocab_train, chunk sums its scan takes per tile)"""
+    c, t = C.c_int(), C.c_int()
+    load_library().jsorb_vocab_train_build_caps(C.byref(c), C.byref(t))
+    return c.value, t.value
+
+
+WEIGHTING_TF_IDF, WEIGHTING_TF, WEIGHTING_IDF, WEIGHTING_BINARY = 0, 1, 2, 3     # DBoW2::WeightingType
+
+
+def train_vocabulary(descriptors, doc_start, k, L, weighting=WEIGHTING_TF_IDF, scoring=0, seed=0, max_iterations=0, stream_ptr=None, device_id=0):
+    """jsorb_vocabulary_train (include/jsorb.h): TemplatedVocabulary::create on the device.  descriptors: uint8[n, 32], a contiguous torch device
+    tensor (16-byte aligned) or a numpy array, which is uploaded; doc_start: n_docs + 1 ascending offsets from 0 to n (host).  Returns the tree
+    as the dict jetson_slam_amd.vocabulary builds (n_nodes, depth_L, k, child_start, children, descriptors, word_id, weight: what orb.Vocabulary
+    and vocabulary.save_text take) with scoring, weighting, parent, Ni (per node), leaf (the node each descriptor's associations ended in) and the
+    statistics n_words, n_kmeans_runs, n_draws, n_empty_clusters, n_unconverged, lloyd_passes (per level).  stream_ptr: a hipStream_t to enqueue
+    on (None: the null stream); the call waits for the current torch stream before it starts and for its own work before it returns."""
+    import torch
+    lib = load_library()
+    if isinstance(descriptors, np.ndarray):
+        descriptors = torch.from_numpy(np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)).to(torch.device("cuda", device_id))
+    if not getattr(descriptors, "is_cuda", False) or descriptors.dtype != torch.uint8:
+        raise JsorbError("train_vocabulary: descriptors must be a uint8 device tensor or a numpy array")
+    if descriptors.dim() != 2 or descriptors.shape[1] != 32 or not descriptors.is_contiguous():
+        raise JsorbError("train_vocabulary: descriptors must be contiguous, of shape (n, 32)")
+    n = int(descriptors.shape[0])
+    ds = np.ascontiguousarray(doc_start, np.int32)
+    if ds.ndim != 1 or len(ds) < 1:
+        raise JsorbError("train_vocabulary: doc_start must hold n_docs + 1 offsets")
+    torch.cuda.current_stream(descriptors.device).synchronize()
+    res = C.c_void_p()
+    rc = lib.jsorb_vocabulary_train(descriptors.device.index or 0, stream_ptr, descriptors.data_ptr() if n else None, n, ds.ctypes.data, len(ds) - 1,
+                                    int(k), int(L), int(weighting), int(scoring), int(seed) & (2 ** 64 - 1), int(max_iterations), C.byref(res))
+    if rc != 0:
+        raise JsorbError("jsorb_vocabulary_train rc=%d: %s" % (rc, lib.jsorb_vocabulary_train_last_error().decode()))
+    try:
+        v = [C.c_int() for _ in range(7)]
+        lib.jsorb_vocab_train_result_info(res, *[C.byref(x) for x in v])
+        nn, n_words = v[0].value, v[1].value
+        t = dict(n_nodes=nn, n_words=n_words, depth_L=int(L), k=int(k), scoring=int(scoring), weighting=int(weighting),
+                 parent=np.zeros(nn, np.int32), child_start=np.zeros(nn + 1, np.int32), children=np.zeros(nn - 1, np.int32),
+                 descriptors=np.zeros((nn, 32), np.uint8), word_id=np.zeros(nn, np.int32), weight=np.zeros(nn, np.float64), Ni=np.zeros(nn, np.int32),
+                 leaf=np.zeros(n, np.int32))
+        lib.jsorb_vocab_train_result_copy(res, *[t[key].ctypes.data for key in ("parent", "child_start", "children", "descriptors", "word_id", "weight", "Ni")])
+        lib.jsorb_vocab_train_result_copy_assignment(res, t["leaf"].ctypes.data)
+        runs, draws, empty, unconv, passes = C.c_int(), C.c_longlong(), C.c_int(), C.c_int(), np.zeros(16, np.int32)
+        lib.jsorb_vocab_train_stats(res, C.byref(runs), C.byref(draws), C.byref(empty), C.byref(unconv), passes.ctypes.data)
+        t.update(n_kmeans_runs=runs.value, n_draws=draws.value, n_empty_clusters=empty.value, n_unconverged=unconv.value, lloyd_passes=[int(x) for x in passes])
+    finally:
+        lib.jsorb_vocab_train_result_destroy(res)
+    return t
 
 
 class KeyframeDatabase:
