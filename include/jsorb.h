@@ -863,6 +863,83 @@ int jsorb_distinctive_descriptors_stats(jsorb_keyframe_matcher *m, int *n_group,
  * tier holds in LDS (1024).  Any pointer may be NULL. */
 int jsorb_distinct_build_caps(int *group_lanes, int *wave_max, int *lds_descriptors);
 
+/* ---- the local map on the device: Tracking::UpdateLocalPoints (src/Tracking.cpp:1818-1841), the frame marks and the map_points list of
+ * Tracking::SearchLocalPoints (:1352-1367, :1410-1420) and K16 (src/cuda/tracking_isinfrustum.cu:19-117) over that list, in ONE call on the
+ * handle's stream whose outputs are the inputs of jsorb_search_local_points_async ----
+ * The map points live in a DEVICE table of n_rows rows chosen by the caller - the rows of desc_out in jsorb_distinctive_descriptors, which
+ * writes `desc` in place; jsorb_map_points_scatter_async below writes the rest.  A keyframe's GetMapPointMatches() is its run of kf_point_row (one
+ * row per keypoint, -1 = NULL); the local keyframes are concatenated under kf_start as for the keyframe matchers, in the order of
+ * mvpLocalKeyFrames.  E = kf_start[n_keyframes] - kf_start[0] entries; entry j is kf_point_row[kf_start[0] + j].  frame_point_row[k] is the row of
+ * mCurrentFrame.mvpMapPoints[k] (-1 = NULL) for the N keypoints of image `image` of the last extract.  In this order:
+ *   1. frame marks (:1352-1367): keypoint k with r = frame_point_row[k] in [0, n_rows) and bad[r] == 0 marks row r as seen (mnLastFrameSeen) and
+ *      gets blocked_in[k] = 1; every other keypoint - -1, any other row outside the table, a bad row (the reference sets it to NULL) - gets
+ *      blocked_in[k] = 0.  frame_point_row NULL: no row is seen, blocked_in all 0.  blocked_in NULL: not written.
+ *   2. mvpLocalMapPoints (:1822-1840): the entries in order; an entry is dropped when its row is negative (!pMP, n_null), when its row is
+ *      >= n_rows (n_invalid_rows: counted, the table is never read there), when bad[row] != 0 (n_bad), or when an earlier entry that is not
+ *      dropped has the same row (mnTrackReferenceForFrame, n_duplicates).  counts[0] = the entries kept.
+ *   3. map_points (:1410-1420): those without the rows seen in step 1 (n_seen of them).  counts[1] = its size.
+ *   4. K16 for each of them with the host values `prm` (the arguments of jsorb_is_in_frustum, Rcw / tcw / Ow by value): the same device function
+ *      k_is_in_frustum runs, so u, v, invz, predicted_level, view_cos and the verdict are bit-equal to jsorb_is_in_frustum on the gathered
+ *      arrays.  counts[2] = the points inside (nToMatch).
+ *   5. output: the points inside, in list order, compacted: slot i < min(counts[2], capacity) holds point_row[i] = the table row, u, v, invz,
+ *      predicted_level, view_cos, in_frustum[i] = 1 and mp_descriptors[32 i ..] = desc[32 row ..].  Every slot from there to `capacity` holds
+ *      in_frustum = 0, point_row = -1, zeros in the other arrays.  counts[3] = the slots written, counts[4] = 1 when counts[2] > capacity: the
+ *      points kept are then the first `capacity` of the list, a prefix.
+ * jsorb_search_local_points_async(e, image, params, n_points = capacity, u, v, invz, predicted_level, view_cos, in_frustum, mp_descriptors,
+ * u_right, blocked_in, ...) on these arrays gives the reference's matches, match_kp[i] belonging to row point_row[i]: SearchByProjection skips the
+ * points outside the frustum (src/ORBmatcher.cpp:43-47), so leaving them out changes nothing, and the order is kept.
+ * All arrays are DEVICE pointers except kf_start (HOST, n_keyframes + 1, ascending, >= 0); the outputs have `capacity` entries, blocked_in N,
+ * counts_dev 5; table->desc and mp_descriptors 16-byte aligned.  Defined for every device input: a row is range-checked before anything is read
+ * through it.  What stays on the host: UpdateLocalKeyFrames' graph walk, IncreaseVisible over point_row, mbTrackInView, applying match_kp.
+ * Enqueued on the handle's stream behind the last extract, no host decision after the argument checks, launch shapes from E, N and capacity
+ * alone, capturable once the scratch has its size (a call with the same or larger n_rows, E and capacity has run); the call does not
+ * synchronise.  Four kernels: k_lm_marks, k_lm_list, k_lm_scan, k_lm_write.  The scratch is one word per table row in the handle, grown only,
+ * and every call restores the words it touched through its own entries and keypoints: the cost follows E + N + capacity, not n_rows.
+ * JSORB_ERR_INVALID: NULL table, prm, kf_start (with n_keyframes > 0), counts_dev, a NULL table array with n_rows > 0, kf_point_row NULL with
+ * E > 0, a NULL output with capacity > 0; n_rows < 0, n_keyframes < 0, capacity < 0; kf_start negative or descending; desc or mp_descriptors not
+ * 16-byte aligned; E >= 2^24.  JSORB_ERR_STATE: no extract result for `image`.  n_keyframes == 0 or E == 0 is a valid call: the padding and
+ * zero counts are written (and blocked_in, from the frame marks). */
+typedef struct jsorb_map_point_table {       /* DEVICE arrays of n_rows entries */
+    int n_rows;
+    const float *Px, *Py, *Pz, *Pnx, *Pny, *Pnz;                                   /* MapPoint::GetWorldPosNormalExp */
+    const float *MaxDistance, *invariance_maxDistance, *invariance_minDistance;    /* MapPoint::GetDistanceInvariances */
+    const uint8_t *desc;                                                           /* n_rows x 32, 16-byte aligned: mDescriptor */
+    const uint8_t *bad;                                                            /* isBad() */
+} jsorb_map_point_table;
+typedef struct jsorb_frustum_params {        /* host values, the arguments of jsorb_is_in_frustum */
+    float Rcw[9], tcw[3], Ow[3], fx, fy, cx, cy;
+    int minX, maxX, minY, maxY, nScaleLevels;
+    float logScaleFactor, viewCosAngle;
+} jsorb_frustum_params;
+int jsorb_local_map_points_async(jsorb_extractor *e, int image, const jsorb_map_point_table *table, const jsorb_frustum_params *prm, int n_keyframes,
+                                 const int32_t *kf_start, const int32_t *kf_point_row, const int32_t *frame_point_row, int capacity,
+                                 int32_t *point_row, float *u, float *v, float *invz, int32_t *predicted_level, float *view_cos, uint8_t *in_frustum,
+                                 uint8_t *mp_descriptors, uint8_t *blocked_in, int32_t *counts_dev);
+/* Synchronous: the same, then point_row_host[capacity] and counts_host[5] (host) in one copy back.  point_row and counts_dev may be NULL here
+ * (buffers of the handle take their place); when given they are written too. */
+int jsorb_local_map_points(jsorb_extractor *e, int image, const jsorb_map_point_table *table, const jsorb_frustum_params *prm, int n_keyframes,
+                           const int32_t *kf_start, const int32_t *kf_point_row, const int32_t *frame_point_row, int capacity, int32_t *point_row,
+                           float *u, float *v, float *invz, int32_t *predicted_level, float *view_cos, uint8_t *in_frustum, uint8_t *mp_descriptors,
+                           uint8_t *blocked_in, int32_t *counts_dev, int32_t *point_row_host, int32_t counts_host[5]);
+/* Diagnostics of the last call (waits for it): E and the entries dropped by each rule of steps 2 and 3.  JSORB_ERR_STATE before the first call.
+ * Any pointer may be NULL. */
+int jsorb_local_map_stats(jsorb_extractor *e, int *n_entries, int *n_null, int *n_invalid_rows, int *n_duplicates, int *n_bad, int *n_seen);
+/* The compile-time cap of the library in use: entries per chunk of the order-preserving compaction (1024). */
+int jsorb_local_map_build_caps(int *scan_chunk);
+/* Keeping the table current: everything a local BA, MapPoint::UpdateNormalAndDepth (src/MapPoint.cpp:367-408) or SetBadFlag (:182-206) changed,
+ * in one kernel from one upload.  records[i] is written to row rows[i] of the nine float arrays and of `bad` (DEVICE arrays of n_rows entries;
+ * rows and records DEVICE, n entries); a row outside [0, n_rows) is skipped; with the same row twice each field takes the value of one of
+ * those records (the caller lists a row once).
+ * Descriptors are not part of it: jsorb_distinctive_descriptors_async writes those in place.  Enqueued on hip_stream, does not synchronise.
+ * JSORB_ERR_INVALID: n < 0, n_rows < 0, or a NULL array with n > 0. */
+typedef struct jsorb_map_point_record {
+    float P[3], Pn[3], MaxDistance, invariance_maxDistance, invariance_minDistance;
+    uint8_t bad, pad[3];
+} jsorb_map_point_record;
+int jsorb_map_points_scatter_async(void *hip_stream, int n_rows, float *Px, float *Py, float *Pz, float *Pnx, float *Pny, float *Pnz, float *MaxDistance,
+                                   float *invariance_maxDistance, float *invariance_minDistance, uint8_t *bad, int n, const int32_t *rows,
+                                   const jsorb_map_point_record *records);
+
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF
  * weights, L1 norm, L1 score.  An object of its own like the keyframe matcher: its stream, its scratch, its error text; whoever creates none

@@ -680,6 +680,75 @@ private:
     jsorb_keyframe_database *d_ = nullptr;
     int max_keyframes_ = 0;
 };
+// The map points as the device table jsorb_local_map_points reads (jsorb_map_point_table, include/jsorb.h): RAII over eleven device arrays of
+// n_rows rows.  A row is the caller's index for a MapPoint* (INTEGRATION.md), the same as the rows of ComputeDistinctiveDescriptors' table, whose
+// device array descriptors() is.  scatter() writes the rows a local BA, UpdateNormalAndDepth or SetBadFlag changed: one upload, one kernel.
+class MapPointTable {
+public:
+    explicit MapPointTable(int n_rows) : n_rows_(n_rows)
+    {
+        const size_t n = n_rows > 0 ? (size_t)n_rows : 1;
+        for (int i = 0; i < 9; i++) check(jsorb_mem_alloc_device(n * sizeof(float), (void **)&f_[i]), "alloc");
+        check(jsorb_mem_alloc_device(n * 32, (void **)&desc_), "alloc");
+        check(jsorb_mem_alloc_device(n, (void **)&bad_), "alloc");
+        for (int i = 0; i < 9; i++) check(jsorb_mem_set_zero(f_[i], n * sizeof(float)), "zero");
+        check(jsorb_mem_set_zero(desc_, n * 32), "zero");
+        check(jsorb_mem_set_zero(bad_, n), "zero");
+    }
+    MapPointTable(const MapPointTable &) = delete;
+    MapPointTable &operator=(const MapPointTable &) = delete;
+    ~MapPointTable()
+    {
+        for (int i = 0; i < 9; i++) jsorb_mem_free_device(f_[i]);
+        jsorb_mem_free_device(desc_); jsorb_mem_free_device(bad_); jsorb_mem_free_device(rows_); jsorb_mem_free_device(rec_);
+    }
+    int n_rows() const { return n_rows_; }
+    unsigned char *descriptors() const { return desc_; }      // n_rows x 32 bytes, DEVICE
+    jsorb_map_point_table view() const { return jsorb_map_point_table{n_rows_, f_[0], f_[1], f_[2], f_[3], f_[4], f_[5], f_[6], f_[7], f_[8], desc_, bad_}; }
+    // the changed rows and their records (host); hip_stream: the stream the table's readers run on (the extractor's)
+    void scatter(const std::vector<int32_t> &rows, const std::vector<jsorb_map_point_record> &records, void *hip_stream = nullptr)
+    {
+        const size_t n = rows.size();
+        if (records.size() != n) throw std::runtime_error("MapPointTable::scatter: one record per row");
+        if (n == 0) return;
+        if (n > cap_) {
+            jsorb_mem_free_device(rows_); jsorb_mem_free_device(rec_);
+            rows_ = nullptr; rec_ = nullptr; cap_ = 0;
+            check(jsorb_mem_alloc_device(n * sizeof(int32_t), (void **)&rows_), "alloc");
+            check(jsorb_mem_alloc_device(n * sizeof(jsorb_map_point_record), (void **)&rec_), "alloc");
+            cap_ = n;
+        }
+        check(jsorb_mem_h2d(rows_, rows.data(), n * sizeof(int32_t)), "upload");
+        check(jsorb_mem_h2d(rec_, records.data(), n * sizeof(jsorb_map_point_record)), "upload");
+        check(jsorb_map_points_scatter_async(hip_stream, n_rows_, f_[0], f_[1], f_[2], f_[3], f_[4], f_[5], f_[6], f_[7], f_[8], bad_, (int)n, rows_, rec_),
+              "scatter");
+        check(jsorb_mem_stream_sync(hip_stream), "sync");      // (the staging arrays are reused by the next scatter)
+    }
+    // n descriptor rows from the host, from row `first` on (a map whose descriptors are not picked on the device)
+    void set_descriptors(int first, int n, const unsigned char *d) { if (n > 0) check(jsorb_mem_h2d(desc_ + 32 * (size_t)first, d, 32 * (size_t)n), "upload"); }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::MapPointTable ") + what + ": " + jsorb_mem_last_error());
+    }
+    int n_rows_ = 0;
+    float *f_[9] = {};
+    unsigned char *desc_ = nullptr, *bad_ = nullptr;
+    int32_t *rows_ = nullptr;
+    jsorb_map_point_record *rec_ = nullptr;
+    size_t cap_ = 0;
+};
+// What UpdateLocalPoints leaves on the device for SearchLocalPoints: `capacity` slots, the map points inside the frustum first, in the order of
+// mvpLocalMapPoints; point_row[i] (host) is the table row of slot i, -1 behind the last; counts as jsorb_local_map_points defines them.
+struct LocalMapPoints {
+    orb_cuda::SyncedMem<float> u, v, invz, viewCos;
+    orb_cuda::SyncedMem<int> predictedlevel, point_row_gpu;
+    orb_cuda::SyncedMem<unsigned char> isinfrustum, descriptors, blocked;
+    std::vector<int32_t> point_row;
+    int32_t counts[5] = {0, 0, 0, 0, 0};
+    int capacity = 0;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -829,6 +898,35 @@ inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params
         throw std::runtime_error(std::string("jsorb_search_local_points: ") + jsorb_last_error(ex.handle()));
     match_kp.resize(n_points > 0 ? n_points : 0);
     return n_matches;
+}
+
+// Tracking::UpdateLocalPoints (Tracking.cpp:1818-1841) and the front half of SearchLocalPoints - the frame marks (:1352-1367), map_points
+// (:1410-1420), the gathers, the uploads and compute_isInFrustum_GPU (:1427-1600) - in one call on the extractor's stream: kf_start (host) and
+// kf_point_row_gpu are mvpLocalKeyFrames' GetMapPointMatches() as table rows, concatenated; frame_point_row_gpu mCurrentFrame.mvpMapPoints as rows
+// (nullptr: none).  Returns nToMatch; out feeds SearchLocalPoints(ex, params, out) below.  The host keeps IncreaseVisible over out.point_row,
+// mbTrackInView and applying the matches.
+inline int UpdateLocalPoints(ORBExtractor &ex, const jsorb::MapPointTable &table, const jsorb_frustum_params &frustum, const std::vector<int32_t> &kf_start,
+                             const int32_t *kf_point_row_gpu, const int32_t *frame_point_row_gpu, int capacity, jsorb::LocalMapPoints &out)
+{
+    const int n = jsorb_n_keypoints(ex.handle(), 0), cap = capacity > 0 ? capacity : 1;
+    out.capacity = capacity;
+    out.u.resize(cap); out.v.resize(cap); out.invz.resize(cap); out.viewCos.resize(cap); out.predictedlevel.resize(cap); out.point_row_gpu.resize(cap);
+    out.isinfrustum.resize(cap); out.descriptors.resize(32 * cap); out.blocked.resize(n > 0 ? n : 1);
+    out.point_row.assign(cap, -1);
+    const jsorb_map_point_table t = table.view();
+    if (jsorb_local_map_points(ex.handle(), 0, &t, &frustum, kf_start.empty() ? 0 : (int)kf_start.size() - 1, kf_start.data(), kf_point_row_gpu, frame_point_row_gpu, capacity,
+                               out.point_row_gpu.gpu_data(), out.u.gpu_data(), out.v.gpu_data(), out.invz.gpu_data(), out.predictedlevel.gpu_data(),
+                               out.viewCos.gpu_data(), out.isinfrustum.gpu_data(), out.descriptors.gpu_data(), out.blocked.gpu_data(), nullptr,
+                               out.point_row.data(), out.counts) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_local_map_points: ") + jsorb_last_error(ex.handle()));
+    out.point_row.resize(capacity > 0 ? capacity : 0);
+    return out.counts[2];
+}
+// ... and the matcher over those slots: match_kp[i] = the keypoint matched to the map point of row out.point_row[i], or -1
+inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params, jsorb::LocalMapPoints &pts, const float *u_right_gpu, std::vector<int> &match_kp)
+{
+    return SearchLocalPoints(ex, params, pts.capacity, pts.u, pts.v, pts.invz, pts.predictedlevel, pts.viewCos, pts.isinfrustum, pts.descriptors, u_right_gpu,
+                             pts.blocked.gpu_data(), match_kp);
 }
 
 // TrackWithMotionModel's matcher.SearchByProjection(mCurrentFrame, mLastFrame, th, bMono) and its retry at 2 th (Tracking.cpp:1045-1064,

@@ -675,6 +675,7 @@ void jsorb_destroy(jsorb_extractor *e)
     rgbd_release(e);
     grid_release(e);
     search_local_release(e);
+    local_map_release(e);
     search_last_release(e);
     search_kf_release(e);
     search_init_release(e);

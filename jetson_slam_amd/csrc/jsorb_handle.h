@@ -1,6 +1,6 @@
 // jsorb_handle.h - internal, host only: the extractor handle and the host helpers shared by the translation units of the C ABI
 // (jsorb_api.hip: handles, streams, timing, memory calls; jsorb_extract.hip: the extract pipeline and its results; jsorb_stereo.hip:
-// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid; jsorb_search.hip: the four grid matchers; jsorb_bow.hip:
+// stereo match and speculation; jsorb_frame.hip: rectification, camera, RGB-D, grid; jsorb_search.hip: the four grid matchers; jsorb_localmap.hip: the local map; jsorb_bow.hip:
 // vocabulary, BoW transform and BoW matching; jsorb_keyframes.hip, jsorb_loop.hip and jsorb_mappoints.hip: the keyframe matcher, which shares the helpers that take any owner).
 // include/jsorb.h only forward-declares the handle, so its layout is free to change.
 #pragma once
@@ -269,6 +269,21 @@ struct jsorb_extractor {
         int out_points = 0;
         bool done = false;
     } kf;
+
+    // ---- the local map (jsorb_localmap.hip, jsorb_local_map_points*): allocated on the first call, grown only ----
+    struct {
+        uint32_t *word = nullptr;          // one word per table row, all ones between calls: bit 31 = not seen by the frame, below it the first entry with the row
+        int rows = 0;
+        bool dirty = false;                // a call's launches were cut short: the next call sets every word again
+        uint8_t *keep = nullptr;           // one byte per entry: inside the frustum
+        int entries = 0;
+        uint32_t *chunk = nullptr;         // chunks sums, then chunks + 1 prefixes
+        int chunks = 0;
+        int32_t *stats = nullptr;          // E, null, invalid rows, duplicates, bad, seen of the last call (device)
+        int32_t *out = nullptr;            // synchronous call: counts (8 words, 5 used), then point_row (out_cap)
+        int out_cap = 0;
+        bool done = false;
+    } lm;
 
     // ---- bag of words (jsorb_bow.hip, jsorb_bow_transform_async / jsorb_search_by_bow*): allocated on first use, the keyframe parts grown only ----
     struct {
@@ -630,6 +645,9 @@ void search_local_release(jsorb_extractor *e);
 void search_last_release(jsorb_extractor *e);
 void search_init_release(jsorb_extractor *e);
 void search_kf_release(jsorb_extractor *e);
+
+// ---- jsorb_localmap.hip ----
+void local_map_release(jsorb_extractor *e);
 
 // ---- jsorb_bow.hip ----
 void bow_after_extract(jsorb_extractor *e);

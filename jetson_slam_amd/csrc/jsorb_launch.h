@@ -468,6 +468,29 @@ void launch_vocab_train_means(const VocabTrainArgs &a, hipStream_t s);
 void launch_vocab_train_regroup(const VocabTrainArgs &a, hipStream_t s);
 void launch_vocab_train_doc_words(const int32_t *word_id, int i0, int i1, const int32_t *doc_start, int d0, int d1, int n_words, uint32_t *bitmap,
                                   int32_t *ni, hipStream_t s);
+// k_lm_marks / k_lm_list / k_lm_scan / k_lm_write (k_local_map.hip): Tracking::UpdateLocalPoints, the frame marks and map_points of
+// SearchLocalPoints and K16 over them, compacted in order into the arrays jsorb_search_local_points_async reads
+struct LocalMapArgs {
+    jsorb_map_point_table t;
+    jsorb_frustum_params p;
+    int E, N, capacity;
+    const int32_t *entry_row;                    // E: kf_point_row from the first keyframe's offset on
+    const int32_t *frame_row;                    // N, or NULL
+    // scratch
+    uint32_t *word;                              // t.n_rows: bit 31 = not seen, the low bits the first entry with the row; all ones between calls
+    uint8_t *keep;                               // E: the entry is a point inside the frustum
+    uint32_t *chunk_sum, *chunk_pre;             // chunks, chunks + 1
+    int32_t *stats;                              // E, null, invalid rows, duplicates, bad, seen
+    // outputs
+    int32_t *point_row, *level;
+    float *u, *v, *invz, *view_cos;
+    uint8_t *in_frustum, *mp_desc, *blocked_in;
+    int32_t *counts;                             // 5
+};
+int local_map_chunk();                           // the compile-time cap of k_local_map.hip (jsorb_local_map_build_caps)
+inline int local_map_chunks(int E) { return (E + local_map_chunk() - 1) / local_map_chunk(); }
+void launch_local_map(const LocalMapArgs &a, hipStream_t s);      // the four kernels
+void launch_map_points_scatter(int n_rows, float *const dst[9], uint8_t *bad, int n, const int32_t *rows, const jsorb_map_point_record *records, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -76,6 +76,7 @@ EXPORTS = [
     "jsorb_detect_candidates_stats", "jsorb_keyframe_database_copy_state", "jsorb_kfdb_build_caps",
     "jsorb_vocabulary_train", "jsorb_vocabulary_train_last_error", "jsorb_vocab_train_result_destroy", "jsorb_vocab_train_result_info",
     "jsorb_vocab_train_result_copy", "jsorb_vocab_train_result_copy_assignment", "jsorb_vocab_train_stats", "jsorb_vocab_train_build_caps",
+    "jsorb_local_map_points_async", "jsorb_local_map_points", "jsorb_local_map_stats", "jsorb_local_map_build_caps", "jsorb_map_points_scatter_async",
 ]
 
 
@@ -262,6 +263,72 @@ def scw_params(camera, bounds, grid, log_scale_factor, scale_factor, Rcw, tcw, O
             raise JsorbError("scw_params: %s must hold %d floats" % (name, size))
         setattr(p, name, (C.c_float * size)(*v.tolist()))
     return p
+
+
+class JsorbMapPointTable(C.Structure):
+    _fields_ = [("n_rows", C.c_int)] + [(k, C.c_void_p) for k in ("Px", "Py", "Pz", "Pnx", "Pny", "Pnz", "MaxDistance", "invariance_maxDistance",
+                                                                 "invariance_minDistance", "desc", "bad")]
+
+
+class JsorbFrustumParams(C.Structure):
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)] + [(k, C.c_float) for k in ("fx", "fy", "cx", "cy")] + \
+               [(k, C.c_int) for k in ("minX", "maxX", "minY", "maxY", "nScaleLevels")] + [("logScaleFactor", C.c_float), ("viewCosAngle", C.c_float)]
+
+
+def make_frustum_params(Rcw, tcw, Ow, camera, bounds, n_levels, log_scale_factor, view_cos_angle=0.5):
+    """jsorb_frustum_params, the host arguments of jsorb_is_in_frustum: Rcw (3x3), tcw (3) and Ow (3) as float32, camera = (fx, fy, cx, cy), bounds =
+    (minX, maxX, minY, maxY) as ints, n_levels = nScaleLevels, log_scale_factor = mfLogScaleFactor, view_cos_angle = viewingCosLimit (0.5)"""
+    R = np.asarray(Rcw, np.float32).ravel()
+    t = np.asarray(tcw, np.float32).ravel()
+    o = np.asarray(Ow, np.float32).ravel()
+    assert R.size == 9 and t.size == 3 and o.size == 3
+    return JsorbFrustumParams((C.c_float * 9)(*R.tolist()), (C.c_float * 3)(*t.tolist()), (C.c_float * 3)(*o.tolist()), *[float(x) for x in camera],
+                               *[int(b) for b in bounds], int(n_levels), float(log_scale_factor), float(view_cos_angle))
+
+
+# jsorb_map_point_record: what MapPointTable.scatter uploads per changed row
+MAP_POINT_RECORD_DTYPE = np.dtype([("P", "<f4", 3), ("Pn", "<f4", 3), ("MaxDistance", "<f4"), ("invariance_maxDistance", "<f4"),
+                                   ("invariance_minDistance", "<f4"), ("bad", "u1"), ("pad", "u1", 3)])
+MAP_POINT_FLOATS = ("Px", "Py", "Pz", "Pnx", "Pny", "Pnz", "MaxDistance", "invariance_maxDistance", "invariance_minDistance")
+
+
+class MapPointTable:
+    """The device table of map points jsorb_local_map_points reads (jsorb_map_point_table): nine float32[n_rows] arrays, desc uint8[n_rows, 32] and
+    bad uint8[n_rows] as torch tensors it owns, rows chosen by the caller (the rows of desc_out in distinctive_descriptors, which may write
+    `desc` in place).  scatter() writes the rows a local BA, UpdateNormalAndDepth or SetBadFlag changed."""
+
+    def __init__(self, n_rows, device="cuda"):
+        import torch
+        self.n_rows = int(n_rows)
+        n = max(self.n_rows, 1)
+        self.floats = torch.zeros((9, n), dtype=torch.float32, device=device)
+        self.desc = torch.zeros((n, 32), dtype=torch.uint8, device=device)
+        self.bad = torch.zeros(n, dtype=torch.uint8, device=device)
+
+    def struct(self):
+        return JsorbMapPointTable(self.n_rows, *[self.floats[i].data_ptr() for i in range(9)], self.desc.data_ptr(), self.bad.data_ptr())
+
+    def scatter(self, rows, records, stream_ptr=None, wait=True):
+        """rows int32[n] (numpy or device tensor) and records MAP_POINT_RECORD_DTYPE[n] (numpy, or a uint8[n, 40] device tensor): one upload each, one
+        kernel.  Rows outside the table are skipped."""
+        import torch
+        dev = self.floats.device
+        if not hasattr(rows, "data_ptr"):
+            rows = torch.from_numpy(np.ascontiguousarray(rows, np.int32)).to(dev)
+        if not hasattr(records, "data_ptr"):
+            rec = np.ascontiguousarray(records, MAP_POINT_RECORD_DTYPE)
+            records = torch.from_numpy(rec.view(np.uint8).reshape(len(rec), MAP_POINT_RECORD_DTYPE.itemsize)).to(dev)
+        n = int(rows.shape[0])
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or records.dtype != torch.uint8 or tuple(records.shape) != (n, 40) or not records.is_contiguous():
+            raise JsorbError("MapPointTable.scatter: rows must be int32[n] and records %d bytes each" % MAP_POINT_RECORD_DTYPE.itemsize)
+        if stream_ptr is None:
+            torch.cuda.current_stream(dev).synchronize()
+        rc = load_library().jsorb_map_points_scatter_async(stream_ptr, self.n_rows, *[self.floats[i].data_ptr() for i in range(9)], self.bad.data_ptr(), n,
+                                                           rows.data_ptr(), records.data_ptr())
+        if rc:
+            raise JsorbError("jsorb_map_points_scatter_async: error %d" % rc)
+        if wait:
+            torch.cuda.synchronize(dev)
 
 
 def make_camera(K, D):
@@ -454,6 +521,11 @@ def load_library(path=None):
         "jsorb_vocab_train_result_copy_assignment": (I, [P, P]),
         "jsorb_vocab_train_stats": (I, [P, C.POINTER(I), C.POINTER(C.c_longlong), C.POINTER(I), C.POINTER(I), P]),
         "jsorb_vocab_train_build_caps": (I, [C.POINTER(I)] * 2),
+        "jsorb_local_map_points_async": (I, [P, I, C.POINTER(JsorbMapPointTable), C.POINTER(JsorbFrustumParams), I, P, P, P, I] + [P] * 10),
+        "jsorb_local_map_points": (I, [P, I, C.POINTER(JsorbMapPointTable), C.POINTER(JsorbFrustumParams), I, P, P, P, I] + [P] * 12),
+        "jsorb_local_map_stats": (I, [P] + [C.POINTER(I)] * 6),
+        "jsorb_local_map_build_caps": (I, [C.POINTER(I)]),
+        "jsorb_map_points_scatter_async": (I, [P, I] + [P] * 10 + [I, P, P]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1026,6 +1098,13 @@ def vocab_train_build_caps():
     c, t = C.c_int(), C.c_int()
     load_library().jsorb_vocab_train_build_caps(C.byref(c), C.byref(t))
     return c.value, t.value
+
+
+def local_map_build_caps():
+    """jsorb_local_map_build_caps of the loaded library: entries per chunk of k_local_map's compaction"""
+    c = C.c_int()
+    load_library().jsorb_local_map_build_caps(C.byref(c))
+    return c.value
 
 
 WEIGHTING_TF_IDF, WEIGHTING_TF, WEIGHTING_IDF, WEIGHTING_BINARY = 0, 1, 2, 3     # DBoW2::WeightingType
@@ -1635,6 +1714,61 @@ class ORBExtractor:
         """{kernel: (total_ms, launches)} of the grid, candidate and resolve kernels, measured like kernel_times()"""
         return {name: self._kernel_time(k) for name, k in (("k_assign_grid", K_ASSIGN_GRID), ("k_local_candidates", K_LOCAL_CANDIDATES),
                                                            ("k_local_resolve", K_LOCAL_RESOLVE))}
+
+    # ---- the local map: Tracking::UpdateLocalPoints, the frame marks and K16 (Tracking.cpp:1818-1841, :1352-1367, :1410-1420) on the device ----
+    def local_map_points(self, table, frustum, kf_start, kf_point_row, frame_point_row, capacity, image=0, sync=False, out=None, wait=True):
+        """jsorb_local_map_points*: table a MapPointTable, frustum a JsorbFrustumParams (make_frustum_params), kf_start host ints (n_keyframes + 1),
+        kf_point_row int32 device tensor (kf_start[-1] entries), frame_point_row int32[N] device tensor or None.  Returns a dict of device
+        tensors with `capacity` entries - point_row, u, v, invz, predicted_level, view_cos, in_frustum, mp_descriptors (capacity x 32) -
+        blocked_in uint8[N] and counts int32[5]: the point arguments of search_local_points.  out: the dict of an earlier call, written again
+        (nothing is allocated).  sync=True: the synchronous form; the dict also holds point_row_host and counts_host (numpy).  Otherwise the
+        call waits for the current torch stream before it starts and for its own work before it returns; wait=False: it only enqueues on the
+        handle's stream (the caller orders the streams - the form a graph capture of that stream takes)."""
+        import torch
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("local_map_points: no extract result for image %d" % image)
+        ks = np.ascontiguousarray(kf_start, np.int32).ravel()
+        n_kf = len(ks) - 1
+        if n_kf < 0:
+            raise JsorbError("local_map_points: kf_start needs n_keyframes + 1 entries")
+        dev = table.floats.device
+
+        def chk(t, name, n):
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or int(t.shape[0]) < n:
+                raise JsorbError("local_map_points: %s must be a contiguous int32 device tensor of at least %d entries" % (name, n))
+            return t.data_ptr()
+
+        kp = chk(kf_point_row, "kf_point_row", int(ks[-1])) if n_kf > 0 and ks[-1] > 0 else None
+        fp = None if frame_point_row is None else chk(frame_point_row, "frame_point_row", N)
+        cap = int(capacity)
+        if out is None:
+            c1 = max(cap, 1)
+            out = dict(point_row=torch.empty(c1, dtype=torch.int32, device=dev)[:max(cap, 0)], predicted_level=torch.empty(c1, dtype=torch.int32, device=dev)[:max(cap, 0)],
+                       in_frustum=torch.empty(c1, dtype=torch.uint8, device=dev)[:max(cap, 0)], mp_descriptors=torch.empty((c1, 32), dtype=torch.uint8, device=dev)[:max(cap, 0)],
+                       blocked_in=torch.empty(max(N, 1), dtype=torch.uint8, device=dev)[:N], counts=torch.empty(5, dtype=torch.int32, device=dev))
+            for k in ("u", "v", "invz", "view_cos"):
+                out[k] = torch.empty(c1, dtype=torch.float32, device=dev)[:max(cap, 0)]
+        tb = table.struct()
+        args = [self._h, image, C.byref(tb), C.byref(frustum), n_kf, ks.ctypes.data, kp, fp, cap] + \
+               [out[k].data_ptr() for k in ("point_row", "u", "v", "invz", "predicted_level", "view_cos", "in_frustum", "mp_descriptors", "blocked_in", "counts")]
+        if wait or sync:
+            torch.cuda.current_stream(dev).synchronize()
+        if sync:
+            rows_h, counts_h = np.full(max(cap, 1), -2, np.int32), np.zeros(5, np.int32)
+            self._chk(self._lib.jsorb_local_map_points(*args, rows_h.ctypes.data, counts_h.ctypes.data))
+            out = dict(out, point_row_host=rows_h[:max(cap, 0)], counts_host=counts_h)
+        else:
+            self._chk(self._lib.jsorb_local_map_points_async(*args))
+            if wait:
+                self.sync()
+        return out
+
+    def local_map_stats(self):
+        """dict(n_entries, n_null, n_invalid_rows, n_duplicates, n_bad, n_seen) of the last local_map_points"""
+        v = [C.c_int() for _ in range(6)]
+        self._chk(self._lib.jsorb_local_map_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_entries", "n_null", "n_invalid_rows", "n_duplicates", "n_bad", "n_seen"), (x.value for x in v)))
 
     # ---- motion-model matching: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cpp:1647-1963) on the device ----
     def search_last_frame(self, Px, Py, Pz, last_octave, last_angle, mp_descriptors, params, u_right=None, image=0):
