@@ -890,7 +890,8 @@ int jsorb_distinct_build_caps(int *group_lanes, int *wave_max, int *lds_descript
  * points outside the frustum (src/ORBmatcher.cpp:43-47), so leaving them out changes nothing, and the order is kept.
  * All arrays are DEVICE pointers except kf_start (HOST, n_keyframes + 1, ascending, >= 0); the outputs have `capacity` entries, blocked_in N,
  * counts_dev 5; table->desc and mp_descriptors 16-byte aligned.  Defined for every device input: a row is range-checked before anything is read
- * through it.  What stays on the host: UpdateLocalKeyFrames' graph walk, IncreaseVisible over point_row, mbTrackInView, applying match_kp.
+ * through it.  UpdateLocalKeyFrames' graph walk and the concatenation are jsorb_local_keyframes_async below (n_keyframes = 1 over its
+ * local_point_row).  What stays on the host: IncreaseVisible over point_row, mbTrackInView, applying match_kp.
  * Enqueued on the handle's stream behind the last extract, no host decision after the argument checks, launch shapes from E, N and capacity
  * alone, capturable once the scratch has its size (a call with the same or larger n_rows, E and capacity has run); the call does not
  * synchronise.  Four kernels: k_lm_marks, k_lm_list, k_lm_scan, k_lm_write.  The scratch is one word per table row in the handle, grown only,
@@ -939,6 +940,78 @@ typedef struct jsorb_map_point_record {
 int jsorb_map_points_scatter_async(void *hip_stream, int n_rows, float *Px, float *Py, float *Pz, float *Pnx, float *Pny, float *Pnz, float *MaxDistance,
                                    float *invariance_maxDistance, float *invariance_minDistance, uint8_t *bad, int n, const int32_t *rows,
                                    const jsorb_map_point_record *records);
+
+/* ---- the local keyframes on the device: Tracking::UpdateLocalKeyFrames (src/Tracking.cpp:1844-1952) and the concatenation of their
+ * GetMapPointMatches() that jsorb_local_map_points_async reads, in ONE call on the handle's stream ----
+ * With it TrackLocalMap runs from the frame's rows to the matches with no host list in between:
+ *   jsorb_local_keyframes_async(e, graph, table, frame_point_row, n_frame, kf_capacity, entry_capacity, local_kf_slot, state_io, local_kf_start,
+ *                               local_point_row, counts) and then
+ *   jsorb_local_map_points_async(e, image, table, prm, 1, kf_start = {0, entry_capacity}, local_point_row, ...): the -1 padding behind E_total is
+ *   dropped there as NULL entries (only n_null of its statistics grows by it) and the order is the reference's.
+ * The graph is a struct of DEVICE arrays over S = max_keyframes slots chosen by the caller, as for the keyframe database:
+ *   state[s]       0 = absent (a free slot, or a keyframe in no point's observations that LocalMapping::ProcessNewKeyFrame has not seen),
+ *                  1 = in the map and good, anything else = isBad()
+ *   order_key[s]   the order of std::map<KeyFrame*, int> (:1847): the binding writes (intptr_t)pKF; equal keys are ordered by slot
+ *   point_off[s], point_len[s] into point_pool[pool_entries]: GetMapPointMatches() as table rows, -1 = NULL - the run the caller keeps for
+ *                  kf_point_row.  registered[pool_entries], or NULL = all 1: 1 where that entry's point holds the keyframe in mObservations.  The
+ *                  reference votes over observations (:1855), and a keyframe made by CreateNewKeyFrame is in its tracked points' observations
+ *                  only after ProcessNewKeyFrame (src/LocalMapping.cpp:158).
+ *   neighbours[s][10]   GetBestCovisibilityKeyFrames(10) as slots in its order, -1 padded: the keyframe database's table
+ *   child_off[s], child_len[s] into child_pool[child_entries]: GetChilds() as slots in std::set<KeyFrame*> order;  parent[s]: -1 = none
+ * A run with len < 0, off < 0 or off + len > entries is an empty run; nothing is read through it.  n_invalid_runs counts the point runs and the
+ * child runs of that kind over the slots with state != 0.  A slot reference is USABLE when it lies in [0, S) and state != 0; every other one
+ * (-1, out of range, absent) is skipped.  This is the one difference from the reference, which would read through the pointer.
+ * In this order, `table` giving n_rows and bad (nothing else of it is read):
+ *   1. mult[r] = the keypoints k < n_frame with frame_point_row[k] == r, 0 <= r < n_rows, bad[r] == 0 (:1848-1864; a point at two keypoints votes
+ *      twice; the mvpMapPoints[i] = NULL of :1861 is what blocked_in of jsorb_local_map_points_async reports).  frame_point_row NULL or n_frame == 0:
+ *      all 0.
+ *   2. vote[s], for state[s] != 0: the sum of mult[row] over the entries of the slot's point run with registered != 0 and row in [0, n_rows)
+ *      (:1855-1857; a run that lists a row twice counts it twice - the caller lists a row once).  n_counter = the slots with vote > 0.
+ *   3. n_counter == 0 (:1866): local_kf_slot, n_local and ref_slot stay, counts[7] = 1, and step 6 runs over the kept list.
+ *   4. the first list (:1876-1891): the slots with state == 1 and vote > 0 in ascending (order_key, slot) order, n_first of them; ref_slot = the
+ *      first in that order whose vote is greater than every earlier one's, unchanged when the list is empty.  n_first > kf_capacity: the first
+ *      kf_capacity are kept, counts[5] = 1 (ref_slot is still that of the whole list).
+ *   5. the expansion (:1895-1945), over the elements of the first list in order: stop when the list holds more than 80; append the first usable
+ *      slot of the element's neighbour row with state == 1 that is not in the list; the same for its child run; its parent, if usable and not in
+ *      the list, is appended whatever its state and ENDS the expansion (the break of :1941 leaves the outer loop).  What an earlier element
+ *      appended is in the list for the later ones.
+ *   6. local_kf_start[i], i <= kf_capacity = the running sum of the point-run lengths of the list (an absent slot or an invalid run counts 0;
+ *      E_total from n_local on); local_point_row[local_kf_start[i] + j] = the run's entries unchanged; -1 from E_total to entry_capacity;
+ *      E_total > entry_capacity: the prefix is kept, counts[6] = 1.
+ *   counts[8] = n_counter, n_first, n_local, ref_slot, E_total, kf_overflow, entry_overflow, kept_previous.
+ * local_kf_slot[kf_capacity] and state_io[2] = {n_local, ref_slot} are IN/OUT (step 3): the caller sets state_io = {0, -1} once.
+ * mpReferenceKF is the keyframe of ref_slot.  All arrays are DEVICE pointers.  Defined for every device input: a slot, a row or a run is
+ * range-checked before anything is read through it.  Enqueued on the handle's stream, no host decision after the argument checks, launch shapes
+ * from S, n_frame and the capacities alone, capturable once the scratch has its size; the call does not synchronise.  Five kernels: k_lk_marks,
+ * k_lk_votes, k_lk_rank, k_lk_expand, k_lk_gather.  mult lives in the row words of jsorb_local_map_points_async and every call sets back the
+ * words it touched, so the two calls follow each other on one handle in either order.
+ * JSORB_ERR_INVALID: NULL graph, table, local_kf_slot, state_io, local_kf_start or counts_dev; a NULL graph array (other than registered, and
+ * the pools of 0 entries) with S > 0; table->bad NULL with n_rows > 0; local_point_row NULL with entry_capacity > 0; a negative size;
+ * S >= 2^24; kf_capacity < 84; entry_capacity >= 2^24. */
+typedef struct jsorb_keyframe_graph {
+    int max_keyframes, pool_entries, child_entries;
+    const uint8_t *state;
+    const int64_t *order_key;
+    const int32_t *point_off, *point_len, *point_pool;
+    const uint8_t *registered;
+    const int32_t *neighbours, *child_off, *child_len, *child_pool, *parent;
+} jsorb_keyframe_graph;
+int jsorb_local_keyframes_async(jsorb_extractor *e, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table,
+                                const int32_t *frame_point_row, int n_frame, int kf_capacity, int entry_capacity, int32_t *local_kf_slot,
+                                int32_t *state_io, int32_t *local_kf_start, int32_t *local_point_row, int32_t *counts_dev);
+/* Synchronous: the same, then local_kf_slot_host[kf_capacity], state_host[2] and counts_host[8] (host) in one copy back
+ * (src/Tracking.cpp:1947-1951: mpReferenceKF from state_host[1]). */
+int jsorb_local_keyframes(jsorb_extractor *e, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table, const int32_t *frame_point_row,
+                          int n_frame, int kf_capacity, int entry_capacity, int32_t *local_kf_slot, int32_t *state_io, int32_t *local_kf_start,
+                          int32_t *local_point_row, int32_t *counts_dev, int32_t *local_kf_slot_host, int32_t state_host[2], int32_t counts_host[8]);
+/* Diagnostics of the last call (waits for it): steps 2-5 of src/Tracking.cpp:1844-1952 - n_counter, n_first, n_local, the keyframes appended as
+ * a neighbour, as a child and as a parent, n_invalid_runs, and what ended the expansion (0 the list's end, 1 more than 80, 2 a parent).
+ * JSORB_ERR_STATE before the first call.  Any pointer may be NULL. */
+int jsorb_local_keyframes_stats(jsorb_extractor *e, int *n_counter, int *n_first, int *n_local, int *n_neighbours, int *n_children, int *n_parents,
+                                int *n_invalid_runs, int *end_reason);
+/* The compile-time caps of the library in use (the walk of src/Tracking.cpp:1895-1945): slots whose membership bit lives in LDS (32768; beyond,
+ * a byte in global memory) and child candidates held in LDS (4096; a run that does not fit is read from global memory). */
+int jsorb_local_keyframes_build_caps(int *member_lds_slots, int *child_lds_entries);
 
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF

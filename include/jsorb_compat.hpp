@@ -749,6 +749,115 @@ struct LocalMapPoints {
     int32_t counts[5] = {0, 0, 0, 0, 0};
     int capacity = 0;
 };
+// The keyframes as the device arrays jsorb_local_keyframes reads (jsorb_keyframe_graph, include/jsorb.h): RAII over eleven device arrays of
+// max_keyframes slots, the caller's index for a KeyFrame* as for KeyframeDatabase.  The binding calls a setter where the reference changes the
+// map (INTEGRATION.md lists which event rewrites which array); each setter is one small upload.  Runs are handed out from the pools front to
+// back and rewritten in place while they fit; a full pool throws.
+class KeyframeGraph {
+public:
+    enum { ABSENT = 0, GOOD = 1, BAD = 2 };
+    KeyframeGraph(int max_keyframes, int pool_entries, int child_entries) : S_(max_keyframes), pool_(pool_entries), child_(child_entries)
+    {
+        const size_t s = S_ > 0 ? S_ : 1, p = pool_ > 0 ? pool_ : 1, c = child_ > 0 ? child_ : 1;
+        alloc(state_, s, 0); alloc(key_, s, 0); alloc(point_off_, s, 0); alloc(point_len_, s, 0); alloc(point_pool_, p, -1); alloc(registered_, p, 1);
+        alloc(neighbours_, 10 * s, -1); alloc(child_off_, s, 0); alloc(child_len_, s, 0); alloc(child_pool_, c, -1); alloc(parent_, s, -1);
+        point_run_.assign(s, {0, -1}); child_run_.assign(s, {0, -1});
+    }
+    KeyframeGraph(const KeyframeGraph &) = delete;
+    KeyframeGraph &operator=(const KeyframeGraph &) = delete;
+    ~KeyframeGraph()
+    {
+        void *const all[11] = {state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_, child_pool_, parent_};
+        for (void *p : all) jsorb_mem_free_device(p);
+    }
+    int max_keyframes() const { return S_; }
+    jsorb_keyframe_graph view() const
+    {
+        return jsorb_keyframe_graph{S_, pool_, child_, state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_,
+                                    child_pool_, parent_};
+    }
+    // GetMapPointMatches() as table rows (-1 = NULL), (intptr_t)pKF, the state, and per entry whether the point holds the keyframe in mObservations
+    void set_keyframe(int slot, const std::vector<int32_t> &rows, int64_t key, int state = GOOD, const std::vector<unsigned char> *registered = nullptr)
+    {
+        const int at = write_run(slot, rows, point_run_, point_used_, pool_, point_pool_, point_off_, point_len_);
+        if (!rows.empty()) {
+            std::vector<unsigned char> ones;
+            if (!registered) { ones.assign(rows.size(), 1); registered = &ones; }
+            if (registered->size() != rows.size()) throw std::runtime_error("KeyframeGraph::set_keyframe: one registered byte per row");
+            check(jsorb_mem_h2d(registered_ + at, registered->data(), rows.size()), "upload");
+        }
+        put(key_, slot, key);
+        set_state(slot, state);
+    }
+    void set_state(int slot, int state) { put(state_, in(slot), (unsigned char)state); }
+    void set_neighbours(int slot, const std::vector<int32_t> &slots)      // GetBestCovisibilityKeyFrames(10), in its order
+    {
+        int32_t row[10];
+        for (int i = 0; i < 10; i++) row[i] = i < (int)slots.size() ? slots[i] : -1;
+        check(jsorb_mem_h2d(neighbours_ + 10 * (size_t)in(slot), row, sizeof(row)), "upload");
+    }
+    void set_children(int slot, const std::vector<int32_t> &slots) { write_run(slot, slots, child_run_, child_used_, child_, child_pool_, child_off_, child_len_); }      // GetChilds(), std::set's order
+    void set_parent(int slot, int parent) { put(parent_, in(slot), (int32_t)parent); }
+    void erase(int slot)
+    {
+        set_state(slot, ABSENT); put(point_len_, slot, (int32_t)0); put(child_len_, slot, (int32_t)0); set_parent(slot, -1); set_neighbours(slot, {});
+    }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeGraph ") + what + ": " + jsorb_mem_last_error());
+    }
+    template <class T> static void alloc(T *&p, size_t n, int fill)
+    {
+        check(jsorb_mem_alloc_device(n * sizeof(T), (void **)&p), "alloc");
+        const std::vector<T> h(n, (T)fill);
+        check(jsorb_mem_h2d(p, h.data(), n * sizeof(T)), "upload");
+    }
+    template <class T> static void put(T *p, int i, T v) { check(jsorb_mem_h2d(p + i, &v, sizeof(T)), "upload"); }
+    int in(int slot) const
+    {
+        if (slot < 0 || slot >= S_) throw std::runtime_error("jsorb::KeyframeGraph: slot outside [0, max_keyframes)");
+        return slot;
+    }
+    int write_run(int slot, const std::vector<int32_t> &v, std::vector<std::pair<int, int>> &runs, int &used, int total, int32_t *pool, int32_t *off, int32_t *len)
+    {
+        std::pair<int, int> &r = runs[in(slot)];       // (offset, entries reserved)
+        const int n = (int)v.size();
+        if (n > r.second) {
+            if (used + n > total) throw std::runtime_error("jsorb::KeyframeGraph: pool full");
+            r = {used, n};
+            used += n;
+        }
+        if (n) check(jsorb_mem_h2d(pool + r.first, v.data(), (size_t)n * sizeof(int32_t)), "upload");
+        put(off, slot, (int32_t)r.first); put(len, slot, (int32_t)n);
+        return r.first;
+    }
+    int S_ = 0, pool_ = 0, child_ = 0, point_used_ = 0, child_used_ = 0;
+    unsigned char *state_ = nullptr, *registered_ = nullptr;
+    int64_t *key_ = nullptr;
+    int32_t *point_off_ = nullptr, *point_len_ = nullptr, *point_pool_ = nullptr, *neighbours_ = nullptr, *child_off_ = nullptr, *child_len_ = nullptr,
+            *child_pool_ = nullptr, *parent_ = nullptr;
+    std::vector<std::pair<int, int>> point_run_, child_run_;
+};
+// mvpLocalKeyFrames and mpReferenceKF as UpdateLocalKeyFrames keeps them from frame to frame, and the local keyframes' rows concatenated for
+// UpdateLocalPoints: slots[i] (host) the slot of the i-th local keyframe, ref_slot the slot of mpReferenceKF (-1: none yet), counts as
+// jsorb_local_keyframes defines them; the device arrays hold the persistent state the next call reads.
+struct LocalKeyFrames {
+    LocalKeyFrames(int kf_capacity_, int entry_capacity_) : kf_capacity(kf_capacity_), entry_capacity(entry_capacity_)
+    {
+        slot_gpu.resize(kf_capacity); start_gpu.resize(kf_capacity + 1); point_row_gpu.resize(entry_capacity > 0 ? entry_capacity : 1);
+        state_gpu.resize(2); counts_gpu.resize(8);
+        slot_gpu.set_zero_gpu();
+        state_gpu.cpu_data()[0] = 0; state_gpu.cpu_data()[1] = -1;
+        state_gpu.to_gpu();
+    }
+    orb_cuda::SyncedMem<int> slot_gpu, state_gpu, start_gpu, point_row_gpu, counts_gpu;
+    std::vector<int32_t> slots;
+    int ref_slot = -1;
+    int32_t counts[8] = {0, 0, 0, -1, 0, 0, 0, 0};
+    int kf_capacity, entry_capacity;
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -921,6 +1030,31 @@ inline int UpdateLocalPoints(ORBExtractor &ex, const jsorb::MapPointTable &table
         throw std::runtime_error(std::string("jsorb_local_map_points: ") + jsorb_last_error(ex.handle()));
     out.point_row.resize(capacity > 0 ? capacity : 0);
     return out.counts[2];
+}
+// Tracking::UpdateLocalKeyFrames (Tracking.cpp:1844-1952) on the device: the votes of the frame's map points (frame_rows_gpu,
+// mCurrentFrame.mvpMapPoints as table rows, n_frame of them; nullptr: none), the first list, the expansion over neighbours, children and parents,
+// and the keyframes' rows concatenated into local.point_row_gpu.  local carries mvpLocalKeyFrames and mpReferenceKF from frame to frame, as the
+// reference does when no keyframe gets a vote.  Returns the number of local keyframes; the binding sets mpReferenceKF = slot_to_kf[local.ref_slot].
+inline int UpdateLocalKeyFrames(ORBExtractor &ex, const jsorb::KeyframeGraph &graph, const jsorb::MapPointTable &table, const int32_t *frame_rows_gpu,
+                                int n_frame, jsorb::LocalKeyFrames &local)
+{
+    const jsorb_keyframe_graph g = graph.view();
+    const jsorb_map_point_table t = table.view();
+    local.slots.assign(local.kf_capacity, -1);
+    int32_t state[2] = {0, -1};
+    if (jsorb_local_keyframes(ex.handle(), &g, &t, frame_rows_gpu, n_frame, local.kf_capacity, local.entry_capacity, local.slot_gpu.gpu_data(),
+                              local.state_gpu.gpu_data(), local.start_gpu.gpu_data(), local.point_row_gpu.gpu_data(), local.counts_gpu.gpu_data(),
+                              local.slots.data(), state, local.counts) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_local_keyframes: ") + jsorb_last_error(ex.handle()));
+    local.slots.resize(state[0]);
+    local.ref_slot = state[1];
+    return state[0];
+}
+// ... and UpdateLocalPoints over that list: ONE keyframe of local.entry_capacity entries, the padding behind the last row dropped as NULL entries
+inline int UpdateLocalPoints(ORBExtractor &ex, const jsorb::MapPointTable &table, const jsorb_frustum_params &frustum, jsorb::LocalKeyFrames &local,
+                             const int32_t *frame_rows_gpu, int capacity, jsorb::LocalMapPoints &pts)
+{
+    return UpdateLocalPoints(ex, table, frustum, std::vector<int32_t>{0, local.entry_capacity}, local.point_row_gpu.gpu_data(), frame_rows_gpu, capacity, pts);
 }
 // ... and the matcher over those slots: match_kp[i] = the keypoint matched to the map point of row out.point_row[i], or -1
 inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params, jsorb::LocalMapPoints &pts, const float *u_right_gpu, std::vector<int> &match_kp)

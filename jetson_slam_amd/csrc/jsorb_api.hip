@@ -676,6 +676,7 @@ void jsorb_destroy(jsorb_extractor *e)
     grid_release(e);
     search_local_release(e);
     local_map_release(e);
+    local_kf_release(e);
     search_last_release(e);
     search_kf_release(e);
     search_init_release(e);

@@ -285,6 +285,16 @@ struct jsorb_extractor {
         bool done = false;
     } lm;
 
+    // ---- the local keyframes (jsorb_localkf.hip, jsorb_local_keyframes*): allocated on the first call, grown only; the row words are lm.word ----
+    struct {
+        int32_t *slot = nullptr;           // per graph slot: vote, then the first list in order (2 x slots words), then slots bytes `first`
+        int slots = 0;
+        int32_t *stats = nullptr;          // LK_STATS words of the last call, then the 64-bit `best` (device)
+        int32_t *out = nullptr;            // synchronous call: counts (8), state_io (2), then local_kf_slot (out_cap)
+        int out_cap = 0;
+        bool done = false;
+    } lk;
+
     // ---- bag of words (jsorb_bow.hip, jsorb_bow_transform_async / jsorb_search_by_bow*): allocated on first use, the keyframe parts grown only ----
     struct {
         int32_t *ids = nullptr;            // B x T word ids, then B x T node ids, then 2 statistics words (descriptors with a shallow leaf)
@@ -648,6 +658,10 @@ void search_kf_release(jsorb_extractor *e);
 
 // ---- jsorb_localmap.hip ----
 void local_map_release(jsorb_extractor *e);
+int local_map_row_words(jsorb_extractor *e, int n_rows, hipStream_t st);      // lm.word for a table of n_rows rows, all ones (grown and set again on demand)
+
+// ---- jsorb_localkf.hip ----
+void local_kf_release(jsorb_extractor *e);
 
 // ---- jsorb_bow.hip ----
 void bow_after_extract(jsorb_extractor *e);

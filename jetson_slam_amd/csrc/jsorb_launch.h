@@ -491,6 +491,30 @@ int local_map_chunk();                           // the compile-time cap of k_lo
 inline int local_map_chunks(int E) { return (E + local_map_chunk() - 1) / local_map_chunk(); }
 void launch_local_map(const LocalMapArgs &a, hipStream_t s);      // the four kernels
 void launch_map_points_scatter(int n_rows, float *const dst[9], uint8_t *bad, int n, const int32_t *rows, const jsorb_map_point_record *records, hipStream_t s);
+// k_lk_marks / k_lk_votes / k_lk_rank / k_lk_expand / k_lk_gather (k_local_keyframes.hip): Tracking::UpdateLocalKeyFrames over the keyframe graph's
+// device arrays, and the local keyframes' rows concatenated for launch_local_map
+struct LocalKfArgs {
+    jsorb_keyframe_graph g;
+    int n_rows;                                  // of the map-point table
+    const uint8_t *bad;                          // n_rows
+    const int32_t *frame_row;                    // n_frame, or NULL
+    int n_frame, kf_capacity, entry_capacity;
+    // scratch
+    uint32_t *word;                              // n_rows: all ones minus the row's multiplicity in the frame; all ones between calls
+    int32_t *vote;                               // S
+    uint8_t *first;                              // S: state == 1 && vote > 0 - the first list, and the membership beyond the LDS bitmap
+    int32_t *order;                              // S: the first list in (order_key, slot) order
+    unsigned long long *best;                    // 1: vote << 32 | ~rank of the voter with the largest vote, the lowest rank among equals
+    int32_t *stats;                              // LK_STATS words, jsorb_local_keyframes_stats' order
+    // in / out
+    int32_t *local_kf_slot, *state_io;           // kf_capacity, 2
+    // outputs
+    int32_t *local_kf_start, *local_point_row, *counts;      // kf_capacity + 1, entry_capacity, 8
+};
+enum { LK_STATS = 8 };
+int local_kf_member_lds();                       // the compile-time caps of k_local_keyframes.hip (jsorb_local_keyframes_build_caps)
+int local_kf_child_lds();
+void launch_local_keyframes(const LocalKfArgs &a, hipStream_t s);      // the five kernels
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -8,6 +8,18 @@ namespace jsorb_host __attribute__((visibility("hidden"))) {
 
 void local_map_release(jsorb_extractor *e) { free_device(e->lm.word, e->lm.keep, e->lm.chunk, e->lm.stats, e->lm.out); }
 
+// the scratch: grown only; a word is all ones between calls
+int local_map_row_words(jsorb_extractor *e, int n_rows, hipStream_t st)
+{
+    const int rows_before = e->lm.rows;
+    RCCHK(reserve_device(e, e->lm.word, (size_t)std::max(n_rows, 1) * sizeof(uint32_t), &e->lm.rows, std::max(n_rows, 1)));
+    if (e->lm.rows != rows_before || e->lm.dirty) {
+        HIPCHK(e, hipMemsetAsync(e->lm.word, 0xff, (size_t)e->lm.rows * sizeof(uint32_t), st));
+        e->lm.dirty = false;
+    }
+    return JSORB_OK;
+}
+
 } // namespace jsorb_host
 
 namespace {
@@ -48,13 +60,7 @@ int jsorb_local_map_points_async(jsorb_extractor *e, int image, const jsorb_map_
     const int N = jsorb_n_keypoints(e, image);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    // the scratch: grown only; a word is all ones between calls
-    const int rows_before = e->lm.rows;
-    RCCHK(reserve_device(e, e->lm.word, (size_t)std::max(t.n_rows, 1) * sizeof(uint32_t), &e->lm.rows, std::max(t.n_rows, 1)));
-    if (e->lm.rows != rows_before || e->lm.dirty) {
-        HIPCHK(e, hipMemsetAsync(e->lm.word, 0xff, (size_t)e->lm.rows * sizeof(uint32_t), st));
-        e->lm.dirty = false;
-    }
+    RCCHK(local_map_row_words(e, t.n_rows, st));
     const int chunks = local_map_chunks(E);
     RCCHK(reserve_device(e, e->lm.keep, (size_t)std::max(E, 1), &e->lm.entries, std::max(E, 1)));
     RCCHK(reserve_device(e, e->lm.chunk, ((size_t)2 * (chunks + 1) + 1) * sizeof(uint32_t), &e->lm.chunks, chunks + 1));

@@ -77,6 +77,7 @@ EXPORTS = [
     "jsorb_vocabulary_train", "jsorb_vocabulary_train_last_error", "jsorb_vocab_train_result_destroy", "jsorb_vocab_train_result_info",
     "jsorb_vocab_train_result_copy", "jsorb_vocab_train_result_copy_assignment", "jsorb_vocab_train_stats", "jsorb_vocab_train_build_caps",
     "jsorb_local_map_points_async", "jsorb_local_map_points", "jsorb_local_map_stats", "jsorb_local_map_build_caps", "jsorb_map_points_scatter_async",
+    "jsorb_local_keyframes_async", "jsorb_local_keyframes", "jsorb_local_keyframes_stats", "jsorb_local_keyframes_build_caps",
 ]
 
 
@@ -331,6 +332,121 @@ class MapPointTable:
             torch.cuda.synchronize(dev)
 
 
+class JsorbKeyframeGraph(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("max_keyframes", "pool_entries", "child_entries")] + \
+               [(k, C.c_void_p) for k in ("state", "order_key", "point_off", "point_len", "point_pool", "registered", "neighbours", "child_off", "child_len",
+                                          "child_pool", "parent")]
+
+
+KF_ABSENT, KF_GOOD, KF_BAD = 0, 1, 2             # jsorb_keyframe_graph.state
+KF_NEIGHBOURS = 10                               # GetBestCovisibilityKeyFrames(10)
+LOCAL_KF_MIN_CAPACITY = 84                       # the first list up to 80 and three more (Tracking.cpp:1898)
+LOCAL_KF_COUNTS = ("n_counter", "n_first", "n_local", "ref_slot", "E_total", "kf_overflow", "entry_overflow", "kept_previous")
+
+
+class KeyframeGraph:
+    """The keyframes as jsorb_local_keyframes reads them (jsorb_keyframe_graph): torch device arrays over max_keyframes slots the caller chooses, as
+    for KeyframeDatabase.  What the reference changes, and where it lands here: AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch -> the
+    keyframe's run in point_pool (set_keyframe, or a write into point_pool at point_off[slot] + i); AddObservation / EraseObservation ->
+    `registered`; UpdateBestCovisibles -> set_neighbours; AddChild / EraseChild / ChangeParent -> set_children, set_parent; SetBadFlag ->
+    set_state(slot, KF_BAD); erase(slot) frees the slot.  Runs are handed out from the pools front to back; a run that still fits is rewritten
+    in place, and a full pool is an error (the caller builds a new graph)."""
+    ARRAYS = ("state", "order_key", "point_off", "point_len", "point_pool", "registered", "neighbours", "child_off", "child_len", "child_pool", "parent")
+
+    def __init__(self, max_keyframes, pool_entries, child_entries, device="cuda"):
+        import torch
+        self.max_keyframes, self.pool_entries, self.child_entries = int(max_keyframes), int(pool_entries), int(child_entries)
+        S, Pn, Cn = max(self.max_keyframes, 1), max(self.pool_entries, 1), max(self.child_entries, 1)
+        z = lambda n, dt, fill=0: torch.full((n,), fill, dtype=dt, device=device)
+        self.state, self.order_key = z(S, torch.uint8), z(S, torch.int64)
+        self.point_off, self.point_len, self.point_pool, self.registered = z(S, torch.int32), z(S, torch.int32), z(Pn, torch.int32, -1), z(Pn, torch.uint8, 1)
+        self.neighbours = torch.full((S, KF_NEIGHBOURS), -1, dtype=torch.int32, device=device)
+        self.child_off, self.child_len, self.child_pool, self.parent = z(S, torch.int32), z(S, torch.int32), z(Cn, torch.int32, -1), z(S, torch.int32, -1)
+        self._run = {"point": {}, "child": {}}     # slot -> (offset, entries reserved)
+        self._used = {"point": 0, "child": 0}
+
+    def struct(self):
+        """(`registered` may be set to None: every entry then counts as registered)"""
+        ptr = [None if getattr(self, k) is None else getattr(self, k).data_ptr() for k in self.ARRAYS]
+        return JsorbKeyframeGraph(self.max_keyframes, self.pool_entries, self.child_entries, *ptr)
+
+    def load(self, **arrays):
+        """whole arrays at once (numpy, the layouts of jsorb_keyframe_graph); the setters then rewrite the loaded runs in place
+        and hand out new ones behind the largest run end"""
+        import torch
+        for k, v in arrays.items():
+            if k not in self.ARRAYS:
+                raise JsorbError("KeyframeGraph.load: no array %s" % k)
+            t = getattr(self, k)
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(t.device)
+            if v.dtype != t.dtype or v.numel() > t.numel():
+                raise JsorbError("KeyframeGraph.load: %s must be %s with at most %d entries" % (k, t.dtype, t.numel()))
+            t.view(-1)[:v.numel()].copy_(v.view(-1))
+        for kind, off, ln, total in (("point", self.point_off, self.point_len, self.pool_entries), ("child", self.child_off, self.child_len, self.child_entries)):
+            o, n = off.cpu().numpy().astype(np.int64)[:self.max_keyframes], ln.cpu().numpy().astype(np.int64)[:self.max_keyframes]
+            ok = (o >= 0) & (n >= 0) & (o + n <= total)
+            self._run[kind] = {int(s): (int(o[s]), int(n[s])) for s in np.nonzero(ok)[0]}
+            self._used[kind] = int((o + n)[ok].max()) if ok.any() else 0
+
+    def _slot(self, slot):
+        if not 0 <= int(slot) < self.max_keyframes:
+            raise JsorbError("KeyframeGraph: slot %d outside [0, %d)" % (slot, self.max_keyframes))
+        return int(slot)
+
+    def _write_run(self, kind, slot, values, pool, off, length, total):
+        import torch
+        n = len(values)
+        at, room = self._run[kind].get(slot, (0, -1))
+        if n > room:
+            at, room = self._used[kind], n
+            if at + n > total:
+                raise JsorbError("KeyframeGraph: the %s pool is full (%d of %d entries used, %d wanted)" % (kind, at, total, n))
+            self._used[kind] += n
+            self._run[kind][slot] = (at, room)
+        if n:
+            pool[at:at + n] = torch.from_numpy(values).to(pool.device)
+        off[slot], length[slot] = at, n
+        return at
+
+    def set_keyframe(self, slot, rows, key, state=KF_GOOD, registered=None):
+        """GetMapPointMatches() of the keyframe as table rows (-1 = NULL), its place in std::map<KeyFrame*, int> ((intptr_t)pKF in the binding), its
+        state, and per entry whether the point holds the keyframe in its observations (None: all do)"""
+        import torch
+        slot = self._slot(slot)
+        rows = np.ascontiguousarray(rows, np.int32).ravel()
+        at = self._write_run("point", slot, rows, self.point_pool, self.point_off, self.point_len, self.pool_entries)
+        if len(rows) and self.registered is not None:
+            reg = np.ones(len(rows), np.uint8) if registered is None else np.ascontiguousarray(registered, np.uint8).ravel()
+            if len(reg) != len(rows):
+                raise JsorbError("KeyframeGraph.set_keyframe: one registered byte per row")
+            self.registered[at:at + len(rows)] = torch.from_numpy(reg).to(self.registered.device)
+        self.order_key[slot] = int(key)
+        self.state[slot] = int(state)
+
+    def set_state(self, slot, state):
+        self.state[self._slot(slot)] = int(state)
+
+    def set_neighbours(self, slot, slots):
+        import torch
+        row = np.full(KF_NEIGHBOURS, -1, np.int32)
+        v = np.asarray(slots, np.int32).ravel()[:KF_NEIGHBOURS]
+        row[:len(v)] = v
+        self.neighbours[self._slot(slot)] = torch.from_numpy(row).to(self.neighbours.device)
+
+    def set_children(self, slot, slots):
+        """GetChilds() as slots in std::set<KeyFrame*> order"""
+        slot = self._slot(slot)
+        self._write_run("child", slot, np.ascontiguousarray(slots, np.int32).ravel(), self.child_pool, self.child_off, self.child_len, self.child_entries)
+
+    def set_parent(self, slot, parent):
+        self.parent[self._slot(slot)] = -1 if parent is None else int(parent)
+
+    def erase(self, slot):
+        slot = self._slot(slot)
+        self.state[slot], self.point_len[slot], self.child_len[slot], self.parent[slot] = KF_ABSENT, 0, 0, -1
+        self.neighbours[slot] = -1
+
+
 def make_camera(K, D):
     """jsorb_camera from Tracking's mK (3x3) and mDistCoef (k1, k2, p1, p2[, k3]) - both taken as float32, as the reference stores them (Tracking.cpp:80-91)"""
     K = np.asarray(K, np.float32)
@@ -525,6 +641,10 @@ def load_library(path=None):
         "jsorb_local_map_points": (I, [P, I, C.POINTER(JsorbMapPointTable), C.POINTER(JsorbFrustumParams), I, P, P, P, I] + [P] * 12),
         "jsorb_local_map_stats": (I, [P] + [C.POINTER(I)] * 6),
         "jsorb_local_map_build_caps": (I, [C.POINTER(I)]),
+        "jsorb_local_keyframes_async": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), P, I, I, I] + [P] * 5),
+        "jsorb_local_keyframes": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), P, I, I, I] + [P] * 8),
+        "jsorb_local_keyframes_stats": (I, [P] + [C.POINTER(I)] * 8),
+        "jsorb_local_keyframes_build_caps": (I, [C.POINTER(I)] * 2),
         "jsorb_map_points_scatter_async": (I, [P, I] + [P] * 10 + [I, P, P]),
     }
     for name, (rt, at) in sig.items():
@@ -1105,6 +1225,13 @@ def local_map_build_caps():
     c = C.c_int()
     load_library().jsorb_local_map_build_caps(C.byref(c))
     return c.value
+
+
+def local_keyframes_build_caps():
+    """jsorb_local_keyframes_build_caps of the loaded library: (slots whose membership bit k_lk_expand keeps in LDS, child candidates it keeps there)"""
+    m, c = C.c_int(), C.c_int()
+    load_library().jsorb_local_keyframes_build_caps(C.byref(m), C.byref(c))
+    return m.value, c.value
 
 
 WEIGHTING_TF_IDF, WEIGHTING_TF, WEIGHTING_IDF, WEIGHTING_BINARY = 0, 1, 2, 3     # DBoW2::WeightingType
@@ -1769,6 +1896,54 @@ class ORBExtractor:
         v = [C.c_int() for _ in range(6)]
         self._chk(self._lib.jsorb_local_map_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("n_entries", "n_null", "n_invalid_rows", "n_duplicates", "n_bad", "n_seen"), (x.value for x in v)))
+
+    # ---- the local keyframes: Tracking::UpdateLocalKeyFrames (Tracking.cpp:1844-1952) and the concatenation of their rows on the device ----
+    def local_keyframes(self, graph, table, frame_point_row, kf_capacity, entry_capacity, state=None, sync=False, out=None, wait=True):
+        """jsorb_local_keyframes*: graph a KeyframeGraph, table a MapPointTable, frame_point_row an int32 device tensor (all of it is read) or None.
+        state: the `state` of the previous call's result - (local_kf_slot, state_io), the list and {n_local, ref_slot} the reference keeps when no
+        keyframe gets a vote; None starts with an empty list and ref_slot -1.  Returns a dict of device tensors - local_kf_slot
+        int32[kf_capacity], state_io int32[2], local_kf_start int32[kf_capacity + 1], local_point_row int32[entry_capacity], counts int32[8]
+        (LOCAL_KF_COUNTS) - and `state` for the next call; local_map_points(table, frustum, [0, entry_capacity], local_point_row, ...) takes
+        it from there.  out: the dict of an earlier call, written again.  sync=True: the synchronous form; the dict also holds
+        local_kf_slot_host, state_host and counts_host (numpy).  wait as for local_map_points."""
+        import torch
+        dev = table.floats.device
+        kc, ec = int(kf_capacity), int(entry_capacity)
+        fp, n_frame = None, 0
+        if frame_point_row is not None:
+            t = frame_point_row
+            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise JsorbError("local_keyframes: frame_point_row must be a contiguous int32 device tensor")
+            fp, n_frame = t.data_ptr(), int(t.shape[0])
+        if out is None:
+            if state is None:
+                state = (torch.zeros(max(kc, 1), dtype=torch.int32, device=dev), torch.tensor([0, -1], dtype=torch.int32, device=dev))
+            slot, sio = state
+            if slot.dtype != torch.int32 or sio.dtype != torch.int32 or int(slot.shape[0]) < kc or int(sio.shape[0]) != 2 or not slot.is_contiguous():
+                raise JsorbError("local_keyframes: state must be (int32[kf_capacity], int32[2]) of an earlier call")
+            out = dict(local_kf_slot=slot, state_io=sio, local_kf_start=torch.empty(max(kc, 0) + 1, dtype=torch.int32, device=dev),
+                       local_point_row=torch.empty(max(ec, 1), dtype=torch.int32, device=dev)[:max(ec, 0)], counts=torch.empty(8, dtype=torch.int32, device=dev))
+        gs, tb = graph.struct(), table.struct()
+        args = [self._h, C.byref(gs), C.byref(tb), fp, n_frame, kc, ec] + [out[k].data_ptr() for k in ("local_kf_slot", "state_io", "local_kf_start", "local_point_row", "counts")]
+        if wait or sync:
+            torch.cuda.current_stream(dev).synchronize()
+        if sync:
+            slot_h, state_h, counts_h = np.full(max(kc, 1), -2, np.int32), np.zeros(2, np.int32), np.zeros(8, np.int32)
+            self._chk(self._lib.jsorb_local_keyframes(*args, slot_h.ctypes.data, state_h.ctypes.data, counts_h.ctypes.data))
+            out = dict(out, local_kf_slot_host=slot_h[:max(kc, 0)], state_host=state_h, counts_host=counts_h)
+        else:
+            self._chk(self._lib.jsorb_local_keyframes_async(*args))
+            if wait:
+                self.sync()
+        out["state"] = (out["local_kf_slot"], out["state_io"])
+        return out
+
+    def local_keyframes_stats(self):
+        """dict(n_counter, n_first, n_local, n_neighbours, n_children, n_parents, n_invalid_runs, end_reason) of the last local_keyframes; end_reason: 0
+        the list's end, 1 more than 80 keyframes, 2 a parent"""
+        v = [C.c_int() for _ in range(8)]
+        self._chk(self._lib.jsorb_local_keyframes_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_counter", "n_first", "n_local", "n_neighbours", "n_children", "n_parents", "n_invalid_runs", "end_reason"), (x.value for x in v)))
 
     # ---- motion-model matching: ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cpp:1647-1963) on the device ----
     def search_last_frame(self, Px, Py, Pz, last_octave, last_angle, mp_descriptors, params, u_right=None, image=0):
