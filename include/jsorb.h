@@ -1013,6 +1013,97 @@ int jsorb_local_keyframes_stats(jsorb_extractor *e, int *n_counter, int *n_first
  * a byte in global memory) and child candidates held in LDS (4096; a run that does not fit is read from global memory). */
 int jsorb_local_keyframes_build_caps(int *member_lds_slots, int *child_lds_entries);
 
+/* ---- the covisibility graph on the device: KeyFrame::UpdateConnections (src/KeyFrame.cpp:293-383), AddConnection / UpdateBestCovisibles
+ * (:127-161), EraseConnection (:557-571) and the getters over them, on a keyframe matcher (its stream, its scratch; LocalMapping and LoopClosing
+ * each own one; no extractor handle is involved) ----
+ * jsorb_covisibility is a struct of DEVICE arrays over the graph's S = max_keyframes slots, owned by the binding like jsorb_keyframe_graph, with
+ * conn_capacity = C entries per slot, C within jsorb_covisibility_build_caps (16 to 2048):
+ *   conn_len[S], conn_slot[S*C], conn_weight[S*C]   mConnectedKeyFrameWeights in ascending (order_key, slot) order - std::map<KeyFrame*, int>'s
+ *   ord_len[S], ord_slot[S*C], ord_weight[S*C]      mvpOrderedConnectedKeyFrames / mvOrderedWeights.  Separate state, not a function of the map:
+ *                  after a keyframe's own UpdateConnections they hold only the entries at or above the threshold, after an
+ *                  UpdateBestCovisibles the whole map
+ *   first_connection[S]   one byte: mbFirstConnection && mnId != 0; the binding writes 1 when it creates a keyframe other than the first
+ * All of it starts as zeros.  The definitions of jsorb_local_keyframes_async hold: USABLE slot, valid run, (order_key, slot) order.
+ *
+ * jsorb_update_connections_async is UpdateConnections() of the keyframes update_slot[0 .. n_update) (a DEVICE array, n_update <= 32; a longer
+ * list is the caller's to split, the state persists) one after the other in that order.  `table` gives n_rows and bad; nothing else is read.
+ *   Valid members.  A = update_slot[i] is processed when it is usable and its point run is valid.  A slot that occurred earlier in the list is
+ *     skipped and counted (the caller lists a slot once).
+ *   rows(A): the rows r of A's run with 0 <= r < n_rows and bad[r] == 0 (:306-314).  A's own `registered` bytes are not read: the reference
+ *     walks mvpMapPoints.  STATED DIFFERENCE: a row that A's run lists more than once counts once (the binding lists a row once).
+ *   cnt(A, B), for B != A with state[B] != 0 and a valid run: the entries of B's run with registered != 0 (or registered == NULL) whose row is
+ *     in rows(A) (:316-323).
+ *   K(A) = {B : cnt > 0}.  Empty: the member does nothing at all (:327).
+ *   T(A) = the members of K(A) with cnt >= 15; if there are none, the single slot with the largest cnt, the lowest (order_key, slot) among equals
+ *     (the first strict maximum of :338-344 and :352-356).
+ *   A's own state: conn(A) := K(A) with its counts; ord(A) := T(A) by (weight, order_key, slot) DESCENDING (sort() of pair<int, KeyFrame*>, then
+ *     push_front, :358-365).  first_connection[A] set: parent_out[i] = ord(A)[0] and the byte is cleared (:375-380); else parent_out[i] = -1.
+ *     AddChild / set_parent / set_children stay with the binding.
+ *   A's effect on others: for every B in T(A), AddConnection(A, cnt(A, B)) on B (:127-140): if conn(B) lacks A or holds another weight it is
+ *     set and ord(B) becomes ALL of conn(B) sorted as above, entries below the threshold included; if the weight is there already nothing
+ *     changes and ord(B) keeps its form - the early return is behaviour.
+ *   neighbours: a writable int32[S][10] or NULL - the array jsorb_keyframe_graph.neighbours and the database point at.  Every slot whose ord
+ *     list was rewritten gets its row rewritten (the first 10, -1 padded); other rows are untouched.
+ *   conn_snapshot (or NULL): slot[n_update][C], weight[n_update][C], len[n_update]: K(update_slot[i]) as the member's own update left it,
+ *     before later members touch it - what src/LoopClosing.cpp:560 reads inside its loop.  len = -1 for a member that was skipped or had an
+ *     empty K (its map is whatever it was).
+ *   Capacity.  T(A) and the AddConnections come from the full K(A).  A stored map keeps the C lowest entries in (order_key, slot) order of the
+ *     merge (its base - K of its own update, or its stored map - and the incoming connections); a re-sorted list is that stored map sorted, a
+ *     member's own list the first C of T(A).  counts says how many slots overflowed.  Past capacity the result is defined and deterministic
+ *     (tests/covis_cases.py restates it), no longer the reference's.
+ *   counts_dev[8] = the members processed, skipped (unusable, invalid run, repeated), empty (K empty), the AddConnection calls (the sum of
+ *     |T(A)|), the slots whose list ends as a full re-sort, the members that took the fallback, the slots whose merge exceeded C, 0.
+ * Enqueued on the matcher's stream, no host decision after the argument checks, launch shapes from S, n_update and C alone, capturable once the
+ * scratch has its size (a call with the same or larger S and n_rows has run); the call does not synchronise.  Five kernels: k_cv_marks,
+ * k_cv_counts, k_cv_select, k_cv_apply, k_cv_reset.  The scratch is one word per table row, all zero between calls (every call sets back the
+ * words it touched), and 128 words per slot.  Every slot, row and run read from device memory is range-checked before anything is read through it.
+ * JSORB_ERR_INVALID: NULL graph, table, cov or counts_dev; a NULL graph array (other than registered, neighbours, the child arrays, parent and
+ * the pool of 0 entries) or covisibility array with S > 0; cov->max_keyframes != graph->max_keyframes; conn_capacity outside the build caps;
+ * n_update outside [0, 32]; update_slot NULL with n_update > 0; table->bad NULL with n_rows > 0; a snapshot with a NULL array; a negative size;
+ * S >= 2^24. */
+typedef struct jsorb_covisibility {
+    int max_keyframes, conn_capacity;
+    int32_t *conn_len, *conn_slot, *conn_weight, *ord_len, *ord_slot, *ord_weight;
+    uint8_t *first_connection;
+} jsorb_covisibility;
+typedef struct jsorb_conn_snapshot {
+    int32_t *slot, *weight, *len;
+} jsorb_conn_snapshot;
+int jsorb_update_connections_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table,
+                                   const jsorb_covisibility *cov, int n_update, const int32_t *update_slot, int32_t *neighbours, int32_t *parent_out,
+                                   const jsorb_conn_snapshot *conn_snapshot, int32_t *counts_dev);
+/* Synchronous: the same, then parent_host[n_update] (may be NULL when parent_out is) and counts_host[8] in one copy back. */
+int jsorb_update_connections(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table,
+                             const jsorb_covisibility *cov, int n_update, const int32_t *update_slot, int32_t *neighbours, int32_t *parent_out,
+                             const jsorb_conn_snapshot *conn_snapshot, int32_t *counts_dev, int32_t *parent_host, int32_t counts_host[8]);
+/* Diagnostics of the last jsorb_update_connections* (waits for it): counts_dev's first seven words.  JSORB_ERR_STATE before the first call.
+ * Any pointer may be NULL. */
+int jsorb_update_connections_stats(jsorb_keyframe_matcher *m, int *n_processed, int *n_skipped, int *n_empty, int *n_add_connection, int *n_resorted,
+                                   int *n_fallback, int *n_overflow);
+/* The row words of the matcher's scratch (waits for the last call): how many there are and how many are not zero - 0 between calls.  For tests.
+ * JSORB_ERR_STATE before the first call. */
+int jsorb_update_connections_scratch(jsorb_keyframe_matcher *m, int *n_words, int *n_nonzero);
+/* SetBadFlag's :470-471 and :480-481 for `slot` (a host int in [0, S)): for every key B of the slot's map, if conn(B) holds the slot it is
+ * erased from it and ord(B) becomes the whole of conn(B) re-sorted, with its neighbours row (EraseConnection, :557-571); a keyframe whose map
+ * did not hold the slot is left alone, lists included.  Afterwards the slot's own map and lists are empty and its neighbours row is -1.
+ * graph gives order_key only.  counts_dev[2] = the keys walked, the maps that held the slot.  Two kernels: k_cv_erase, k_cv_erase_clear.  The
+ * spanning-tree repair (:483-541) stays on the host over jsorb_covisibility_copy. */
+int jsorb_erase_connections_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_covisibility *cov, int slot,
+                                  int32_t *neighbours, int32_t *counts_dev);
+/* GetConnectedKeyFrames() (:163-170) of `slot` as the byte per slot that jsorb_detect_loop_candidates takes: mask[S], DEVICE. */
+int jsorb_connected_mask_async(jsorb_keyframe_matcher *m, const jsorb_covisibility *cov, int slot, uint8_t *mask);
+/* GetBestCovisibilityKeyFrames(N) (:178-186) of slots[0 .. n) (DEVICE): out[n*N] -1 padded, out_len[n] (or NULL); an unusable slot gives an
+ * empty list. */
+int jsorb_best_covisibles_async(jsorb_keyframe_matcher *m, const jsorb_covisibility *cov, int n, const int32_t *slots, int N, int32_t *out,
+                                int32_t *out_len);
+/* One slot's map and ordered lists to the host, behind everything the device has been given (it waits for the device): lens[2] = {conn_len,
+ * ord_len}, the four arrays C entries each (any may be NULL).  GetVectorCovisibleKeyFrames / GetWeight for the spanning-tree repair. */
+int jsorb_covisibility_copy(const jsorb_covisibility *cov, int slot, int32_t lens[2], int32_t *conn_slot, int32_t *conn_weight, int32_t *ord_slot,
+                            int32_t *ord_weight);
+/* The compile-time bounds on conn_capacity of the library in use (16 and 2048: a map of C entries and 32 incoming ones are sorted in one
+ * workgroup's LDS). */
+int jsorb_covisibility_build_caps(int *min_capacity, int *max_capacity);
+
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF
  * weights, L1 norm, L1 score.  An object of its own like the keyframe matcher: its stream, its scratch, its error text; whoever creates none

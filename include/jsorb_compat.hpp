@@ -858,6 +858,88 @@ struct LocalKeyFrames {
     int32_t counts[8] = {0, 0, 0, -1, 0, 0, 0, 0};
     int kf_capacity, entry_capacity;
 };
+// The covisibility graph as jsorb_update_connections keeps it on the device (jsorb_covisibility, include/jsorb.h): RAII over seven device arrays
+// of max_keyframes slots, conn_capacity entries per slot, all zero at first.  created(slot) is the binding's part of the KeyFrame constructor.
+class Covisibility {
+public:
+    Covisibility(int max_keyframes, int conn_capacity) : S_(max_keyframes), C_(conn_capacity)
+    {
+        int lo = 0, hi = 0;
+        jsorb_covisibility_build_caps(&lo, &hi);
+        if (C_ < lo || C_ > hi) throw std::runtime_error("jsorb::Covisibility: conn_capacity outside the library's bounds");
+        const size_t s = S_ > 0 ? S_ : 1;
+        int32_t **const arr[6] = {&v_.conn_len, &v_.conn_slot, &v_.conn_weight, &v_.ord_len, &v_.ord_slot, &v_.ord_weight};
+        const size_t n[6] = {s, s * C_, s * C_, s, s * C_, s * C_};
+        for (int i = 0; i < 6; i++) zeros((void **)arr[i], n[i] * sizeof(int32_t));
+        zeros((void **)&v_.first_connection, s);
+        v_.max_keyframes = S_; v_.conn_capacity = C_;
+    }
+    Covisibility(const Covisibility &) = delete;
+    Covisibility &operator=(const Covisibility &) = delete;
+    ~Covisibility()
+    {
+        void *const all[7] = {v_.conn_len, v_.conn_slot, v_.conn_weight, v_.ord_len, v_.ord_slot, v_.ord_weight, v_.first_connection};
+        for (void *p : all) jsorb_mem_free_device(p);
+    }
+    int max_keyframes() const { return S_; }
+    int conn_capacity() const { return C_; }
+    const jsorb_covisibility &view() const { return v_; }
+    // a new keyframe in `slot`: empty map and lists; mbFirstConnection && mnId != 0
+    void created(int slot, bool first_keyframe = false)
+    {
+        if (slot < 0 || slot >= S_) throw std::runtime_error("jsorb::Covisibility: slot outside [0, max_keyframes)");
+        const int32_t zero = 0;
+        const unsigned char first = first_keyframe ? 0 : 1;
+        check(jsorb_mem_h2d(v_.conn_len + slot, &zero, sizeof(zero)), "upload");
+        check(jsorb_mem_h2d(v_.ord_len + slot, &zero, sizeof(zero)), "upload");
+        check(jsorb_mem_h2d(v_.first_connection + slot, &first, 1), "upload");
+    }
+    // one slot on the host (it waits for the device): the map in (order_key, slot) order and the ordered lists
+    struct Slot {
+        std::vector<int32_t> conn_slot, conn_weight, ord_slot, ord_weight;
+    };
+    Slot copy(int slot) const
+    {
+        Slot o;
+        int32_t lens[2] = {0, 0};
+        o.conn_slot.resize(C_); o.conn_weight.resize(C_); o.ord_slot.resize(C_); o.ord_weight.resize(C_);
+        if (jsorb_covisibility_copy(&v_, slot, lens, o.conn_slot.data(), o.conn_weight.data(), o.ord_slot.data(), o.ord_weight.data()) != JSORB_OK)
+            throw std::runtime_error("jsorb_covisibility_copy failed");
+        const int nc = lens[0] < 0 ? 0 : lens[0] > C_ ? C_ : lens[0], no = lens[1] < 0 ? 0 : lens[1] > C_ ? C_ : lens[1];
+        o.conn_slot.resize(nc); o.conn_weight.resize(nc); o.ord_slot.resize(no); o.ord_weight.resize(no);
+        return o;
+    }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::Covisibility ") + what + ": " + jsorb_mem_last_error());
+    }
+    static void zeros(void **p, size_t bytes)
+    {
+        check(jsorb_mem_alloc_device(bytes, p), "alloc");
+        check(jsorb_mem_set_zero(*p, bytes), "clear");
+    }
+    int S_ = 0, C_ = 0;
+    jsorb_covisibility v_{};
+};
+// a few device words for the length of a call
+struct DeviceInts {
+    explicit DeviceInts(size_t n)
+    {
+        if (jsorb_mem_alloc_device((n ? n : 1) * sizeof(int32_t), (void **)&p) != JSORB_OK) throw std::runtime_error("jsorb::DeviceInts: alloc failed");
+    }
+    DeviceInts(const DeviceInts &) = delete;
+    DeviceInts &operator=(const DeviceInts &) = delete;
+    ~DeviceInts() { jsorb_mem_free_device(p); }
+    int32_t *p = nullptr;
+};
+// What UpdateConnections gives back for its keyframes: parent[i] = the slot the binding makes mpParent of slots[i] (AddChild on it), -1 = none;
+// counts as jsorb_update_connections defines them.
+struct UpdatedConnections {
+    std::vector<int32_t> parent;
+    int32_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
 } // namespace jsorb
 
 namespace Jetson_SLAM {
@@ -1049,6 +1131,61 @@ inline int UpdateLocalKeyFrames(ORBExtractor &ex, const jsorb::KeyframeGraph &gr
     local.slots.resize(state[0]);
     local.ref_slot = state[1];
     return state[0];
+}
+// KeyFrame::UpdateConnections (KeyFrame.cpp:293-383) of the keyframes `slots` (at most 32) one after the other on the matcher's stream: the maps,
+// the ordered lists and the graph's neighbours rows follow on the device; result.parent says whose child a keyframe with its first connection
+// becomes.  Returns the keyframes processed.
+inline int UpdateConnections(jsorb::KeyframeMatcher &matcher, const jsorb::KeyframeGraph &graph, const jsorb::MapPointTable &table, jsorb::Covisibility &cov,
+                             const std::vector<int32_t> &slots, jsorb::UpdatedConnections &result)
+{
+    const jsorb_keyframe_graph g = graph.view();
+    const jsorb_map_point_table t = table.view();
+    const int n = (int)slots.size();
+    jsorb::DeviceInts dev(2 * (size_t)n + 9);     // the slots, the counts, parent_out
+    int32_t *d = dev.p;
+    if (n > 0 && jsorb_mem_h2d(d, slots.data(), (size_t)n * sizeof(int32_t)) != JSORB_OK) throw std::runtime_error("UpdateConnections: upload failed");
+    result.parent.assign(n > 0 ? n : 1, -1);
+    if (jsorb_update_connections(matcher.handle(), &g, &t, &cov.view(), n, d, const_cast<int32_t *>(g.neighbours), d + n + 8, nullptr, d + n,
+                                 result.parent.data(), result.counts) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_update_connections: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    result.parent.resize(n);
+    return result.counts[0];
+}
+// SetBadFlag's EraseConnection walk (KeyFrame.cpp:470-471, :480-481) for `slot`; returns the maps that held it.  It waits for the matcher.
+inline int EraseConnections(jsorb::KeyframeMatcher &matcher, const jsorb::KeyframeGraph &graph, jsorb::Covisibility &cov, int slot)
+{
+    const jsorb_keyframe_graph g = graph.view();
+    jsorb::DeviceInts counts(2);
+    if (jsorb_erase_connections_async(matcher.handle(), &g, &cov.view(), slot, const_cast<int32_t *>(g.neighbours), counts.p) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_erase_connections: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    int32_t h[2] = {0, 0};
+    if (jsorb_mem_stream_sync(matcher.stream()) != JSORB_OK || jsorb_mem_d2h(h, counts.p, sizeof(h)) != JSORB_OK)
+        throw std::runtime_error("EraseConnections: copy back failed");
+    return h[1];
+}
+// The getters of KeyFrame.cpp:163-212 over one slot's copy, as slots; argument orders as the reference's
+inline std::vector<int32_t> GetConnectedKeyFrames(const jsorb::Covisibility &cov, int slot) { return cov.copy(slot).conn_slot; }
+inline std::vector<int32_t> GetVectorCovisibleKeyFrames(const jsorb::Covisibility &cov, int slot) { return cov.copy(slot).ord_slot; }
+inline std::vector<int32_t> GetBestCovisibilityKeyFrames(const jsorb::Covisibility &cov, int slot, int N)
+{
+    std::vector<int32_t> v = cov.copy(slot).ord_slot;
+    if ((int)v.size() > N) v.resize(N > 0 ? N : 0);
+    return v;
+}
+inline std::vector<int32_t> GetCovisiblesByWeight(const jsorb::Covisibility &cov, int slot, int w)
+{
+    const jsorb::Covisibility::Slot s = cov.copy(slot);
+    size_t n = 0;                                // upper_bound with weightComp (a > b): the first weight below w
+    while (n < s.ord_weight.size() && s.ord_weight[n] >= w) n++;
+    if (s.ord_slot.empty() || n == s.ord_weight.size()) return {};       // :192-197: empty when every weight is at or above w
+    return std::vector<int32_t>(s.ord_slot.begin(), s.ord_slot.begin() + n);
+}
+inline int GetWeight(const jsorb::Covisibility &cov, int slot, int other)
+{
+    const jsorb::Covisibility::Slot s = cov.copy(slot);
+    for (size_t i = 0; i < s.conn_slot.size(); i++)
+        if (s.conn_slot[i] == other) return s.conn_weight[i];
+    return 0;
 }
 // ... and UpdateLocalPoints over that list: ONE keyframe of local.entry_capacity entries, the padding behind the last row dropped as NULL entries
 inline int UpdateLocalPoints(ORBExtractor &ex, const jsorb::MapPointTable &table, const jsorb_frustum_params &frustum, jsorb::LocalKeyFrames &local,

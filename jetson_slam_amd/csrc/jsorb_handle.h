@@ -335,7 +335,7 @@ struct jsorb_keyframe_matcher {
     // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all;
     // scw: the count, then match_kp, match_dist and kp_match, out_cap in all
     // distinct: best_obs, then best_median, out_cap entries each
-    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, N_CALLS };
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, COVIS, N_CALLS };
     KfCall call[N_CALLS];
     int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
@@ -349,6 +349,13 @@ struct jsorb_keyframe_matcher {
         int *list = nullptr;                                    // 3 x list_cap points
         int list_cap = 0;
     } distinct;
+    struct {                                                    // jsorb_update_connections* (jsorb_covis.hip), grown only
+        uint32_t *word = nullptr;                               // one word per table row (rows): the members' bits, all zero between calls
+        int rows = 0;
+        int32_t *slot = nullptr;                                // 4 x 32 x slots words: count, kraw, klist, tlist; then 32 x 4 words minfo
+        int slots = 0;
+        bool dirty = false;                                     // a call failed between its kernels: the words are cleared again
+    } covis;
     std::string err;
 };
 

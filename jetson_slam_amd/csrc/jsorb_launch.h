@@ -515,6 +515,33 @@ enum { LK_STATS = 8 };
 int local_kf_member_lds();                       // the compile-time caps of k_local_keyframes.hip (jsorb_local_keyframes_build_caps)
 int local_kf_child_lds();
 void launch_local_keyframes(const LocalKfArgs &a, hipStream_t s);      // the five kernels
+// k_cv_* (k_covisibility.hip): KeyFrame::UpdateConnections / AddConnection / UpdateBestCovisibles / EraseConnection over the covisibility state's
+// device arrays
+enum { CV_MAX_UPDATE = 32 };
+struct CovisArgs {
+    jsorb_keyframe_graph g;
+    jsorb_covisibility cv;
+    int n_rows;                                  // of the map-point table
+    const uint8_t *bad;                          // n_rows
+    int n_update;
+    const int32_t *update_slot;                  // n_update
+    int32_t *neighbours;                         // S x 10, or NULL
+    int32_t *parent_out;                         // n_update, or NULL
+    int32_t *snap_slot, *snap_weight, *snap_len; // n_update x C twice and n_update, or all NULL
+    int32_t *counts;                             // 8
+    // scratch
+    uint32_t *word;                              // n_rows: bit i = the row is in rows(update_slot[i]); all zero between calls
+    int32_t *count;                              // 32 x S: cnt(update_slot[i], B)
+    int32_t *kraw, *klist, *tlist;               // 32 x S each: K as found, K in (order_key, slot) order, T in the ordered list's order
+    int32_t *minfo;                              // 32 x 4: the member's slot (-1 = skipped), |K|, |T|, the fallback slot or -1
+    int32_t *stats;                              // KF_STATS words: the counts of the last call
+};
+int covis_cap_min();                             // the compile-time caps of k_covisibility.hip (jsorb_covisibility_build_caps)
+int covis_cap_max();
+void launch_update_connections(const CovisArgs &a, hipStream_t s);       // the five kernels
+void launch_erase_connections(const jsorb_covisibility &cv, int32_t *neighbours, const int64_t *order_key, int slot, int32_t *counts, hipStream_t s);
+void launch_connected_mask(const jsorb_covisibility &cv, int slot, uint8_t *mask, hipStream_t s);
+void launch_best_covisibles(const jsorb_covisibility &cv, int n, const int32_t *slots, int N, int32_t *out, int32_t *out_len, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

@@ -78,6 +78,9 @@ EXPORTS = [
     "jsorb_vocab_train_result_copy", "jsorb_vocab_train_result_copy_assignment", "jsorb_vocab_train_stats", "jsorb_vocab_train_build_caps",
     "jsorb_local_map_points_async", "jsorb_local_map_points", "jsorb_local_map_stats", "jsorb_local_map_build_caps", "jsorb_map_points_scatter_async",
     "jsorb_local_keyframes_async", "jsorb_local_keyframes", "jsorb_local_keyframes_stats", "jsorb_local_keyframes_build_caps",
+    "jsorb_update_connections_async", "jsorb_update_connections", "jsorb_update_connections_stats", "jsorb_erase_connections_async",
+    "jsorb_connected_mask_async", "jsorb_best_covisibles_async", "jsorb_covisibility_copy", "jsorb_covisibility_build_caps",
+    "jsorb_update_connections_scratch",
 ]
 
 
@@ -348,7 +351,7 @@ class KeyframeGraph:
     """The keyframes as jsorb_local_keyframes reads them (jsorb_keyframe_graph): torch device arrays over max_keyframes slots the caller chooses, as
     for KeyframeDatabase.  What the reference changes, and where it lands here: AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch -> the
     keyframe's run in point_pool (set_keyframe, or a write into point_pool at point_off[slot] + i); AddObservation / EraseObservation ->
-    `registered`; UpdateBestCovisibles -> set_neighbours; AddChild / EraseChild / ChangeParent -> set_children, set_parent; SetBadFlag ->
+    `registered`; UpdateBestCovisibles -> set_neighbours, or nothing where KeyframeMatcher.update_connections keeps `neighbours` current; AddChild / EraseChild / ChangeParent -> set_children, set_parent; SetBadFlag ->
     set_state(slot, KF_BAD); erase(slot) frees the slot.  Runs are handed out from the pools front to back; a run that still fits is rewritten
     in place, and a full pool is an error (the caller builds a new graph)."""
     ARRAYS = ("state", "order_key", "point_off", "point_len", "point_pool", "registered", "neighbours", "child_off", "child_len", "child_pool", "parent")
@@ -445,6 +448,106 @@ class KeyframeGraph:
         slot = self._slot(slot)
         self.state[slot], self.point_len[slot], self.child_len[slot], self.parent[slot] = KF_ABSENT, 0, 0, -1
         self.neighbours[slot] = -1
+
+
+class JsorbCovisibility(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("max_keyframes", "conn_capacity")] + \
+               [(k, C.c_void_p) for k in ("conn_len", "conn_slot", "conn_weight", "ord_len", "ord_slot", "ord_weight", "first_connection")]
+
+
+class JsorbConnSnapshot(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("slot", "weight", "len")]
+
+
+UPDATE_CONNECTIONS_MAX = 32                      # keyframes per jsorb_update_connections call
+UPDATE_CONNECTIONS_COUNTS = ("n_processed", "n_skipped", "n_empty", "n_add_connection", "n_resorted", "n_fallback", "n_overflow")
+
+
+class Covisibility:
+    """The covisibility graph as jsorb_update_connections keeps it (jsorb_covisibility): torch device arrays over the max_keyframes slots of a
+    KeyframeGraph, conn_capacity entries per slot.  conn_*: mConnectedKeyFrameWeights in (order_key, slot) order; ord_*:
+    mvpOrderedConnectedKeyFrames / mvOrderedWeights; first_connection: mbFirstConnection && mnId != 0 (created(slot) sets it).  The getters copy
+    one slot to the host (jsorb_covisibility_copy) and wait for the device."""
+    ARRAYS = ("conn_len", "conn_slot", "conn_weight", "ord_len", "ord_slot", "ord_weight", "first_connection")
+
+    def __init__(self, max_keyframes, conn_capacity, device="cuda"):
+        import torch
+        self.max_keyframes, self.conn_capacity = int(max_keyframes), int(conn_capacity)
+        lo, hi = covisibility_build_caps()
+        if not lo <= self.conn_capacity <= hi:
+            raise JsorbError("Covisibility: conn_capacity must be in [%d, %d]" % (lo, hi))
+        S, Cn = max(self.max_keyframes, 1), self.conn_capacity
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        self.conn_len, self.conn_slot, self.conn_weight = z(S), z(S, Cn), z(S, Cn)
+        self.ord_len, self.ord_slot, self.ord_weight = z(S), z(S, Cn), z(S, Cn)
+        self.first_connection = torch.zeros(S, dtype=torch.uint8, device=device)
+
+    def struct(self):
+        return JsorbCovisibility(self.max_keyframes, self.conn_capacity, *[getattr(self, k).data_ptr() for k in self.ARRAYS])
+
+    def load(self, **arrays):
+        """whole arrays at once (numpy, the layouts of jsorb_covisibility)"""
+        import torch
+        for k, v in arrays.items():
+            if k not in self.ARRAYS:
+                raise JsorbError("Covisibility.load: no array %s" % k)
+            t = getattr(self, k)
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(t.device)
+            if v.dtype != t.dtype or v.shape != t.shape:
+                raise JsorbError("Covisibility.load: %s must be %s of shape %s" % (k, t.dtype, tuple(t.shape)))
+            t.copy_(v)
+
+    def arrays(self):
+        """every array on the host (numpy)"""
+        return {k: getattr(self, k).cpu().numpy() for k in self.ARRAYS}
+
+    def created(self, slot, first_keyframe=False):
+        """a new keyframe in `slot`: empty map and lists, first_connection = 1 unless it is the map's first keyframe"""
+        if not 0 <= int(slot) < self.max_keyframes:
+            raise JsorbError("Covisibility: slot %d outside [0, %d)" % (slot, self.max_keyframes))
+        self.conn_len[slot], self.ord_len[slot], self.first_connection[slot] = 0, 0, 0 if first_keyframe else 1
+
+    def _copy(self, slot):
+        Cn = self.conn_capacity
+        lens = np.zeros(2, np.int32)
+        a = [np.zeros(Cn, np.int32) for _ in range(4)]
+        st = self.struct()
+        rc = load_library().jsorb_covisibility_copy(C.byref(st), int(slot), lens.ctypes.data, *[x.ctypes.data for x in a])
+        if rc != 0:
+            raise JsorbError("jsorb_covisibility_copy rc=%d" % rc)
+        nc, no = (int(min(max(v, 0), Cn)) for v in lens)
+        return a[0][:nc], a[1][:nc], a[2][:no], a[3][:no]
+
+    def ordered(self, slot):
+        """GetVectorCovisibleKeyFrames(): the ordered list's slots"""
+        return self._copy(slot)[2]
+
+    def weights(self, slot):
+        """mvOrderedWeights"""
+        return self._copy(slot)[3]
+
+    def connected(self, slot):
+        """GetConnectedKeyFrames(): the map's slots in (order_key, slot) order"""
+        return self._copy(slot)[0]
+
+    def weight(self, slot, other):
+        """GetWeight(pKF) (KeyFrame.cpp:205-212): 0 when the map does not hold it"""
+        cs, cw, _, _ = self._copy(slot)
+        hit = np.nonzero(cs == int(other))[0]
+        return int(cw[hit[0]]) if len(hit) else 0
+
+    def best(self, slot, N):
+        """GetBestCovisibilityKeyFrames(N) (KeyFrame.cpp:178-186)"""
+        return self._copy(slot)[2][:max(int(N), 0)]
+
+    def by_weight(self, slot, w):
+        """GetCovisiblesByWeight(w) (KeyFrame.cpp:188-203): upper_bound over the descending weights with weightComp (a > b) - the entries whose
+        weight is at least w, and, as the reference has it, an EMPTY list when every weight is (it == end)"""
+        _, _, os_, ow = self._copy(slot)
+        if len(os_) == 0:
+            return os_
+        n = int(np.count_nonzero(ow >= int(w)))          # upper_bound(first, last, w, a > b): the first element with w > element
+        return os_[:0] if n == len(ow) else os_[:n]
 
 
 def make_camera(K, D):
@@ -646,6 +749,17 @@ def load_library(path=None):
         "jsorb_local_keyframes_stats": (I, [P] + [C.POINTER(I)] * 8),
         "jsorb_local_keyframes_build_caps": (I, [C.POINTER(I)] * 2),
         "jsorb_map_points_scatter_async": (I, [P, I] + [P] * 10 + [I, P, P]),
+        "jsorb_update_connections_async": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), C.POINTER(JsorbCovisibility), I, P, P, P,
+                                               C.POINTER(JsorbConnSnapshot), P]),
+        "jsorb_update_connections": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), C.POINTER(JsorbCovisibility), I, P, P, P,
+                                         C.POINTER(JsorbConnSnapshot), P, P, P]),
+        "jsorb_update_connections_stats": (I, [P] + [C.POINTER(I)] * 7),
+        "jsorb_update_connections_scratch": (I, [P] + [C.POINTER(I)] * 2),
+        "jsorb_erase_connections_async": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbCovisibility), I, P, P]),
+        "jsorb_connected_mask_async": (I, [P, C.POINTER(JsorbCovisibility), I, P]),
+        "jsorb_best_covisibles_async": (I, [P, C.POINTER(JsorbCovisibility), I, P, I, P, P]),
+        "jsorb_covisibility_copy": (I, [C.POINTER(JsorbCovisibility), I] + [P] * 5),
+        "jsorb_covisibility_build_caps": (I, [C.POINTER(I)] * 2),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1204,6 +1318,127 @@ class KeyframeMatcher:
         v = [C.c_int() for _ in range(8)]
         self._chk(self._lib.jsorb_distinctive_descriptors_stats(self._m, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    # ---- the covisibility graph: KeyFrame::UpdateConnections / AddConnection / EraseConnection (KeyFrame.cpp:127-161, :293-383, :557-571) ----
+    @staticmethod
+    def _i32(what, t, n=None):
+        import torch
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or (n is not None and t.numel() < n):
+            raise JsorbError("%s must be a contiguous int32 device tensor%s" % (what, "" if n is None else " of at least %d entries" % n))
+        return t.data_ptr()
+
+    def update_connections(self, graph, table, cov, slots, neighbours=None, snapshot=False, sync=False, out=None, wait=True):
+        """jsorb_update_connections*: UpdateConnections() of the keyframes `slots` (at most 32: an int32 device tensor, or a host sequence that is
+        uploaded) one after the other.  graph a KeyframeGraph, table a MapPointTable, cov a Covisibility.  neighbours: None, or the writable
+        int32[S, 10] table (graph.neighbours) whose rows follow the rewritten lists.  snapshot=True also returns each member's map as its own
+        update left it.  Returns a dict of device tensors - parent_out int32[n], counts int32[8] (UPDATE_CONNECTIONS_COUNTS), with snapshot
+        snap_slot / snap_weight int32[n, C] and snap_len int32[n] - and with sync=True parent_host and counts_host (numpy).  out: the dict of an
+        earlier call with as many slots, written again.  wait=True waits for the current torch stream before and for the matcher behind; with
+        wait=False the call only enqueues, and waits for the torch stream just where it made a tensor itself (slots uploaded, out=None)."""
+        import torch
+        dev = cov.conn_len.device
+        made = out is None or not torch.is_tensor(slots)
+        if not torch.is_tensor(slots):
+            slots = torch.tensor([int(x) for x in slots], dtype=torch.int32, device=dev)
+        n = int(slots.numel())
+        sp = self._i32("update_connections: slots", slots) if n else None
+        nb = None
+        if neighbours is not None:
+            nb = self._i32("update_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
+        if out is None:
+            Cn, n1 = cov.conn_capacity, max(n, 1)   # (a call with no slots still hands over valid arrays)
+            bufs = dict(parent_out=torch.empty(n1, dtype=torch.int32, device=dev), counts=torch.empty(8, dtype=torch.int32, device=dev))
+            if snapshot:
+                bufs.update(snap_slot=torch.zeros((n1, Cn), dtype=torch.int32, device=dev), snap_weight=torch.zeros((n1, Cn), dtype=torch.int32, device=dev),
+                            snap_len=torch.empty(n1, dtype=torch.int32, device=dev))
+            out = {k: (v if k == "counts" else v[:n]) for k, v in bufs.items()}
+            out["_bufs"] = bufs
+        bufs = out["_bufs"]
+        snap = None
+        if "snap_len" in bufs:
+            snap = C.byref(JsorbConnSnapshot(bufs["snap_slot"].data_ptr(), bufs["snap_weight"].data_ptr(), bufs["snap_len"].data_ptr()))
+        gs, tb, cs = graph.struct(), table.struct(), cov.struct()
+        args = [self._m, C.byref(gs), C.byref(tb), C.byref(cs), n, sp, nb, bufs["parent_out"].data_ptr(), snap, bufs["counts"].data_ptr()]
+        if wait or sync or made:
+            torch.cuda.current_stream(dev).synchronize()
+        if sync:
+            parent_h, counts_h = np.full(max(n, 1), -2, np.int32), np.zeros(8, np.int32)
+            self._chk(self._lib.jsorb_update_connections(*args, parent_h.ctypes.data, counts_h.ctypes.data))
+            out = dict(out, parent_host=parent_h[:n], counts_host=counts_h)
+        else:
+            self._chk(self._lib.jsorb_update_connections_async(*args))
+            if wait:
+                self.sync()
+        out["slots"] = slots                     # (kept alive with the result: the device reads it after the call returns)
+        return out
+
+    def update_connections_stats(self):
+        """dict of UPDATE_CONNECTIONS_COUNTS of the last update_connections (waits for it)"""
+        v = [C.c_int() for _ in range(7)]
+        self._chk(self._lib.jsorb_update_connections_stats(self._m, *[C.byref(x) for x in v]))
+        return dict(zip(UPDATE_CONNECTIONS_COUNTS, (x.value for x in v)))
+
+    def update_connections_scratch(self):
+        """(row words of the scratch, how many are not zero - 0 between calls) after the last update_connections (waits for it)"""
+        n, nz = C.c_int(), C.c_int()
+        self._chk(self._lib.jsorb_update_connections_scratch(self._m, C.byref(n), C.byref(nz)))
+        return n.value, nz.value
+
+    def erase_connections(self, graph, cov, slot, neighbours=None, wait=True):
+        """jsorb_erase_connections_async: SetBadFlag's EraseConnection walk for `slot`; returns counts int32[2] (device): the keys walked, the maps
+        that held the slot"""
+        import torch
+        dev = cov.conn_len.device
+        nb = None if neighbours is None else self._i32("erase_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        gs, cs = graph.struct(), cov.struct()
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_erase_connections_async(self._m, C.byref(gs), C.byref(cs), int(slot), nb, counts.data_ptr()))
+        if wait:
+            self.sync()
+        return counts
+
+    def connected_mask(self, cov, slot, out=None, wait=True):
+        """jsorb_connected_mask_async: GetConnectedKeyFrames() of `slot` as a uint8[S] device tensor (what detect_loop_candidates takes)"""
+        import torch
+        dev = cov.conn_len.device
+        if out is None:
+            out = torch.empty(max(cov.max_keyframes, 1), dtype=torch.uint8, device=dev)[:cov.max_keyframes]
+        cs = cov.struct()
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_connected_mask_async(self._m, C.byref(cs), int(slot), out.data_ptr()))
+        if wait:
+            self.sync()
+        return out
+
+    def best_covisibles(self, cov, slots, N, wait=True):
+        """jsorb_best_covisibles_async: GetBestCovisibilityKeyFrames(N) of many slots (an int32 device tensor or a host sequence); returns
+        (out int32[n, N] -1 padded, out_len int32[n]) device tensors"""
+        import torch
+        dev = cov.conn_len.device
+        made = not torch.is_tensor(slots)
+        if made:
+            slots = torch.tensor([int(x) for x in slots], dtype=torch.int32, device=dev)
+        n, N = int(slots.numel()), int(N)
+        sp = self._i32("best_covisibles: slots", slots) if n else None
+        out = torch.empty((max(n, 1), max(N, 1)), dtype=torch.int32, device=dev)[:n]
+        out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        cs = cov.struct()
+        if wait or made:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_best_covisibles_async(self._m, C.byref(cs), n, sp, N, out.data_ptr(), out_len.data_ptr()))
+        if wait:
+            self.sync()
+        return out, out_len
+
+
+def covisibility_build_caps():
+    """jsorb_covisibility_build_caps of the loaded library: the smallest and the largest conn_capacity"""
+    lo, hi = C.c_int(), C.c_int()
+    load_library().jsorb_covisibility_build_caps(C.byref(lo), C.byref(hi))
+    return lo.value, hi.value
 
 
 def kfdb_build_caps():
