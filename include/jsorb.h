@@ -1086,8 +1086,9 @@ int jsorb_update_connections_scratch(jsorb_keyframe_matcher *m, int *n_words, in
 /* SetBadFlag's :470-471 and :480-481 for `slot` (a host int in [0, S)): for every key B of the slot's map, if conn(B) holds the slot it is
  * erased from it and ord(B) becomes the whole of conn(B) re-sorted, with its neighbours row (EraseConnection, :557-571); a keyframe whose map
  * did not hold the slot is left alone, lists included.  Afterwards the slot's own map and lists are empty and its neighbours row is -1.
- * graph gives order_key only.  counts_dev[2] = the keys walked, the maps that held the slot.  Two kernels: k_cv_erase, k_cv_erase_clear.  The
- * spanning-tree repair (:483-541) stays on the host over jsorb_covisibility_copy. */
+ * graph gives order_key only.  counts_dev[2] = the keys walked, the maps that held the slot.  Two kernels: k_cv_erase, k_cv_erase_clear.  This
+ * entry repairs no spanning tree (:483-541): jsorb_cull_keyframes_async below runs the whole of SetBadFlag, the repair of parent[] included, for
+ * the keyframes it culls; a caller that erases a keyframe for another reason repairs the tree over jsorb_covisibility_copy. */
 int jsorb_erase_connections_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_covisibility *cov, int slot,
                                   int32_t *neighbours, int32_t *counts_dev);
 /* GetConnectedKeyFrames() (:163-170) of `slot` as the byte per slot that jsorb_detect_loop_candidates takes: mask[S], DEVICE. */
@@ -1103,6 +1104,95 @@ int jsorb_covisibility_copy(const jsorb_covisibility *cov, int slot, int32_t len
 /* The compile-time bounds on conn_capacity of the library in use (16 and 2048: a map of C entries and 32 incoming ones are sorted in one
  * workgroup's LDS). */
 int jsorb_covisibility_build_caps(int *min_capacity, int *max_capacity);
+
+/* ---- culling redundant keyframes on the device: LocalMapping::KeyFrameCulling (src/LocalMapping.cpp:638-702) with KeyFrame::SetBadFlag
+ * (src/KeyFrame.cpp:457-549) and MapPoint::EraseObservation / SetBadFlag (src/MapPoint.cpp:142-168, :182-199), on a keyframe matcher ----
+ * The candidates cand_slot[0 .. n_cand) (a DEVICE array, n_cand a host count) are what jsorb_best_covisibles_async(cov, {current}, N =
+ * conn_capacity) wrote BEFORE the call - the reference's copy of GetVectorCovisibleKeyFrames() (:644).  They are processed one after the other
+ * in that order, and a culled keyframe's SetBadFlag is complete before the next candidate is examined: it can take a later candidate below
+ * three qualifying observers, and it can turn rows bad, which lowers a later candidate's n_mps and pushes it over 0.9.
+ * jsorb_keyframe_views holds DEVICE arrays parallel to graph->point_pool (pool_entries entries): octave = mvKeysUn[i].octave, stereo =
+ * mvuRight[i] >= 0, depth = mvDepth[i] (or NULL), and th_depth[S] = mThDepth per slot (read only with depth).  monocular != 0 turns the depth
+ * test off: depth is not read and may be NULL.
+ * jsorb_culling_state holds the arrays the call WRITES: the same device arrays graph->state, registered, point_pool, parent and table->bad
+ * point at, handed over once more as writable pointers (another address is JSORB_ERR_INVALID), and not_erase[S] = mbNotErase (or NULL = none),
+ * to_be_erased[S] = mbToBeErased (NULL only with not_erase NULL), ref_slot[n_rows] = the slot of mpRefKF (or NULL).
+ * The definitions of jsorb_local_keyframes_async hold: USABLE slot, valid run, (order_key, slot) order.
+ *   An OBSERVATION of row r is an entry e of the run of a slot B with state[B] == 1, a valid run, point_pool[e] == r, 0 <= r < n_rows,
+ *     bad[r] == 0 and registered[e] != 0.  Observations(r) = the sum of 1 + (stereo[e] != 0) over them (nObs, MapPoint.cpp:129-140).
+ *     STATED DIFFERENCES: a run that lists a row twice makes two observations (the binding lists a row once); nObs is recomputed from the
+ *     observations, not stored - the two are equal wherever AddObservation / EraseObservation can reach.
+ *   Candidate A = cand_slot[i]:
+ *   1. SKIPPED (decision 3): not usable (-1 padding included), state != 1, an invalid run, A == first_slot (mnId == 0, :649; -1 = none), or a
+ *      slot that occurred earlier in the list.
+ *   2. over the entries e of A's run whose row r is in range with bad[r] == 0, registered or not (:657-662 walks mvpMapPoints): unless monocular
+ *      the entry is dropped when depth[e] > th_depth[A] || depth[e] < 0 in float (:666; depth == th_depth, -0.0f and a NaN pass); n_mps++; if
+ *      Observations(r) > 3, q = the observations of r in slots other than A with octave[e'] <= octave[e] + 1 (:671-689); q >= 3: n_redundant++.
+ *   3. CULLED if (double)n_redundant > 0.9 * (double)n_mps (:699); n_mps == 0 is not culled.
+ *   4. kept: decision 0, nothing changes.
+ *   5. culled with not_erase[A] != 0: decision 2, to_be_erased[A] = 1, nothing else changes (:463-467).
+ *   6. otherwise decision 1: EraseConnection on every key of conn(A) exactly as jsorb_erase_connections_async does it, the neighbours rows of
+ *      the rewritten lists, conn(A) and ord(A) emptied and A's neighbours row -1 (:470-471, :480-481).
+ *   7. for every observation e of A with row r (:473-475): registered[e] = 0; if ref_slot[r] == A it becomes the observer of r lowest in
+ *      (order_key, slot) among those left, -1 if none is (MapPoint.cpp:157-158); if Observations(r) <= 2 afterwards bad[r] = 1 and every remaining
+ *      observation e' of r gets point_pool[e'] = -1 and registered[e'] = 0 (EraseMapPointMatch, :182-199).  A's own point_pool[e] stays r.
+ *   8. state[A] = 2.
+ *   9. the spanning tree (:483-541) in parent[] only.  Ch = the slots with parent == A and state != 0 in (order_key, slot) order; P =
+ *      {parent[A]} if that slot is usable, else empty.  Repeat: over the members c of Ch with state[c] == 1 in order, over the entries j of
+ *      ord(c) in list order, whenever ord_slot(c)[j] is in P take w = its weight in conn(c), 0 when conn(c) lacks it (GetWeight); the FIRST pair
+ *      (c, p) whose w is strictly greater than every earlier one (and than -1) wins: parent[c] = p, c joins P and leaves Ch.  Stop when a pass
+ *      finds nothing or Ch is empty; every slot left in Ch, bad ones included, gets parent = parent[A].  Each assignment is appended to
+ *      reparent_out[reparent_cap][2] = (child, new parent) in the order it is made.  parent[A] is kept.  STATED DIFFERENCE: Ch is read from
+ *      parent[], so a keyframe culled earlier stays a child of its parent (the reference's EraseChild, :541, has removed it) and is handed on
+ *      by the fallback.  The child runs (child_off / child_len / child_pool) and mTcp stay with the binding.
+ *   10. after the max_cull-th decision 1 the call stops: later candidates keep decision -1, and the state is the reference's at that point of
+ *      its loop.  A second call with cand_slot + next and n_cand - next continues (the caller passes first_slot again; a slot decided in the
+ *      earlier call is no longer state 1 when culled, and the reference's list holds a slot once).
+ * Outputs (DEVICE): decision[n_cand] (-1 not reached, 0 kept, 1 culled, 2 deferred, 3 skipped), n_mps[n_cand] and n_redundant[n_cand] as seen at
+ * the candidate's turn (0 where skipped or not reached), culled_slot[max_cull] -1 padded, reparent_out -1 padded, counts_dev[10] = next (the
+ * first candidate not decided), kept, culled, deferred, skipped, rows turned bad, observations erased, ref_slot entries moved, reparent records
+ * (all of them), 1 when they exceeded reparent_cap (the parent[] writes are complete regardless; the log is a prefix).
+ * Enqueued on the matcher's stream, no host decision after the argument checks, launch shapes from S, n_rows, n_cand, max_cull and C
+ * alone, capturable once the scratch has its size (a call with the same or larger sizes has run); the call does not synchronise.
+ * The observations are grouped by row once (k_kc_count, k_kc_scan_blocks, k_kc_scan_top, k_kc_scatter), then max_cull rounds of k_kc_eval (a
+ * workgroup per undecided candidate on the current state), k_kc_pick (the first cull at or behind the cursor; every decision before it is final),
+ * k_cv_erase_dev and k_kc_apply (steps 6-9 for that slot).  Order comes from the launches alone.  The scratch is the call's own: the row words of
+ * jsorb_update_connections_async are not touched, and the two calls follow each other on one matcher in either order.
+ * JSORB_ERR_INVALID: NULL graph, table, cov, views, state, an output or counts_dev; a NULL graph array (other than neighbours and the child
+ * arrays) or covisibility array with S > 0; graph->registered NULL (the call writes those bytes); a state array that is not the graph's or the
+ * table's; views->octave or stereo NULL with pool_entries > 0; views->pool_entries != graph->pool_entries; monocular == 0 with depth or
+ * th_depth NULL; to_be_erased NULL with not_erase given; cov->max_keyframes != graph->max_keyframes; conn_capacity outside the build caps;
+ * max_cull outside [1, 16]; n_cand < 0 or above jsorb_cull_keyframes_build_caps (4096); cand_slot NULL with n_cand > 0; reparent_cap < 0 or
+ * reparent_out NULL with reparent_cap > 0; first_slot outside [-1, S); table->bad NULL with n_rows > 0; a negative size; S >= 2^24. */
+typedef struct jsorb_keyframe_views {
+    int pool_entries;
+    const uint8_t *octave, *stereo;
+    const float *depth, *th_depth;
+} jsorb_keyframe_views;
+typedef struct jsorb_culling_state {
+    uint8_t *state, *registered, *bad;
+    int32_t *point_pool, *parent;
+    const uint8_t *not_erase;
+    uint8_t *to_be_erased;
+    int32_t *ref_slot;
+} jsorb_culling_state;
+int jsorb_cull_keyframes_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table,
+                               const jsorb_covisibility *cov, const jsorb_keyframe_views *views, const jsorb_culling_state *state, int monocular,
+                               int first_slot, int n_cand, const int32_t *cand_slot, int max_cull, int32_t *neighbours, int reparent_cap,
+                               int32_t *decision, int32_t *n_mps, int32_t *n_redundant, int32_t *culled_slot, int32_t *reparent_out,
+                               int32_t *counts_dev);
+/* Synchronous: the same, then the outputs and the counts in one copy back (host arrays of the same sizes; reparent_host may be NULL when
+ * reparent_cap is 0). */
+int jsorb_cull_keyframes(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *graph, const jsorb_map_point_table *table,
+                         const jsorb_covisibility *cov, const jsorb_keyframe_views *views, const jsorb_culling_state *state, int monocular,
+                         int first_slot, int n_cand, const int32_t *cand_slot, int max_cull, int32_t *neighbours, int reparent_cap, int32_t *decision,
+                         int32_t *n_mps, int32_t *n_redundant, int32_t *culled_slot, int32_t *reparent_out, int32_t *counts_dev,
+                         int32_t *decision_host, int32_t *n_mps_host, int32_t *n_redundant_host, int32_t *culled_slot_host, int32_t *reparent_host,
+                         int32_t counts_host[10]);
+/* The counts of the last jsorb_cull_keyframes* (waits for it): counts[10] as above.  JSORB_ERR_STATE before the first call. */
+int jsorb_cull_keyframes_stats(jsorb_keyframe_matcher *m, int32_t counts[10]);
+/* The compile-time caps of the library in use: the candidates of one call (4096, twice the largest conn_capacity) and max_cull (16). */
+int jsorb_cull_keyframes_build_caps(int *max_candidates, int *max_cull);
 
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF

@@ -771,6 +771,8 @@ public:
         for (void *p : all) jsorb_mem_free_device(p);
     }
     int max_keyframes() const { return S_; }
+    int pool_entries() const { return pool_; }
+    int point_offset(int slot) const { return point_run_[in(slot)].first; }        // where the slot's run starts in point_pool (set_keyframe)
     jsorb_keyframe_graph view() const
     {
         return jsorb_keyframe_graph{S_, pool_, child_, state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_,
@@ -922,6 +924,99 @@ private:
     }
     int S_ = 0, C_ = 0;
     jsorb_covisibility v_{};
+};
+// What KeyFrameCulling reads of the keyframes' keypoints (jsorb_keyframe_views, include/jsorb.h): device arrays parallel to the graph's
+// point_pool - mvKeysUn[i].octave, mvuRight[i] >= 0, mvDepth[i] (none for a monocular map) - and mThDepth per slot.
+class KeyframeViews {
+public:
+    KeyframeViews(const KeyframeGraph &graph, bool with_depth) : pool_(graph.pool_entries()), S_(graph.max_keyframes())
+    {
+        const size_t p = pool_ > 0 ? pool_ : 1, s = S_ > 0 ? S_ : 1;
+        zeros((void **)&octave_, p); zeros((void **)&stereo_, p);
+        if (with_depth) zeros((void **)&depth_, p * sizeof(float));
+        zeros((void **)&th_depth_, s * sizeof(float));
+    }
+    KeyframeViews(const KeyframeViews &) = delete;
+    KeyframeViews &operator=(const KeyframeViews &) = delete;
+    ~KeyframeViews() { jsorb_mem_free_device(octave_); jsorb_mem_free_device(stereo_); jsorb_mem_free_device(depth_); jsorb_mem_free_device(th_depth_); }
+    jsorb_keyframe_views view() const { return jsorb_keyframe_views{pool_, octave_, stereo_, depth_, th_depth_}; }
+    // the keyframe in `slot`, one entry per entry of its run (after graph.set_keyframe); depth may be NULL for a monocular map
+    void set_keyframe_views(const KeyframeGraph &graph, int slot, const std::vector<unsigned char> &octave, const std::vector<unsigned char> &stereo,
+                            const std::vector<float> *depth, float th_depth)
+    {
+        const size_t at = (size_t)graph.point_offset(slot), n = octave.size();
+        if (stereo.size() != n || (depth && depth->size() != n) || at + n > (size_t)(pool_ > 0 ? pool_ : 0) || (depth_ && !depth))
+            throw std::runtime_error("jsorb::KeyframeViews: one octave, stereo and depth entry per entry of the run");
+        if (n) {
+            check(jsorb_mem_h2d(octave_ + at, octave.data(), n), "upload");
+            check(jsorb_mem_h2d(stereo_ + at, stereo.data(), n), "upload");
+            if (depth_) check(jsorb_mem_h2d(depth_ + at, depth->data(), n * sizeof(float)), "upload");
+        }
+        check(jsorb_mem_h2d(th_depth_ + slot, &th_depth, sizeof(float)), "upload");
+    }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeViews ") + what + ": " + jsorb_mem_last_error());
+    }
+    static void zeros(void **p, size_t bytes)
+    {
+        check(jsorb_mem_alloc_device(bytes, p), "alloc");
+        check(jsorb_mem_set_zero(*p, bytes), "clear");
+    }
+    int pool_ = 0, S_ = 0;
+    unsigned char *octave_ = nullptr, *stereo_ = nullptr;
+    float *depth_ = nullptr, *th_depth_ = nullptr;
+};
+// The arrays jsorb_cull_keyframes writes (jsorb_culling_state): the graph's and the table's own arrays once more as writable pointers, and
+// mbNotErase / mbToBeErased per slot and the slot of mpRefKF per table row, which this class owns (zeros, zeros, -1).
+class CullingState {
+public:
+    CullingState(const KeyframeGraph &graph, const MapPointTable &table) : S_(graph.max_keyframes()), rows_(table.n_rows())
+    {
+        const jsorb_keyframe_graph g = graph.view();
+        const jsorb_map_point_table t = table.view();
+        const size_t s = S_ > 0 ? S_ : 1, r = rows_ > 0 ? rows_ : 1;
+        check(jsorb_mem_alloc_device(s, (void **)&not_erase_), "alloc"); check(jsorb_mem_set_zero(not_erase_, s), "clear");
+        check(jsorb_mem_alloc_device(s, (void **)&to_be_erased_), "alloc"); check(jsorb_mem_set_zero(to_be_erased_, s), "clear");
+        check(jsorb_mem_alloc_device(r * sizeof(int32_t), (void **)&ref_slot_), "alloc");
+        const std::vector<int32_t> none(r, -1);
+        check(jsorb_mem_h2d(ref_slot_, none.data(), r * sizeof(int32_t)), "upload");
+        v_ = jsorb_culling_state{const_cast<uint8_t *>(g.state), const_cast<uint8_t *>(g.registered), const_cast<uint8_t *>(t.bad),
+                                 const_cast<int32_t *>(g.point_pool), const_cast<int32_t *>(g.parent), not_erase_, to_be_erased_, ref_slot_};
+    }
+    CullingState(const CullingState &) = delete;
+    CullingState &operator=(const CullingState &) = delete;
+    ~CullingState() { jsorb_mem_free_device(not_erase_); jsorb_mem_free_device(to_be_erased_); jsorb_mem_free_device(ref_slot_); }
+    const jsorb_culling_state &view() const { return v_; }
+    void set_not_erase(int slot, bool on) { const unsigned char b = on; check(jsorb_mem_h2d(not_erase_ + in(slot, S_), &b, 1), "upload"); }       // SetNotErase / SetErase
+    void set_ref_slot(int row, int slot) { const int32_t v = slot; check(jsorb_mem_h2d(ref_slot_ + in(row, rows_), &v, sizeof(v)), "upload"); }   // mpRefKF
+    bool to_be_erased(int slot) const { unsigned char b = 0; check(jsorb_mem_d2h(&b, to_be_erased_ + in(slot, S_), 1), "copy back"); return b != 0; }
+    int ref_slot(int row) const { int32_t v = -1; check(jsorb_mem_d2h(&v, ref_slot_ + in(row, rows_), sizeof(v)), "copy back"); return v; }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::CullingState ") + what + ": " + jsorb_mem_last_error());
+    }
+    static int in(int i, int n)
+    {
+        if (i < 0 || i >= n) throw std::runtime_error("jsorb::CullingState: index out of range");
+        return i;
+    }
+    int S_ = 0, rows_ = 0;
+    unsigned char *not_erase_ = nullptr, *to_be_erased_ = nullptr;
+    int32_t *ref_slot_ = nullptr;
+    jsorb_culling_state v_{};
+};
+// What KeyFrameCulling gives back: per candidate of the current keyframe's list the decision (0 kept, 1 culled, 2 deferred by mbNotErase,
+// 3 skipped) with n_mps and n_redundant as seen at its turn, the culled slots in order, every ChangeParent as (child, new parent) in order, and
+// the counts of jsorb_cull_keyframes summed over the calls (counts[0] = the candidates).
+struct CulledKeyFrames {
+    std::vector<int32_t> candidates, decision, n_mps, n_redundant, culled;
+    std::vector<std::pair<int32_t, int32_t>> reparent;
+    int32_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 // a few device words for the length of a call
 struct DeviceInts {
@@ -1162,6 +1257,48 @@ inline int EraseConnections(jsorb::KeyframeMatcher &matcher, const jsorb::Keyfra
     if (jsorb_mem_stream_sync(matcher.stream()) != JSORB_OK || jsorb_mem_d2h(h, counts.p, sizeof(h)) != JSORB_OK)
         throw std::runtime_error("EraseConnections: copy back failed");
     return h[1];
+}
+// LocalMapping::KeyFrameCulling (LocalMapping.cpp:638-702) for the current keyframe, with the whole of SetBadFlag (KeyFrame.cpp:457-549) for every
+// keyframe it culls, on the matcher's stream: the candidates are the current keyframe's ordered list read on the device, and the call is repeated
+// past its 4 culls until the list is done.  first_slot: the slot of keyframe 0 (-1: none).  What stays with the binding afterwards: the child
+// runs (graph.set_children from result.reparent), mTcp, Map::EraseKeyFrame and KeyframeDatabase::erase for result.culled.  Returns the culled.
+inline int KeyFrameCulling(jsorb::KeyframeMatcher &matcher, const jsorb::KeyframeGraph &graph, const jsorb::MapPointTable &table, jsorb::Covisibility &cov,
+                           const jsorb::KeyframeViews &views, jsorb::CullingState &state, int current_slot, bool monocular, jsorb::CulledKeyFrames &result,
+                           int first_slot = -1)
+{
+    const jsorb_keyframe_graph g = graph.view();
+    const jsorb_map_point_table t = table.view();
+    const jsorb_keyframe_views v = views.view();
+    const int C = cov.conn_capacity(), S = cov.max_keyframes(), max_cull = 4, cap = S > (1 << 21) ? (1 << 23) : max_cull * (S > 0 ? S : 1);      // (every round is enqueued whether it culls or not: four per call, and the loop below goes on)
+    jsorb::DeviceInts dev((size_t)4 * C + 2 + max_cull + 2 * (size_t)cap + 10);
+    int32_t *cand = dev.p, *len = cand + C, *slot = len + 1, *decision = slot + 1, *n_mps = decision + C, *n_red = n_mps + C, *culled = n_red + C,
+            *reparent = culled + max_cull, *counts = reparent + 2 * (size_t)cap;
+    const int32_t cur = current_slot;
+    int32_t n = 0;
+    if (jsorb_mem_h2d(slot, &cur, sizeof(cur)) != JSORB_OK) throw std::runtime_error("KeyFrameCulling: upload failed");
+    if (jsorb_best_covisibles_async(matcher.handle(), &cov.view(), 1, slot, C, cand, len) != JSORB_OK)       // the copy of :644
+        throw std::runtime_error(std::string("jsorb_best_covisibles: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    if (jsorb_mem_stream_sync(matcher.stream()) != JSORB_OK || jsorb_mem_d2h(&n, len, sizeof(n)) != JSORB_OK) throw std::runtime_error("KeyFrameCulling: copy back failed");
+    result = jsorb::CulledKeyFrames();
+    result.candidates.resize(n); result.decision.assign(n, -1); result.n_mps.assign(n, 0); result.n_redundant.assign(n, 0);
+    if (n > 0 && jsorb_mem_d2h(result.candidates.data(), cand, (size_t)n * sizeof(int32_t)) != JSORB_OK) throw std::runtime_error("KeyFrameCulling: copy back failed");
+    std::vector<int32_t> h_culled(max_cull), h_rep(2 * (size_t)cap);
+    int done = 0;
+    while (done < n) {
+        int32_t c[10];
+        if (jsorb_cull_keyframes(matcher.handle(), &g, &t, &cov.view(), &v, &state.view(), monocular ? 1 : 0, first_slot, n - done, cand + done, max_cull,
+                                 const_cast<int32_t *>(g.neighbours), cap, decision, n_mps, n_red, culled, reparent, counts, result.decision.data() + done,
+                                 result.n_mps.data() + done, result.n_redundant.data() + done, h_culled.data(), h_rep.data(), c) != JSORB_OK)
+            throw std::runtime_error(std::string("jsorb_cull_keyframes: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+        if (c[9] != 0) throw std::runtime_error("KeyFrameCulling: the reparent log overflowed");      // (a cull hands on at most S children: not reached)
+        for (int i = 0; i < max_cull && h_culled[i] >= 0; i++) result.culled.push_back(h_culled[i]);
+        for (int i = 0; i < c[8] && i < cap; i++) result.reparent.push_back({h_rep[2 * i], h_rep[2 * i + 1]});
+        for (int i = 1; i < 10; i++) result.counts[i] += c[i];
+        if (c[0] <= 0) break;                    // (every call decides at least one candidate)
+        done += c[0];
+    }
+    result.counts[0] = n;
+    return (int)result.culled.size();
 }
 // The getters of KeyFrame.cpp:163-212 over one slot's copy, as slots; argument orders as the reference's
 inline std::vector<int32_t> GetConnectedKeyFrames(const jsorb::Covisibility &cov, int slot) { return cov.copy(slot).conn_slot; }

@@ -540,8 +540,35 @@ int covis_cap_min();                             // the compile-time caps of k_c
 int covis_cap_max();
 void launch_update_connections(const CovisArgs &a, hipStream_t s);       // the five kernels
 void launch_erase_connections(const jsorb_covisibility &cv, int32_t *neighbours, const int64_t *order_key, int slot, int32_t *counts, hipStream_t s);
+void launch_erase_connections_dev(const jsorb_covisibility &cv, int32_t *neighbours, const int64_t *order_key, const int32_t *slot_dev, int32_t *counts,
+                                  hipStream_t s);              // k_cv_erase for a slot in device memory (< 0: nothing); the slot's own map stays
 void launch_connected_mask(const jsorb_covisibility &cv, int slot, uint8_t *mask, hipStream_t s);
 void launch_best_covisibles(const jsorb_covisibility &cv, int n, const int32_t *slots, int N, int32_t *out, int32_t *out_len, hipStream_t s);
+// k_kc_* (k_kf_culling.hip): LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag and MapPoint::EraseObservation / SetBadFlag over the keyframe
+// graph, the map-point table and the covisibility state
+enum { KC_MAX_CULL = 16, KC_MAX_CAND = 4096, KC_COUNTS = 10, KC_SCAN = 256 };
+struct CullArgs {
+    jsorb_keyframe_graph g;                      // order_key, point_off, point_len and the sizes; the arrays the call writes are read through `st`
+    jsorb_covisibility cv;
+    jsorb_keyframe_views v;
+    jsorb_culling_state st;
+    int n_rows, monocular, first_slot, n_cand, max_cull, reparent_cap;
+    const int32_t *cand_slot;                    // n_cand
+    int32_t *neighbours;                         // S x 10, or NULL
+    // outputs
+    int32_t *decision, *n_mps, *n_redundant;     // n_cand each
+    int32_t *culled_slot, *reparent_out, *counts;// max_cull, reparent_cap x 2, 10
+    // scratch
+    int32_t *cnt, *fill, *off, *bsum;            // n_rows each: a row's observations, the scatter's cursor, the start inside its block of 256 rows;
+                                                 // the blocks' starts
+    int32_t *csr_slot, *csr_ent, *was_obs;       // pool_entries each: the observations grouped by row; the culled keyframe's erased entries
+    int32_t *pmark, *ch_raw, *ch, *ch_done;      // S each: the parent candidates' stamp, the children as found, in (order_key, slot) order, reparented
+    int32_t *ev;                                 // n_cand x 3: verdict (0 kept, 1 culled, 3 skipped), n_mps, n_redundant on the state of this round
+    int32_t *ctl;                                // 8: the cursor, done, the slot culled in this round or -1, the keyframes culled so far
+    int32_t *erase_counts;                       // 2: k_cv_erase's counts (not reported)
+    int32_t *stats;                              // KC_COUNTS words: the counts of the last call
+};
+void launch_cull_keyframes(const CullArgs &a, hipStream_t s);
 void launch_gather_counts(const int *countsL, const int *countsR, const int *stats, int32_t *dst, int n_pairs, hipStream_t s);
 void launch_median(const Geometry &g, const int *countsL, float *u_right, float *depth, const int *best_l1, const unsigned *aux,
                    int *stats, int n_pairs, hipStream_t s, DeliverStereo dl = DeliverStereo{nullptr, nullptr, nullptr});

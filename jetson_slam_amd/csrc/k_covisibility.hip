@@ -15,7 +15,8 @@
 // k_cv_apply    a workgroup per slot that leaves at once when it is no member and no member targets it: base and incoming connections merged in
 //               LDS, the map in key order and the list re-sorted by counting rank, the slot's neighbours row
 // k_cv_reset    a workgroup per member: its rows' words back to zero; the counts copied for jsorb_update_connections_stats
-// k_cv_erase    a workgroup per key of the erased slot's map (EraseConnection), k_cv_erase_clear empties the slot itself
+// k_cv_erase    a workgroup per key of the erased slot's map (EraseConnection), k_cv_erase_clear empties the slot itself; k_cv_erase_dev is the
+//               same walk for a slot read from device memory (the keyframe culling's rounds, k_kf_culling.hip)
 // k_cv_mask, k_cv_best   the two getters
 // Every slot, row and run read from device memory is used only after a range check: nothing is read or written outside the arrays whatever they
 // hold.
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(256) void k_cv_reset(CovisArgs a)
 }
 
 // counts[2]: the keys walked, the maps that held the slot
-__global__ __launch_bounds__(256) void k_cv_erase(jsorb_covisibility cv, int32_t *neighbours, const int64_t *order_key, int slot, int32_t *counts)
+__device__ __forceinline__ void cv_erase_body(const jsorb_covisibility &cv, int32_t *neighbours, const int64_t *order_key, int slot, int32_t *counts)
 {
     __shared__ int s_slot[CV_LDS], s_w[CV_LDS], s_kr[CV_LDS];
     __shared__ long long s_key[CV_LDS];
@@ -334,6 +335,19 @@ __global__ __launch_bounds__(256) void k_cv_erase(jsorb_covisibility cv, int32_t
     if (tid == 0) { atomicAdd(&counts[0], 1); if (held) atomicAdd(&counts[1], 1); }
     if (!held) return;                           // its map did not hold the slot: left alone, lists included
     cv_store(cv, neighbours, B, nb, s_slot, s_w, s_key, s_kr, true);
+}
+
+__global__ __launch_bounds__(256) void k_cv_erase(jsorb_covisibility cv, int32_t *neighbours, const int64_t *order_key, int slot, int32_t *counts)
+{
+    cv_erase_body(cv, neighbours, order_key, slot, counts);
+}
+
+// the same walk for a slot the device chose (jsorb_cull_keyframes_async, k_kf_culling.hip): *slot_dev < 0 = nothing to erase in this round
+__global__ __launch_bounds__(256) void k_cv_erase_dev(jsorb_covisibility cv, int32_t *neighbours, const int64_t *order_key, const int32_t *slot_dev, int32_t *counts)
+{
+    const int slot = *slot_dev;
+    if (!cv_slot_ok(slot, cv.max_keyframes)) return;                     // (uniform over the launch)
+    cv_erase_body(cv, neighbours, order_key, slot, counts);
 }
 
 __global__ void k_cv_erase_clear(jsorb_covisibility cv, int32_t *neighbours, int slot)
@@ -387,6 +401,12 @@ void launch_erase_connections(const jsorb_covisibility &cv, int32_t *neighbours,
 {
     hipLaunchKernelGGL(k_cv_erase, dim3(cv.conn_capacity), dim3(256), 0, s, cv, neighbours, order_key, slot, counts);
     hipLaunchKernelGGL(k_cv_erase_clear, dim3(1), dim3(64), 0, s, cv, neighbours, slot);
+}
+
+void launch_erase_connections_dev(const jsorb_covisibility &cv, int32_t *neighbours, const int64_t *order_key, const int32_t *slot_dev, int32_t *counts,
+                                  hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cv_erase_dev, dim3(cv.conn_capacity), dim3(256), 0, s, cv, neighbours, order_key, slot_dev, counts);
 }
 
 void launch_connected_mask(const jsorb_covisibility &cv, int slot, uint8_t *mask, hipStream_t s)

@@ -81,6 +81,7 @@ EXPORTS = [
     "jsorb_update_connections_async", "jsorb_update_connections", "jsorb_update_connections_stats", "jsorb_erase_connections_async",
     "jsorb_connected_mask_async", "jsorb_best_covisibles_async", "jsorb_covisibility_copy", "jsorb_covisibility_build_caps",
     "jsorb_update_connections_scratch",
+    "jsorb_cull_keyframes_async", "jsorb_cull_keyframes", "jsorb_cull_keyframes_stats", "jsorb_cull_keyframes_build_caps",
 ]
 
 
@@ -352,7 +353,9 @@ class KeyframeGraph:
     for KeyframeDatabase.  What the reference changes, and where it lands here: AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch -> the
     keyframe's run in point_pool (set_keyframe, or a write into point_pool at point_off[slot] + i); AddObservation / EraseObservation ->
     `registered`; UpdateBestCovisibles -> set_neighbours, or nothing where KeyframeMatcher.update_connections keeps `neighbours` current; AddChild / EraseChild / ChangeParent -> set_children, set_parent; SetBadFlag ->
-    set_state(slot, KF_BAD); erase(slot) frees the slot.  Runs are handed out from the pools front to back; a run that still fits is rewritten
+    set_state(slot, KF_BAD), and for the keyframes KeyframeMatcher.cull_keyframes culls nothing: the call itself sets state, clears the
+    keyframe's `registered` bytes and the observers' entries of the rows it turns bad, and repairs `parent` (with apply=True the child runs
+    too); erase(slot) frees the slot.  Runs are handed out from the pools front to back; a run that still fits is rewritten
     in place, and a full pool is an error (the caller builds a new graph)."""
     ARRAYS = ("state", "order_key", "point_off", "point_len", "point_pool", "registered", "neighbours", "child_off", "child_len", "child_pool", "parent")
 
@@ -548,6 +551,92 @@ class Covisibility:
             return os_
         n = int(np.count_nonzero(ow >= int(w)))          # upper_bound(first, last, w, a > b): the first element with w > element
         return os_[:0] if n == len(ow) else os_[:n]
+
+
+class JsorbKeyframeViews(C.Structure):
+    _fields_ = [("pool_entries", C.c_int)] + [(k, C.c_void_p) for k in ("octave", "stereo", "depth", "th_depth")]
+
+
+class JsorbCullingState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("state", "registered", "bad", "point_pool", "parent", "not_erase", "to_be_erased", "ref_slot")]
+
+
+CULL_MAX = 16                                    # keyframes culled per jsorb_cull_keyframes call
+CULL_COUNTS = ("next", "n_kept", "n_culled", "n_deferred", "n_skipped", "n_rows_bad", "n_observations_erased", "n_ref_moved", "n_reparent",
+               "reparent_overflow")
+CULL_KEPT, CULL_CULLED, CULL_DEFERRED, CULL_SKIPPED, CULL_NOT_REACHED = 0, 1, 2, 3, -1      # decision[i]
+
+
+class KeyframeViews:
+    """What LocalMapping::KeyFrameCulling reads of a keyframe's keypoints (jsorb_keyframe_views): torch device arrays parallel to a
+    KeyframeGraph's point_pool - octave uint8 (mvKeysUn[i].octave), stereo uint8 (mvuRight[i] >= 0), depth float32 (mvDepth[i]; None for a
+    monocular map) - and th_depth float32[max_keyframes] (mThDepth)."""
+
+    def __init__(self, graph, depth=True):
+        import torch
+        dev = graph.point_pool.device
+        self.pool_entries, self.max_keyframes = graph.pool_entries, graph.max_keyframes
+        n = max(self.pool_entries, 1)
+        self.octave = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.stereo = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.depth = torch.zeros(n, dtype=torch.float32, device=dev) if depth else None
+        self.th_depth = torch.zeros(max(self.max_keyframes, 1), dtype=torch.float32, device=dev)
+
+    def struct(self):
+        return JsorbKeyframeViews(self.pool_entries, self.octave.data_ptr(), self.stereo.data_ptr(), None if self.depth is None else self.depth.data_ptr(),
+                                  self.th_depth.data_ptr())
+
+    def load(self, **arrays):
+        """whole arrays at once (numpy): octave, stereo, depth, th_depth"""
+        import torch
+        for k, v in arrays.items():
+            t = getattr(self, k, None) if k in ("octave", "stereo", "depth", "th_depth") else None
+            if t is None:
+                raise JsorbError("KeyframeViews.load: no array %s" % k)
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(t.device)
+            if v.dtype != t.dtype or v.numel() > t.numel():
+                raise JsorbError("KeyframeViews.load: %s must be %s with at most %d entries" % (k, t.dtype, t.numel()))
+            t.view(-1)[:v.numel()].copy_(v.view(-1))
+
+    def set_keyframe_views(self, graph, slot, octave, stereo, depth=None, th_depth=0.0):
+        """the views of the keyframe in `slot`, written at its run (after graph.set_keyframe)"""
+        set_keyframe_views(graph, self, slot, octave, stereo, depth, th_depth)
+
+
+def set_keyframe_views(graph, views, slot, octave, stereo, depth=None, th_depth=0.0):
+    """the views of the keyframe in `slot`, written at its run in the graph's point_pool (after graph.set_keyframe): one entry per entry of the run"""
+    import torch
+    slot = graph._slot(slot)
+    at, n = int(graph.point_off[slot]), int(graph.point_len[slot])
+    for name, v, dt in (("octave", octave, np.uint8), ("stereo", stereo, np.uint8), ("depth", depth, np.float32)):
+        t = getattr(views, name)
+        if t is None or v is None:
+            if name != "depth" or (t is not None and v is None):
+                raise JsorbError("set_keyframe_views: %s is missing" % name)
+            continue
+        v = np.ascontiguousarray(v, dt).ravel()
+        if len(v) != n:
+            raise JsorbError("set_keyframe_views: %s must have the run's %d entries" % (name, n))
+        if n:
+            t[at:at + n] = torch.from_numpy(v).to(t.device)
+    views.th_depth[slot] = float(th_depth)
+
+
+def culling_state(graph, table, not_erase=None, to_be_erased=None, ref_slot=None):
+    """jsorb_culling_state: the graph's and the table's arrays as the writable pointers jsorb_cull_keyframes takes, with not_erase /
+    to_be_erased uint8[max_keyframes] and ref_slot int32[n_rows] device tensors (or None).  The caller keeps the tensors alive."""
+    import torch
+    if graph.registered is None:
+        raise JsorbError("culling_state: the graph has no registered bytes (the call writes them)")
+    for name, t, dt, n in (("not_erase", not_erase, torch.uint8, graph.max_keyframes), ("to_be_erased", to_be_erased, torch.uint8, graph.max_keyframes),
+                           ("ref_slot", ref_slot, torch.int32, table.n_rows)):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < n):
+            raise JsorbError("culling_state: %s must be a contiguous %s device tensor of at least %d entries" % (name, dt, n))
+    if not_erase is not None and to_be_erased is None:
+        raise JsorbError("culling_state: not_erase needs to_be_erased")
+    p = lambda t: None if t is None else t.data_ptr()
+    return JsorbCullingState(graph.state.data_ptr(), graph.registered.data_ptr(), table.bad.data_ptr(), graph.point_pool.data_ptr(), graph.parent.data_ptr(),
+                             p(not_erase), p(to_be_erased), p(ref_slot))
 
 
 def make_camera(K, D):
@@ -760,6 +849,12 @@ def load_library(path=None):
         "jsorb_best_covisibles_async": (I, [P, C.POINTER(JsorbCovisibility), I, P, I, P, P]),
         "jsorb_covisibility_copy": (I, [C.POINTER(JsorbCovisibility), I] + [P] * 5),
         "jsorb_covisibility_build_caps": (I, [C.POINTER(I)] * 2),
+        "jsorb_cull_keyframes_async": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), C.POINTER(JsorbCovisibility),
+                                           C.POINTER(JsorbKeyframeViews), C.POINTER(JsorbCullingState), I, I, I, P, I, P, I] + [P] * 6),
+        "jsorb_cull_keyframes": (I, [P, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable), C.POINTER(JsorbCovisibility),
+                                     C.POINTER(JsorbKeyframeViews), C.POINTER(JsorbCullingState), I, I, I, P, I, P, I] + [P] * 12),
+        "jsorb_cull_keyframes_stats": (I, [P, P]),
+        "jsorb_cull_keyframes_build_caps": (I, [C.POINTER(I)] * 2),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1432,6 +1527,82 @@ class KeyframeMatcher:
         if wait:
             self.sync()
         return out, out_len
+
+
+    # ---- culling: LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag (LocalMapping.cpp:638-702, KeyFrame.cpp:457-549) ----
+    def cull_keyframes(self, graph, table, cov, views, state, candidates, first_slot=-1, monocular=False, max_cull=4, neighbours=None,
+                       reparent_cap=64, sync=False, wait=True, apply=False, database=None, out=None):
+        """jsorb_cull_keyframes*: KeyFrameCulling over `candidates` (an int32 device tensor - what best_covisibles(cov, [current],
+        cov.conn_capacity) returned, flattened - or a host sequence that is uploaded), in order, each culled keyframe's SetBadFlag complete before the
+        next candidate is looked at.  views a KeyframeViews, state a culling_state(graph, table, ...).  At most max_cull (<= 16) keyframes are culled
+        per call (every round is enqueued whether it finds a cull or not, about 7 us each on an MI355X, hence the default of 4); counts[0] = next
+        says where a second call continues (candidates[next:]).  Returns a dict of device tensors: decision, n_mps,
+        n_redundant int32[n], culled_slot int32[max_cull], reparent_out int32[reparent_cap, 2], counts int32[10] (CULL_COUNTS); with sync=True
+        the same as numpy arrays under *_host.  apply=True (implies sync) does the binding's part of SetBadFlag from what came back: the child runs
+        of the culled keyframes and of every parent that lost or gained a child are rewritten with graph.set_children (children in (order_key,
+        slot) order; only keyframes with state 1 are listed - a bad keyframe that parent[] still names as a child, which the fallback hands on,
+        is in no child run, as after the reference's EraseChild), and the culled slots are erased from `database` (a KeyframeDatabase) when one
+        is passed.  out: the dict of an earlier call with the same n, max_cull and reparent_cap, written again.  The call waits for the current
+        torch stream before it enqueues, except with wait=False, out given and candidates a device tensor: then it makes no tensor, waits for
+        nothing and only enqueues - the form a graph capture takes."""
+        import torch
+        dev = cov.conn_len.device
+        made = not torch.is_tensor(candidates)
+        if made:
+            candidates = torch.tensor([int(x) for x in candidates], dtype=torch.int32, device=dev)
+        candidates = candidates.reshape(-1)
+        n, max_cull, cap = int(candidates.numel()), int(max_cull), int(reparent_cap)
+        cp = self._i32("cull_keyframes: candidates", candidates) if n else None
+        nb = None if neighbours is None else self._i32("cull_keyframes: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
+        new = lambda *shape: torch.empty([max(int(x), 1) for x in shape], dtype=torch.int32, device=dev)
+        made = made or out is None
+        bufs = out["_bufs"] if out is not None else dict(decision=new(n), n_mps=new(n), n_redundant=new(n), culled_slot=new(max(max_cull, 1)),
+                                                         reparent_out=new(cap, 2), counts=new(10))
+        shapes = dict(decision=(n,), n_mps=(n,), n_redundant=(n,), culled_slot=(max(max_cull, 0),), reparent_out=(max(cap, 0), 2), counts=(10,))
+        gs, tb, cs, vs = graph.struct(), table.struct(), cov.struct(), views.struct()
+        keys = ("decision", "n_mps", "n_redundant", "culled_slot", "reparent_out", "counts")
+        args = [self._m, C.byref(gs), C.byref(tb), C.byref(cs), C.byref(vs), C.byref(state), int(bool(monocular)), int(first_slot), n, cp, max_cull, nb, cap] + \
+               [bufs[k].data_ptr() for k in keys]
+        if wait or sync or apply or made:
+            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
+        out = {k: bufs[k].reshape(-1)[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys}
+        out["_bufs"] = bufs
+        if sync or apply:
+            host = {k: np.full(max(int(np.prod(shapes[k])), 1), -7, np.int32) for k in keys}
+            self._chk(self._lib.jsorb_cull_keyframes(*args, *[host[k].ctypes.data for k in keys]))
+            out.update({k + "_host": host[k][:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys})
+        else:
+            self._chk(self._lib.jsorb_cull_keyframes_async(*args))
+            if wait:
+                self.sync()
+        out["candidates"] = candidates           # (kept alive with the result: the device reads it after the call returns)
+        if apply:
+            culled = [int(s) for s in out["culled_slot_host"] if s >= 0]
+            if culled:
+                parent, st, key = graph.parent.cpu().numpy(), graph.state.cpu().numpy(), graph.order_key.cpu().numpy()
+                rec = out["reparent_out_host"][:min(int(out["counts_host"][8]), cap)]
+                touched = set(culled) | {int(p) for p in rec[:, 1]} | {int(parent[s]) for s in culled}
+                for p in sorted(t for t in touched if 0 <= t < graph.max_keyframes):
+                    kids = [] if p in culled else [int(s) for s in np.nonzero((parent[:graph.max_keyframes] == p) & (st[:graph.max_keyframes] == KF_GOOD))[0]]
+                    graph.set_children(p, sorted(kids, key=lambda s: (int(key[s]), s)))
+                if database is not None:
+                    for s in culled:
+                        database.erase(s)
+            out["culled"] = culled
+        return out
+
+    def cull_keyframes_stats(self):
+        """dict of CULL_COUNTS of the last cull_keyframes (waits for it)"""
+        v = np.zeros(10, np.int32)
+        self._chk(self._lib.jsorb_cull_keyframes_stats(self._m, v.ctypes.data))
+        return dict(zip(CULL_COUNTS, (int(x) for x in v)))
+
+
+def cull_keyframes_build_caps():
+    """jsorb_cull_keyframes_build_caps of the loaded library: the most candidates and the largest max_cull of one call"""
+    a, b = C.c_int(), C.c_int()
+    load_library().jsorb_cull_keyframes_build_caps(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def covisibility_build_caps():
