@@ -733,6 +733,7 @@ int jsorb_search_for_triangulation_stats(jsorb_keyframe_matcher *m, int *n_node_
  *     nothing is searched again: the survivor of a Replace is either the point at hand, whose search there is over, or the point in the
  *     keyframe's slot, which the head test skips there.  Without this step the replay differs from the reference's loop (run against the
  *     reference's own ORBmatcher.cpp: tests/fuse_replay.py, tests/test_ref_matcher.py).
+ * (A caller that keeps the map on the device takes jsorb_fuse_map_async below instead: the search, the head test and the tail in one call.)
  * With it the replay equals the sequential loop, because
  *   - vpMapPointMatches is a copy taken before the loop, so the point list of a call does not change under it;
  *   - the head test only ever goes from pass to skip while the loops run: isBad never reverts, and in a map whose slots and observations agree a
@@ -1193,6 +1194,87 @@ int jsorb_cull_keyframes(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *
 int jsorb_cull_keyframes_stats(jsorb_keyframe_matcher *m, int32_t counts[10]);
 /* The compile-time caps of the library in use: the candidates of one call (4096, twice the largest conn_capacity) and max_cull (16). */
 int jsorb_cull_keyframes_build_caps(int *max_candidates, int *max_cull);
+
+/* ---- Fuse applied to the map on the device: ORBmatcher::Fuse(pKF, vpMapPoints, th) WITH its tail (src/ORBmatcher.cpp:812-962) as
+ * LocalMapping::SearchInNeighbors runs it (src/LocalMapping.cpp:490-531), and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:964-1087) with the
+ * Replace loop of LoopClosing::SearchAndFuse (src/LoopClosing.cpp:596-617), over the state the calls above keep - the graph's point_pool and
+ * registered, the table's bad and desc - for ALL target keyframes in one call on the keyframe matcher's stream, in the reference's order: keyframe
+ * t is searched from the map as it is then, its tail runs, then keyframe t + 1 (tests/fuse_replay.py, mode "sequential").  No host decision between
+ * the argument checks and the result.  params->check_reprojection picks the overload as for jsorb_fuse: 1 the first, 0 the one with Scw (Rcw, tcw,
+ * Ow derived from it, :967-974); replace_loop is read only with 0.
+ * The definitions of jsorb_local_keyframes_async and jsorb_cull_keyframes_async hold: USABLE slot, valid run, (order_key, slot) order.  kp: DEVICE
+ * arrays parallel to graph->point_pool (a keypoint's index within its keyframe is its index within the run).  The keyframe of target t is the run
+ * point_off[A], point_len[A] of A = target_slot[t], read on the device.  An ENTRY OF ROW r is an entry e with point_pool[e] == r, registered[e] != 0,
+ * 0 <= r < n_rows, in a valid run of a slot with state != 0 (an entry inside two overlapping runs belongs to one of them); it is an OBSERVATION
+ * when that slot has state == 1.  Observations(r) = the sum of 1 + (uright[e] >= 0) over the observations (uright NULL: 1 each), recomputed, not
+ * stored.  list_row (DEVICE) int32[n_list]: the points' rows, -1 = NULL.  target_slot, Rcw, tcw, Ow: HOST arrays per target as for jsorb_fuse.
+ * Per target t, in order:
+ *   0. A not usable, state[A] != 1, an invalid run or one of 262144 entries or more: n_fused[t] = 0, row t of best_idx, best_dist and replace_point is
+ *      -1, the target is counted, nothing else happens.
+ *   1. Overload 2: the snapshot = the rows in A's run that are in range and not bad at this moment (:980).
+ *   2. Every list point whose head test (below) passes at this moment is searched in A with the arithmetic of jsorb_fuse_async items 1-10 over the
+ *      table's fields as they are now, desc included; every other pair gets -1 / -1.
+ *   3. i = 0 .. n_list-1 in order, r = list_row[i].  The head test, evaluated at i's turn: r in [0, n_rows), bad[r] == 0, and - overload 1 - r has no
+ *      observation in A (IsInKeyFrame, :835), - overload 2 - r not in the snapshot (:992).  Failed, or best_idx[t][i] < 0: the next point.
+ *      Otherwise e = point_off[A] + best_idx[t][i], q = point_pool[e], n_fused[t] += 1 and
+ *        q outside [-1, n_rows): the pair is dropped and counted (the reference would read through the pointer)
+ *        q == -1: point_pool[e] = r, registered[e] = 1 (AddObservation, AddMapPoint), logged as (3, r, A, best_idx)
+ *        overload 1, q >= 0 (:941-956): bad[q] != 0: nothing; else Observations(q) > Observations(r): Replace(r -> q); else Replace(q -> r)
+ *        overload 2, q >= 0 (:1071-1081): replace_point[t][i] = q when bad[q] == 0 (else it stays -1)
+ *   4. Overload 2 with replace_loop: for i in order with replace_point[t][i] >= 0, Replace(replace_point[t][i] -> list_row[i]).
+ *   5. Every row that was the target q of a Replace in 3-4, is not bad now and has an observation gets desc[q] = ComputeDistinctiveDescriptors by
+ *      rules 1-5 of jsorb_distinctive_descriptors_async over its observations in (order_key, slot) order, from kp->desc.  (The reference does this
+ *      inside every Replace; within one target the set at the end is the set at q's last Replace, and nothing reads the descriptor in between:
+ *      tests/test_fuse_apply_host.py holds this against the immediate recomputation.)
+ *   Replace(p -> q) (src/MapPoint.cpp:208-246): nothing when p == q.  Otherwise every entry e of p, in slot B: q has no entry in B (as the map is
+ *   before this Replace): point_pool[e] = q; it has one: point_pool[e] = -1, registered[e] = 0.  Then bad[p] = 1, replaced[p] = q, found[q] +=
+ *   found[p], visible[q] += visible[p], logged as (2, p, q, -1).  Entries that hold p with registered == 0 stay as they are.  (Entries in slots of
+ *   state 2 move with the others, as mObservations keeps a bad keyframe until it erases itself; they count for neither Observations() nor step 5.)
+ * state: what the call WRITES - point_pool, registered (the graph's arrays), bad, desc (the table's), handed over writable: another address is
+ * JSORB_ERR_INVALID, as for jsorb_culling_state; replaced int32[n_rows] (mpReplaced as a row; may be NULL); visible, found int32[n_rows] (both NULL
+ * or both given).
+ * Outputs (DEVICE): best_idx, best_dist int32[n_targets x n_list], every entry written; replace_point int32[n_targets x n_list] (needed for overload 2,
+ * else may be NULL: when given every entry is written); n_fused int32[n_targets]; log_out int32[log_cap][4], -1 padded: the events in the order they
+ * are made, codes 2 and 3 above - the map writes are complete whatever log_cap is; counts_dev int32[10] = fused, Replace calls, AddMapPoint calls,
+ * matches whose slot held a bad point, rows turned bad, descriptors written with other bytes, skipped targets, dropped pairs, log records made, 1
+ * when they exceed log_cap.
+ * What stays on the host: Map::EraseMapPoint and the host objects' mirrors (from log_out and replaced), UpdateNormalAndDepth
+ * (jsorb_map_points_scatter_async), the candidate list of SearchInNeighbors' second direction (LocalMapping.cpp:498-516).
+ * Enqueued on the matcher's stream, launch shapes from the host sizes alone, no synchronisation, capturable once the scratch has its size.
+ * JSORB_ERR_INVALID for a NULL required pointer, the parameter limits of jsorb_fuse_async, negative sizes, n_targets outside [0, 256],
+ * kp->pool_entries != graph->pool_entries, a state array that is not the graph's or the table's, graph->registered NULL, kp->desc or the table's desc
+ * not 16-byte aligned, visible without found or the reverse, overload 2 without replace_point; JSORB_ERR_UNSUPPORTED when n_targets x n_list exceeds
+ * INT_MAX - 256.  n_list == 0 and n_targets == 0 are valid calls. */
+typedef struct jsorb_keyframe_keypoints {   /* DEVICE arrays parallel to graph->point_pool */
+    int pool_entries;
+    const float *x, *y;                     /* mvKeysUn */
+    const int32_t *octave;
+    const float *uright;                    /* mvuRight; NULL: monocular everywhere */
+    const uint8_t *desc;                    /* pool_entries x 32, 16-byte aligned */
+} jsorb_keyframe_keypoints;
+typedef struct jsorb_fuse_state {
+    int32_t *point_pool;
+    uint8_t *registered;
+    uint8_t *bad, *desc;
+    int32_t *replaced;
+    int32_t *visible, *found;
+} jsorb_fuse_state;
+int jsorb_fuse_map_async(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int replace_loop, const jsorb_keyframe_graph *graph,
+                         const jsorb_map_point_table *table, const jsorb_keyframe_keypoints *kp, const jsorb_fuse_state *state, int n_list,
+                         const int32_t *list_row, int n_targets, const int32_t *target_slot, const float *Rcw, const float *tcw, const float *Ow,
+                         int32_t *best_idx, int32_t *best_dist, int32_t *replace_point, int32_t *n_fused, int log_cap, int32_t *log_out,
+                         int32_t *counts_dev);
+/* Synchronous: the same, then the outputs in one copy back (host arrays of the same sizes; replace_point_host may be NULL when replace_point is). */
+int jsorb_fuse_map(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, int replace_loop, const jsorb_keyframe_graph *graph,
+                   const jsorb_map_point_table *table, const jsorb_keyframe_keypoints *kp, const jsorb_fuse_state *state, int n_list,
+                   const int32_t *list_row, int n_targets, const int32_t *target_slot, const float *Rcw, const float *tcw, const float *Ow,
+                   int32_t *best_idx, int32_t *best_dist, int32_t *replace_point, int32_t *n_fused, int log_cap, int32_t *log_out, int32_t *counts_dev,
+                   int32_t *best_idx_host, int32_t *best_dist_host, int32_t *replace_point_host, int32_t *n_fused_host, int32_t *log_host,
+                   int32_t counts_host[10]);
+/* The counts of the last jsorb_fuse_map* (waits for it): counts[10] as above.  JSORB_ERR_STATE before the first call. */
+int jsorb_fuse_map_stats(jsorb_keyframe_matcher *m, int32_t counts[10]);
+/* The compile-time cap of the library in use: the entries of an observation list the applying workgroup stages at a time (256). */
+int jsorb_fuse_map_build_caps(int *list_chunk);
 
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <utility>
 #include <string>
+#include <array>
 #include <vector>
 
 #include "jsorb.h"
@@ -761,7 +762,7 @@ public:
         const size_t s = S_ > 0 ? S_ : 1, p = pool_ > 0 ? pool_ : 1, c = child_ > 0 ? child_ : 1;
         alloc(state_, s, 0); alloc(key_, s, 0); alloc(point_off_, s, 0); alloc(point_len_, s, 0); alloc(point_pool_, p, -1); alloc(registered_, p, 1);
         alloc(neighbours_, 10 * s, -1); alloc(child_off_, s, 0); alloc(child_len_, s, 0); alloc(child_pool_, c, -1); alloc(parent_, s, -1);
-        point_run_.assign(s, {0, -1}); child_run_.assign(s, {0, -1});
+        point_run_.assign(s, {0, -1}); child_run_.assign(s, {0, -1}); point_n_.assign(s, 0);
     }
     KeyframeGraph(const KeyframeGraph &) = delete;
     KeyframeGraph &operator=(const KeyframeGraph &) = delete;
@@ -773,6 +774,7 @@ public:
     int max_keyframes() const { return S_; }
     int pool_entries() const { return pool_; }
     int point_offset(int slot) const { return point_run_[in(slot)].first; }        // where the slot's run starts in point_pool (set_keyframe)
+    int point_length(int slot) const { return point_n_[in(slot)]; }                // the entries of the slot's run (set_keyframe; 0 after erase)
     jsorb_keyframe_graph view() const
     {
         return jsorb_keyframe_graph{S_, pool_, child_, state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_,
@@ -782,6 +784,7 @@ public:
     void set_keyframe(int slot, const std::vector<int32_t> &rows, int64_t key, int state = GOOD, const std::vector<unsigned char> *registered = nullptr)
     {
         const int at = write_run(slot, rows, point_run_, point_used_, pool_, point_pool_, point_off_, point_len_);
+        point_n_[slot] = (int)rows.size();
         if (!rows.empty()) {
             std::vector<unsigned char> ones;
             if (!registered) { ones.assign(rows.size(), 1); registered = &ones; }
@@ -803,6 +806,7 @@ public:
     void erase(int slot)
     {
         set_state(slot, ABSENT); put(point_len_, slot, (int32_t)0); put(child_len_, slot, (int32_t)0); set_parent(slot, -1); set_neighbours(slot, {});
+        point_n_[slot] = 0;
     }
 
 private:
@@ -841,6 +845,7 @@ private:
     int32_t *point_off_ = nullptr, *point_len_ = nullptr, *point_pool_ = nullptr, *neighbours_ = nullptr, *child_off_ = nullptr, *child_len_ = nullptr,
             *child_pool_ = nullptr, *parent_ = nullptr;
     std::vector<std::pair<int, int>> point_run_, child_run_;
+    std::vector<int> point_n_;
 };
 // mvpLocalKeyFrames and mpReferenceKF as UpdateLocalKeyFrames keeps them from frame to frame, and the local keyframes' rows concatenated for
 // UpdateLocalPoints: slots[i] (host) the slot of the i-th local keyframe, ref_slot the slot of mpReferenceKF (-1: none yet), counts as
@@ -1009,6 +1014,110 @@ private:
     unsigned char *not_erase_ = nullptr, *to_be_erased_ = nullptr;
     int32_t *ref_slot_ = nullptr;
     jsorb_culling_state v_{};
+};
+// What ORBmatcher::Fuse reads of the keyframes' keypoints (jsorb_keyframe_keypoints, include/jsorb.h): device arrays parallel to the graph's
+// point_pool - mvKeysUn (x, y, octave), mvuRight (none for a monocular map) and the descriptors.
+class KeyframeKeypoints {
+public:
+    KeyframeKeypoints(const KeyframeGraph &graph, bool stereo) : pool_(graph.pool_entries())
+    {
+        const size_t p = pool_ > 0 ? pool_ : 1;
+        zeros((void **)&x_, p * sizeof(float)); zeros((void **)&y_, p * sizeof(float)); zeros((void **)&octave_, p * sizeof(int32_t));
+        zeros((void **)&desc_, p * 32);
+        if (stereo) {
+            zeros((void **)&uright_, p * sizeof(float));
+            const std::vector<float> none(p, -1.0f);
+            check(jsorb_mem_h2d(uright_, none.data(), p * sizeof(float)), "upload");
+        }
+    }
+    KeyframeKeypoints(const KeyframeKeypoints &) = delete;
+    KeyframeKeypoints &operator=(const KeyframeKeypoints &) = delete;
+    ~KeyframeKeypoints() { jsorb_mem_free_device(x_); jsorb_mem_free_device(y_); jsorb_mem_free_device(octave_); jsorb_mem_free_device(uright_); jsorb_mem_free_device(desc_); }
+    jsorb_keyframe_keypoints view() const { return jsorb_keyframe_keypoints{pool_, x_, y_, octave_, uright_, desc_}; }
+    // the keyframe in `slot`, one entry per entry of its run (after graph.set_keyframe); uright may be NULL (a monocular keyframe); desc: 32 bytes each
+    void set_keyframe(const KeyframeGraph &graph, int slot, const std::vector<float> &x, const std::vector<float> &y, const std::vector<int32_t> &octave,
+                      const std::vector<float> *uright, const std::vector<unsigned char> &desc)
+    {
+        const size_t at = (size_t)graph.point_offset(slot), n = x.size();
+        if (n != (size_t)graph.point_length(slot) || y.size() != n || octave.size() != n || desc.size() != 32 * n || (uright && uright->size() != n) ||
+            at + n > (size_t)(pool_ > 0 ? pool_ : 0) || (uright && !uright_))
+            throw std::runtime_error("jsorb::KeyframeKeypoints: one x, y, octave, uright and descriptor per entry of the run");
+        if (!n) return;
+        check(jsorb_mem_h2d(x_ + at, x.data(), n * sizeof(float)), "upload");
+        check(jsorb_mem_h2d(y_ + at, y.data(), n * sizeof(float)), "upload");
+        check(jsorb_mem_h2d(octave_ + at, octave.data(), n * sizeof(int32_t)), "upload");
+        check(jsorb_mem_h2d(desc_ + 32 * at, desc.data(), 32 * n), "upload");
+        if (uright_) {
+            const std::vector<float> none(n, -1.0f);
+            check(jsorb_mem_h2d(uright_ + at, uright ? uright->data() : none.data(), n * sizeof(float)), "upload");
+        }
+    }
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeKeypoints ") + what + ": " + jsorb_mem_last_error());
+    }
+    static void zeros(void **p, size_t bytes)
+    {
+        check(jsorb_mem_alloc_device(bytes, p), "alloc");
+        check(jsorb_mem_set_zero(*p, bytes), "clear");
+    }
+    int pool_ = 0;
+    float *x_ = nullptr, *y_ = nullptr, *uright_ = nullptr;
+    int32_t *octave_ = nullptr;
+    unsigned char *desc_ = nullptr;
+};
+// The arrays jsorb_fuse_map writes (jsorb_fuse_state): the graph's point_pool / registered and the table's bad / desc once more as writable
+// pointers, and mpReplaced as a row (-1), mnVisible and mnFound per table row, which this class owns.
+class FuseState {
+public:
+    FuseState(const KeyframeGraph &graph, const MapPointTable &table) : rows_(table.n_rows())
+    {
+        const jsorb_keyframe_graph g = graph.view();
+        const jsorb_map_point_table t = table.view();
+        const size_t r = rows_ > 0 ? rows_ : 1;
+        int32_t **own[3] = {&replaced_, &visible_, &found_};
+        for (int i = 0; i < 3; i++) {
+            check(jsorb_mem_alloc_device(r * sizeof(int32_t), (void **)own[i]), "alloc");
+            const std::vector<int32_t> fill(r, i == 0 ? -1 : 0);
+            check(jsorb_mem_h2d(*own[i], fill.data(), r * sizeof(int32_t)), "upload");
+        }
+        v_ = jsorb_fuse_state{const_cast<int32_t *>(g.point_pool), const_cast<uint8_t *>(g.registered), const_cast<uint8_t *>(t.bad), const_cast<uint8_t *>(t.desc),
+                              replaced_, visible_, found_};
+    }
+    FuseState(const FuseState &) = delete;
+    FuseState &operator=(const FuseState &) = delete;
+    ~FuseState() { jsorb_mem_free_device(replaced_); jsorb_mem_free_device(visible_); jsorb_mem_free_device(found_); }
+    const jsorb_fuse_state &view() const { return v_; }
+    int replaced(int row) const { return get(replaced_, row); }      // mpReplaced as a row, -1
+    int visible(int row) const { return get(visible_, row); }
+    int found(int row) const { return get(found_, row); }
+    void set_counters(int row, int visible, int found) { put(visible_, row, visible); put(found_, row, found); }      // mnVisible, mnFound
+
+private:
+    static void check(int rc, const char *what)
+    {
+        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::FuseState ") + what + ": " + jsorb_mem_last_error());
+    }
+    int in(int row) const
+    {
+        if (row < 0 || row >= rows_) throw std::runtime_error("jsorb::FuseState: row out of range");
+        return row;
+    }
+    int get(const int32_t *p, int row) const { int32_t v = 0; check(jsorb_mem_d2h(&v, p + in(row), sizeof(v)), "copy back"); return v; }
+    void put(int32_t *p, int row, int v) { const int32_t w = v; check(jsorb_mem_h2d(p + in(row), &w, sizeof(w)), "upload"); }
+    int rows_ = 0;
+    int32_t *replaced_ = nullptr, *visible_ = nullptr, *found_ = nullptr;
+    jsorb_fuse_state v_{};
+};
+// What FuseMap gives back: per (target, list point) the keypoint searched (-1: none) with its distance and, for the overload with Scw,
+// vpReplacePoint as a row; nFused per target; the Replace (2, p, q, -1) and AddMapPoint (3, row, slot, keypoint) events in order; the counts of
+// jsorb_fuse_map.
+struct FusedMap {
+    std::vector<int32_t> best_idx, best_dist, replace_point, n_fused;
+    std::vector<std::array<int32_t, 4>> events;
+    int32_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 // What KeyFrameCulling gives back: per candidate of the current keyframe's list the decision (0 kept, 1 culled, 2 deferred by mbNotErase,
 // 3 skipped) with n_mps and n_redundant as seen at its turn, the culled slots in order, every ChangeParent as (child, new parent) in order, and
@@ -1258,6 +1367,33 @@ inline int EraseConnections(jsorb::KeyframeMatcher &matcher, const jsorb::Keyfra
         throw std::runtime_error("EraseConnections: copy back failed");
     return h[1];
 }
+// ORBmatcher::Fuse with its map mutations (ORBmatcher.cpp:812-1087, MapPoint.cpp:208-246) for all `targets` (slots) in order, on the device state:
+// one direction of LocalMapping::SearchInNeighbors (prm.check_reprojection = 1), or LoopClosing::SearchAndFuse's calls with their Replace loop
+// (check_reprojection = 0, replace_loop).  list: the points' table rows, -1 = NULL.  Returns the number of fused points.  The host objects follow
+// from result.events and state.replaced(); Map::EraseMapPoint and UpdateNormalAndDepth stay with the caller.
+inline int FuseMap(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &prm, const jsorb::KeyframeGraph &graph, const jsorb::MapPointTable &table,
+                   const jsorb::KeyframeKeypoints &kp, jsorb::FuseState &state, const std::vector<int32_t> &list, const std::vector<int32_t> &targets,
+                   const jsorb::FusePoses &poses, jsorb::FusedMap &result, bool replace_loop = false)
+{
+    const size_t n = list.size(), T = targets.size(), pairs = n * T, cap = pairs ? pairs : 1;
+    if (T && (!poses.Rcw || !poses.tcw || !poses.Ow)) throw std::runtime_error("FuseMap: 9 + 3 + 3 pose floats per target (host arrays, as for Fuse)");
+    jsorb::DeviceInts dl(n), out(3 * pairs + T + 4 * cap + 10);
+    if (n && jsorb_mem_h2d(dl.p, list.data(), n * sizeof(int32_t)) != JSORB_OK) throw std::runtime_error("FuseMap: upload failed");
+    int32_t *bi = out.p, *bd = bi + pairs, *rp = bd + pairs, *nf = rp + pairs, *lg = nf + T, *cn = lg + 4 * cap;
+    const jsorb_keyframe_graph g = graph.view();
+    const jsorb_map_point_table t = table.view();
+    const jsorb_keyframe_keypoints k = kp.view();
+    result.best_idx.assign(pairs, -1); result.best_dist.assign(pairs, -1); result.replace_point.assign(pairs, -1); result.n_fused.assign(T, 0);
+    std::vector<int32_t> log(4 * cap, -1);
+    const int rc = jsorb_fuse_map(matcher.handle(), &prm, replace_loop ? 1 : 0, &g, &t, &k, &state.view(), (int)n, dl.p, (int)T, targets.data(), poses.Rcw,
+                                  poses.tcw, poses.Ow, bi, bd, rp, nf, (int)cap, lg, cn, result.best_idx.data(), result.best_dist.data(),
+                                  result.replace_point.data(), result.n_fused.data(), log.data(), result.counts);
+    if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_fuse_map: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    result.events.clear();
+    for (size_t i = 0; i < cap && log[4 * i] >= 0; i++) result.events.push_back({log[4 * i], log[4 * i + 1], log[4 * i + 2], log[4 * i + 3]});
+    return result.counts[0];
+}
+
 // LocalMapping::KeyFrameCulling (LocalMapping.cpp:638-702) for the current keyframe, with the whole of SetBadFlag (KeyFrame.cpp:457-549) for every
 // keyframe it culls, on the matcher's stream: the candidates are the current keyframe's ordered list read on the device, and the call is repeated
 // past its 4 culls until the list is done.  first_slot: the slot of keyframe 0 (-1: none).  What stays with the binding afterwards: the child

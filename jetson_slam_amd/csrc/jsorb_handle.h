@@ -335,7 +335,7 @@ struct jsorb_keyframe_matcher {
     // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all;
     // scw: the count, then match_kp, match_dist and kp_match, out_cap in all
     // distinct: best_obs, then best_median, out_cap entries each
-    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, COVIS, CULL, N_CALLS };
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, COVIS, CULL, FUSE_MAP, N_CALLS };
     KfCall call[N_CALLS];
     int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
@@ -362,6 +362,12 @@ struct jsorb_keyframe_matcher {
         int32_t *out = nullptr;                                 // the synchronous form's outputs gathered for one copy back
         long long out_words = 0;
     } cull;
+    struct {                                                    // jsorb_fuse_map* (jsorb_fuse_apply.hip), grown only
+        int32_t *buf = nullptr;                                 // the observation index, the stamps, the target's grid, list points and CSR (FuseMapArgs)
+        long long words = 0;
+        int32_t *out = nullptr;                                 // the synchronous form's outputs gathered for one copy back
+        long long out_words = 0;
+    } fmap;
     std::string err;
 };
 

@@ -297,6 +297,44 @@ struct FusePose {
 };
 void launch_fuse_grids(const FuseGridArgs &g, int n_kf, hipStream_t s);
 void launch_fuse_match(const FuseArgs &a, const FusePose &g, hipStream_t s);
+// k_fuse_match_run (k_fuse.hip): k_fuse_match over one keyframe of a jsorb_keyframe_graph, its run read on the device
+struct FuseRun {
+    int row, slot;                               // the row of best_idx / best_dist (the target's number), the target's slot
+    int n_slots, pool_entries;
+    const uint8_t *state;                        // the graph's arrays
+    const int32_t *point_off, *point_len;
+    float pose[15];                              // Rcw row-major, tcw, Ow
+};
+void launch_fuse_match_run(const FuseArgs &a, const FuseRun &r, hipStream_t s);
+// k_fa_* (k_fuse_apply.hip): ORBmatcher::Fuse with its map mutations over the device state (jsorb_fuse_map_async)
+#define FM_COUNTS 10
+struct FuseMapArgs {
+    jsorb_keyframe_graph g;
+    jsorb_keyframe_keypoints kp;
+    jsorb_fuse_state st;
+    jsorb_fuse_params p;
+    int n_rows;
+    const float *tab[9];                         // the table's Px .. invariance_minDistance in FuseArgs' order (Px Py Pz Nx Ny Nz max_distance min_dist_inv max_dist_inv)
+    int n_list, n_targets, sim3, replace_loop, log_cap;
+    const int32_t *list_row;
+    // the observation index: the lists threaded through the pool (cleared per call: head and ent_slot to -1)
+    int32_t *head, *next, *ent_slot;             // [n_rows] first entry of the row's list, [pool] the next one, [pool] the slot whose run holds the entry
+    int32_t *mark, *snap, *slot_mark;            // stamps (cleared to 0 per call): [n_rows] Replace target in target t (t + 1), [n_rows] in vpMatched's set of
+                                                 // target t (t + 1), [S] the survivor observes this slot (the Replace's number)
+    int32_t *grid_start, *grid_items;            // the target's grid: cells + 1 starts, its run's items
+    float *gf;                                   // [9][n_list] the list points' floats for k_fuse_match_run
+    uint8_t *gdesc, *skip;                       // [n_list][32], [n_list]
+    int32_t *marked, *obs_start, *out_row, *csr_ent;     // the target's Replace targets, their observations as a CSR ([n_list + 1], [pool]) for k_distinct
+    int32_t *ctl;                                // 0 Replace calls so far, 1 marked rows of this target
+    int32_t *ds;                                 // k_distinct's statistics words of this call
+    int32_t *best_idx, *replace_point, *n_fused, *log_out, *counts_dev;
+    int *stats;                                  // FM_COUNTS words (cleared to 0)
+};
+int fuse_map_list_chunk();                       // the compile-time cap of k_fuse_apply.hip (jsorb_fuse_map_build_caps)
+void launch_fuse_map_index(const FuseMapArgs &a, hipStream_t s);
+void launch_fuse_map_head(const FuseMapArgs &a, int t, int slot, hipStream_t s);      // the snapshot, the grid, the head tests and the gather
+void launch_fuse_map_apply(const FuseMapArgs &a, int t, int slot, hipStream_t s);     // the walk, the Replace loop, the CSR of the marked rows
+void launch_fuse_map_finish(const FuseMapArgs &a, hipStream_t s);
 // k_loop_bow_match (k_loop.hip): ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) for several candidates KF2 of LoopClosing::ComputeSim3; the grouping
 // is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over the same rows
 struct LoopBowArgs {

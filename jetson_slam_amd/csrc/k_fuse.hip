@@ -11,6 +11,7 @@
 //               window_best - walk_window<true> dealt over the lanes, the minimum of distance << 18 | CSR position - with the chi-square test
 //               as the per-keypoint filter, block_totals for the counts and statistics (one atomic per workgroup and word).  No candidate list, no cap; the
 //               per-keyframe pose comes in the launch arguments, FUSE_KF_CHUNK keyframes per launch.
+// k_fuse_match_run  the same body over one keyframe whose run is read from the graph on the device (jsorb_fuse_map_async, k_fuse_apply.hip).
 // Items 3 and 8 of the contract (ur and the chi-square sums) are written with __fmul_rn / __fadd_rn / __fsub_rn: every product and sum rounded on
 // its own, whatever the contraction setting of the build.
 // The contract (include/jsorb.h, jsorb_fuse_async) is restated in numpy in tests/test_fuse_host.py.
@@ -46,23 +47,24 @@ __device__ __forceinline__ bool fuse_point(const FuseArgs &a, const float *T, in
     return proj_cells(p, a.max_distance[i], dist, w);                                             // :877
 }
 
-__global__ __launch_bounds__(256) void k_fuse_match(FuseArgs a, FusePose g)
+// one (keyframe, point) per SL_LANES lanes.  kf: the keyframe's row of the outputs, of `skip` and of n_matched; grid: its CSR among cell_start's;
+// off, len: its run of the concatenated keyframe arrays; T: its pose
+__device__ __forceinline__ void fuse_match_body(const FuseArgs &a, const float *T, int kf, int grid, int off, int len)
 {
-    const int lane = threadIdx.x % SL_LANES, slot = blockIdx.y, kf = g.kf0 + slot;
+    const int lane = threadIdx.x % SL_LANES;
     const int i = blockIdx.x * (256 / SL_LANES) + threadIdx.x / SL_LANES;
-    const int off = g.start[slot], len = g.start[slot + 1] - off;
     const bool in_range = i < a.n_points;
     const size_t o = (size_t)kf * a.n_points + (in_range ? i : 0);
     // every lane stays to the end (the reductions below take whole waves and the workgroup meets at a barrier)
     const bool live = in_range && len > 0 && !(a.skip && a.skip[o]);
     ProjWindow w;
     float ur;
-    const bool win = live && fuse_point(a, g.pose[slot], i, w, ur);      // uniform across the lanes of a point
+    const bool win = live && fuse_point(a, T, i, w, ur);                 // uniform across the lanes of a point
     const jsorb_fuse_params &p = a.p;
     const float *uright = a.uright ? a.uright + off : nullptr;
     int sum[4] = {0, win && lane == 0 ? 1 : 0, 0, 0}, window;             // matched, pairs with a window, keypoints walked, distances
     const unsigned key = window_best(
-        win, w, a.cell_start + (size_t)kf * (p.cols * p.rows + 1), p.rows, a.cell_items + off, a.x + off, a.y + off, a.octave + off,
+        win, w, a.cell_start + (size_t)grid * (p.cols * p.rows + 1), p.rows, a.cell_items + off, a.x + off, a.y + off, a.octave + off,
         a.kf_desc + 32 * (size_t)off, a.mp_desc + 32 * (size_t)i,
         [&](int k, float kx, float ky, int oct) {                                        // :898 left the level; the chi-square test
             if ((unsigned)oct >= (unsigned)p.n_levels) return false;                     // defined here: never a candidate
@@ -98,6 +100,24 @@ __global__ __launch_bounds__(256) void k_fuse_match(FuseArgs a, FusePose g)
     }
 }
 
+__global__ __launch_bounds__(256) void k_fuse_match(FuseArgs a, FusePose g)
+{
+    const int slot = blockIdx.y, kf = g.kf0 + slot;
+    fuse_match_body(a, g.pose[slot], kf, kf, g.start[slot], g.start[slot + 1] - g.start[slot]);
+}
+
+// the same over ONE keyframe whose run is read on the device (jsorb_fuse_map_async): the keyframe arrays are the whole pool, the run that of slot
+// r.slot where the slot is a live target (fuse_target_run), the output row r.row of best_idx / best_dist, `skip` and the grid the target's own
+__global__ __launch_bounds__(256) void k_fuse_match_run(FuseArgs a, FuseRun r)
+{
+    int off, len;
+    fuse_target_run(r.state, r.point_off, r.point_len, r.n_slots, r.pool_entries, r.slot, off, len);
+    a.best_idx += (size_t)r.row * a.n_points;
+    a.best_dist += (size_t)r.row * a.n_points;
+    a.n_matched += r.row;
+    fuse_match_body(a, r.pose, 0, 0, off, len);
+}
+
 void launch_fuse_grids(const FuseGridArgs &g, int n_kf, hipStream_t s)
 {
     if (n_kf <= 0) return;
@@ -110,6 +130,13 @@ void launch_fuse_match(const FuseArgs &a, const FusePose &g, hipStream_t s)
     if (a.n_points <= 0 || g.n <= 0) return;
     const int per_block = 256 / SL_LANES;
     hipLaunchKernelGGL(k_fuse_match, dim3((a.n_points + per_block - 1) / per_block, g.n), dim3(256), 0, s, a, g);
+}
+
+void launch_fuse_match_run(const FuseArgs &a, const FuseRun &r, hipStream_t s)
+{
+    if (a.n_points <= 0) return;
+    const int per_block = 256 / SL_LANES;
+    hipLaunchKernelGGL(k_fuse_match_run, dim3((a.n_points + per_block - 1) / per_block), dim3(256), 0, s, a, r);
 }
 
 } // namespace jsorb

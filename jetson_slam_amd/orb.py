@@ -82,6 +82,7 @@ EXPORTS = [
     "jsorb_connected_mask_async", "jsorb_best_covisibles_async", "jsorb_covisibility_copy", "jsorb_covisibility_build_caps",
     "jsorb_update_connections_scratch",
     "jsorb_cull_keyframes_async", "jsorb_cull_keyframes", "jsorb_cull_keyframes_stats", "jsorb_cull_keyframes_build_caps",
+    "jsorb_fuse_map_async", "jsorb_fuse_map", "jsorb_fuse_map_stats", "jsorb_fuse_map_build_caps",
 ]
 
 
@@ -639,6 +640,87 @@ def culling_state(graph, table, not_erase=None, to_be_erased=None, ref_slot=None
                              p(not_erase), p(to_be_erased), p(ref_slot))
 
 
+class JsorbKeyframeKeypoints(C.Structure):
+    _fields_ = [("pool_entries", C.c_int)] + [(k, C.c_void_p) for k in ("x", "y", "octave", "uright", "desc")]
+
+
+class JsorbFuseState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("point_pool", "registered", "bad", "desc", "replaced", "visible", "found")]
+
+
+FUSE_MAP_COUNTS = ("n_fused", "n_replace", "n_add", "n_bad_in_slot", "n_rows_bad", "n_descriptors_changed", "n_skipped_targets", "n_dropped", "n_log",
+                   "log_overflow")
+FUSE_MAP_OUTPUTS = ("best_idx", "best_dist", "replace_point", "n_fused", "log", "counts")
+EV_REPLACE, EV_ADD_MAP_POINT = 2, 3              # the codes of fuse_map's log records: (2, p, q, -1), (3, row, slot, keypoint)
+
+
+class KeyframeKeypoints:
+    """What ORBmatcher::Fuse reads of the keyframes' keypoints (jsorb_keyframe_keypoints): torch device arrays parallel to a KeyframeGraph's
+    point_pool - x, y float32 (mvKeysUn), octave int32, uright float32 (mvuRight; None for a monocular map), desc uint8[., 32]."""
+    ARRAYS = ("x", "y", "octave", "uright", "desc")
+
+    def __init__(self, graph, stereo=True):
+        import torch
+        dev = graph.point_pool.device
+        self.pool_entries = graph.pool_entries
+        n = max(self.pool_entries, 1)
+        self.x = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.y = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.octave = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.uright = torch.full((n,), -1.0, dtype=torch.float32, device=dev) if stereo else None
+        self.desc = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+
+    def struct(self):
+        return JsorbKeyframeKeypoints(self.pool_entries, self.x.data_ptr(), self.y.data_ptr(), self.octave.data_ptr(),
+                                      None if self.uright is None else self.uright.data_ptr(), self.desc.data_ptr())
+
+    def load(self, **arrays):
+        """whole arrays at once (numpy): x, y, octave, uright, desc"""
+        import torch
+        for k, v in arrays.items():
+            t = getattr(self, k, None) if k in self.ARRAYS else None
+            if t is None:
+                raise JsorbError("KeyframeKeypoints.load: no array %s" % k)
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(t.device)
+            if v.dtype != t.dtype or v.numel() > t.numel():
+                raise JsorbError("KeyframeKeypoints.load: %s must be %s with at most %d entries" % (k, t.dtype, t.numel()))
+            t.view(-1)[:v.numel()].copy_(v.view(-1))
+
+    def set_keyframe(self, graph, slot, x, y, octave, desc, uright=None):
+        """the keypoints of the keyframe in `slot`, written at its run (after graph.set_keyframe): one entry per entry of the run"""
+        import torch
+        slot = graph._slot(slot)
+        at, n = int(graph.point_off[slot]), int(graph.point_len[slot])
+        for name, v, dt in (("x", x, np.float32), ("y", y, np.float32), ("octave", octave, np.int32), ("uright", uright, np.float32), ("desc", desc, np.uint8)):
+            t = getattr(self, name)
+            if t is None or v is None:
+                if name != "uright" or (t is None and v is not None):
+                    raise JsorbError("KeyframeKeypoints.set_keyframe: %s is missing" % name)
+                v = np.full(n, -1.0, np.float32)     # (a monocular keyframe in a stereo map)
+                if t is None:
+                    continue
+            v = np.ascontiguousarray(v, dt).reshape((n, 32) if name == "desc" else (-1,))
+            if len(v) != n:
+                raise JsorbError("KeyframeKeypoints.set_keyframe: %s must have the run's %d entries" % (name, n))
+            if n:
+                t[at:at + n] = torch.from_numpy(v).to(t.device)
+
+
+def fuse_state(graph, table, replaced=None, visible=None, found=None):
+    """jsorb_fuse_state: the graph's point_pool / registered and the table's bad / desc as the writable pointers jsorb_fuse_map takes, with
+    replaced, visible, found int32[n_rows] device tensors (or None; visible and found both or neither).  The caller keeps the tensors alive."""
+    import torch
+    if graph.registered is None:
+        raise JsorbError("fuse_state: the graph has no registered bytes (the call writes them)")
+    for name, t in (("replaced", replaced), ("visible", visible), ("found", found)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < table.n_rows):
+            raise JsorbError("fuse_state: %s must be a contiguous int32 device tensor of at least %d entries" % (name, table.n_rows))
+    if (visible is None) != (found is None):
+        raise JsorbError("fuse_state: visible and found go together")
+    p = lambda t: None if t is None else t.data_ptr()
+    return JsorbFuseState(graph.point_pool.data_ptr(), graph.registered.data_ptr(), table.bad.data_ptr(), table.desc.data_ptr(), p(replaced), p(visible), p(found))
+
+
 def make_camera(K, D):
     """jsorb_camera from Tracking's mK (3x3) and mDistCoef (k1, k2, p1, p2[, k3]) - both taken as float32, as the reference stores them (Tracking.cpp:80-91)"""
     K = np.asarray(K, np.float32)
@@ -855,6 +937,12 @@ def load_library(path=None):
                                      C.POINTER(JsorbKeyframeViews), C.POINTER(JsorbCullingState), I, I, I, P, I, P, I] + [P] * 12),
         "jsorb_cull_keyframes_stats": (I, [P, P]),
         "jsorb_cull_keyframes_build_caps": (I, [C.POINTER(I)] * 2),
+        "jsorb_fuse_map_async": (I, [P, C.POINTER(JsorbFuseParams), I, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable),
+                                     C.POINTER(JsorbKeyframeKeypoints), C.POINTER(JsorbFuseState), I, P, I] + [P] * 8 + [I, P, P]),
+        "jsorb_fuse_map": (I, [P, C.POINTER(JsorbFuseParams), I, C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable),
+                               C.POINTER(JsorbKeyframeKeypoints), C.POINTER(JsorbFuseState), I, P, I] + [P] * 8 + [I, P, P] + [P] * 6),
+        "jsorb_fuse_map_stats": (I, [P, P]),
+        "jsorb_fuse_map_build_caps": (I, [C.POINTER(I)]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1596,6 +1684,79 @@ class KeyframeMatcher:
         v = np.zeros(10, np.int32)
         self._chk(self._lib.jsorb_cull_keyframes_stats(self._m, v.ctypes.data))
         return dict(zip(CULL_COUNTS, (int(x) for x in v)))
+
+    # ---- Fuse applied to the map: ORBmatcher::Fuse with MapPoint::Replace / AddObservation (ORBmatcher.cpp:812-1087, MapPoint.cpp:208-246) ----
+    def fuse_map(self, params, graph, table, kp, state, list_row, target_slots, Rcw, tcw, Ow, replace_loop=False, log_cap=None, sync=False, wait=True,
+                 out=None):
+        """jsorb_fuse_map*: Fuse with its map mutations of the points `list_row` (an int32 device tensor of table rows, -1 = NULL, or a host
+        sequence that is uploaded) into the keyframes `target_slots` (HOST sequence of slots, at most 256) one after the other, on the device state:
+        graph a KeyframeGraph, table a MapPointTable, kp a KeyframeKeypoints, state a fuse_state(graph, table, ...).  params from make_fuse_params:
+        check_reprojection picks the overload (False: the one with Scw, whose Replace loop runs with replace_loop=True); Rcw host float32[T, 9]
+        row-major, tcw and Ow host float32[T, 3].  log_cap: records the log holds (default T x n).  Returns a dict of device tensors: best_idx,
+        best_dist, replace_point int32[T, n], n_fused int32[T], log int32[log_cap, 4] (-1 padded: (EV_REPLACE, p, q, -1) and (EV_ADD_MAP_POINT,
+        row, slot, keypoint) in the order they were made), counts int32[10] (FUSE_MAP_COUNTS); with sync=True the same as numpy arrays under
+        *_host.  out: the dict of an earlier call with the same sizes, written again.  The call waits for the current torch stream before it
+        enqueues, except with wait=False, out given and list_row a device tensor: then it makes no tensor, waits for nothing and only enqueues -
+        the form a graph capture takes (the targets and their poses are host values: a replay runs the captured ones)."""
+        import torch
+        what = "fuse_map"
+        if not isinstance(params, JsorbFuseParams):
+            raise JsorbError("%s: params must come from make_fuse_params" % what)
+        dev = graph.point_pool.device
+        made = not torch.is_tensor(list_row)
+        if made:
+            list_row = torch.tensor([int(x) for x in list_row], dtype=torch.int32, device=dev)
+        list_row = list_row.reshape(-1)
+        n = int(list_row.numel())
+        lp = self._i32("%s: list_row" % what, list_row) if n else None
+        ts = np.ascontiguousarray(target_slots, np.int32).reshape(-1)
+        T = len(ts)
+        R, t, O = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (Rcw, tcw, Ow))
+        if len(R) != 9 * T or len(t) != 3 * T or len(O) != 3 * T:
+            raise JsorbError("%s: Rcw must hold 9, tcw 3 and Ow 3 floats per target" % what)
+        cap = max(T * n, 1) if log_cap is None else int(log_cap)
+        new = lambda *shape: torch.empty([max(int(x), 1) for x in shape], dtype=torch.int32, device=dev)
+        made = made or out is None
+        bufs = out["_bufs"] if out is not None else dict(best_idx=new(T, n), best_dist=new(T, n), replace_point=new(T, n), n_fused=new(T), log=new(cap, 4),
+                                                         counts=new(10))
+        shapes = dict(best_idx=(T, n), best_dist=(T, n), replace_point=(T, n), n_fused=(T,), log=(max(cap, 0), 4), counts=(10,))
+        gs, tb, ks = graph.struct(), table.struct(), kp.struct()
+        keys = FUSE_MAP_OUTPUTS
+        b = {k: bufs[k].data_ptr() for k in keys}
+        args = [self._m, C.byref(params), int(bool(replace_loop)), C.byref(gs), C.byref(tb), C.byref(ks), C.byref(state), n, lp, T, ts.ctypes.data, R.ctypes.data,
+                t.ctypes.data, O.ctypes.data, b["best_idx"], b["best_dist"], b["replace_point"], b["n_fused"], cap, b["log"], b["counts"]]
+        if wait or sync or made:
+            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
+        out = {k: bufs[k].reshape(-1)[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys}
+        out["_bufs"] = bufs
+        if sync:
+            host = {k: np.full(max(int(np.prod(shapes[k])), 1), -7, np.int32) for k in keys}
+            self._chk(self._lib.jsorb_fuse_map(*args, *[host[k].ctypes.data for k in keys]))
+            out.update({k + "_host": host[k][:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys})
+        else:
+            self._chk(self._lib.jsorb_fuse_map_async(*args))
+            if wait:
+                self.sync()
+        out["list_row"] = list_row               # (kept alive with the result: the device reads it after the call returns)
+        return out
+
+    def fuse_map_host(self, params, graph, table, kp, state, list_row, target_slots, Rcw, tcw, Ow, replace_loop=False, log_cap=None):
+        """jsorb_fuse_map, the synchronous form: the same inputs, the outputs as numpy arrays (one copy back) under the keys of FUSE_MAP_OUTPUTS"""
+        out = self.fuse_map(params, graph, table, kp, state, list_row, target_slots, Rcw, tcw, Ow, replace_loop=replace_loop, log_cap=log_cap, sync=True)
+        return {k: out[k + "_host"] for k in FUSE_MAP_OUTPUTS}
+
+    def fuse_map_stats(self):
+        """dict of FUSE_MAP_COUNTS of the last fuse_map (waits for it)"""
+        v = np.zeros(10, np.int32)
+        self._chk(self._lib.jsorb_fuse_map_stats(self._m, v.ctypes.data))
+        return dict(zip(FUSE_MAP_COUNTS, (int(x) for x in v)))
+
+
+def fuse_map_build_caps():
+    """jsorb_fuse_map_build_caps of the loaded library: the entries of an observation list staged at a time"""
+    a = C.c_int()
+    load_library().jsorb_fuse_map_build_caps(C.byref(a))
+    return a.value
 
 
 def cull_keyframes_build_caps():
