@@ -681,64 +681,97 @@ private:
     jsorb_keyframe_database *d_ = nullptr;
     int max_keyframes_ = 0;
 };
+// What the device-state classes below share: the memory calls' error as an exception that names the class, and one owned device array.
+namespace detail {
+inline void check(int rc, const char *cls, const char *what)
+{
+    if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::") + cls + " " + what + ": " + jsorb_mem_last_error());
+}
+// n elements of T on the device (at least one is allocated), all zero, all `fill` or left as they come (reserve); freed with the object, not
+// copyable.  cls: the class that holds it, for the exceptions' texts.  put / get move one element and check its index against n; upload writes a
+// span the caller has checked.
+template <class T> class DeviceArray {
+public:
+    DeviceArray() = default;
+    DeviceArray(const char *cls, size_t n) { alloc(cls, n); }
+    DeviceArray(const char *cls, size_t n, T fill) { alloc(cls, n, fill); }
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    ~DeviceArray() { jsorb_mem_free_device(p_); }
+    void reserve(const char *cls, size_t n)      // contents undefined (again: what it held before is freed)
+    {
+        jsorb_mem_free_device(p_);
+        p_ = nullptr; cls_ = cls; n_ = n;
+        check(jsorb_mem_alloc_device((n ? n : 1) * sizeof(T), (void **)&p_), cls_, "alloc");
+    }
+    void alloc(const char *cls, size_t n)
+    {
+        reserve(cls, n);
+        check(jsorb_mem_set_zero(p_, (n ? n : 1) * sizeof(T)), cls_, "clear");
+    }
+    void alloc(const char *cls, size_t n, T fill)
+    {
+        reserve(cls, n);
+        const std::vector<T> h(n ? n : 1, fill);
+        upload(0, h.data(), h.size());
+    }
+    T *ptr() const { return p_; }      // NULL before alloc
+    size_t size() const { return n_; }
+    void upload(size_t at, const T *src, size_t n) { if (n) check(jsorb_mem_h2d(p_ + at, src, n * sizeof(T)), cls_, "upload"); }
+    void put(long long i, T v) { check(jsorb_mem_h2d(p_ + in(i), &v, sizeof(T)), cls_, "upload"); }
+    T get(long long i) const { T v = T(); check(jsorb_mem_d2h(&v, p_ + in(i), sizeof(T)), cls_, "copy back"); return v; }
+
+private:
+    size_t in(long long i) const
+    {
+        if (i < 0 || (size_t)i >= n_) throw std::runtime_error(std::string("jsorb::") + cls_ + ": index out of range");
+        return (size_t)i;
+    }
+    T *p_ = nullptr;
+    size_t n_ = 0;
+    const char *cls_ = "";
+};
+} // namespace detail
 // The map points as the device table jsorb_local_map_points reads (jsorb_map_point_table, include/jsorb.h): RAII over eleven device arrays of
 // n_rows rows.  A row is the caller's index for a MapPoint* (INTEGRATION.md), the same as the rows of ComputeDistinctiveDescriptors' table, whose
 // device array descriptors() is.  scatter() writes the rows a local BA, UpdateNormalAndDepth or SetBadFlag changed: one upload, one kernel.
 class MapPointTable {
 public:
-    explicit MapPointTable(int n_rows) : n_rows_(n_rows)
+    explicit MapPointTable(int n_rows) : n_rows_(n_rows), desc_(CLS, 32 * (size_t)(n_rows > 0 ? n_rows : 1)), bad_(CLS, n_rows > 0 ? n_rows : 0)
     {
-        const size_t n = n_rows > 0 ? (size_t)n_rows : 1;
-        for (int i = 0; i < 9; i++) check(jsorb_mem_alloc_device(n * sizeof(float), (void **)&f_[i]), "alloc");
-        check(jsorb_mem_alloc_device(n * 32, (void **)&desc_), "alloc");
-        check(jsorb_mem_alloc_device(n, (void **)&bad_), "alloc");
-        for (int i = 0; i < 9; i++) check(jsorb_mem_set_zero(f_[i], n * sizeof(float)), "zero");
-        check(jsorb_mem_set_zero(desc_, n * 32), "zero");
-        check(jsorb_mem_set_zero(bad_, n), "zero");
-    }
-    MapPointTable(const MapPointTable &) = delete;
-    MapPointTable &operator=(const MapPointTable &) = delete;
-    ~MapPointTable()
-    {
-        for (int i = 0; i < 9; i++) jsorb_mem_free_device(f_[i]);
-        jsorb_mem_free_device(desc_); jsorb_mem_free_device(bad_); jsorb_mem_free_device(rows_); jsorb_mem_free_device(rec_);
+        for (detail::DeviceArray<float> &f : f_) f.alloc(CLS, n_rows > 0 ? n_rows : 0);
     }
     int n_rows() const { return n_rows_; }
-    unsigned char *descriptors() const { return desc_; }      // n_rows x 32 bytes, DEVICE
-    jsorb_map_point_table view() const { return jsorb_map_point_table{n_rows_, f_[0], f_[1], f_[2], f_[3], f_[4], f_[5], f_[6], f_[7], f_[8], desc_, bad_}; }
+    unsigned char *descriptors() const { return desc_.ptr(); }      // n_rows x 32 bytes, DEVICE
+    jsorb_map_point_table view() const
+    {
+        return jsorb_map_point_table{n_rows_, f_[0].ptr(), f_[1].ptr(), f_[2].ptr(), f_[3].ptr(), f_[4].ptr(), f_[5].ptr(), f_[6].ptr(), f_[7].ptr(), f_[8].ptr(),
+                                     desc_.ptr(), bad_.ptr()};
+    }
     // the changed rows and their records (host); hip_stream: the stream the table's readers run on (the extractor's)
     void scatter(const std::vector<int32_t> &rows, const std::vector<jsorb_map_point_record> &records, void *hip_stream = nullptr)
     {
         const size_t n = rows.size();
         if (records.size() != n) throw std::runtime_error("MapPointTable::scatter: one record per row");
         if (n == 0) return;
-        if (n > cap_) {
-            jsorb_mem_free_device(rows_); jsorb_mem_free_device(rec_);
-            rows_ = nullptr; rec_ = nullptr; cap_ = 0;
-            check(jsorb_mem_alloc_device(n * sizeof(int32_t), (void **)&rows_), "alloc");
-            check(jsorb_mem_alloc_device(n * sizeof(jsorb_map_point_record), (void **)&rec_), "alloc");
-            cap_ = n;
-        }
-        check(jsorb_mem_h2d(rows_, rows.data(), n * sizeof(int32_t)), "upload");
-        check(jsorb_mem_h2d(rec_, records.data(), n * sizeof(jsorb_map_point_record)), "upload");
-        check(jsorb_map_points_scatter_async(hip_stream, n_rows_, f_[0], f_[1], f_[2], f_[3], f_[4], f_[5], f_[6], f_[7], f_[8], bad_, (int)n, rows_, rec_),
-              "scatter");
-        check(jsorb_mem_stream_sync(hip_stream), "sync");      // (the staging arrays are reused by the next scatter)
+        if (n > rows_.size()) { rows_.reserve(CLS, n); rec_.reserve(CLS, n); }
+        rows_.upload(0, rows.data(), n);
+        rec_.upload(0, records.data(), n);
+        detail::check(jsorb_map_points_scatter_async(hip_stream, n_rows_, f_[0].ptr(), f_[1].ptr(), f_[2].ptr(), f_[3].ptr(), f_[4].ptr(), f_[5].ptr(), f_[6].ptr(),
+                                                     f_[7].ptr(), f_[8].ptr(), bad_.ptr(), (int)n, rows_.ptr(), rec_.ptr()),
+                      CLS, "scatter");
+        detail::check(jsorb_mem_stream_sync(hip_stream), CLS, "sync");      // (the staging arrays are reused by the next scatter)
     }
     // n descriptor rows from the host, from row `first` on (a map whose descriptors are not picked on the device)
-    void set_descriptors(int first, int n, const unsigned char *d) { if (n > 0) check(jsorb_mem_h2d(desc_ + 32 * (size_t)first, d, 32 * (size_t)n), "upload"); }
+    void set_descriptors(int first, int n, const unsigned char *d) { if (n > 0) desc_.upload(32 * (size_t)first, d, 32 * (size_t)n); }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::MapPointTable ") + what + ": " + jsorb_mem_last_error());
-    }
+    static constexpr const char *CLS = "MapPointTable";
     int n_rows_ = 0;
-    float *f_[9] = {};
-    unsigned char *desc_ = nullptr, *bad_ = nullptr;
-    int32_t *rows_ = nullptr;
-    jsorb_map_point_record *rec_ = nullptr;
-    size_t cap_ = 0;
+    detail::DeviceArray<float> f_[9];
+    detail::DeviceArray<unsigned char> desc_, bad_;
+    detail::DeviceArray<int32_t> rows_;
+    detail::DeviceArray<jsorb_map_point_record> rec_;
 };
 // What UpdateLocalPoints leaves on the device for SearchLocalPoints: `capacity` slots, the map points inside the frustum first, in the order of
 // mvpLocalMapPoints; point_row[i] (host) is the table row of slot i, -1 behind the last; counts as jsorb_local_map_points defines them.
@@ -755,21 +788,17 @@ struct LocalMapPoints {
 // map (INTEGRATION.md lists which event rewrites which array); each setter is one small upload.  Runs are handed out from the pools front to
 // back and rewritten in place while they fit; a full pool throws.
 class KeyframeGraph {
+    using Ints = detail::DeviceArray<int32_t>;
+    using Bytes = detail::DeviceArray<unsigned char>;
+
 public:
     enum { ABSENT = 0, GOOD = 1, BAD = 2 };
-    KeyframeGraph(int max_keyframes, int pool_entries, int child_entries) : S_(max_keyframes), pool_(pool_entries), child_(child_entries)
+    KeyframeGraph(int max_keyframes, int pool_entries, int child_entries)
+        : S_(max_keyframes), pool_(pool_entries), child_(child_entries), state_(CLS, slots()), registered_(CLS, entries(pool_), 1), key_(CLS, slots()),
+          point_off_(CLS, slots()), point_len_(CLS, slots()), point_pool_(CLS, entries(pool_), -1), neighbours_(CLS, 10 * slots(), -1), child_off_(CLS, slots()),
+          child_len_(CLS, slots()), child_pool_(CLS, entries(child_), -1), parent_(CLS, slots(), -1)
     {
-        const size_t s = S_ > 0 ? S_ : 1, p = pool_ > 0 ? pool_ : 1, c = child_ > 0 ? child_ : 1;
-        alloc(state_, s, 0); alloc(key_, s, 0); alloc(point_off_, s, 0); alloc(point_len_, s, 0); alloc(point_pool_, p, -1); alloc(registered_, p, 1);
-        alloc(neighbours_, 10 * s, -1); alloc(child_off_, s, 0); alloc(child_len_, s, 0); alloc(child_pool_, c, -1); alloc(parent_, s, -1);
-        point_run_.assign(s, {0, -1}); child_run_.assign(s, {0, -1}); point_n_.assign(s, 0);
-    }
-    KeyframeGraph(const KeyframeGraph &) = delete;
-    KeyframeGraph &operator=(const KeyframeGraph &) = delete;
-    ~KeyframeGraph()
-    {
-        void *const all[11] = {state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_, child_pool_, parent_};
-        for (void *p : all) jsorb_mem_free_device(p);
+        point_run_.assign(slots(), {0, -1}); child_run_.assign(slots(), {0, -1}); point_n_.assign(slots(), 0);
     }
     int max_keyframes() const { return S_; }
     int pool_entries() const { return pool_; }
@@ -777,8 +806,8 @@ public:
     int point_length(int slot) const { return point_n_[in(slot)]; }                // the entries of the slot's run (set_keyframe; 0 after erase)
     jsorb_keyframe_graph view() const
     {
-        return jsorb_keyframe_graph{S_, pool_, child_, state_, key_, point_off_, point_len_, point_pool_, registered_, neighbours_, child_off_, child_len_,
-                                    child_pool_, parent_};
+        return jsorb_keyframe_graph{S_, pool_, child_, state_.ptr(), key_.ptr(), point_off_.ptr(), point_len_.ptr(), point_pool_.ptr(), registered_.ptr(),
+                                    neighbours_.ptr(), child_off_.ptr(), child_len_.ptr(), child_pool_.ptr(), parent_.ptr()};
     }
     // GetMapPointMatches() as table rows (-1 = NULL), (intptr_t)pKF, the state, and per entry whether the point holds the keyframe in mObservations
     void set_keyframe(int slot, const std::vector<int32_t> &rows, int64_t key, int state = GOOD, const std::vector<unsigned char> *registered = nullptr)
@@ -789,44 +818,36 @@ public:
             std::vector<unsigned char> ones;
             if (!registered) { ones.assign(rows.size(), 1); registered = &ones; }
             if (registered->size() != rows.size()) throw std::runtime_error("KeyframeGraph::set_keyframe: one registered byte per row");
-            check(jsorb_mem_h2d(registered_ + at, registered->data(), rows.size()), "upload");
+            registered_.upload(at, registered->data(), rows.size());
         }
-        put(key_, slot, key);
+        key_.put(slot, key);
         set_state(slot, state);
     }
-    void set_state(int slot, int state) { put(state_, in(slot), (unsigned char)state); }
+    void set_state(int slot, int state) { state_.put(in(slot), (unsigned char)state); }
     void set_neighbours(int slot, const std::vector<int32_t> &slots)      // GetBestCovisibilityKeyFrames(10), in its order
     {
         int32_t row[10];
         for (int i = 0; i < 10; i++) row[i] = i < (int)slots.size() ? slots[i] : -1;
-        check(jsorb_mem_h2d(neighbours_ + 10 * (size_t)in(slot), row, sizeof(row)), "upload");
+        neighbours_.upload(10 * (size_t)in(slot), row, 10);
     }
     void set_children(int slot, const std::vector<int32_t> &slots) { write_run(slot, slots, child_run_, child_used_, child_, child_pool_, child_off_, child_len_); }      // GetChilds(), std::set's order
-    void set_parent(int slot, int parent) { put(parent_, in(slot), (int32_t)parent); }
+    void set_parent(int slot, int parent) { parent_.put(in(slot), parent); }
     void erase(int slot)
     {
-        set_state(slot, ABSENT); put(point_len_, slot, (int32_t)0); put(child_len_, slot, (int32_t)0); set_parent(slot, -1); set_neighbours(slot, {});
+        set_state(slot, ABSENT); point_len_.put(slot, 0); child_len_.put(slot, 0); set_parent(slot, -1); set_neighbours(slot, {});
         point_n_[slot] = 0;
     }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeGraph ") + what + ": " + jsorb_mem_last_error());
-    }
-    template <class T> static void alloc(T *&p, size_t n, int fill)
-    {
-        check(jsorb_mem_alloc_device(n * sizeof(T), (void **)&p), "alloc");
-        const std::vector<T> h(n, (T)fill);
-        check(jsorb_mem_h2d(p, h.data(), n * sizeof(T)), "upload");
-    }
-    template <class T> static void put(T *p, int i, T v) { check(jsorb_mem_h2d(p + i, &v, sizeof(T)), "upload"); }
-    int in(int slot) const
+    static constexpr const char *CLS = "KeyframeGraph";
+    size_t slots() const { return S_ > 0 ? S_ : 1; }      // (the host vectors and the per-slot arrays have at least one entry)
+    static size_t entries(int n) { return n > 0 ? n : 1; }
+    int in(int slot) const      // (it also guards the host vectors, so it stays the class's own)
     {
         if (slot < 0 || slot >= S_) throw std::runtime_error("jsorb::KeyframeGraph: slot outside [0, max_keyframes)");
         return slot;
     }
-    int write_run(int slot, const std::vector<int32_t> &v, std::vector<std::pair<int, int>> &runs, int &used, int total, int32_t *pool, int32_t *off, int32_t *len)
+    int write_run(int slot, const std::vector<int32_t> &v, std::vector<std::pair<int, int>> &runs, int &used, int total, Ints &pool, Ints &off, Ints &len)
     {
         std::pair<int, int> &r = runs[in(slot)];       // (offset, entries reserved)
         const int n = (int)v.size();
@@ -835,15 +856,14 @@ private:
             r = {used, n};
             used += n;
         }
-        if (n) check(jsorb_mem_h2d(pool + r.first, v.data(), (size_t)n * sizeof(int32_t)), "upload");
-        put(off, slot, (int32_t)r.first); put(len, slot, (int32_t)n);
+        pool.upload(r.first, v.data(), n);
+        off.put(slot, r.first); len.put(slot, n);
         return r.first;
     }
     int S_ = 0, pool_ = 0, child_ = 0, point_used_ = 0, child_used_ = 0;
-    unsigned char *state_ = nullptr, *registered_ = nullptr;
-    int64_t *key_ = nullptr;
-    int32_t *point_off_ = nullptr, *point_len_ = nullptr, *point_pool_ = nullptr, *neighbours_ = nullptr, *child_off_ = nullptr, *child_len_ = nullptr,
-            *child_pool_ = nullptr, *parent_ = nullptr;
+    Bytes state_, registered_;
+    detail::DeviceArray<int64_t> key_;
+    Ints point_off_, point_len_, point_pool_, neighbours_, child_off_, child_len_, child_pool_, parent_;
     std::vector<std::pair<int, int>> point_run_, child_run_;
     std::vector<int> point_n_;
 };
@@ -874,19 +894,10 @@ public:
         int lo = 0, hi = 0;
         jsorb_covisibility_build_caps(&lo, &hi);
         if (C_ < lo || C_ > hi) throw std::runtime_error("jsorb::Covisibility: conn_capacity outside the library's bounds");
-        const size_t s = S_ > 0 ? S_ : 1;
-        int32_t **const arr[6] = {&v_.conn_len, &v_.conn_slot, &v_.conn_weight, &v_.ord_len, &v_.ord_slot, &v_.ord_weight};
-        const size_t n[6] = {s, s * C_, s * C_, s, s * C_, s * C_};
-        for (int i = 0; i < 6; i++) zeros((void **)arr[i], n[i] * sizeof(int32_t));
-        zeros((void **)&v_.first_connection, s);
-        v_.max_keyframes = S_; v_.conn_capacity = C_;
-    }
-    Covisibility(const Covisibility &) = delete;
-    Covisibility &operator=(const Covisibility &) = delete;
-    ~Covisibility()
-    {
-        void *const all[7] = {v_.conn_len, v_.conn_slot, v_.conn_weight, v_.ord_len, v_.ord_slot, v_.ord_weight, v_.first_connection};
-        for (void *p : all) jsorb_mem_free_device(p);
+        const size_t s = S_ > 0 ? S_ : 0, row = s ? s * C_ : (size_t)C_;      // (an empty graph still has one slot's arrays)
+        conn_len_.alloc(CLS, s); ord_len_.alloc(CLS, s); first_.alloc(CLS, s);
+        conn_slot_.alloc(CLS, row); conn_weight_.alloc(CLS, row); ord_slot_.alloc(CLS, row); ord_weight_.alloc(CLS, row);
+        v_ = jsorb_covisibility{S_, C_, conn_len_.ptr(), conn_slot_.ptr(), conn_weight_.ptr(), ord_len_.ptr(), ord_slot_.ptr(), ord_weight_.ptr(), first_.ptr()};
     }
     int max_keyframes() const { return S_; }
     int conn_capacity() const { return C_; }
@@ -895,11 +906,7 @@ public:
     void created(int slot, bool first_keyframe = false)
     {
         if (slot < 0 || slot >= S_) throw std::runtime_error("jsorb::Covisibility: slot outside [0, max_keyframes)");
-        const int32_t zero = 0;
-        const unsigned char first = first_keyframe ? 0 : 1;
-        check(jsorb_mem_h2d(v_.conn_len + slot, &zero, sizeof(zero)), "upload");
-        check(jsorb_mem_h2d(v_.ord_len + slot, &zero, sizeof(zero)), "upload");
-        check(jsorb_mem_h2d(v_.first_connection + slot, &first, 1), "upload");
+        conn_len_.put(slot, 0); ord_len_.put(slot, 0); first_.put(slot, first_keyframe ? 0 : 1);
     }
     // one slot on the host (it waits for the device): the map in (order_key, slot) order and the ordered lists
     struct Slot {
@@ -918,197 +925,125 @@ public:
     }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::Covisibility ") + what + ": " + jsorb_mem_last_error());
-    }
-    static void zeros(void **p, size_t bytes)
-    {
-        check(jsorb_mem_alloc_device(bytes, p), "alloc");
-        check(jsorb_mem_set_zero(*p, bytes), "clear");
-    }
+    static constexpr const char *CLS = "Covisibility";
     int S_ = 0, C_ = 0;
+    detail::DeviceArray<int32_t> conn_len_, conn_slot_, conn_weight_, ord_len_, ord_slot_, ord_weight_;
+    detail::DeviceArray<unsigned char> first_;
     jsorb_covisibility v_{};
 };
 // What KeyFrameCulling reads of the keyframes' keypoints (jsorb_keyframe_views, include/jsorb.h): device arrays parallel to the graph's
 // point_pool - mvKeysUn[i].octave, mvuRight[i] >= 0, mvDepth[i] (none for a monocular map) - and mThDepth per slot.
 class KeyframeViews {
 public:
-    KeyframeViews(const KeyframeGraph &graph, bool with_depth) : pool_(graph.pool_entries()), S_(graph.max_keyframes())
+    KeyframeViews(const KeyframeGraph &graph, bool with_depth)
+        : pool_(graph.pool_entries()), octave_(CLS, entries()), stereo_(CLS, entries()), th_depth_(CLS, graph.max_keyframes() > 0 ? graph.max_keyframes() : 0)
     {
-        const size_t p = pool_ > 0 ? pool_ : 1, s = S_ > 0 ? S_ : 1;
-        zeros((void **)&octave_, p); zeros((void **)&stereo_, p);
-        if (with_depth) zeros((void **)&depth_, p * sizeof(float));
-        zeros((void **)&th_depth_, s * sizeof(float));
+        if (with_depth) depth_.alloc(CLS, entries());
     }
-    KeyframeViews(const KeyframeViews &) = delete;
-    KeyframeViews &operator=(const KeyframeViews &) = delete;
-    ~KeyframeViews() { jsorb_mem_free_device(octave_); jsorb_mem_free_device(stereo_); jsorb_mem_free_device(depth_); jsorb_mem_free_device(th_depth_); }
-    jsorb_keyframe_views view() const { return jsorb_keyframe_views{pool_, octave_, stereo_, depth_, th_depth_}; }
+    jsorb_keyframe_views view() const { return jsorb_keyframe_views{pool_, octave_.ptr(), stereo_.ptr(), depth_.ptr(), th_depth_.ptr()}; }
     // the keyframe in `slot`, one entry per entry of its run (after graph.set_keyframe); depth may be NULL for a monocular map
     void set_keyframe_views(const KeyframeGraph &graph, int slot, const std::vector<unsigned char> &octave, const std::vector<unsigned char> &stereo,
                             const std::vector<float> *depth, float th_depth)
     {
         const size_t at = (size_t)graph.point_offset(slot), n = octave.size();
-        if (stereo.size() != n || (depth && depth->size() != n) || at + n > (size_t)(pool_ > 0 ? pool_ : 0) || (depth_ && !depth))
+        if (stereo.size() != n || (depth && depth->size() != n) || at + n > entries() || (depth_.ptr() && !depth))
             throw std::runtime_error("jsorb::KeyframeViews: one octave, stereo and depth entry per entry of the run");
-        if (n) {
-            check(jsorb_mem_h2d(octave_ + at, octave.data(), n), "upload");
-            check(jsorb_mem_h2d(stereo_ + at, stereo.data(), n), "upload");
-            if (depth_) check(jsorb_mem_h2d(depth_ + at, depth->data(), n * sizeof(float)), "upload");
-        }
-        check(jsorb_mem_h2d(th_depth_ + slot, &th_depth, sizeof(float)), "upload");
+        octave_.upload(at, octave.data(), n);
+        stereo_.upload(at, stereo.data(), n);
+        if (depth_.ptr()) depth_.upload(at, depth->data(), n);
+        th_depth_.put(slot, th_depth);
     }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeViews ") + what + ": " + jsorb_mem_last_error());
-    }
-    static void zeros(void **p, size_t bytes)
-    {
-        check(jsorb_mem_alloc_device(bytes, p), "alloc");
-        check(jsorb_mem_set_zero(*p, bytes), "clear");
-    }
-    int pool_ = 0, S_ = 0;
-    unsigned char *octave_ = nullptr, *stereo_ = nullptr;
-    float *depth_ = nullptr, *th_depth_ = nullptr;
+    static constexpr const char *CLS = "KeyframeViews";
+    size_t entries() const { return pool_ > 0 ? pool_ : 0; }
+    int pool_ = 0;
+    detail::DeviceArray<unsigned char> octave_, stereo_;
+    detail::DeviceArray<float> depth_, th_depth_;
 };
 // The arrays jsorb_cull_keyframes writes (jsorb_culling_state): the graph's and the table's own arrays once more as writable pointers, and
 // mbNotErase / mbToBeErased per slot and the slot of mpRefKF per table row, which this class owns (zeros, zeros, -1).
 class CullingState {
 public:
-    CullingState(const KeyframeGraph &graph, const MapPointTable &table) : S_(graph.max_keyframes()), rows_(table.n_rows())
+    CullingState(const KeyframeGraph &graph, const MapPointTable &table)
+        : not_erase_(CLS, count(graph.max_keyframes())), to_be_erased_(CLS, count(graph.max_keyframes())), ref_slot_(CLS, count(table.n_rows()), -1)
     {
         const jsorb_keyframe_graph g = graph.view();
         const jsorb_map_point_table t = table.view();
-        const size_t s = S_ > 0 ? S_ : 1, r = rows_ > 0 ? rows_ : 1;
-        check(jsorb_mem_alloc_device(s, (void **)&not_erase_), "alloc"); check(jsorb_mem_set_zero(not_erase_, s), "clear");
-        check(jsorb_mem_alloc_device(s, (void **)&to_be_erased_), "alloc"); check(jsorb_mem_set_zero(to_be_erased_, s), "clear");
-        check(jsorb_mem_alloc_device(r * sizeof(int32_t), (void **)&ref_slot_), "alloc");
-        const std::vector<int32_t> none(r, -1);
-        check(jsorb_mem_h2d(ref_slot_, none.data(), r * sizeof(int32_t)), "upload");
         v_ = jsorb_culling_state{const_cast<uint8_t *>(g.state), const_cast<uint8_t *>(g.registered), const_cast<uint8_t *>(t.bad),
-                                 const_cast<int32_t *>(g.point_pool), const_cast<int32_t *>(g.parent), not_erase_, to_be_erased_, ref_slot_};
+                                 const_cast<int32_t *>(g.point_pool), const_cast<int32_t *>(g.parent), not_erase_.ptr(), to_be_erased_.ptr(), ref_slot_.ptr()};
     }
-    CullingState(const CullingState &) = delete;
-    CullingState &operator=(const CullingState &) = delete;
-    ~CullingState() { jsorb_mem_free_device(not_erase_); jsorb_mem_free_device(to_be_erased_); jsorb_mem_free_device(ref_slot_); }
     const jsorb_culling_state &view() const { return v_; }
-    void set_not_erase(int slot, bool on) { const unsigned char b = on; check(jsorb_mem_h2d(not_erase_ + in(slot, S_), &b, 1), "upload"); }       // SetNotErase / SetErase
-    void set_ref_slot(int row, int slot) { const int32_t v = slot; check(jsorb_mem_h2d(ref_slot_ + in(row, rows_), &v, sizeof(v)), "upload"); }   // mpRefKF
-    bool to_be_erased(int slot) const { unsigned char b = 0; check(jsorb_mem_d2h(&b, to_be_erased_ + in(slot, S_), 1), "copy back"); return b != 0; }
-    int ref_slot(int row) const { int32_t v = -1; check(jsorb_mem_d2h(&v, ref_slot_ + in(row, rows_), sizeof(v)), "copy back"); return v; }
+    void set_not_erase(int slot, bool on) { not_erase_.put(slot, on); }       // SetNotErase / SetErase
+    void set_ref_slot(int row, int slot) { ref_slot_.put(row, slot); }        // mpRefKF
+    bool to_be_erased(int slot) const { return to_be_erased_.get(slot) != 0; }
+    int ref_slot(int row) const { return ref_slot_.get(row); }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::CullingState ") + what + ": " + jsorb_mem_last_error());
-    }
-    static int in(int i, int n)
-    {
-        if (i < 0 || i >= n) throw std::runtime_error("jsorb::CullingState: index out of range");
-        return i;
-    }
-    int S_ = 0, rows_ = 0;
-    unsigned char *not_erase_ = nullptr, *to_be_erased_ = nullptr;
-    int32_t *ref_slot_ = nullptr;
+    static constexpr const char *CLS = "CullingState";
+    static size_t count(int n) { return n > 0 ? n : 0; }
+    detail::DeviceArray<unsigned char> not_erase_, to_be_erased_;
+    detail::DeviceArray<int32_t> ref_slot_;
     jsorb_culling_state v_{};
 };
 // What ORBmatcher::Fuse reads of the keyframes' keypoints (jsorb_keyframe_keypoints, include/jsorb.h): device arrays parallel to the graph's
 // point_pool - mvKeysUn (x, y, octave), mvuRight (none for a monocular map) and the descriptors.
 class KeyframeKeypoints {
 public:
-    KeyframeKeypoints(const KeyframeGraph &graph, bool stereo) : pool_(graph.pool_entries())
+    KeyframeKeypoints(const KeyframeGraph &graph, bool stereo)
+        : pool_(graph.pool_entries()), x_(CLS, entries()), y_(CLS, entries()), octave_(CLS, entries()), desc_(CLS, 32 * (entries() ? entries() : 1))
     {
-        const size_t p = pool_ > 0 ? pool_ : 1;
-        zeros((void **)&x_, p * sizeof(float)); zeros((void **)&y_, p * sizeof(float)); zeros((void **)&octave_, p * sizeof(int32_t));
-        zeros((void **)&desc_, p * 32);
-        if (stereo) {
-            zeros((void **)&uright_, p * sizeof(float));
-            const std::vector<float> none(p, -1.0f);
-            check(jsorb_mem_h2d(uright_, none.data(), p * sizeof(float)), "upload");
-        }
+        if (stereo) uright_.alloc(CLS, entries(), -1.0f);
     }
-    KeyframeKeypoints(const KeyframeKeypoints &) = delete;
-    KeyframeKeypoints &operator=(const KeyframeKeypoints &) = delete;
-    ~KeyframeKeypoints() { jsorb_mem_free_device(x_); jsorb_mem_free_device(y_); jsorb_mem_free_device(octave_); jsorb_mem_free_device(uright_); jsorb_mem_free_device(desc_); }
-    jsorb_keyframe_keypoints view() const { return jsorb_keyframe_keypoints{pool_, x_, y_, octave_, uright_, desc_}; }
+    jsorb_keyframe_keypoints view() const { return jsorb_keyframe_keypoints{pool_, x_.ptr(), y_.ptr(), octave_.ptr(), uright_.ptr(), desc_.ptr()}; }
     // the keyframe in `slot`, one entry per entry of its run (after graph.set_keyframe); uright may be NULL (a monocular keyframe); desc: 32 bytes each
     void set_keyframe(const KeyframeGraph &graph, int slot, const std::vector<float> &x, const std::vector<float> &y, const std::vector<int32_t> &octave,
                       const std::vector<float> *uright, const std::vector<unsigned char> &desc)
     {
         const size_t at = (size_t)graph.point_offset(slot), n = x.size();
         if (n != (size_t)graph.point_length(slot) || y.size() != n || octave.size() != n || desc.size() != 32 * n || (uright && uright->size() != n) ||
-            at + n > (size_t)(pool_ > 0 ? pool_ : 0) || (uright && !uright_))
+            at + n > entries() || (uright && !uright_.ptr()))
             throw std::runtime_error("jsorb::KeyframeKeypoints: one x, y, octave, uright and descriptor per entry of the run");
-        if (!n) return;
-        check(jsorb_mem_h2d(x_ + at, x.data(), n * sizeof(float)), "upload");
-        check(jsorb_mem_h2d(y_ + at, y.data(), n * sizeof(float)), "upload");
-        check(jsorb_mem_h2d(octave_ + at, octave.data(), n * sizeof(int32_t)), "upload");
-        check(jsorb_mem_h2d(desc_ + 32 * at, desc.data(), 32 * n), "upload");
-        if (uright_) {
+        x_.upload(at, x.data(), n);
+        y_.upload(at, y.data(), n);
+        octave_.upload(at, octave.data(), n);
+        desc_.upload(32 * at, desc.data(), 32 * n);
+        if (uright_.ptr()) {
             const std::vector<float> none(n, -1.0f);
-            check(jsorb_mem_h2d(uright_ + at, uright ? uright->data() : none.data(), n * sizeof(float)), "upload");
+            uright_.upload(at, uright ? uright->data() : none.data(), n);
         }
     }
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::KeyframeKeypoints ") + what + ": " + jsorb_mem_last_error());
-    }
-    static void zeros(void **p, size_t bytes)
-    {
-        check(jsorb_mem_alloc_device(bytes, p), "alloc");
-        check(jsorb_mem_set_zero(*p, bytes), "clear");
-    }
+    static constexpr const char *CLS = "KeyframeKeypoints";
+    size_t entries() const { return pool_ > 0 ? pool_ : 0; }
     int pool_ = 0;
-    float *x_ = nullptr, *y_ = nullptr, *uright_ = nullptr;
-    int32_t *octave_ = nullptr;
-    unsigned char *desc_ = nullptr;
+    detail::DeviceArray<float> x_, y_, uright_;
+    detail::DeviceArray<int32_t> octave_;
+    detail::DeviceArray<unsigned char> desc_;
 };
 // The arrays jsorb_fuse_map writes (jsorb_fuse_state): the graph's point_pool / registered and the table's bad / desc once more as writable
 // pointers, and mpReplaced as a row (-1), mnVisible and mnFound per table row, which this class owns.
 class FuseState {
 public:
-    FuseState(const KeyframeGraph &graph, const MapPointTable &table) : rows_(table.n_rows())
+    FuseState(const KeyframeGraph &graph, const MapPointTable &table)
+        : replaced_(CLS, rows(table), -1), visible_(CLS, rows(table)), found_(CLS, rows(table))
     {
         const jsorb_keyframe_graph g = graph.view();
         const jsorb_map_point_table t = table.view();
-        const size_t r = rows_ > 0 ? rows_ : 1;
-        int32_t **own[3] = {&replaced_, &visible_, &found_};
-        for (int i = 0; i < 3; i++) {
-            check(jsorb_mem_alloc_device(r * sizeof(int32_t), (void **)own[i]), "alloc");
-            const std::vector<int32_t> fill(r, i == 0 ? -1 : 0);
-            check(jsorb_mem_h2d(*own[i], fill.data(), r * sizeof(int32_t)), "upload");
-        }
         v_ = jsorb_fuse_state{const_cast<int32_t *>(g.point_pool), const_cast<uint8_t *>(g.registered), const_cast<uint8_t *>(t.bad), const_cast<uint8_t *>(t.desc),
-                              replaced_, visible_, found_};
+                              replaced_.ptr(), visible_.ptr(), found_.ptr()};
     }
-    FuseState(const FuseState &) = delete;
-    FuseState &operator=(const FuseState &) = delete;
-    ~FuseState() { jsorb_mem_free_device(replaced_); jsorb_mem_free_device(visible_); jsorb_mem_free_device(found_); }
     const jsorb_fuse_state &view() const { return v_; }
-    int replaced(int row) const { return get(replaced_, row); }      // mpReplaced as a row, -1
-    int visible(int row) const { return get(visible_, row); }
-    int found(int row) const { return get(found_, row); }
-    void set_counters(int row, int visible, int found) { put(visible_, row, visible); put(found_, row, found); }      // mnVisible, mnFound
+    int replaced(int row) const { return replaced_.get(row); }      // mpReplaced as a row, -1
+    int visible(int row) const { return visible_.get(row); }
+    int found(int row) const { return found_.get(row); }
+    void set_counters(int row, int visible, int found) { visible_.put(row, visible); found_.put(row, found); }      // mnVisible, mnFound
 
 private:
-    static void check(int rc, const char *what)
-    {
-        if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb::FuseState ") + what + ": " + jsorb_mem_last_error());
-    }
-    int in(int row) const
-    {
-        if (row < 0 || row >= rows_) throw std::runtime_error("jsorb::FuseState: row out of range");
-        return row;
-    }
-    int get(const int32_t *p, int row) const { int32_t v = 0; check(jsorb_mem_d2h(&v, p + in(row), sizeof(v)), "copy back"); return v; }
-    void put(int32_t *p, int row, int v) { const int32_t w = v; check(jsorb_mem_h2d(p + in(row), &w, sizeof(w)), "upload"); }
-    int rows_ = 0;
-    int32_t *replaced_ = nullptr, *visible_ = nullptr, *found_ = nullptr;
+    static constexpr const char *CLS = "FuseState";
+    static size_t rows(const MapPointTable &table) { return table.n_rows() > 0 ? table.n_rows() : 0; }
+    detail::DeviceArray<int32_t> replaced_, visible_, found_;
     jsorb_fuse_state v_{};
 };
 // What FuseMap gives back: per (target, list point) the keypoint searched (-1: none) with its distance and, for the overload with Scw,
@@ -1129,13 +1064,8 @@ struct CulledKeyFrames {
 };
 // a few device words for the length of a call
 struct DeviceInts {
-    explicit DeviceInts(size_t n)
-    {
-        if (jsorb_mem_alloc_device((n ? n : 1) * sizeof(int32_t), (void **)&p) != JSORB_OK) throw std::runtime_error("jsorb::DeviceInts: alloc failed");
-    }
-    DeviceInts(const DeviceInts &) = delete;
-    DeviceInts &operator=(const DeviceInts &) = delete;
-    ~DeviceInts() { jsorb_mem_free_device(p); }
+    explicit DeviceInts(size_t n) { words.reserve("DeviceInts", n); p = words.ptr(); }
+    detail::DeviceArray<int32_t> words;
     int32_t *p = nullptr;
 };
 // What UpdateConnections gives back for its keyframes: parent[i] = the slot the binding makes mpParent of slots[i] (AddChild on it), -1 = none;

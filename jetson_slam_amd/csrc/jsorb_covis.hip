@@ -13,8 +13,7 @@ int covis_check(jsorb_keyframe_matcher *m, const char *name, const jsorb_covisib
     if (!cov) return kf_fail(m, name, "NULL cov");
     if (cov->max_keyframes < 0) return kf_fail(m, name, "max_keyframes must not be negative");
     if (cov->max_keyframes >= (1 << 24)) return kf_fail(m, name, "more than 16777215 keyframe slots");
-    if (cov->conn_capacity < covis_cap_min() || cov->conn_capacity > covis_cap_max())
-        return kf_fail(m, name, "conn_capacity outside [" + std::to_string(covis_cap_min()) + ", " + std::to_string(covis_cap_max()) + "]");
+    RCCHK(check_conn_capacity(m, name, cov->conn_capacity));
     if (cov->max_keyframes > 0 && (!cov->conn_len || !cov->conn_slot || !cov->conn_weight || !cov->ord_len || !cov->ord_slot || !cov->ord_weight ||
                                    !cov->first_connection))
         return kf_fail(m, name, "NULL covisibility array");
@@ -45,13 +44,8 @@ int jsorb_update_connections_async(jsorb_keyframe_matcher *m, const jsorb_keyfra
     hipStream_t st = m->stream;
     KfCall &c = m->call[jsorb_keyframe_matcher::COVIS];
     RCCHK(reserve_device(m, c.stats, KF_STATS * sizeof(int)));
-    // the scratch: grown only; a word is zero between calls
-    const int rows_before = m->covis.rows, rows = std::max(table->n_rows, 1), slots = std::max(S, 1);
-    RCCHK(reserve_device(m, m->covis.word, (size_t)rows * sizeof(uint32_t), &m->covis.rows, rows));
-    if (m->covis.rows != rows_before || m->covis.dirty) {
-        HIPCHK(m, hipMemsetAsync(m->covis.word, 0, (size_t)m->covis.rows * sizeof(uint32_t), st));
-        m->covis.dirty = false;
-    }
+    const int slots = std::max(S, 1);
+    RCCHK(reserve_row_words(m, m->covis.row, table->n_rows, 0, st));      // the scratch: grown only; a word is zero between calls
     RCCHK(reserve_device(m, m->covis.slot, ((size_t)4 * CV_MAX_UPDATE * slots + 4 * CV_MAX_UPDATE) * sizeof(int32_t), &m->covis.slots, slots));
     CovisArgs a{};
     a.g = g; a.cv = *cov;
@@ -61,14 +55,14 @@ int jsorb_update_connections_async(jsorb_keyframe_matcher *m, const jsorb_keyfra
     if (conn_snapshot) { a.snap_slot = conn_snapshot->slot; a.snap_weight = conn_snapshot->weight; a.snap_len = conn_snapshot->len; }
     a.counts = counts_dev;
     const size_t plane = (size_t)CV_MAX_UPDATE * m->covis.slots;
-    a.word = m->covis.word;
+    a.word = m->covis.row.word;
     a.count = m->covis.slot; a.kraw = a.count + plane; a.klist = a.kraw + plane; a.tlist = a.klist + plane; a.minfo = a.tlist + plane;
     // the planes are laid out for the slots reserved, and indexed by S <= that
     a.stats = c.stats;
-    m->covis.dirty = true;             // until all five kernels are enqueued: k_cv_reset is the one that sets the words back
+    m->covis.row.dirty = true;         // until all five kernels are enqueued: k_cv_reset is the one that sets the words back
     launch_update_connections(a, st);
     HIPCHK(m, hipGetLastError());
-    m->covis.dirty = false;
+    m->covis.row.dirty = false;
     c.done = true;
     return JSORB_OK;
 }
@@ -80,18 +74,10 @@ int jsorb_update_connections(jsorb_keyframe_matcher *m, const jsorb_keyframe_gra
     if (!m) return JSORB_ERR_INVALID;
     if (!counts_host || (parent_out && n_update > 0 && !parent_host)) return kf_fail(m, UC, "NULL host output");
     RCCHK(jsorb_update_connections_async(m, graph, table, cov, n_update, update_slot, neighbours, parent_out, conn_snapshot, counts_dev));
-    KfCall &c = m->call[jsorb_keyframe_matcher::COVIS];
-    hipStream_t st = m->stream;
-    RCCHK(reserve_device(m, c.out, (size_t)(8 + CV_MAX_UPDATE) * sizeof(int32_t), &c.out_cap, CV_MAX_UPDATE));
-    const bool par = parent_out && n_update > 0;
-    HIPCHK(m, hipMemcpyAsync(c.out, counts_dev, 8 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (par) HIPCHK(m, hipMemcpyAsync(c.out + 8, parent_out, (size_t)n_update * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    int32_t h[8 + CV_MAX_UPDATE];
-    HIPCHK(m, hipMemcpyAsync(h, c.out, (size_t)(8 + (par ? n_update : 0)) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(m, hipStreamSynchronize(st));
-    memcpy(counts_host, h, 8 * sizeof(int32_t));
-    if (par) memcpy(parent_host, h + 8, (size_t)n_update * sizeof(int32_t));
-    return JSORB_OK;
+    const int32_t *const src[2] = {counts_dev, parent_out};
+    int32_t *const dst[2] = {counts_host, parent_host};
+    const size_t n[2] = {8, parent_out ? (size_t)n_update : 0};
+    return read_back(m, m->stream, m->staging, 2, src, dst, n);
 }
 
 int jsorb_update_connections_stats(jsorb_keyframe_matcher *m, int *n_processed, int *n_skipped, int *n_empty, int *n_add_connection, int *n_resorted,
@@ -111,10 +97,10 @@ int jsorb_update_connections_scratch(jsorb_keyframe_matcher *m, int *n_words, in
     if (!m) return JSORB_ERR_INVALID;
     if (!m->call[jsorb_keyframe_matcher::COVIS].done) return kf_fail(m, UC, "update_connections_scratch before jsorb_update_connections", JSORB_ERR_STATE);
     HIPCHK(m, hipSetDevice(m->device));
-    std::vector<uint32_t> h((size_t)m->covis.rows);
-    HIPCHK(m, hipMemcpyAsync(h.data(), m->covis.word, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+    std::vector<uint32_t> h((size_t)m->covis.row.rows);
+    HIPCHK(m, hipMemcpyAsync(h.data(), m->covis.row.word, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(m, hipStreamSynchronize(m->stream));
-    if (n_words) *n_words = m->covis.rows;
+    if (n_words) *n_words = m->covis.row.rows;
     if (n_nonzero) *n_nonzero = (int)std::count_if(h.begin(), h.end(), [](uint32_t w) { return w != 0; });
     return JSORB_OK;
 }

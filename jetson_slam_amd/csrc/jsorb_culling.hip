@@ -8,6 +8,17 @@ namespace {
 
 const char *const CK = "cull_keyframes";
 
+// The scratch of one call in 32-bit words, placed into a: the order and the sizes of the pieces.  Returns the words it takes (base NULL: only that).
+long long cull_layout(CullArgs &a, int32_t *base, long long rows, long long pool, long long slots, long long cands)
+{
+    Carve c(base);
+    a.cnt = c.take(rows); a.fill = c.take(rows); a.off = c.take(rows); a.bsum = c.take((rows + KC_SCAN - 1) / KC_SCAN);
+    a.csr_slot = c.take(pool); a.csr_ent = c.take(pool); a.was_obs = c.take(pool);
+    a.pmark = c.take(slots); a.ch_raw = c.take(slots); a.ch = c.take(slots); a.ch_done = c.take(slots);
+    a.ev = c.take(3 * cands); a.ctl = c.take(8); a.erase_counts = c.take(2);
+    return c.at;
+}
+
 } // namespace
 
 extern "C" {
@@ -25,8 +36,7 @@ int jsorb_cull_keyframes_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_g
     if (S < 0 || g.pool_entries < 0 || table->n_rows < 0) return kf_fail(m, CK, "max_keyframes, pool_entries and n_rows must not be negative");
     if (S >= (1 << 24)) return kf_fail(m, CK, "more than 16777215 keyframe slots");
     if (S != cov->max_keyframes) return kf_fail(m, CK, "the graph and the covisibility state differ in max_keyframes");
-    if (cov->conn_capacity < covis_cap_min() || cov->conn_capacity > covis_cap_max())
-        return kf_fail(m, CK, "conn_capacity outside [" + std::to_string(covis_cap_min()) + ", " + std::to_string(covis_cap_max()) + "]");
+    RCCHK(check_conn_capacity(m, CK, cov->conn_capacity));
     if (S > 0 && (!cov->conn_len || !cov->conn_slot || !cov->conn_weight || !cov->ord_len || !cov->ord_slot || !cov->ord_weight))
         return kf_fail(m, CK, "NULL covisibility array");
     if (max_cull < 1 || max_cull > KC_MAX_CULL) return kf_fail(m, CK, "max_cull must be in [1, 16]");
@@ -50,24 +60,13 @@ int jsorb_cull_keyframes_async(jsorb_keyframe_matcher *m, const jsorb_keyframe_g
     KfCall &c = m->call[jsorb_keyframe_matcher::CULL];
     RCCHK(reserve_device(m, c.stats, 16 * sizeof(int)));
     const long long rows = std::max(table->n_rows, 1), slots = std::max(S, 1), pool = std::max(g.pool_entries, 1), cands = std::max(n_cand, 1);
-    const long long n_blocks = (rows + KC_SCAN - 1) / KC_SCAN;
-    const long long need = 3 * rows + n_blocks + 3 * pool + 4 * slots + 3 * cands + 8 + 2;
-    if (m->cull.words < need) {                  // grown only
-        free_device(m->cull.buf);
-        m->cull.words = 0;
-        HIPCHK(m, hipMalloc(&m->cull.buf, (size_t)need * sizeof(int32_t)));
-        m->cull.words = need;
-    }
     CullArgs a{};
+    RCCHK(reserve_words(m, m->cull, cull_layout(a, nullptr, rows, pool, slots, cands)));
+    cull_layout(a, m->cull.p, rows, pool, slots, cands);
     a.g = g; a.cv = *cov; a.v = *views; a.st = *state;
     a.n_rows = table->n_rows; a.monocular = monocular != 0; a.first_slot = first_slot; a.n_cand = n_cand; a.max_cull = max_cull; a.reparent_cap = reparent_cap;
     a.cand_slot = cand_slot; a.neighbours = neighbours;
     a.decision = decision; a.n_mps = n_mps; a.n_redundant = n_redundant; a.culled_slot = culled_slot; a.reparent_out = reparent_out; a.counts = counts_dev;
-    int32_t *p = m->cull.buf;
-    a.cnt = p; p += rows; a.fill = p; p += rows; a.off = p; p += rows; a.bsum = p; p += n_blocks;
-    a.csr_slot = p; p += pool; a.csr_ent = p; p += pool; a.was_obs = p; p += pool;
-    a.pmark = p; p += slots; a.ch_raw = p; p += slots; a.ch = p; p += slots; a.ch_done = p; p += slots;
-    a.ev = p; p += 3 * cands; a.ctl = p; p += 8; a.erase_counts = p;
     a.stats = c.stats;
     launch_cull_keyframes(a, st);
     HIPCHK(m, hipGetLastError());
@@ -87,33 +86,11 @@ int jsorb_cull_keyframes(jsorb_keyframe_matcher *m, const jsorb_keyframe_graph *
         return kf_fail(m, CK, "NULL host output");
     RCCHK(jsorb_cull_keyframes_async(m, graph, table, cov, views, state, monocular, first_slot, n_cand, cand_slot, max_cull, neighbours, reparent_cap,
                                      decision, n_mps, n_redundant, culled_slot, reparent_out, counts_dev));
-    hipStream_t st = m->stream;
     const size_t nc = (size_t)n_cand, nr = (size_t)reparent_cap * 2;
-    const long long words = (long long)(KC_COUNTS + KC_MAX_CULL + 3 * nc + nr);
-    if (m->cull.out_words < words) {
-        free_device(m->cull.out);
-        m->cull.out_words = 0;
-        HIPCHK(m, hipMalloc(&m->cull.out, (size_t)words * sizeof(int32_t)));
-        m->cull.out_words = words;
-    }
-    int32_t *o = m->cull.out;
     const int32_t *const src[6] = {counts_dev, culled_slot, decision, n_mps, n_redundant, reparent_out};
     int32_t *const dst[6] = {counts_host, culled_slot_host, decision_host, n_mps_host, n_redundant_host, reparent_host};
     const size_t n[6] = {KC_COUNTS, (size_t)max_cull, nc, nc, nc, nr};
-    size_t at = 0;
-    for (int i = 0; i < 6; i++) {
-        if (n[i]) HIPCHK(m, hipMemcpyAsync(o + at, src[i], n[i] * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        at += n[i];
-    }
-    std::vector<int32_t> h(at);
-    HIPCHK(m, hipMemcpyAsync(h.data(), o, at * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(m, hipStreamSynchronize(st));
-    at = 0;
-    for (int i = 0; i < 6; i++) {
-        if (n[i]) memcpy(dst[i], h.data() + at, n[i] * sizeof(int32_t));
-        at += n[i];
-    }
-    return JSORB_OK;
+    return read_back(m, m->stream, m->staging, 6, src, dst, n);
 }
 
 int jsorb_cull_keyframes_stats(jsorb_keyframe_matcher *m, int32_t counts[10])

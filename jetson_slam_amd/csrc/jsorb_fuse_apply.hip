@@ -8,6 +8,29 @@ namespace {
 
 const char *const FM = "fuse_map";
 
+// the pieces of the scratch that are not k_fuse_apply's own: the spans the call clears and what k_fuse_match_run and k_distinct write
+struct FuseMapScratch {
+    int32_t *minus, *zero, *rest;                // [minus, zero) is cleared to -1, [zero, rest) to 0
+    int32_t *search_stats, *n_matched;           // k_fuse_match_run's counts per target: cleared with the rest, read by nobody (n_fused is the call's count)
+    int32_t *best_obs, *best_median, *dlist;
+};
+
+// The scratch of one call in 32-bit words, placed into a and s: the list points' descriptors first (16-byte aligned), the words cleared to -1,
+// those cleared to 0, the rest.  Returns the words it takes (base NULL: only that).
+long long fuse_map_layout(FuseMapArgs &a, FuseMapScratch &s, int32_t *base, long long rows, long long slots, long long ents, long long nl, long long cells)
+{
+    Carve c(base);
+    a.gdesc = (uint8_t *)c.take(8 * nl);
+    s.minus = a.head = c.take(rows); a.ent_slot = c.take(ents);
+    s.zero = a.mark = c.take(rows); a.snap = c.take(rows); a.slot_mark = c.take(slots); a.ctl = c.take(8); a.ds = c.take(8);
+    s.search_stats = c.take(16); s.n_matched = c.take(JSORB_BOW_MAX_KEYFRAMES);
+    s.rest = a.next = c.take(ents); a.csr_ent = c.take(ents); a.grid_items = c.take(ents); a.grid_start = c.take(cells);
+    a.gf = (float *)c.take(9 * nl); a.skip = (uint8_t *)c.take((nl + 3) / 4);
+    a.marked = c.take(nl); a.obs_start = c.take(nl + 1); a.out_row = c.take(nl);
+    s.best_obs = c.take(nl); s.best_median = c.take(nl); s.dlist = c.take(3 * nl);
+    return c.at;
+}
+
 } // namespace
 
 extern "C" {
@@ -49,41 +72,21 @@ int jsorb_fuse_map_async(jsorb_keyframe_matcher *m, const jsorb_fuse_params *par
     hipStream_t st = m->stream;
     KfCall &c = m->call[jsorb_keyframe_matcher::FUSE_MAP];
     RCCHK(reserve_device(m, c.stats, 16 * sizeof(int)));
-    // the scratch, in 32-bit words: the list points' descriptors first (16-byte aligned), the words cleared to -1, those cleared to 0, the rest
     const long long rows = std::max(n_rows, 1), slots = std::max(S, 1), ents = std::max(pool, 1), nl = std::max(n_list, 1), cells = (long long)params->cols * params->rows + 1;
-    const long long need = 8 * nl + (rows + ents) + (2 * rows + slots + 32) + (3 * ents + cells + 9 * nl + (nl + 3) / 4 + 8 * nl + 2 + JSORB_BOW_MAX_KEYFRAMES);
-    if (m->fmap.words < need) {                  // grown only
-        free_device(m->fmap.buf);
-        m->fmap.words = 0;
-        HIPCHK(m, hipMalloc(&m->fmap.buf, (size_t)need * sizeof(int32_t)));
-        m->fmap.words = need;
-    }
     FuseMapArgs a{};
+    FuseMapScratch s{};
+    RCCHK(reserve_words(m, m->fmap, fuse_map_layout(a, s, nullptr, rows, slots, ents, nl, cells)));
+    fuse_map_layout(a, s, m->fmap.p, rows, slots, ents, nl, cells);
     a.g = g; a.kp = *kp; a.st = *state; a.p = *params; a.n_rows = n_rows;
     const float *const tab[9] = {table->Px, table->Py, table->Pz, table->Pnx, table->Pny, table->Pnz, table->MaxDistance, table->invariance_minDistance,
                                  table->invariance_maxDistance};
     memcpy(a.tab, tab, sizeof(tab));
     a.n_list = n_list; a.n_targets = n_targets; a.sim3 = sim3; a.replace_loop = replace_loop != 0; a.log_cap = log_cap; a.list_row = list_row;
-    int32_t *p = m->fmap.buf;
-    a.gdesc = (uint8_t *)p; p += 8 * nl;
-    int32_t *const minus = p;
-    a.head = p; p += rows; a.ent_slot = p; p += ents;
-    int32_t *const zero = p;
-    a.mark = p; p += rows; a.snap = p; p += rows; a.slot_mark = p; p += slots; a.ctl = p; p += 8; a.ds = p; p += 8;
-    int32_t *const search_stats = p; p += 16;
-    int32_t *const n_matched = p; p += JSORB_BOW_MAX_KEYFRAMES;      // k_fuse_match_run's counts per target: cleared with the rest, read by nobody (n_fused is the call's count)
-    int32_t *const rest = p;
-    a.next = p; p += ents; a.csr_ent = p; p += ents; a.grid_items = p; p += ents; a.grid_start = p; p += cells;
-    a.gf = (float *)p; p += 9 * nl; a.skip = (uint8_t *)p; p += (nl + 3) / 4;
-    a.marked = p; p += nl; a.obs_start = p; p += nl + 1; a.out_row = p; p += nl;
-    int32_t *const best_obs = p; p += nl;
-    int32_t *const best_median = p; p += nl;
-    int32_t *const dlist = p; p += 3 * nl;
     a.best_idx = best_idx; a.replace_point = replace_point; a.n_fused = n_fused; a.log_out = log_out; a.counts_dev = counts_dev; a.stats = c.stats;
     HIPCHK(m, hipMemsetAsync(c.stats, 0, 16 * sizeof(int), st));
     c.done = true;
-    HIPCHK(m, hipMemsetAsync(minus, 0xFF, (size_t)(zero - minus) * sizeof(int32_t), st));
-    HIPCHK(m, hipMemsetAsync(zero, 0, (size_t)(rest - zero) * sizeof(int32_t), st));
+    HIPCHK(m, hipMemsetAsync(s.minus, 0xFF, (size_t)(s.zero - s.minus) * sizeof(int32_t), st));
+    HIPCHK(m, hipMemsetAsync(s.zero, 0, (size_t)(s.rest - s.zero) * sizeof(int32_t), st));
     if (log_cap > 0) HIPCHK(m, hipMemsetAsync(log_out, 0xFF, (size_t)log_cap * 4 * sizeof(int32_t), st));
     if (n_targets > 0) {
         launch_fuse_map_index(a, st);
@@ -98,11 +101,11 @@ int jsorb_fuse_map_async(jsorb_keyframe_matcher *m, const jsorb_fuse_params *par
     f.mp_desc = a.gdesc;
     f.x = kp->x; f.y = kp->y; f.uright = kp->uright; f.octave = kp->octave; f.kf_desc = kp->desc;
     f.skip = a.skip; f.cell_start = a.grid_start; f.cell_items = a.grid_items;
-    f.best_idx = best_idx; f.best_dist = best_dist; f.n_matched = n_matched; f.stats = search_stats;
+    f.best_idx = best_idx; f.best_dist = best_dist; f.n_matched = s.n_matched; f.stats = s.search_stats;
     DistinctArgs d{};
     d.n_points = n_list; d.n_obs = pool; d.n_rows = pool; d.n_out_rows = n_rows;
     d.obs_start = a.obs_start; d.obs_row = a.csr_ent; d.kf_desc = kp->desc; d.out_row = a.out_row;
-    d.list = dlist; d.best_obs = best_obs; d.best_median = best_median; d.desc_out = state->desc; d.changed = nullptr; d.stats = a.ds;
+    d.list = s.dlist; d.best_obs = s.best_obs; d.best_median = s.best_median; d.desc_out = state->desc; d.changed = nullptr; d.stats = a.ds;
     for (int t = 0; t < n_targets; t++) {
         const int slot = target_slot[t];
         launch_fuse_map_head(a, t, slot, st);
@@ -140,33 +143,10 @@ int jsorb_fuse_map(jsorb_keyframe_matcher *m, const jsorb_fuse_params *params, i
         return kf_fail(m, FM, "NULL host output");
     RCCHK(jsorb_fuse_map_async(m, params, replace_loop, graph, table, kp, state, n_list, list_row, n_targets, target_slot, Rcw, tcw, Ow, best_idx, best_dist,
                                replace_point, n_fused, log_cap, log_out, counts_dev));
-    hipStream_t st = m->stream;
-    const size_t nrp = replace_point ? pairs : 0;
-    const long long words = (long long)(FM_COUNTS + nt + 2 * pairs + nrp + nlog);
-    if (m->fmap.out_words < words) {
-        free_device(m->fmap.out);
-        m->fmap.out_words = 0;
-        HIPCHK(m, hipMalloc(&m->fmap.out, (size_t)words * sizeof(int32_t)));
-        m->fmap.out_words = words;
-    }
-    int32_t *o = m->fmap.out;
     const int32_t *const src[6] = {counts_dev, n_fused, best_idx, best_dist, replace_point, log_out};
     int32_t *const dst[6] = {counts_host, n_fused_host, best_idx_host, best_dist_host, replace_point_host, log_host};
-    const size_t n[6] = {FM_COUNTS, nt, pairs, pairs, nrp, nlog};
-    size_t at = 0;
-    for (int i = 0; i < 6; i++) {
-        if (n[i]) HIPCHK(m, hipMemcpyAsync(o + at, src[i], n[i] * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        at += n[i];
-    }
-    std::vector<int32_t> h(at);
-    HIPCHK(m, hipMemcpyAsync(h.data(), o, at * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(m, hipStreamSynchronize(st));
-    at = 0;
-    for (int i = 0; i < 6; i++) {
-        if (n[i]) memcpy(dst[i], h.data() + at, n[i] * sizeof(int32_t));
-        at += n[i];
-    }
-    return JSORB_OK;
+    const size_t n[6] = {FM_COUNTS, nt, pairs, pairs, replace_point ? pairs : 0, nlog};
+    return read_back(m, m->stream, m->staging, 6, src, dst, n);
 }
 
 int jsorb_fuse_map_stats(jsorb_keyframe_matcher *m, int32_t counts[10])

@@ -61,6 +61,29 @@ struct KfCall {
 };
 #define KF_STATS 8
 
+// What the map-maintenance calls share (the routines are further down).  A device buffer of 32-bit words that only grows:
+// scratch or the staging buffer of a synchronous form.  reserve_words(owner, buf, need) frees and allocates when `need` exceeds it (hipFree waits
+// for the device: the last call may still read it), the contents are not kept; free_device(p) releases it.
+struct WordBuf {
+    int32_t *p = nullptr;
+    long long words = 0;
+};
+// One word per table row with the value every call leaves behind (`fill` bytes): set after growth, and again after a call whose launches were
+// cut short (dirty).  reserve_row_words below.
+struct RowWords {
+    uint32_t *word = nullptr;
+    int rows = 0;
+    bool dirty = false;
+};
+// A call's scratch layout, written once as a sequence of take(n): run without a base it only adds up the words the layout needs, run with the
+// base it places the pieces, so the two cannot disagree.
+struct Carve {
+    int32_t *base;
+    long long at = 0;
+    explicit Carve(int32_t *b) : base(b) {}
+    int32_t *take(long long n) { int32_t *p = base ? base + at : nullptr; at += n; return p; }
+};
+
 struct jsorb_extractor {
     // ---- core buffers and geometry (jsorb_api.hip: jsorb_create_masked / jsorb_destroy) ----
     jsorb_params p{};
@@ -272,9 +295,7 @@ struct jsorb_extractor {
 
     // ---- the local map (jsorb_localmap.hip, jsorb_local_map_points*): allocated on the first call, grown only ----
     struct {
-        uint32_t *word = nullptr;          // one word per table row, all ones between calls: bit 31 = not seen by the frame, below it the first entry with the row
-        int rows = 0;
-        bool dirty = false;                // a call's launches were cut short: the next call sets every word again
+        RowWords row;                      // all ones between calls: bit 31 = not seen by the frame, below it the first entry with the row
         uint8_t *keep = nullptr;           // one byte per entry: inside the frustum
         int entries = 0;
         uint32_t *chunk = nullptr;         // chunks sums, then chunks + 1 prefixes
@@ -285,13 +306,12 @@ struct jsorb_extractor {
         bool done = false;
     } lm;
 
-    // ---- the local keyframes (jsorb_localkf.hip, jsorb_local_keyframes*): allocated on the first call, grown only; the row words are lm.word ----
+    // ---- the local keyframes (jsorb_localkf.hip, jsorb_local_keyframes*): allocated on the first call, grown only; the row words are lm.row ----
     struct {
         int32_t *slot = nullptr;           // per graph slot: vote, then the first list in order (2 x slots words), then slots bytes `first`
         int slots = 0;
         int32_t *stats = nullptr;          // LK_STATS words of the last call, then the 64-bit `best` (device)
-        int32_t *out = nullptr;            // synchronous call: counts (8), state_io (2), then local_kf_slot (out_cap)
-        int out_cap = 0;
+        WordBuf out;                       // synchronous call: counts (8), state_io (2), then local_kf_slot, gathered for one copy back
         bool done = false;
     } lk;
 
@@ -350,24 +370,13 @@ struct jsorb_keyframe_matcher {
         int list_cap = 0;
     } distinct;
     struct {                                                    // jsorb_update_connections* (jsorb_covis.hip), grown only
-        uint32_t *word = nullptr;                               // one word per table row (rows): the members' bits, all zero between calls
-        int rows = 0;
+        RowWords row;                                           // the members' bits, all zero between calls
         int32_t *slot = nullptr;                                // 4 x 32 x slots words: count, kraw, klist, tlist; then 32 x 4 words minfo
         int slots = 0;
-        bool dirty = false;                                     // a call failed between its kernels: the words are cleared again
     } covis;
-    struct {                                                    // jsorb_cull_keyframes* (jsorb_culling.hip), grown only
-        int32_t *buf = nullptr;                                 // the observations grouped by row, the rounds' verdicts, the tree repair's lists (CullArgs)
-        long long words = 0;
-        int32_t *out = nullptr;                                 // the synchronous form's outputs gathered for one copy back
-        long long out_words = 0;
-    } cull;
-    struct {                                                    // jsorb_fuse_map* (jsorb_fuse_apply.hip), grown only
-        int32_t *buf = nullptr;                                 // the observation index, the stamps, the target's grid, list points and CSR (FuseMapArgs)
-        long long words = 0;
-        int32_t *out = nullptr;                                 // the synchronous form's outputs gathered for one copy back
-        long long out_words = 0;
-    } fmap;
+    WordBuf cull;                                               // jsorb_cull_keyframes* (jsorb_culling.hip): the observations grouped by row, the rounds' verdicts, the tree repair's lists (CullArgs)
+    WordBuf fmap;                                               // jsorb_fuse_map* (jsorb_fuse_apply.hip): the observation index, the stamps, the target's grid, list points and CSR (FuseMapArgs)
+    WordBuf staging;                                            // the synchronous forms of the three: their outputs gathered for one copy back (read_back; the call waits for it)
     std::string err;
 };
 
@@ -587,6 +596,62 @@ int kf_sync(H *h, const char *name, KfCall &c, int n_keyframes, int n, const cha
 // The statistics words of a call's last run into s[KF_STATS] (read_stats; `before`: the error when none has run)
 template <class H> int kf_stats(H *h, const KfCall &c, const char *before, int32_t *s) { return read_stats(h, c.done, before, c.stats, s, KF_STATS); }
 
+template <class T> int reserve_pinned(jsorb_extractor *e, T *&p, size_t bytes) { if (!p) HIPCHK(e, hipHostMalloc(&p, bytes)); return JSORB_OK; }
+// release functions: free (and forget) what a feature allocated
+template <class... T> void free_device(T *&...p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+template <class... T> void free_pinned(T *&...p) { ((p ? (void)hipHostFree(p) : (void)0, p = nullptr), ...); }
+template <class... T> void destroy_event(T &...ev) { ((ev ? (void)hipEventDestroy(ev) : (void)0, ev = nullptr), ...); }
+
+// ---- what the map-maintenance calls share: jsorb_localmap.hip, jsorb_localkf.hip, jsorb_covis.hip, jsorb_culling.hip,
+// jsorb_fuse_apply.hip.  Each entry point's own NULL / range / alignment checks stay written out where they fire. ----
+template <class H> int reserve_words(H *h, WordBuf &b, long long need)
+{
+    if (b.words >= need) return JSORB_OK;
+    free_device(b.p);
+    b.words = 0;
+    HIPCHK(h, hipMalloc(&b.p, (size_t)need * sizeof(int32_t)));
+    b.words = need;
+    return JSORB_OK;
+}
+
+// r for a table of n_rows rows: grown on demand; every byte set to `fill` on st after growth or a call that was cut short
+template <class H> int reserve_row_words(H *h, RowWords &r, int n_rows, int fill, hipStream_t st)
+{
+    const int rows_before = r.rows, want = std::max(n_rows, 1);
+    RCCHK(reserve_device(h, r.word, (size_t)want * sizeof(uint32_t), &r.rows, want));
+    if (r.rows != rows_before || r.dirty) {
+        HIPCHK(h, hipMemsetAsync(r.word, fill, (size_t)r.rows * sizeof(uint32_t), st));
+        r.dirty = false;
+    }
+    return JSORB_OK;
+}
+
+// The synchronous forms' end: the device arrays src[i] of n[i] words each are gathered into `staging` behind what st carries, come back in one
+// copy, and are handed out to dst[i] once the stream has been waited for.  An empty segment is skipped: its src and dst may be NULL.
+template <class H> int read_back(H *h, hipStream_t st, WordBuf &staging, int n_segments, const int32_t *const src[], int32_t *const dst[], const size_t n[])
+{
+    size_t total = 0, at = 0;
+    for (int i = 0; i < n_segments; i++) total += n[i];
+    RCCHK(reserve_words(h, staging, (long long)total));
+    for (int i = 0; i < n_segments; at += n[i++])
+        if (n[i]) HIPCHK(h, hipMemcpyAsync(staging.p + at, src[i], n[i] * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    std::vector<int32_t> host(total);
+    HIPCHK(h, hipMemcpyAsync(host.data(), staging.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    at = 0;
+    for (int i = 0; i < n_segments; at += n[i++])
+        if (n[i]) memcpy(dst[i], host.data() + at, n[i] * sizeof(int32_t));
+    return JSORB_OK;
+}
+
+// conn_capacity of a jsorb_covisibility against what the build's kernels take
+inline int check_conn_capacity(jsorb_keyframe_matcher *m, const char *name, int conn_capacity)
+{
+    if (conn_capacity < covis_cap_min() || conn_capacity > covis_cap_max())
+        return kf_fail(m, name, "conn_capacity outside [" + std::to_string(covis_cap_min()) + ", " + std::to_string(covis_cap_max()) + "]");
+    return JSORB_OK;
+}
+
 // k_bow_group's launch arguments: the single side (f_node, N) and the concatenated keyframes (kf_node at the rebased offsets `rel`)
 inline BowMatchArgs bow_group_args(const int *rel, const int32_t *f_node, int N, int n_kf, const int32_t *kf_node, unsigned long long *f_sorted,
                                    unsigned long long *kf_sorted)
@@ -632,12 +697,6 @@ template <class P> FuseGridArgs fuse_grid_args(const P &p, const float *x, const
     return g;
 }
 
-template <class T> int reserve_pinned(jsorb_extractor *e, T *&p, size_t bytes) { if (!p) HIPCHK(e, hipHostMalloc(&p, bytes)); return JSORB_OK; }
-// release functions: free (and forget) what a feature allocated
-template <class... T> void free_device(T *&...p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
-template <class... T> void free_pinned(T *&...p) { ((p ? (void)hipHostFree(p) : (void)0, p = nullptr), ...); }
-template <class... T> void destroy_event(T &...ev) { ((ev ? (void)hipEventDestroy(ev) : (void)0, ev = nullptr), ...); }
-
 // ---- jsorb_api.hip ----
 int pool_stream(jsorb_extractor *e, int j, hipStream_t *out);      // lane stream j of the device's pool
 int pool_copy_stream(jsorb_extractor *e, hipStream_t *out);         // the device's upload stream
@@ -677,7 +736,6 @@ void search_kf_release(jsorb_extractor *e);
 
 // ---- jsorb_localmap.hip ----
 void local_map_release(jsorb_extractor *e);
-int local_map_row_words(jsorb_extractor *e, int n_rows, hipStream_t st);      // lm.word for a table of n_rows rows, all ones (grown and set again on demand)
 
 // ---- jsorb_localkf.hip ----
 void local_kf_release(jsorb_extractor *e);

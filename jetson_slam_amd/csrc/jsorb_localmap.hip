@@ -6,31 +6,13 @@
 
 namespace jsorb_host __attribute__((visibility("hidden"))) {
 
-void local_map_release(jsorb_extractor *e) { free_device(e->lm.word, e->lm.keep, e->lm.chunk, e->lm.stats, e->lm.out); }
-
-// the scratch: grown only; a word is all ones between calls
-int local_map_row_words(jsorb_extractor *e, int n_rows, hipStream_t st)
-{
-    const int rows_before = e->lm.rows;
-    RCCHK(reserve_device(e, e->lm.word, (size_t)std::max(n_rows, 1) * sizeof(uint32_t), &e->lm.rows, std::max(n_rows, 1)));
-    if (e->lm.rows != rows_before || e->lm.dirty) {
-        HIPCHK(e, hipMemsetAsync(e->lm.word, 0xff, (size_t)e->lm.rows * sizeof(uint32_t), st));
-        e->lm.dirty = false;
-    }
-    return JSORB_OK;
-}
+void local_map_release(jsorb_extractor *e) { free_device(e->lm.row.word, e->lm.keep, e->lm.chunk, e->lm.stats, e->lm.out); }
 
 } // namespace jsorb_host
 
 namespace {
 
 const char *const LM = "local_map_points";
-
-int lm_fail(jsorb_extractor *e, const char *what, int rc = JSORB_ERR_INVALID)
-{
-    e->err = std::string(LM) + ": " + what;
-    return rc;
-}
 
 } // namespace
 
@@ -42,25 +24,25 @@ int jsorb_local_map_points_async(jsorb_extractor *e, int image, const jsorb_map_
                                  uint8_t *mp_descriptors, uint8_t *blocked_in, int32_t *counts_dev)
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!check_image(e, image)) return lm_fail(e, "no extract result for this image", JSORB_ERR_STATE);
-    if (!table || !prm || !counts_dev) return lm_fail(e, "NULL table, prm or counts_dev");
+    if (!check_image(e, image)) return kf_fail(e, LM, "no extract result for this image", JSORB_ERR_STATE);
+    if (!table || !prm || !counts_dev) return kf_fail(e, LM, "NULL table, prm or counts_dev");
     const jsorb_map_point_table &t = *table;
-    if (t.n_rows < 0 || n_keyframes < 0 || capacity < 0) return lm_fail(e, "n_rows, n_keyframes and capacity must not be negative");
+    if (t.n_rows < 0 || n_keyframes < 0 || capacity < 0) return kf_fail(e, LM, "n_rows, n_keyframes and capacity must not be negative");
     if (t.n_rows > 0 && (!t.Px || !t.Py || !t.Pz || !t.Pnx || !t.Pny || !t.Pnz || !t.MaxDistance || !t.invariance_maxDistance || !t.invariance_minDistance ||
                          !t.desc || !t.bad))
-        return lm_fail(e, "NULL table array");
-    if (n_keyframes > 0 && !kf_start) return lm_fail(e, "NULL kf_start");
+        return kf_fail(e, LM, "NULL table array");
+    if (n_keyframes > 0 && !kf_start) return kf_fail(e, LM, "NULL kf_start");
     for (int i = 0; i < n_keyframes; i++)
-        if (kf_start[i] < 0 || kf_start[i + 1] < kf_start[i]) return lm_fail(e, "kf_start must be ascending offsets");
+        if (kf_start[i] < 0 || kf_start[i + 1] < kf_start[i]) return kf_fail(e, LM, "kf_start must be ascending offsets");
     const int first = n_keyframes > 0 ? kf_start[0] : 0, E = n_keyframes > 0 ? kf_start[n_keyframes] - first : 0;
-    if (E >= (1 << 24)) return lm_fail(e, "more than 16777215 entries");
-    if (E > 0 && !kf_point_row) return lm_fail(e, "NULL kf_point_row");
-    if (capacity > 0 && (!point_row || !u || !v || !invz || !predicted_level || !view_cos || !in_frustum || !mp_descriptors)) return lm_fail(e, "NULL output");
-    if ((uintptr_t)t.desc % 16 || (uintptr_t)mp_descriptors % 16) return lm_fail(e, "desc and mp_descriptors must be 16-byte aligned");
+    if (E >= (1 << 24)) return kf_fail(e, LM, "more than 16777215 entries");
+    if (E > 0 && !kf_point_row) return kf_fail(e, LM, "NULL kf_point_row");
+    if (capacity > 0 && (!point_row || !u || !v || !invz || !predicted_level || !view_cos || !in_frustum || !mp_descriptors)) return kf_fail(e, LM, "NULL output");
+    if ((uintptr_t)t.desc % 16 || (uintptr_t)mp_descriptors % 16) return kf_fail(e, LM, "desc and mp_descriptors must be 16-byte aligned");
     const int N = jsorb_n_keypoints(e, image);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    RCCHK(local_map_row_words(e, t.n_rows, st));
+    RCCHK(reserve_row_words(e, e->lm.row, t.n_rows, 0xff, st));      // the scratch: grown only; a word is all ones between calls
     const int chunks = local_map_chunks(E);
     RCCHK(reserve_device(e, e->lm.keep, (size_t)std::max(E, 1), &e->lm.entries, std::max(E, 1)));
     RCCHK(reserve_device(e, e->lm.chunk, ((size_t)2 * (chunks + 1) + 1) * sizeof(uint32_t), &e->lm.chunks, chunks + 1));
@@ -72,16 +54,16 @@ int jsorb_local_map_points_async(jsorb_extractor *e, int image, const jsorb_map_
     a.E = E; a.N = N; a.capacity = capacity;
     a.entry_row = E > 0 ? kf_point_row + first : nullptr;
     a.frame_row = frame_point_row;
-    a.word = e->lm.word; a.keep = e->lm.keep;
+    a.word = e->lm.row.word; a.keep = e->lm.keep;
     a.chunk_sum = e->lm.chunk; a.chunk_pre = e->lm.chunk + e->lm.chunks;
     a.stats = e->lm.stats;
     a.point_row = point_row; a.level = predicted_level; a.u = u; a.v = v; a.invz = invz; a.view_cos = view_cos;
     a.in_frustum = in_frustum; a.mp_desc = mp_descriptors; a.blocked_in = blocked_in;
     a.counts = counts_dev;
-    e->lm.dirty = true;                // until all four kernels are enqueued: k_lm_write is the one that sets the words back
+    e->lm.row.dirty = true;            // until all four kernels are enqueued: k_lm_write is the one that sets the words back
     launch_local_map(a, st);
     HIPCHK(e, hipGetLastError());
-    e->lm.dirty = false;
+    e->lm.row.dirty = false;
     e->lm.done = true;
     return JSORB_OK;
 }
@@ -92,9 +74,11 @@ int jsorb_local_map_points(jsorb_extractor *e, int image, const jsorb_map_point_
                            uint8_t *blocked_in, int32_t *counts_dev, int32_t *point_row_host, int32_t counts_host[5])
 {
     if (!e) return JSORB_ERR_INVALID;
-    if (!counts_host || (capacity > 0 && !point_row_host)) return lm_fail(e, "NULL host output");
-    if (capacity < 0) return lm_fail(e, "n_rows, n_keyframes and capacity must not be negative");
+    if (!counts_host || (capacity > 0 && !point_row_host)) return kf_fail(e, LM, "NULL host output");
+    if (capacity < 0) return kf_fail(e, LM, "n_rows, n_keyframes and capacity must not be negative");
     HIPCHK(e, hipSetDevice(e->device));
+    // The other way round than read_back: the asynchronous form writes into the staging buffer, and the results are copied out to the caller's
+    // device arrays (point_row and counts_dev may be NULL here).  Left as it is.
     const int cap = std::max(capacity, 1);
     RCCHK(reserve_device(e, e->lm.out, ((size_t)8 + cap) * sizeof(int32_t), &e->lm.out_cap, cap));
     int32_t *cnt = e->lm.out, *rows = cnt + 8;

@@ -1086,40 +1086,53 @@ class Vocabulary:
             pass
 
 
+def _build_caps(name, n):
+    """the n ints jsorb_<name>_build_caps of the loaded library hands back: a tuple, or the value itself when it is one"""
+    v = [C.c_int() for _ in range(n)]
+    getattr(load_library(), "jsorb_%s_build_caps" % name)(*[C.byref(x) for x in v])
+    return v[0].value if n == 1 else tuple(x.value for x in v)
+
+
 def bow_build_caps():
     """jsorb_bow_build_caps of the loaded library: (frame entries per lane k_bow_match keeps in registers, keys k_bow_group sorts in LDS)"""
-    r, l = C.c_int(), C.c_int()
-    load_library().jsorb_bow_build_caps(C.byref(r), C.byref(l))
-    return r.value, l.value
+    return _build_caps("bow", 2)
 
 
 def search_kf_build_caps():
     """jsorb_search_kf_build_caps of the loaded library: (keys k_kf_candidates keeps per point, keypoints up to which k_kf_resolve claims in LDS)"""
-    c, l = C.c_int(), C.c_int()
-    load_library().jsorb_search_kf_build_caps(C.byref(c), C.byref(l))
-    return c.value, l.value
+    return _build_caps("search_kf", 2)
 
 
 def loop_build_caps():
     """jsorb_loop_build_caps of the loaded library: candidate entries of a node a lane of k_loop_bow_match keeps in registers"""
-    r = C.c_int()
-    load_library().jsorb_loop_build_caps(C.byref(r))
-    return r.value
+    return _build_caps("loop", 1)
 
 
 def scw_build_caps():
     """jsorb_scw_build_caps of the loaded library: (keys k_scw_candidates keeps per point, keypoints up to which k_scw_resolve claims in LDS)"""
-    c, l = C.c_int(), C.c_int()
-    load_library().jsorb_scw_build_caps(C.byref(c), C.byref(l))
-    return c.value, l.value
+    return _build_caps("scw", 2)
 
 
 def distinct_build_caps():
     """jsorb_distinct_build_caps of the loaded library: (lanes per point of k_distinct's group tier, the largest N of its wave tier, descriptors its
     block tier holds in LDS)"""
-    g, w, l = C.c_int(), C.c_int(), C.c_int()
-    load_library().jsorb_distinct_build_caps(C.byref(g), C.byref(w), C.byref(l))
-    return g.value, w.value, l.value
+    return _build_caps("distinct", 3)
+
+
+def _i32_ptr(what, t, n=None, flat=False):
+    """the pointer of a contiguous int32 device tensor (of at least n entries; flat: one-dimensional), or the JsorbError that says so about `what`"""
+    import torch
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or (flat and t.dim() != 1) or (n is not None and t.numel() < n):
+        raise JsorbError("%s must be a contiguous int32 device tensor%s" % (what, "" if n is None else " of at least %d entries" % n))
+    return t.data_ptr()
+
+
+def _uploaded_i32(x, dev):
+    """(x as an int32 device tensor, whether it was made here): a tensor as it is, a host sequence uploaded"""
+    import torch
+    if torch.is_tensor(x):
+        return x, False
+    return torch.tensor([int(v) for v in x], dtype=torch.int32, device=dev), True
 
 
 def bow_transform_descriptors(voc, descriptors):
@@ -1503,12 +1516,29 @@ class KeyframeMatcher:
         return tuple(x.value for x in v)
 
     # ---- the covisibility graph: KeyFrame::UpdateConnections / AddConnection / EraseConnection (KeyFrame.cpp:127-161, :293-383, :557-571) ----
-    @staticmethod
-    def _i32(what, t, n=None):
+    def _run_outputs(self, name, args, keys, shapes, out, dev, sync, wait, made):
+        """jsorb_<name>_async, or with sync jsorb_<name>, for the calls that return a dict of int32 outputs.  args: the call's arguments behind the
+        matcher, an output's key standing for its pointer; shapes: per key the shape the call fills.  The buffers are those of `out` (the dict of
+        an earlier call) or new ones of at least one element each.  The current torch stream is waited for first with wait or sync, and where a
+        tensor was made for the call (`made`, or the buffers are new).  Returns the dict: per key the buffer's view of that shape, "_bufs", and
+        with sync the same as numpy arrays under *_host (-7 where the call writes nothing)."""
         import torch
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or (n is not None and t.numel() < n):
-            raise JsorbError("%s must be a contiguous int32 device tensor%s" % (what, "" if n is None else " of at least %d entries" % n))
-        return t.data_ptr()
+        size = {k: int(np.prod(shapes[k])) for k in keys}
+        bufs = out["_bufs"] if out is not None else {k: torch.empty([max(int(x), 1) for x in shapes[k]], dtype=torch.int32, device=dev) for k in keys}
+        args = [self._m] + [bufs[a].data_ptr() if isinstance(a, str) else a for a in args]
+        if wait or sync or made or out is None:
+            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
+        out = {k: bufs[k].reshape(-1)[:size[k]].reshape(shapes[k]) for k in keys}
+        out["_bufs"] = bufs
+        if sync:
+            host = {k: np.full(max(size[k], 1), -7, np.int32) for k in keys}
+            self._chk(getattr(self._lib, "jsorb_" + name)(*args, *[host[k].ctypes.data for k in keys]))
+            out.update({k + "_host": host[k][:size[k]].reshape(shapes[k]) for k in keys})
+        else:
+            self._chk(getattr(self._lib, "jsorb_%s_async" % name)(*args))
+            if wait:
+                self.sync()
+        return out
 
     def update_connections(self, graph, table, cov, slots, neighbours=None, snapshot=False, sync=False, out=None, wait=True):
         """jsorb_update_connections*: UpdateConnections() of the keyframes `slots` (at most 32: an int32 device tensor, or a host sequence that is
@@ -1520,14 +1550,11 @@ class KeyframeMatcher:
         wait=False the call only enqueues, and waits for the torch stream just where it made a tensor itself (slots uploaded, out=None)."""
         import torch
         dev = cov.conn_len.device
-        made = out is None or not torch.is_tensor(slots)
-        if not torch.is_tensor(slots):
-            slots = torch.tensor([int(x) for x in slots], dtype=torch.int32, device=dev)
+        slots, made = _uploaded_i32(slots, dev)
+        made = made or out is None
         n = int(slots.numel())
-        sp = self._i32("update_connections: slots", slots) if n else None
-        nb = None
-        if neighbours is not None:
-            nb = self._i32("update_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
+        sp = _i32_ptr("update_connections: slots", slots) if n else None
+        nb = None if neighbours is None else _i32_ptr("update_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
         if out is None:
             Cn, n1 = cov.conn_capacity, max(n, 1)   # (a call with no slots still hands over valid arrays)
             bufs = dict(parent_out=torch.empty(n1, dtype=torch.int32, device=dev), counts=torch.empty(8, dtype=torch.int32, device=dev))
@@ -1572,7 +1599,7 @@ class KeyframeMatcher:
         that held the slot"""
         import torch
         dev = cov.conn_len.device
-        nb = None if neighbours is None else self._i32("erase_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
+        nb = None if neighbours is None else _i32_ptr("erase_connections: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
         counts = torch.empty(2, dtype=torch.int32, device=dev)
         gs, cs = graph.struct(), cov.struct()
         if wait:
@@ -1601,11 +1628,9 @@ class KeyframeMatcher:
         (out int32[n, N] -1 padded, out_len int32[n]) device tensors"""
         import torch
         dev = cov.conn_len.device
-        made = not torch.is_tensor(slots)
-        if made:
-            slots = torch.tensor([int(x) for x in slots], dtype=torch.int32, device=dev)
+        slots, made = _uploaded_i32(slots, dev)
         n, N = int(slots.numel()), int(N)
-        sp = self._i32("best_covisibles: slots", slots) if n else None
+        sp = _i32_ptr("best_covisibles: slots", slots) if n else None
         out = torch.empty((max(n, 1), max(N, 1)), dtype=torch.int32, device=dev)[:n]
         out_len = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
         cs = cov.struct()
@@ -1633,36 +1658,17 @@ class KeyframeMatcher:
         is passed.  out: the dict of an earlier call with the same n, max_cull and reparent_cap, written again.  The call waits for the current
         torch stream before it enqueues, except with wait=False, out given and candidates a device tensor: then it makes no tensor, waits for
         nothing and only enqueues - the form a graph capture takes."""
-        import torch
         dev = cov.conn_len.device
-        made = not torch.is_tensor(candidates)
-        if made:
-            candidates = torch.tensor([int(x) for x in candidates], dtype=torch.int32, device=dev)
+        candidates, made = _uploaded_i32(candidates, dev)
         candidates = candidates.reshape(-1)
         n, max_cull, cap = int(candidates.numel()), int(max_cull), int(reparent_cap)
-        cp = self._i32("cull_keyframes: candidates", candidates) if n else None
-        nb = None if neighbours is None else self._i32("cull_keyframes: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
-        new = lambda *shape: torch.empty([max(int(x), 1) for x in shape], dtype=torch.int32, device=dev)
-        made = made or out is None
-        bufs = out["_bufs"] if out is not None else dict(decision=new(n), n_mps=new(n), n_redundant=new(n), culled_slot=new(max(max_cull, 1)),
-                                                         reparent_out=new(cap, 2), counts=new(10))
+        cp = _i32_ptr("cull_keyframes: candidates", candidates) if n else None
+        nb = None if neighbours is None else _i32_ptr("cull_keyframes: neighbours", neighbours, cov.max_keyframes * KF_NEIGHBOURS)
         shapes = dict(decision=(n,), n_mps=(n,), n_redundant=(n,), culled_slot=(max(max_cull, 0),), reparent_out=(max(cap, 0), 2), counts=(10,))
         gs, tb, cs, vs = graph.struct(), table.struct(), cov.struct(), views.struct()
         keys = ("decision", "n_mps", "n_redundant", "culled_slot", "reparent_out", "counts")
-        args = [self._m, C.byref(gs), C.byref(tb), C.byref(cs), C.byref(vs), C.byref(state), int(bool(monocular)), int(first_slot), n, cp, max_cull, nb, cap] + \
-               [bufs[k].data_ptr() for k in keys]
-        if wait or sync or apply or made:
-            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
-        out = {k: bufs[k].reshape(-1)[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys}
-        out["_bufs"] = bufs
-        if sync or apply:
-            host = {k: np.full(max(int(np.prod(shapes[k])), 1), -7, np.int32) for k in keys}
-            self._chk(self._lib.jsorb_cull_keyframes(*args, *[host[k].ctypes.data for k in keys]))
-            out.update({k + "_host": host[k][:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys})
-        else:
-            self._chk(self._lib.jsorb_cull_keyframes_async(*args))
-            if wait:
-                self.sync()
+        args = [C.byref(gs), C.byref(tb), C.byref(cs), C.byref(vs), C.byref(state), int(bool(monocular)), int(first_slot), n, cp, max_cull, nb, cap, *keys]
+        out = self._run_outputs("cull_keyframes", args, keys, shapes, out, dev, sync or apply, wait, made)
         out["candidates"] = candidates           # (kept alive with the result: the device reads it after the call returns)
         if apply:
             culled = [int(s) for s in out["culled_slot_host"] if s >= 0]
@@ -1698,45 +1704,25 @@ class KeyframeMatcher:
         *_host.  out: the dict of an earlier call with the same sizes, written again.  The call waits for the current torch stream before it
         enqueues, except with wait=False, out given and list_row a device tensor: then it makes no tensor, waits for nothing and only enqueues -
         the form a graph capture takes (the targets and their poses are host values: a replay runs the captured ones)."""
-        import torch
         what = "fuse_map"
         if not isinstance(params, JsorbFuseParams):
             raise JsorbError("%s: params must come from make_fuse_params" % what)
         dev = graph.point_pool.device
-        made = not torch.is_tensor(list_row)
-        if made:
-            list_row = torch.tensor([int(x) for x in list_row], dtype=torch.int32, device=dev)
+        list_row, made = _uploaded_i32(list_row, dev)
         list_row = list_row.reshape(-1)
         n = int(list_row.numel())
-        lp = self._i32("%s: list_row" % what, list_row) if n else None
+        lp = _i32_ptr("%s: list_row" % what, list_row) if n else None
         ts = np.ascontiguousarray(target_slots, np.int32).reshape(-1)
         T = len(ts)
         R, t, O = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (Rcw, tcw, Ow))
         if len(R) != 9 * T or len(t) != 3 * T or len(O) != 3 * T:
             raise JsorbError("%s: Rcw must hold 9, tcw 3 and Ow 3 floats per target" % what)
         cap = max(T * n, 1) if log_cap is None else int(log_cap)
-        new = lambda *shape: torch.empty([max(int(x), 1) for x in shape], dtype=torch.int32, device=dev)
-        made = made or out is None
-        bufs = out["_bufs"] if out is not None else dict(best_idx=new(T, n), best_dist=new(T, n), replace_point=new(T, n), n_fused=new(T), log=new(cap, 4),
-                                                         counts=new(10))
         shapes = dict(best_idx=(T, n), best_dist=(T, n), replace_point=(T, n), n_fused=(T,), log=(max(cap, 0), 4), counts=(10,))
         gs, tb, ks = graph.struct(), table.struct(), kp.struct()
-        keys = FUSE_MAP_OUTPUTS
-        b = {k: bufs[k].data_ptr() for k in keys}
-        args = [self._m, C.byref(params), int(bool(replace_loop)), C.byref(gs), C.byref(tb), C.byref(ks), C.byref(state), n, lp, T, ts.ctypes.data, R.ctypes.data,
-                t.ctypes.data, O.ctypes.data, b["best_idx"], b["best_dist"], b["replace_point"], b["n_fused"], cap, b["log"], b["counts"]]
-        if wait or sync or made:
-            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
-        out = {k: bufs[k].reshape(-1)[:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys}
-        out["_bufs"] = bufs
-        if sync:
-            host = {k: np.full(max(int(np.prod(shapes[k])), 1), -7, np.int32) for k in keys}
-            self._chk(self._lib.jsorb_fuse_map(*args, *[host[k].ctypes.data for k in keys]))
-            out.update({k + "_host": host[k][:int(np.prod(shapes[k]))].reshape(shapes[k]) for k in keys})
-        else:
-            self._chk(self._lib.jsorb_fuse_map_async(*args))
-            if wait:
-                self.sync()
+        args = [C.byref(params), int(bool(replace_loop)), C.byref(gs), C.byref(tb), C.byref(ks), C.byref(state), n, lp, T, ts.ctypes.data, R.ctypes.data,
+                t.ctypes.data, O.ctypes.data, "best_idx", "best_dist", "replace_point", "n_fused", cap, "log", "counts"]
+        out = self._run_outputs(what, args, FUSE_MAP_OUTPUTS, shapes, out, dev, sync, wait, made)
         out["list_row"] = list_row               # (kept alive with the result: the device reads it after the call returns)
         return out
 
@@ -1754,51 +1740,37 @@ class KeyframeMatcher:
 
 def fuse_map_build_caps():
     """jsorb_fuse_map_build_caps of the loaded library: the entries of an observation list staged at a time"""
-    a = C.c_int()
-    load_library().jsorb_fuse_map_build_caps(C.byref(a))
-    return a.value
+    return _build_caps("fuse_map", 1)
 
 
 def cull_keyframes_build_caps():
     """jsorb_cull_keyframes_build_caps of the loaded library: the most candidates and the largest max_cull of one call"""
-    a, b = C.c_int(), C.c_int()
-    load_library().jsorb_cull_keyframes_build_caps(C.byref(a), C.byref(b))
-    return a.value, b.value
+    return _build_caps("cull_keyframes", 2)
 
 
 def covisibility_build_caps():
     """jsorb_covisibility_build_caps of the loaded library: the smallest and the largest conn_capacity"""
-    lo, hi = C.c_int(), C.c_int()
-    load_library().jsorb_covisibility_build_caps(C.byref(lo), C.byref(hi))
-    return lo.value, hi.value
+    return _build_caps("covisibility", 2)
 
 
 def kfdb_build_caps():
     """jsorb_kfdb_build_caps of the loaded library: (query entries k_kfdb stages in LDS, word ids jsorb_bow_vector_async sorts in LDS)"""
-    q, s = C.c_int(), C.c_int()
-    load_library().jsorb_kfdb_build_caps(C.byref(q), C.byref(s))
-    return q.value, s.value
+    return _build_caps("kfdb", 2)
 
 
 def vocab_train_build_caps():
     """jsorb_vocab_train_build_caps of the loaded library: (positions per chunk of k_vocab_train, chunk sums its scan takes per tile)"""
-    c, t = C.c_int(), C.c_int()
-    load_library().jsorb_vocab_train_build_caps(C.byref(c), C.byref(t))
-    return c.value, t.value
+    return _build_caps("vocab_train", 2)
 
 
 def local_map_build_caps():
     """jsorb_local_map_build_caps of the loaded library: entries per chunk of k_local_map's compaction"""
-    c = C.c_int()
-    load_library().jsorb_local_map_build_caps(C.byref(c))
-    return c.value
+    return _build_caps("local_map", 1)
 
 
 def local_keyframes_build_caps():
     """jsorb_local_keyframes_build_caps of the loaded library: (slots whose membership bit k_lk_expand keeps in LDS, child candidates it keeps there)"""
-    m, c = C.c_int(), C.c_int()
-    load_library().jsorb_local_keyframes_build_caps(C.byref(m), C.byref(c))
-    return m.value, c.value
+    return _build_caps("local_keyframes", 2)
 
 
 WEIGHTING_TF_IDF, WEIGHTING_TF, WEIGHTING_IDF, WEIGHTING_BINARY = 0, 1, 2, 3     # DBoW2::WeightingType
@@ -2427,14 +2399,8 @@ class ORBExtractor:
         if n_kf < 0:
             raise JsorbError("local_map_points: kf_start needs n_keyframes + 1 entries")
         dev = table.floats.device
-
-        def chk(t, name, n):
-            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or int(t.shape[0]) < n:
-                raise JsorbError("local_map_points: %s must be a contiguous int32 device tensor of at least %d entries" % (name, n))
-            return t.data_ptr()
-
-        kp = chk(kf_point_row, "kf_point_row", int(ks[-1])) if n_kf > 0 and ks[-1] > 0 else None
-        fp = None if frame_point_row is None else chk(frame_point_row, "frame_point_row", N)
+        kp = _i32_ptr("local_map_points: kf_point_row", kf_point_row, int(ks[-1]), flat=True) if n_kf > 0 and ks[-1] > 0 else None
+        fp = None if frame_point_row is None else _i32_ptr("local_map_points: frame_point_row", frame_point_row, N, flat=True)
         cap = int(capacity)
         if out is None:
             c1 = max(cap, 1)
@@ -2478,10 +2444,7 @@ class ORBExtractor:
         kc, ec = int(kf_capacity), int(entry_capacity)
         fp, n_frame = None, 0
         if frame_point_row is not None:
-            t = frame_point_row
-            if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-                raise JsorbError("local_keyframes: frame_point_row must be a contiguous int32 device tensor")
-            fp, n_frame = t.data_ptr(), int(t.shape[0])
+            fp, n_frame = _i32_ptr("local_keyframes: frame_point_row", frame_point_row, flat=True), int(frame_point_row.shape[0])
         if out is None:
             if state is None:
                 state = (torch.zeros(max(kc, 1), dtype=torch.int32, device=dev), torch.tensor([0, -1], dtype=torch.int32, device=dev))
