@@ -49,8 +49,8 @@ class KeyFrame:
     def GetBestCovisibilityKeyFrames(self, n):
         return self.neighbours[:n]
 
-    def GetChilds(self):
-        return sorted(set(self.children), key=lambda kf: (kf.key, kf.slot))      # std::set<KeyFrame*>
+    def GetChilds(self, by_slot=False):
+        return sorted(set(self.children), key=lambda kf: kf.slot if by_slot else (kf.key, kf.slot))      # std::set<KeyFrame*>
 
     def GetParent(self):
         return self.parent
@@ -99,9 +99,14 @@ def gather(G, slots, kf_capacity, entry_capacity):
     return start.astype(np.int32), out, len(e)
 
 
-def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capacity, prev_list=(), prev_ref=-1, frame_id=7):
+MUTANTS = ("votes_at_least", "end_reevaluated", "size_at_least_80", "parent_bad_tested", "parent_break_inner", "bad_voters_not_counted", "children_slot_order")
+
+
+def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capacity, prev_list=(), prev_ref=-1, frame_id=7, mutant=None):
     """G: the arrays of jsorb_keyframe_graph (numpy; registered may be None); prev_list, prev_ref: mvpLocalKeyFrames (slots) and mpReferenceKF before
-    the call.  Returns dict(list, ref_slot, local_kf_start, local_point_row, counts, stats)."""
+    the call.  Returns dict(list, ref_slot, local_kf_start, local_point_row, counts, stats).  mutant: one of MUTANTS, a decision of the reference's
+    text flipped (tests/test_ref_tracking.py shows that the recorded reference output notices each)."""
+    assert mutant is None or mutant in MUTANTS
     kfs, points, n_invalid = build_objects(G, bad)
     lookup = lambda r: points[r] if 0 <= r < len(points) else None
     mvpMapPoints = [lookup(int(r)) for r in frame_rows] if frame_rows is not None else []
@@ -120,6 +125,8 @@ def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capac
                 if not pMP.isBad():
                     observations = pMP.GetObservations()
                     for kf in observations:
+                        if mutant == "bad_voters_not_counted" and kf.isBad():
+                            continue
                         keyframeCounter[kf] = keyframeCounter.get(kf, 0) + 1
                 else:
                     mvpMapPoints[i] = None
@@ -131,7 +138,7 @@ def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capac
         for pKF, votes in sorted(keyframeCounter.items(), key=lambda it: (it[0].key, it[0].slot)):      # :1876-1891, std::map's order
             if pKF.isBad():
                 continue
-            if votes > maxv:
+            if votes > maxv or (mutant == "votes_at_least" and votes >= maxv):
                 maxv, pKFmax = votes, pKF
             mvpLocalKeyFrames.append(pKF)
             pKF.mnTrackReferenceForFrame = frame_id
@@ -140,8 +147,12 @@ def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capac
             del mvpLocalKeyFrames[kf_capacity:]
             overflow = 1
         itEndKF = len(mvpLocalKeyFrames)                                     # taken once
-        for it in range(itEndKF):                                            # :1895-1945
-            if len(mvpLocalKeyFrames) > LIMIT:
+        it = -1
+        while True:                                                          # :1895-1945
+            it += 1
+            if it >= (len(mvpLocalKeyFrames) if mutant == "end_reevaluated" else itEndKF):
+                break
+            if len(mvpLocalKeyFrames) > LIMIT or (mutant == "size_at_least_80" and len(mvpLocalKeyFrames) >= LIMIT):
                 st["end_reason"] = 1
                 break
             pKF = mvpLocalKeyFrames[it]
@@ -152,7 +163,7 @@ def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capac
                         pNeighKF.mnTrackReferenceForFrame = frame_id
                         st["n_neighbours"] += 1
                         break
-            for pChildKF in pKF.GetChilds():
+            for pChildKF in pKF.GetChilds(by_slot=mutant == "children_slot_order"):
                 if not pChildKF.isBad():
                     if pChildKF.mnTrackReferenceForFrame != frame_id:
                         mvpLocalKeyFrames.append(pChildKF)
@@ -160,11 +171,13 @@ def update_local_keyframes_restated(G, bad, frame_rows, kf_capacity, entry_capac
                         st["n_children"] += 1
                         break
             pParent = pKF.GetParent()
-            if pParent:
+            if pParent and not (mutant == "parent_bad_tested" and pParent.isBad()):
                 if pParent.mnTrackReferenceForFrame != frame_id:
                     mvpLocalKeyFrames.append(pParent)
                     pParent.mnTrackReferenceForFrame = frame_id
                     st["n_parents"] += 1
+                    if mutant == "parent_break_inner":
+                        continue
                     st["end_reason"] = 2
                     break
         if pKFmax:                                                           # :1947-1951
@@ -256,8 +269,9 @@ class Builder:
     """A graph under construction.  kf(): a keyframe whose run holds its own row (the row = its slot) among filler rows; the frame votes for a
     keyframe by naming that row."""
 
-    def __init__(self, name):
+    def __init__(self, name, expressible=False):
         self.rng = np.random.default_rng(zlib.crc32(name.encode()))
+        self.expressible = expressible               # runs the reference's containers can hold: rows of the table or -1, no row twice in a run
         self.state, self.key = np.zeros(S, np.uint8), np.zeros(S, np.int64)
         self.runs, self.reg, self.children = {}, {}, {}
         self.neigh = np.full((S, 10), -1, np.int32)
@@ -273,10 +287,13 @@ class Builder:
         self.key[slot] = 4096 + 16 * slot if key is None else key
         if rows is None:
             n = int(self.rng.integers(1, 41)) if n is None else n
-            rows = self.rng.integers(S, 480, n).astype(np.int32)
+            rows = (self.rng.choice(np.arange(S, 480), n, replace=False) if self.expressible else self.rng.integers(S, 480, n)).astype(np.int32)
             m = self.rng.random(n)
             rows[m < 0.1] = -1
-            rows[(m >= 0.1) & (m < 0.15)] = self.rng.choice([N_ROWS, -7, 2 ** 31 - 1, int(BAD_ROWS[3])])
+            exotic = self.rng.choice([N_ROWS, -7, 2 ** 31 - 1, int(BAD_ROWS[3])])
+            if self.expressible:
+                exotic = [-1, int(BAD_ROWS[3])][int(exotic == BAD_ROWS[3] and ((m >= 0.1) & (m < 0.15)).sum() == 1)]
+            rows[(m >= 0.1) & (m < 0.15)] = exotic
             if n:
                 rows[int(self.rng.integers(0, n))] = own
         self.runs[slot] = np.asarray(rows, np.int32)
@@ -485,11 +502,12 @@ def _make_cases():
 CASES = _make_cases()
 
 
-def random_case(seed):
-    """a seeded random graph at the cases' shapes"""
+def random_case(seed, n_slots=S, expressible=False):
+    """a seeded random graph at the cases' shapes, in the first n_slots slots.  expressible: every slot reference names a present keyframe, every
+    row a row of the table or -1 and no run holds a row twice, so that the reference's own containers can hold the graph (tests/tracking_cases.py)"""
     rng = np.random.default_rng(seed)
-    b = Builder("random_%d" % seed)
-    present = rng.choice(S, int(rng.integers(1, S + 1)), replace=False)
+    b = Builder("random_%d" % seed, expressible)
+    present = rng.choice(n_slots, int(rng.integers(1, n_slots + 1)), replace=False)
     n_voters = int(rng.integers(0, min(len(present), [4, 30, 90][seed % 3]) + 1))
     for i, s in enumerate(present):
         reg = None
@@ -499,12 +517,14 @@ def random_case(seed):
         if seed % 2 and n and rng.random() < 0.3:
             b.reg[int(s)] = (rng.random(n) < 0.6).astype(np.uint8)
     for s in present:
-        b.nb(int(s), rng.integers(-2, S + 2, int(rng.integers(0, 11))).tolist())
+        slots = (lambda n: rng.choice(present, n)) if expressible else None
+        b.nb(int(s), (slots(int(rng.integers(0, 11))) if expressible else rng.integers(-2, S + 2, int(rng.integers(0, 11)))).tolist())
         if rng.random() < 0.6:
-            b.children[int(s)] = sorted({int(c) for c in rng.integers(-1, S + 1, int(rng.integers(0, 6)))}, key=lambda c: (int(b.key[c]) if 0 <= c < S else c, c))
+            drawn = slots(int(rng.integers(0, 6))) if expressible else rng.integers(-1, S + 1, int(rng.integers(0, 6)))
+            b.children[int(s)] = sorted({int(c) for c in drawn}, key=lambda c: (int(b.key[c]) if 0 <= c < S else c, c))
         if rng.random() < (0.1 if seed % 3 else 0.6):
-            b.par(int(s), int(rng.integers(-1, S + 1)))
-    b.frame += rng.integers(-3, N_ROWS + 3, int(rng.integers(0, 20))).tolist()
+            b.par(int(s), int(slots(1)[0]) if expressible else int(rng.integers(-1, S + 1)))
+    b.frame += (rng.integers(-1, N_ROWS, int(rng.integers(0, 20))) if expressible else rng.integers(-3, N_ROWS + 3, int(rng.integers(0, 20)))).tolist()
     b.frame = b.frame[:64]
     steps = [b.step()]
     if seed % 4 == 0:

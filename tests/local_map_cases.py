@@ -35,10 +35,15 @@ class MapPoint:
         return self.bad
 
 
-def update_local_points_restated(bad, keyframes, frame_rows, frame_id=7):
+MUTANTS = ("filter_dropped", "marks_for_bad_frame_points", "list_by_row", "duplicate_after_bad")
+
+
+def update_local_points_restated(bad, keyframes, frame_rows, frame_id=7, mutant=None):
     """bad: uint8[n_rows]; keyframes: the local keyframes in order, each the int rows of its GetMapPointMatches(); frame_rows: the rows of
     mCurrentFrame.mvpMapPoints or None.  A negative row is the NULL pointer; a row >= n_rows names no map point: dropped and counted.
-    Returns dict(blocked_in, local, map_points, stats): the rows of mvpLocalMapPoints and of map_points in order."""
+    Returns dict(blocked_in, local, map_points, stats): the rows of mvpLocalMapPoints and of map_points in order.  mutant: one of MUTANTS, a
+    decision of the reference's text flipped (tests/test_ref_tracking.py shows that the recorded reference output notices each but the last)."""
+    assert mutant is None or mutant in MUTANTS
     n_rows = len(bad)
     points = [MapPoint(r, bad[r]) for r in range(n_rows)]
     lookup = lambda r: points[r] if 0 <= r < n_rows else None
@@ -47,7 +52,7 @@ def update_local_points_restated(bad, keyframes, frame_rows, frame_id=7):
     mvpMapPoints = [lookup(int(r)) for r in frame_rows] if frame_rows is not None else []
     for i, pMP in enumerate(mvpMapPoints):
         if pMP:
-            if pMP.isBad():
+            if pMP.isBad() and mutant != "marks_for_bad_frame_points":
                 mvpMapPoints[i] = None
             else:
                 pMP.nVisible += 1
@@ -65,6 +70,9 @@ def update_local_points_restated(bad, keyframes, frame_rows, frame_id=7):
             if not pMP:
                 stats["n_null"] += 1
                 continue
+            if mutant == "duplicate_after_bad" and pMP.isBad():
+                stats["n_bad"] += 1
+                continue
             if pMP.mnTrackReferenceForFrame == frame_id:
                 stats["n_duplicates"] += 1
                 continue
@@ -73,10 +81,12 @@ def update_local_points_restated(bad, keyframes, frame_rows, frame_id=7):
                 pMP.mnTrackReferenceForFrame = frame_id
             else:
                 stats["n_bad"] += 1
+    if mutant == "list_by_row":
+        mvpLocalMapPoints.sort(key=lambda p: p.row)
     # Tracking.cpp:1410-1420
     map_points = []
     for pMP in mvpLocalMapPoints:
-        if pMP.mnLastFrameSeen == frame_id:
+        if pMP.mnLastFrameSeen == frame_id and mutant != "filter_dropped":
             stats["n_seen"] += 1
             continue
         if pMP.isBad():
