@@ -1276,6 +1276,123 @@ int jsorb_fuse_map_stats(jsorb_keyframe_matcher *m, int32_t counts[10]);
 /* The compile-time cap of the library in use: the entries of an observation list the applying workgroup stages at a time (256). */
 int jsorb_fuse_map_build_caps(int *list_chunk);
 
+/* ---- new map points on the device: the loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cpp:243-457) for ALL given neighbours in one
+ * call on the keyframe matcher's stream, over the state the calls above keep: SearchForTriangulation per neighbour, the triangulation of every
+ * matched pair with its gates (:297-437), and for every accepted pair new MapPoint, two AddObservation, two AddMapPoint,
+ * ComputeDistinctiveDescriptors and UpdateNormalAndDepth (:440-450; MapPoint.cpp:37-49, :385-406) - the one step that adds rows to the table.
+ * THE NEIGHBOURS ARE NOT INDEPENDENT in the reference: ORBmatcher.cpp:686-690 skips a KF1 keypoint that has a map point, and :445 gives it one as
+ * soon as a neighbour triangulates it, so the next neighbour never sees that keypoint.  With check_orientation == 0 (what :221 uses) the dependency
+ * has a closed form: a keypoint's best match in neighbour i depends on no other keypoint, a pair's verdict on nothing but the pair, so idx1 belongs
+ * to the FIRST neighbour, in list order, whose pair is accepted.
+ * The definitions of jsorb_local_keyframes_async hold: USABLE slot, valid run, (order_key, slot) order.  kp: as for jsorb_fuse_map_async, x, y =
+ * mvKeysUn.  extra: DEVICE arrays parallel to the pool - node int32 (the mFeatVec node of the keypoint, -1: none), depth (mvDepth), raw_x, raw_y
+ * (mvKeys, which KeyFrame::UnprojectStereo reads, KeyFrame.cpp:624-625; NULL: kp->x, kp->y), cos_stereo = cos(2*atan2(mb/2, mvDepth[i])) as the
+ * host's libm gives it, computed once when the keyframe is made (the device calls neither cos nor atan2); depth and cos_stereo may be NULL when
+ * kp->uright is.  state: what the call WRITES, the graph's and the table's own arrays handed over writable (another address is
+ * JSORB_ERR_INVALID), and five optional int32[n_rows] arrays: ref_slot, replaced, visible, found (both or neither), first_kf_id.
+ * HOST values: current_slot; n1 = the current keyframe's keypoints (its run's length as the caller knows it); run_capacity = a bound on the
+ * neighbours' run lengths; n_neighbours in [0, 256]; neighbour_slot[] in GetBestCovisibilityKeyFrames(nn) order after the caller's baseline tests
+ * (:250-267); pose[1 + n_neighbours], the current keyframe first; F12[9 t ..] row-major and epipole[2 t ..] per neighbour as for
+ * jsorb_search_for_triangulation_async; params with check_orientation == 0 (else JSORB_ERR_UNSUPPORTED); ratio_factor = 1.5f * mfScaleFactor;
+ * current_kf_id = mnId.  new_row: DEVICE int32[row_capacity], the free table rows in the order they are to be used, each listed once.
+ *   1. The current keyframe: current_slot usable with state 1, a valid run of exactly n1 entries; otherwise EVERY neighbour is skipped.  Neighbour t
+ *      is SKIPPED and counted when its slot is not usable, its state is not 1, its run is invalid or longer than run_capacity, or its slot equals
+ *      current_slot (SetBadFlag removes a bad keyframe from every covisibility list: the reference's list holds none).  A slot that an earlier position of
+ *      the list holds is skipped too (the reference's list holds a keyframe once).
+ *   2. e1 = point_off[current] + idx1, e2 = point_off[neighbour] + idx2.  free(e) is point_pool[e] == -1: a bad row is not free, as GetMapPoint
+ *      returns it; any other value is not free either and nothing is read through it.  stereo(e) is uright[e] >= 0 (uright NULL: never).
+ *   3. match12[t][idx1] is jsorb_search_for_triangulation_async's over (node, free, stereo, x, y, desc) of the two runs AS THEY ARE AT THE START
+ *      OF THE CALL, only_stereo and th_low from params.  A pair whose KF1 octave lies outside [0, n_levels) counts as no match (the reference
+ *      would read mvLevelSigma2 out of bounds).
+ *   4. The verdict of a pair with a match, the reference's arithmetic in its order.  Float unless said otherwise, every operation rounded on its
+ *      own, no fma, divisions and square roots correctly rounded; a float matrix product is summed left to right; norm = sqrtf of the float sum
+ *      of squares (as double where the reference multiplies or divides by it); Mat / double and double * Mat go through (float)s; Mat::dot
+ *      accumulates (double)a * (double)b left to right from the first product and returns double; .t() is exact.
+ *        xn = ((x - cx) * invfx, (y - cy) * invfy, 1); ray = Rwc xn with Rwc = Rcw^T; cosRays = (float)(dot(ray1, ray2) / (norm1 * norm2)) in double
+ *        cosS1 = cosS2 = cosRays + 1; stereo(e1): cosS1 = cos_stereo[e1]; ELSE stereo(e2): cosS2 = cos_stereo[e2]; cosS = cosS2 < cosS1 ? cosS2 : cosS1
+ *        cosRays < cosS && cosRays > 0 && (stereo(e1) || stereo(e2) || (double)cosRays < 0.9998): PATH 1, the linear triangulation.
+ *          A (4x4 float), rows xn1[0]*T1[2] - T1[0], xn1[1]*T1[2] - T1[1], xn2[0]*T2[2] - T2[0], xn2[1]*T2[2] - T2[1] with T = [Rcw | tcw].
+ *          cv::SVD::compute is DEFINED here (nothing in the reference pins it): A widened to double; one-sided (Hestenes) Jacobi on its columns,
+ *          V from the identity, EIGHT sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  Per pair (p, q), every sum over k = 0..3 from the
+ *          first product, left to right: alpha = sum A[k][p]^2, beta = sum A[k][q]^2, gamma = sum A[k][p]*A[k][q]; gamma == 0.0: no rotation;
+ *          zeta = (beta - alpha) / (2.0 * gamma); t = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta*zeta)); c = 1.0 / sqrt(1.0 + t*t);
+ *          s = c * t; for A and then V, k = 0..3: (x[k][p], x[k][q]) = (c*x[k][p] - s*x[k][q], s*x[k][p] + c*x[k][q]).  vt.row(3) = the column j of V
+ *          with the smallest sum A[k][j]^2 after the last sweep (j from 0, replaced by a later j whose sum is <=), each entry rounded to float.
+ *          Its entry 3 == 0: verdict 4; else x3D = the first three entries, each divided by entry 3 (float).
+ *        else stereo(e1) && cosS1 < cosS2: PATH 2, UnprojectStereo(idx1) of the current keyframe; else stereo(e2) && cosS2 < cosS1: PATH 3, of the
+ *          neighbour: z = depth[e]; z <= 0 (or NaN): verdict 12; xc = ((raw_x - cx) * z * invfx, (raw_y - cy) * z * invfy, z); x3D = Rwc xc + Ow
+ *        else verdict 3 (no stereo and low parallax)
+ *        z1 = (float)(dot(Rcw1 row 2, x3D) + (double)tcw1[2]); z1 <= 0: verdict 5.  z2 likewise from the neighbour: verdict 6
+ *        x1c, y1c likewise from rows 0 and 1; invz1 = (float)(1.0 / (double)z1); u = fx*x1c*invz1 + cx, v = fy*y1c*invz1 + cy; ex = u - x, ey = v - y;
+ *        not stereo(e1): (double)(ex*ex + ey*ey) > 5.991 * (double)level_sigma2[octave1]: verdict 7; stereo(e1): ur = u - mbf*invz1, er = ur - uright,
+ *        (double)(ex*ex + ey*ey + er*er) > 7.8 * (double)level_sigma2[octave1]: verdict 7.  The neighbour likewise with its own camera, octave2 and
+ *        THE CURRENT KEYFRAME'S mbf (the reference's :412): verdict 8
+ *        dist1 = norm(x3D - Ow1), dist2 = norm(x3D - Ow2); either == 0: verdict 9.  ratioDist = dist2 / dist1, ratioOctave = scale_factor[octave1] /
+ *        scale_factor[octave2]; ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor: verdict 10.  Otherwise ACCEPTED
+ *   5. idx1 goes to the first neighbour in order whose pair is accepted; its pairs (matches) with later neighbours get verdict 2 (taken), path 0
+ *      and x3D 0, as the reference never looks at them.
+ *   6. The accepted owning pairs are numbered k = 0, 1, .. in (neighbour, ascending idx1) order, the order of :292.  Pair k gets r = new_row[k].
+ *      k >= row_capacity or r outside [0, n_rows): verdict 11 (no row), counted and dropped, nothing is written through it - but it still owns its
+ *      idx1.  (The reference always has memory for a point: the caller sizes the list.)  Every other one has verdict 1 (created).
+ *   7. Per created pair, row r: P = x3D; bad = 0; ref_slot = current_slot, replaced = -1, visible = found = 1, first_kf_id = current_kf_id (where
+ *      given); point_pool[e1] = r, registered[e1] = 1, and the same for e2 (8.); desc[r] = rule 4 of jsorb_distinctive_descriptors_async for the two
+ *      observations in (order_key, slot) order: kp->desc of whichever of the two keyframes comes first; UpdateNormalAndDepth over the same two in
+ *      that order: normal = 0 + n_a / norm(n_a) + n_b / norm(n_b) per component with n_i = P - Ow_i, Pn = normal / 2.0f; dist = norm(P - Ow1);
+ *      MaxDistance = dist * scale_factor[octave1]; invariance_maxDistance = 1.2f * MaxDistance; invariance_minDistance = 0.8f * (MaxDistance /
+ *      scale_factor[n_levels - 1]).
+ *   8. vbMatched2 is never set in the reference, so two created pairs of one neighbour may share idx2; pKF2->AddMapPoint overwrites, so the pair
+ *      LATER in order gets point_pool[e2].  The earlier point's fields are what the reference computed at its creation, but it loses its KF2
+ *      observation in the pool where the reference's mObservations keeps it: a stated difference, counted (counts[4]).  The rule is an atomicMax
+ *      of the pair's position t * n1 + idx1 per (t, idx2): one word per gathered KF2 keypoint, no sort.
+ *   9. CheckNewKeyFrames() (:245) cannot be polled from inside a call: the call does all the neighbours it is given.
+ * Outputs (DEVICE, every entry written): verdict int32[n_neighbours x n1]: 0 no match, 1 created, 2 taken, 3 low parallax, 4 w == 0, 5 z1 <= 0,
+ * 6 z2 <= 0, 7 reprojection in KF1, 8 reprojection in KF2, 9 zero distance, 10 scale ratio, 11 no row, 12 empty unprojection, 13 skipped neighbour;
+ * path uint8[n_neighbours x n1]: 0 none, 1 SVD, 2 UnprojectStereo of KF1, 3 of KF2; x3D float[n_neighbours x n1 x 3] (0 where path is 0);
+ * log_out int32[log_cap][4], -1 padded: record k = (row or -1 for a pair with no row, idx1, neighbour, idx2) of owning pair k - the map writes are
+ * complete whatever log_cap is; counts_dev int32[12] = pairs with a match, accepted pairs (before 5.), owning pairs, created, shared KF2
+ * keypoints (8.), pairs with no row, taken, skipped neighbours, 1 when the owning pairs exceed log_cap, pairs on path 1, on paths 2 and 3, 1 when
+ * the current keyframe failed 1.
+ * Enqueued on the matcher's stream, no host decision after the argument checks, launch shapes from the host sizes alone, capturable once the
+ * scratch has its size; every slot, run and row is range-checked before use.  Kernels: k_np_gather, k_bow_group, k_tri_match (as they are),
+ * k_np_verdict (16 neighbours' poses per launch), k_np_own, k_np_count, k_np_scan, k_np_write, k_np_link, k_np_finish.
+ * JSORB_ERR_INVALID: a NULL required pointer, a state array that is not the graph's or the table's, graph->registered NULL, descriptors not 16-byte
+ * aligned, n_neighbours outside [0, 256], kp->pool_entries != graph->pool_entries, depth or cos_stereo NULL while kp->uright is given, visible
+ * without found, n_levels, th_low out of range, a negative size, n1 or run_capacity of 262144 or more.  JSORB_ERR_UNSUPPORTED: check_orientation
+ * != 0, n_neighbours x max(n1, run_capacity) of 2^24 or more.  n_neighbours == 0 and an empty current run are valid calls. */
+typedef struct jsorb_keyframe_pose {
+    float Rcw[9], tcw[3], Ow[3];             /* GetRotation (row-major), GetTranslation, GetCameraCenter */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+} jsorb_keyframe_pose;
+typedef struct jsorb_new_point_keypoints {  /* DEVICE arrays parallel to graph->point_pool */
+    const int32_t *node;
+    const float *depth, *raw_x, *raw_y, *cos_stereo;
+} jsorb_new_point_keypoints;
+typedef struct jsorb_new_point_state {
+    int32_t *point_pool;
+    uint8_t *registered;
+    uint8_t *bad, *desc;
+    float *Px, *Py, *Pz, *Pnx, *Pny, *Pnz, *MaxDistance, *invariance_maxDistance, *invariance_minDistance;
+    int32_t *ref_slot, *replaced, *visible, *found, *first_kf_id;
+} jsorb_new_point_state;
+int jsorb_create_new_map_points_async(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, const jsorb_keyframe_graph *graph,
+                                      const jsorb_map_point_table *table, const jsorb_keyframe_keypoints *kp, const jsorb_new_point_keypoints *extra,
+                                      const jsorb_new_point_state *state, int current_slot, int n1, int run_capacity, int n_neighbours,
+                                      const int32_t *neighbour_slot, const jsorb_keyframe_pose *pose, const float *F12, const float *epipole,
+                                      float ratio_factor, int current_kf_id, int row_capacity, const int32_t *new_row, int log_cap, int32_t *verdict,
+                                      uint8_t *path, float *x3D, int32_t *log_out, int32_t *counts_dev);
+/* Synchronous: the same, then the outputs in one wait (host arrays of the same sizes). */
+int jsorb_create_new_map_points(jsorb_keyframe_matcher *m, const jsorb_triangulation_params *params, const jsorb_keyframe_graph *graph,
+                                const jsorb_map_point_table *table, const jsorb_keyframe_keypoints *kp, const jsorb_new_point_keypoints *extra,
+                                const jsorb_new_point_state *state, int current_slot, int n1, int run_capacity, int n_neighbours,
+                                const int32_t *neighbour_slot, const jsorb_keyframe_pose *pose, const float *F12, const float *epipole,
+                                float ratio_factor, int current_kf_id, int row_capacity, const int32_t *new_row, int log_cap, int32_t *verdict,
+                                uint8_t *path, float *x3D, int32_t *log_out, int32_t *counts_dev, int32_t *verdict_host, uint8_t *path_host,
+                                float *x3D_host, int32_t *log_host, int32_t counts_host[12]);
+/* The counts of the last jsorb_create_new_map_points* (waits for it): counts[12] as above.  JSORB_ERR_STATE before the first call. */
+int jsorb_create_new_map_points_stats(jsorb_keyframe_matcher *m, int32_t counts[12]);
+/* The compile-time cap of the library in use: pairs per chunk of the order-preserving compaction (1024). */
+int jsorb_create_new_map_points_build_caps(int *scan_chunk);
+
 /* ---- the keyframe database: KeyFrameDatabase (src/KeyFrameDatabase.cpp:44-313) with DBoW2's BowVector fold (BowVector.cpp:34-84 as
  * TemplatedVocabulary.h:1148-1193 drives it) and L1Scoring::score (ScoringObject.cpp:23-68), for the ORB vocabulary's combination only: TF-IDF
  * weights, L1 norm, L1 score.  An object of its own like the keyframe matcher: its stream, its scratch, its error text; whoever creates none

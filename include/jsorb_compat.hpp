@@ -1046,6 +1046,73 @@ private:
     detail::DeviceArray<int32_t> replaced_, visible_, found_;
     jsorb_fuse_state v_{};
 };
+// What CreateNewMapPoints reads of the keyframes' keypoints beyond KeyframeKeypoints (jsorb_new_point_keypoints, include/jsorb.h): device arrays
+// parallel to the graph's point_pool - the mFeatVec node of every keypoint (-1: none), and for a stereo map mvDepth, cos(2*atan2(mb/2, mvDepth[i]))
+// from the host's libm, and mvKeys (which KeyFrame::UnprojectStereo reads).
+class NewPointKeypoints {
+public:
+    NewPointKeypoints(const KeyframeGraph &graph, bool stereo) : pool_(graph.pool_entries()), node_(CLS, entries(), -1)
+    {
+        if (stereo) { depth_.alloc(CLS, entries(), -1.0f); cos_.alloc(CLS, entries(), 1.0f); raw_x_.alloc(CLS, entries()); raw_y_.alloc(CLS, entries()); }
+    }
+    jsorb_new_point_keypoints view() const { return jsorb_new_point_keypoints{node_.ptr(), depth_.ptr(), raw_x_.ptr(), raw_y_.ptr(), cos_.ptr()}; }
+    // the keyframe in `slot`, one entry per entry of its run (after graph.set_keyframe); the last four may be NULL for a monocular keyframe
+    void set_keyframe(const KeyframeGraph &graph, int slot, const std::vector<int32_t> &node, const std::vector<float> *depth, const std::vector<float> *cos_stereo,
+                      const std::vector<float> *raw_x, const std::vector<float> *raw_y)
+    {
+        const size_t at = (size_t)graph.point_offset(slot), n = node.size();
+        const std::vector<float> *const f[4] = {depth, cos_stereo, raw_x, raw_y};
+        bool ok = n == (size_t)graph.point_length(slot) && at + n <= entries();
+        for (const std::vector<float> *v : f) ok = ok && (!v || (v->size() == n && depth_.ptr()));
+        if (!ok) throw std::runtime_error("jsorb::NewPointKeypoints: one node, depth, cos_stereo and raw point per entry of the run");
+        node_.upload(at, node.data(), n);
+        detail::DeviceArray<float> *const d[4] = {&depth_, &cos_, &raw_x_, &raw_y_};
+        for (int i = 0; i < 4; i++)
+            if (f[i]) d[i]->upload(at, f[i]->data(), n);
+    }
+
+private:
+    static constexpr const char *CLS = "NewPointKeypoints";
+    size_t entries() const { return pool_ > 0 ? pool_ : 0; }
+    int pool_ = 0;
+    detail::DeviceArray<int32_t> node_;
+    detail::DeviceArray<float> depth_, cos_, raw_x_, raw_y_;
+};
+// The arrays jsorb_create_new_map_points writes (jsorb_new_point_state): the graph's point_pool / registered and the table's arrays once more as
+// writable pointers, and mpRefKF as a slot, mpReplaced as a row, mnVisible, mnFound and mnFirstKFid per table row, which this class owns.
+class NewPointState {
+public:
+    NewPointState(const KeyframeGraph &graph, const MapPointTable &table)
+        : ref_slot_(CLS, rows(table), -1), replaced_(CLS, rows(table), -1), visible_(CLS, rows(table)), found_(CLS, rows(table)), first_kf_id_(CLS, rows(table), -1)
+    {
+        const jsorb_keyframe_graph g = graph.view();
+        const jsorb_map_point_table t = table.view();
+        auto w = [](const float *p) { return const_cast<float *>(p); };
+        v_ = jsorb_new_point_state{const_cast<int32_t *>(g.point_pool), const_cast<uint8_t *>(g.registered), const_cast<uint8_t *>(t.bad),
+                                   const_cast<uint8_t *>(t.desc), w(t.Px), w(t.Py), w(t.Pz), w(t.Pnx), w(t.Pny), w(t.Pnz), w(t.MaxDistance),
+                                   w(t.invariance_maxDistance), w(t.invariance_minDistance), ref_slot_.ptr(), replaced_.ptr(), visible_.ptr(), found_.ptr(),
+                                   first_kf_id_.ptr()};
+    }
+    const jsorb_new_point_state &view() const { return v_; }
+    int ref_slot(int row) const { return ref_slot_.get(row); }            // mpRefKF as a slot
+    int first_kf_id(int row) const { return first_kf_id_.get(row); }      // mnFirstKFid
+
+private:
+    static constexpr const char *CLS = "NewPointState";
+    static size_t rows(const MapPointTable &table) { return table.n_rows() > 0 ? table.n_rows() : 0; }
+    detail::DeviceArray<int32_t> ref_slot_, replaced_, visible_, found_, first_kf_id_;
+    jsorb_new_point_state v_{};
+};
+// What CreateNewMapPoints gives back: per (neighbour, idx1) the verdict (jsorb.h: 0 no match, 1 created, 2 taken, 3 .. 10 the gates, 11 no row, 12
+// empty unprojection, 13 skipped neighbour), the path (1 SVD, 2 / 3 UnprojectStereo) and x3D; the new points in creation order as (row, idx1,
+// neighbour, idx2) - what `new MapPoint`, the two AddObservation and the two AddMapPoint of the host objects follow; the counts.
+struct NewMapPoints {
+    std::vector<int32_t> verdict;
+    std::vector<unsigned char> path;
+    std::vector<float> x3D;
+    std::vector<std::array<int32_t, 4>> created;
+    int32_t counts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
 // What FuseMap gives back: per (target, list point) the keypoint searched (-1: none) with its distance and, for the overload with Scw,
 // vpReplacePoint as a row; nFused per target; the Replace (2, p, q, -1) and AddMapPoint (3, row, slot, keypoint) events in order; the counts of
 // jsorb_fuse_map.
@@ -1322,6 +1389,42 @@ inline int FuseMap(jsorb::KeyframeMatcher &matcher, const jsorb_fuse_params &prm
     result.events.clear();
     for (size_t i = 0; i < cap && log[4 * i] >= 0; i++) result.events.push_back({log[4 * i], log[4 * i + 1], log[4 * i + 2], log[4 * i + 3]});
     return result.counts[0];
+}
+
+// The loop of LocalMapping::CreateNewMapPoints (LocalMapping.cpp:243-457) for the keyframe in `current_slot` (n1 keypoints) and ALL `neighbours`
+// (slots in GetBestCovisibilityKeyFrames order, after the caller's baseline tests) on the device state: matching, triangulation, the gates, and for
+// every accepted pair the new row with its two observations, descriptor, normal and distance range.  poses: 1 + neighbours records, the current
+// keyframe first; F12, epipole: 9 and 2 floats per neighbour as for SearchForTriangulation; new_rows: the free table rows in the order they are to
+// be used.  A keypoint belongs to the first neighbour whose pair is accepted (the reference's loop gives the same: ORBmatcher.cpp:686-690).
+// Returns the points created.  The host objects follow from result.created.
+inline int CreateNewMapPoints(jsorb::KeyframeMatcher &matcher, const jsorb_triangulation_params &prm, const jsorb::KeyframeGraph &graph,
+                              const jsorb::MapPointTable &table, const jsorb::KeyframeKeypoints &kp, const jsorb::NewPointKeypoints &extra,
+                              jsorb::NewPointState &state, int current_slot, int n1, int run_capacity, const std::vector<int32_t> &neighbours,
+                              const std::vector<jsorb_keyframe_pose> &poses, const float *F12, const float *epipole, float ratio_factor, int current_kf_id,
+                              const std::vector<int32_t> &new_rows, jsorb::NewMapPoints &result)
+{
+    const size_t T = neighbours.size(), pairs = T * (size_t)(n1 > 0 ? n1 : 0), R = new_rows.size(), cap = R ? R : 1;
+    if (poses.size() != T + 1 || (T && (!F12 || !epipole))) throw std::runtime_error("CreateNewMapPoints: 1 + T poses, 9 F12 and 2 epipole floats per neighbour");
+    if (n1 != graph.point_length(current_slot)) throw std::runtime_error("CreateNewMapPoints: n1 is not the length of the current keyframe's run");
+    jsorb::DeviceInts rows(R), out(pairs + 3 * pairs + (pairs + 3) / 4 + 4 * cap + 12);
+    if (R && jsorb_mem_h2d(rows.p, new_rows.data(), R * sizeof(int32_t)) != JSORB_OK) throw std::runtime_error("CreateNewMapPoints: upload failed");
+    int32_t *vd = out.p, *lg = vd + pairs + 3 * pairs, *cn = lg + 4 * cap;
+    float *x3 = reinterpret_cast<float *>(vd + pairs);
+    uint8_t *pt = reinterpret_cast<uint8_t *>(cn + 12);
+    const jsorb_keyframe_graph g = graph.view();
+    const jsorb_map_point_table t = table.view();
+    const jsorb_keyframe_keypoints k = kp.view();
+    const jsorb_new_point_keypoints e = extra.view();
+    result.verdict.assign(pairs, 0); result.path.assign(pairs, 0); result.x3D.assign(3 * pairs, 0.0f);
+    std::vector<int32_t> log(4 * cap, -1);
+    const int rc = jsorb_create_new_map_points(matcher.handle(), &prm, &g, &t, &k, &e, &state.view(), current_slot, n1, run_capacity, (int)T, neighbours.data(),
+                                               poses.data(), F12, epipole, ratio_factor, current_kf_id, (int)R, rows.p, (int)cap, vd, pt, x3, lg, cn,
+                                               result.verdict.data(), result.path.data(), result.x3D.data(), log.data(), result.counts);
+    if (rc != JSORB_OK) throw std::runtime_error(std::string("jsorb_create_new_map_points: ") + jsorb_keyframe_matcher_last_error(matcher.handle()));
+    result.created.clear();
+    for (size_t i = 0; i < cap && log[4 * i + 1] >= 0; i++)
+        if (log[4 * i] >= 0) result.created.push_back({log[4 * i], log[4 * i + 1], log[4 * i + 2], log[4 * i + 3]});
+    return result.counts[3];
 }
 
 // LocalMapping::KeyFrameCulling (LocalMapping.cpp:638-702) for the current keyframe, with the whole of SetBadFlag (KeyFrame.cpp:457-549) for every

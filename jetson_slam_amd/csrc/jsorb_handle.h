@@ -355,7 +355,7 @@ struct jsorb_keyframe_matcher {
     // (triangulation, BoW) or best_idx and best_dist (fuse), out_cap entries each; sim3: the count, then match1, match2 and match12, out_cap in all;
     // scw: the count, then match_kp, match_dist and kp_match, out_cap in all
     // distinct: best_obs, then best_median, out_cap entries each
-    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, COVIS, CULL, FUSE_MAP, N_CALLS };
+    enum { TRIANGULATION, FUSE, BOW_KF, SIM3, SCW, DISTINCT, COVIS, CULL, FUSE_MAP, NEW_POINTS, N_CALLS };
     KfCall call[N_CALLS];
     int32_t *grid_start = nullptr, *grid_items = nullptr;       // fuse, sim3: n_keyframes x (cells + 1) starts (grid_cap), the keypoints' items (items_cap)
     int grid_cap = 0, items_cap = 0;
@@ -376,6 +376,7 @@ struct jsorb_keyframe_matcher {
     } covis;
     WordBuf cull;                                               // jsorb_cull_keyframes* (jsorb_culling.hip): the observations grouped by row, the rounds' verdicts, the tree repair's lists (CullArgs)
     WordBuf fmap;                                               // jsorb_fuse_map* (jsorb_fuse_apply.hip): the observation index, the stamps, the target's grid, list points and CSR (FuseMapArgs)
+    WordBuf npts;                                               // jsorb_create_new_map_points* (jsorb_new_points.hip): the gathered sides, the matches, the compaction (NewPointsArgs)
     WordBuf staging;                                            // the synchronous forms of the three: their outputs gathered for one copy back (read_back; the call waits for it)
     std::string err;
 };

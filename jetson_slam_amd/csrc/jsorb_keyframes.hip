@@ -40,7 +40,7 @@ void jsorb_keyframe_matcher_destroy(jsorb_keyframe_matcher *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipStreamSynchronize(m->stream);
-    free_device(m->sort1, m->sort2, m->grid_start, m->grid_items, m->matched2, m->scw.cand, m->scw.cand_n, m->distinct.list, m->covis.row.word, m->covis.slot, m->cull.p, m->fmap.p, m->staging.p);
+    free_device(m->sort1, m->sort2, m->grid_start, m->grid_items, m->matched2, m->scw.cand, m->scw.cand_n, m->distinct.list, m->covis.row.word, m->covis.slot, m->cull.p, m->fmap.p, m->npts.p, m->staging.p);
     for (KfCall &c : m->call) free_device(c.stats, c.out);
     destroy_event(m->ev_switch);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);

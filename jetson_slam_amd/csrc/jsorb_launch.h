@@ -335,6 +335,47 @@ void launch_fuse_map_index(const FuseMapArgs &a, hipStream_t s);
 void launch_fuse_map_head(const FuseMapArgs &a, int t, int slot, hipStream_t s);      // the snapshot, the grid, the head tests and the gather
 void launch_fuse_map_apply(const FuseMapArgs &a, int t, int slot, hipStream_t s);     // the walk, the Replace loop, the CSR of the marked rows
 void launch_fuse_map_finish(const FuseMapArgs &a, hipStream_t s);
+// k_np_* (k_new_points.hip): LocalMapping::CreateNewMapPoints' loop over the device state (jsorb_create_new_map_points_async); the matching is
+// launch_bow_group / launch_tri_match over the sides k_np_gather copies out of the pool runs
+#define NP_COUNTS 12
+#define NP_KF_CHUNK 16                          // neighbours whose poses one k_np_verdict launch carries in its arguments
+struct NewPointsArgs {
+    jsorb_keyframe_graph g;
+    jsorb_keyframe_keypoints kp;
+    jsorb_new_point_keypoints ex;
+    jsorb_new_point_state st;
+    int n_rows, current_slot, n1, cap, n_nb;     // cap: run_capacity, the stride of a neighbour in the gathered KF2 side
+    int row_capacity, log_cap, current_kf_id, n_levels;
+    float ratio_factor;
+    float scale_factor[JSORB_MAX_LEVELS];
+    double chi2_mono[JSORB_MAX_LEVELS], chi2_stereo[JSORB_MAX_LEVELS];      // 5.991 * (double)mvLevelSigma2[l], 7.8 * (double)mvLevelSigma2[l]
+    const int32_t *new_row;
+    // the gathered sides (TriArgs' inputs): KF1's n1 entries, neighbour t at t * cap
+    int32_t *node1, *node2, *octave2;
+    uint8_t *free1, *free2, *stereo1, *stereo2, *desc1, *desc2;
+    float *x1, *y1, *x2, *y2;
+    int32_t *info;                               // [0] the current run's offset, [1 + t] neighbour t's; -1: skipped
+    int32_t *nb_slot;                            // [n_nb] the neighbours' slots
+    float *ow;                                   // [3 (n_nb + 1)] the neighbours' camera centres, then the current keyframe's (k_np_verdict writes them from its poses, k_np_write reads them)
+    int32_t *match12;                            // n_nb x n1 (cleared to -1)
+    int32_t *claim;                              // n_nb x cap (cleared to -1): the last creating pair of a KF2 keypoint
+    int32_t *pair_row;                           // n_nb x n1: the table row of a created pair
+    unsigned *chunk_sum, *chunk_pre;             // the compaction: creating pairs per chunk, their exclusive prefix (chunks + 1)
+    int32_t *verdict;
+    uint8_t *path;
+    float *x3D;
+    int32_t *log_out, *counts_dev;
+    int *stats;                                  // NP_COUNTS words (cleared to 0)
+};
+struct NewPointsSlots { int32_t slot[JSORB_BOW_MAX_KEYFRAMES]; };
+struct NewPointsPoses {
+    int kf0, n;                                  // the launch's neighbours kf0 .. kf0 + n
+    jsorb_keyframe_pose cur, nb[NP_KF_CHUNK];
+};
+int new_points_chunk();                          // the compile-time cap of k_new_points.hip (jsorb_create_new_map_points_build_caps)
+void launch_new_points_gather(const NewPointsArgs &a, const NewPointsSlots &s, hipStream_t st);
+void launch_new_points_verdict(const NewPointsArgs &a, const NewPointsPoses &p, hipStream_t st);
+void launch_new_points_apply(const NewPointsArgs &a, hipStream_t st);      // ownership, compaction, the rows' writes, the KF2 entries, the counts
 // k_loop_bow_match (k_loop.hip): ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) for several candidates KF2 of LoopClosing::ComputeSim3; the grouping
 // is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over the same rows
 struct LoopBowArgs {

@@ -83,6 +83,7 @@ EXPORTS = [
     "jsorb_update_connections_scratch",
     "jsorb_cull_keyframes_async", "jsorb_cull_keyframes", "jsorb_cull_keyframes_stats", "jsorb_cull_keyframes_build_caps",
     "jsorb_fuse_map_async", "jsorb_fuse_map", "jsorb_fuse_map_stats", "jsorb_fuse_map_build_caps",
+    "jsorb_create_new_map_points_async", "jsorb_create_new_map_points", "jsorb_create_new_map_points_stats", "jsorb_create_new_map_points_build_caps",
 ]
 
 
@@ -721,6 +722,89 @@ def fuse_state(graph, table, replaced=None, visible=None, found=None):
     return JsorbFuseState(graph.point_pool.data_ptr(), graph.registered.data_ptr(), table.bad.data_ptr(), table.desc.data_ptr(), p(replaced), p(visible), p(found))
 
 
+class JsorbNewPointKeypoints(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("node", "depth", "raw_x", "raw_y", "cos_stereo")]
+
+
+class JsorbNewPointState(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("point_pool", "registered", "bad", "desc") + MAP_POINT_FLOATS[:6] +
+                ("MaxDistance", "invariance_maxDistance", "invariance_minDistance", "ref_slot", "replaced", "visible", "found", "first_kf_id")]
+
+
+# jsorb_keyframe_pose: what create_new_map_points takes per keyframe, the current one first (make_keyframe_pose)
+KEYFRAME_POSE_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3)] +
+                               [(k, "<f4") for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")])
+NEW_POINTS_COUNTS = ("n_matches", "n_accepted", "n_owning", "n_created", "n_shared_kf2", "n_no_row", "n_taken", "n_skipped_neighbours", "log_overflow",
+                     "n_svd", "n_unprojected", "no_current")
+NEW_POINTS_OUTPUTS = ("verdict", "path", "x3D", "log", "counts")
+# the verdict codes of create_new_map_points, one per exit of LocalMapping.cpp:297-437
+NEW_POINTS_VERDICTS = ("no_match", "created", "taken", "low_parallax", "w_zero", "z1", "z2", "reprojection1", "reprojection2", "zero_distance",
+                       "scale_ratio", "no_row", "empty_unprojection", "skipped_neighbour")
+NP_PATH_NONE, NP_PATH_SVD, NP_PATH_UNPROJECT1, NP_PATH_UNPROJECT2 = 0, 1, 2, 3
+
+
+def make_keyframe_pose(Rcw, tcw, camera, mb=0.0, mbf=0.0, Ow=None):
+    """one jsorb_keyframe_pose record (KEYFRAME_POSE_DTYPE): Rcw (3x3) and tcw (3) as float32, camera = (fx, fy, cx, cy), mb and mbf the keyframe's.
+    invfx, invfy = 1.0f / fx, 1.0f / fy (Frame.cpp); Ow = -Rcw^T tcw in float32 summed left to right unless given (KeyFrame::SetPose)"""
+    R = np.asarray(Rcw, np.float32).reshape(3, 3)
+    t = np.asarray(tcw, np.float32).reshape(3)
+    if Ow is None:
+        Ow = np.array([-((R[0, i] * t[0] + R[1, i] * t[1]) + R[2, i] * t[2]) for i in range(3)], np.float32)
+    fx, fy, cx, cy = (np.float32(v) for v in camera)
+    rec = np.zeros((), KEYFRAME_POSE_DTYPE)
+    rec["Rcw"], rec["tcw"], rec["Ow"] = R.ravel(), t, np.asarray(Ow, np.float32).reshape(3)
+    rec["fx"], rec["fy"], rec["cx"], rec["cy"] = fx, fy, cx, cy
+    rec["invfx"], rec["invfy"], rec["mb"], rec["mbf"] = np.float32(1) / fx, np.float32(1) / fy, np.float32(mb), np.float32(mbf)
+    return rec
+
+
+class NewPointKeypoints:
+    """What CreateNewMapPoints reads of the keyframes' keypoints beyond KeyframeKeypoints (jsorb_new_point_keypoints): torch device arrays parallel
+    to a KeyframeGraph's point_pool - node int32 (the mFeatVec node, -1: none), depth float32 (mvDepth), cos_stereo float32 (cos(2*atan2(mb/2,
+    depth)) from the host's libm), raw_x / raw_y float32 (mvKeys; raw=False: the undistorted points are used)."""
+    ARRAYS = ("node", "depth", "raw_x", "raw_y", "cos_stereo")
+
+    def __init__(self, graph, stereo=True, raw=True):
+        import torch
+        dev = graph.point_pool.device
+        n = max(graph.pool_entries, 1)
+        self.node = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.depth, self.cos_stereo = ((torch.full((n,), v, dtype=torch.float32, device=dev) if stereo else None) for v in (-1.0, 1.0))
+        self.raw_x, self.raw_y = ((torch.zeros(n, dtype=torch.float32, device=dev) if raw else None) for _ in range(2))
+
+    def struct(self):
+        return JsorbNewPointKeypoints(*[None if getattr(self, k) is None else getattr(self, k).data_ptr() for k in self.ARRAYS])
+
+    def load(self, **arrays):
+        """whole arrays at once (numpy)"""
+        import torch
+        for k, v in arrays.items():
+            t = getattr(self, k, None) if k in self.ARRAYS else None
+            if t is None:
+                raise JsorbError("NewPointKeypoints.load: no array %s" % k)
+            v = torch.from_numpy(np.ascontiguousarray(v)).to(t.device)
+            if v.dtype != t.dtype or v.numel() > t.numel():
+                raise JsorbError("NewPointKeypoints.load: %s must be %s with at most %d entries" % (k, t.dtype, t.numel()))
+            t.view(-1)[:v.numel()].copy_(v.view(-1))
+
+
+def new_point_state(graph, table, ref_slot=None, replaced=None, visible=None, found=None, first_kf_id=None):
+    """jsorb_new_point_state: the graph's point_pool / registered and the table's arrays as the writable pointers jsorb_create_new_map_points takes,
+    with ref_slot, replaced, visible, found, first_kf_id int32[n_rows] device tensors (or None; visible and found both or neither).  The caller
+    keeps the tensors alive."""
+    import torch
+    if graph.registered is None:
+        raise JsorbError("new_point_state: the graph has no registered bytes (the call writes them)")
+    side = (("ref_slot", ref_slot), ("replaced", replaced), ("visible", visible), ("found", found), ("first_kf_id", first_kf_id))
+    for name, t in side:
+        if t is not None and (t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < table.n_rows):
+            raise JsorbError("new_point_state: %s must be a contiguous int32 device tensor of at least %d entries" % (name, table.n_rows))
+    if (visible is None) != (found is None):
+        raise JsorbError("new_point_state: visible and found go together")
+    return JsorbNewPointState(graph.point_pool.data_ptr(), graph.registered.data_ptr(), table.bad.data_ptr(), table.desc.data_ptr(),
+                              *[table.floats[i].data_ptr() for i in range(9)], *[None if t is None else t.data_ptr() for _, t in side])
+
+
 def make_camera(K, D):
     """jsorb_camera from Tracking's mK (3x3) and mDistCoef (k1, k2, p1, p2[, k3]) - both taken as float32, as the reference stores them (Tracking.cpp:80-91)"""
     K = np.asarray(K, np.float32)
@@ -943,6 +1027,14 @@ def load_library(path=None):
                                C.POINTER(JsorbKeyframeKeypoints), C.POINTER(JsorbFuseState), I, P, I] + [P] * 8 + [I, P, P] + [P] * 6),
         "jsorb_fuse_map_stats": (I, [P, P]),
         "jsorb_fuse_map_build_caps": (I, [C.POINTER(I)]),
+        "jsorb_create_new_map_points_async": (I, [P, C.POINTER(JsorbTriangulationParams), C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable),
+                                                  C.POINTER(JsorbKeyframeKeypoints), C.POINTER(JsorbNewPointKeypoints), C.POINTER(JsorbNewPointState),
+                                                  I, I, I, I, P, P, P, P, C.c_float, I, I, P, I] + [P] * 5),
+        "jsorb_create_new_map_points": (I, [P, C.POINTER(JsorbTriangulationParams), C.POINTER(JsorbKeyframeGraph), C.POINTER(JsorbMapPointTable),
+                                            C.POINTER(JsorbKeyframeKeypoints), C.POINTER(JsorbNewPointKeypoints), C.POINTER(JsorbNewPointState),
+                                            I, I, I, I, P, P, P, P, C.c_float, I, I, P, I] + [P] * 10),
+        "jsorb_create_new_map_points_stats": (I, [P, P]),
+        "jsorb_create_new_map_points_build_caps": (I, [C.POINTER(I)]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1736,6 +1828,76 @@ class KeyframeMatcher:
         v = np.zeros(10, np.int32)
         self._chk(self._lib.jsorb_fuse_map_stats(self._m, v.ctypes.data))
         return dict(zip(FUSE_MAP_COUNTS, (int(x) for x in v)))
+
+    # ---- new map points: the loop of LocalMapping::CreateNewMapPoints (LocalMapping.cpp:243-457) ----
+    def create_new_map_points(self, params, graph, table, kp, extra, state, current_slot, n1, run_capacity, neighbour_slots, poses, F12, epipole,
+                              ratio_factor, current_kf_id, new_row, log_cap=None, sync=False, wait=True, out=None):
+        """jsorb_create_new_map_points*: matching, triangulation and the new rows for the keyframe in `current_slot` (n1 keypoints) against the
+        neighbours `neighbour_slots` (HOST sequence of slots in GetBestCovisibilityKeyFrames order, at most 256, each run at most run_capacity
+        long) on the device state: graph a KeyframeGraph, table a MapPointTable, kp a KeyframeKeypoints, extra a NewPointKeypoints, state a
+        new_point_state(graph, table, ...).  params from make_triangulation_params(check_orientation=False); poses KEYFRAME_POSE_DTYPE[1 + T], the
+        current keyframe first; F12 host float32[T, 9], epipole host float32[T, 2]; new_row the free table rows in the order they are used (an
+        int32 device tensor, or a host sequence that is uploaded).  log_cap: records the log holds (default len(new_row)).  Returns a dict of device
+        tensors: verdict int32[T, n1], path uint8[T, n1], x3D float32[T, n1, 3], log int32[log_cap, 4] (-1 padded: (row, idx1, neighbour, idx2) per
+        owning pair), counts int32[12] (NEW_POINTS_COUNTS); with sync=True the same as numpy arrays under *_host.  out: the dict of an earlier
+        call with the same sizes, written again.  The call waits for the current torch stream before it enqueues, except with wait=False, out
+        given and new_row a device tensor: then it makes no tensor, waits for nothing and only enqueues - the form a graph capture takes."""
+        import torch
+        what = "create_new_map_points"
+        if not isinstance(params, JsorbTriangulationParams):
+            raise JsorbError("%s: params must come from make_triangulation_params" % what)
+        dev = graph.point_pool.device
+        new_row, made = _uploaded_i32(new_row, dev)
+        new_row = new_row.reshape(-1)
+        n_new = int(new_row.numel())
+        rp = _i32_ptr("%s: new_row" % what, new_row) if n_new else None
+        ns = np.ascontiguousarray(neighbour_slots, np.int32).reshape(-1)
+        T, n1 = len(ns), int(n1)
+        ps = np.ascontiguousarray(poses, KEYFRAME_POSE_DTYPE).reshape(-1)
+        F, ep = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (F12, epipole))
+        if len(ps) != T + 1 or len(F) != 9 * T or len(ep) != 2 * T:
+            raise JsorbError("%s: poses must hold 1 + T records, F12 9 and epipole 2 floats per neighbour" % what)
+        cap = n_new if log_cap is None else int(log_cap)
+        shapes = dict(verdict=(T, n1), path=(T, n1), x3D=(T, n1, 3), log=(max(cap, 0), 4), counts=(12,))
+        dtypes = dict(verdict=torch.int32, path=torch.uint8, x3D=torch.float32, log=torch.int32, counts=torch.int32)
+        size = {k: int(np.prod(shapes[k])) for k in NEW_POINTS_OUTPUTS}
+        made = made or out is None
+        bufs = out["_bufs"] if out is not None else {k: torch.empty(max(size[k], 1), dtype=dtypes[k], device=dev) for k in NEW_POINTS_OUTPUTS}
+        gs, tb, ks, es = graph.struct(), table.struct(), kp.struct(), extra.struct()
+        args = [self._m, C.byref(params), C.byref(gs), C.byref(tb), C.byref(ks), C.byref(es), C.byref(state), int(current_slot), n1, int(run_capacity), T,
+                ns.ctypes.data, ps.ctypes.data, F.ctypes.data, ep.ctypes.data, float(ratio_factor), int(current_kf_id), n_new, rp, cap] + \
+               [bufs[k].data_ptr() for k in NEW_POINTS_OUTPUTS]
+        if wait or sync or made:
+            torch.cuda.current_stream(dev).synchronize()     # (tensors were made on it)
+        out = {k: bufs[k][:size[k]].reshape(shapes[k]) for k in NEW_POINTS_OUTPUTS}
+        out["_bufs"] = bufs
+        out["new_row"] = new_row                 # (kept alive with the result: the device reads it after the call returns)
+        if sync:
+            np_dtypes = dict(verdict=np.int32, path=np.uint8, x3D=np.float32, log=np.int32, counts=np.int32)
+            host = {k: np.zeros(max(size[k], 1), np_dtypes[k]) for k in NEW_POINTS_OUTPUTS}
+            self._chk(self._lib.jsorb_create_new_map_points(*args, *[host[k].ctypes.data for k in NEW_POINTS_OUTPUTS]))
+            out.update({k + "_host": host[k][:size[k]].reshape(shapes[k]) for k in NEW_POINTS_OUTPUTS})
+        else:
+            self._chk(self._lib.jsorb_create_new_map_points_async(*args))
+            if wait:
+                self.sync()
+        return out
+
+    def create_new_map_points_host(self, *args, **kw):
+        """jsorb_create_new_map_points, the synchronous form: the same inputs, the outputs as numpy arrays under the keys of NEW_POINTS_OUTPUTS"""
+        out = self.create_new_map_points(*args, sync=True, **kw)
+        return {k: out[k + "_host"] for k in NEW_POINTS_OUTPUTS}
+
+    def create_new_map_points_stats(self):
+        """dict of NEW_POINTS_COUNTS of the last create_new_map_points (waits for it)"""
+        v = np.zeros(12, np.int32)
+        self._chk(self._lib.jsorb_create_new_map_points_stats(self._m, v.ctypes.data))
+        return dict(zip(NEW_POINTS_COUNTS, (int(x) for x in v)))
+
+
+def new_points_build_caps():
+    """jsorb_create_new_map_points_build_caps of the loaded library: the pairs per chunk of the order-preserving compaction"""
+    return _build_caps("create_new_map_points", 1)
 
 
 def fuse_map_build_caps():
