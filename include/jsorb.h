@@ -502,6 +502,17 @@ int jsorb_vocabulary_info(const jsorb_vocabulary *v, int *n_nodes, int *n_words,
  *     shallow leaf   the leaf lies above that level (the reference leaves nid uninitialised): node_id = the leaf's own node id; counted in
  *                    jsorb_bow_transform_stats' n_shallow.  Does not occur with a full tree
  *     stopped word   the leaf's weight is not > 0: word_id as usual, node_id = -1 - the keypoint is in no FeatureVector entry (:1157-1161)
+ * Two things the reference leaves UNDEFINED are stated here, not reproduced:
+ *   - the shallow leaf above: the vector form of transform declares `NodeId nid;` without a value (:1151, :1179), the per-feature form writes it
+ *     only at level depth_L - levelsup, and `fv.addFeature(nid, i)` then reads whatever the stack held.  Here: the leaf's own id, counted.
+ *   - loadFromTextFile's `while(!f.eof()) getline` (:1378-1420) reads one more, empty, line after a final newline - which every file
+ *     saveToTextFile writes has (:1445) - and makes a node of it whose parent and leaf flag were never read.  Here (vocabulary.load_text):
+ *     empty lines are skipped, the tree has the file's nodes and no other.  A line without children that is flagged isLeaf = 0 is
+ *     a leaf to the reference's isLeaf() with the constructor's word id 0 (it counts as word 0); here it is a leaf without a word and creation
+ *     refuses the tree (JSORB_ERR_INVALID).
+ * What the reference does define - the first of equal children, the level of nid, levelsup >= L, a stopped word, the BowVector fold of the four
+ * weightings, the order of m_nodes[i].children and of the word ids in a text file - is held to DBoW2's own code, compiled unmodified, by
+ * tests/golden/ref_matcher_bow_transform.npz (tools/ref_bow/, tests/test_ref_bow.py, tests/test_gpu_ref_bow.py).
  * The host folds word_id into mBowVec with the vocabulary's own double weights in feature order (BowVector::addWeight / addIfNotExist), and node_id
  * into mFeatVec (addFeature(node_id[i], i) for node_id[i] >= 0, ascending i).
  * jsorb_bow_transform_descriptors: n descriptors at a DEVICE pointer (n x 32, 16-byte aligned) -> word_id[n], node_id[n] (device, either may be

@@ -51,17 +51,22 @@ def load_text(path):
     return t
 
 
-def save_text(path, t, scoring=0, weighting=0):
-    """the text format of saveToTextFile; the tree's node ids must be in the format's order (every parent before its children)"""
+def save_text(path, t, scoring=0, weighting=0, weight_text=None, final_newline=True):
+    """the text format of saveToTextFile; the tree's node ids must be in the format's order (every parent before its children).  The weights are
+    written with repr (17 significant digits where a double needs them: load_text gives back the bits; saveToTextFile itself writes six), or as
+    the strings weight_text[i] where given.  final_newline=False leaves the last line open: the reference's loader reads one more, empty, line
+    after a final newline and makes a node of it (tests/bow_ref_cases.py)."""
     n = t["n_nodes"]
     parent = np.zeros(n, np.int64)
     for i in range(n):
         parent[t["children"][t["child_start"][i]:t["child_start"][i + 1]]] = i
     leaf = t["child_start"][1:] == t["child_start"][:-1]
+    lines = ["%d %d %d %d" % (t["k"], t["depth_L"], scoring, weighting)]
+    for i in range(1, n):
+        w = weight_text[i] if weight_text is not None else repr(float(t["weight"][i]))
+        lines.append("%d %d %s %s" % (parent[i], int(leaf[i]), " ".join(str(int(b)) for b in t["descriptors"][i]), w))
     with open(path, "w") as f:
-        f.write("%d %d %d %d\n" % (t["k"], t["depth_L"], scoring, weighting))
-        for i in range(1, n):
-            f.write("%d %d %s %r\n" % (parent[i], int(leaf[i]), " ".join(str(int(b)) for b in t["descriptors"][i]), float(t["weight"][i])))
+        f.write("\n".join(lines) + ("\n" if final_newline else ""))
 
 
 def random_tree(seed, k, L, ragged=False, tie=0.0, zero_weight=0.0, leaf_prob=0.25, max_nodes=None):
