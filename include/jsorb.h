@@ -1025,6 +1025,82 @@ int jsorb_local_keyframes_stats(jsorb_extractor *e, int *n_counter, int *n_first
  * a byte in global memory) and child candidates held in LDS (4096; a run that does not fit is read from global memory). */
 int jsorb_local_keyframes_build_caps(int *member_lds_slots, int *child_lds_entries);
 
+/* ---- the frame's pose on the device: Optimizer::PoseOptimization (src/Optimizer.cpp:244-456), the call Tracking makes after every matcher
+ * (src/Tracking.cpp:937, :1077, :1140; :2053, :2069, :2084 per relocalisation candidate), in ONE launch on the handle's stream ----
+ * n_problems problems over image `image` of the last extract (N keypoints): one problem is a tracked frame, several are the relocalisation
+ * candidates, which share the image and each have their own frame_point_row (mvpMapPoints as table rows, -1 = NULL) and Tcw (mTcw, 4x4 row-major).
+ * EDGES (:285-365).  Keypoint k has an edge iff r = frame_point_row[k] lies in [0, n_rows).  bad[r] is not read: the reference does not test
+ *   isBad() here (:287-288).  A row outside the table gives no edge and nothing is read through it (n_outside_rows of the statistics counts the
+ *   rows >= n_rows).  Xw = the table's Px, Py, Pz[r], float widened to double (:315-318).  The observation is mvKeysUn[k].pt: x_un, y_un of
+ *   jsorb_keypoints_un_device with an active camera, else the keypoint's x, y.  The information is inv_level_sigma2[octave of the keypoint], float
+ *   widened to double (:304-305; an octave outside [0, 16) is clamped into it).  The edge is monocular when u_right is NULL or u_right[k] < 0 (:291),
+ *   otherwise stereo with u_right[k] as the third measurement.  nInitialCorrespondences = the edges.
+ * ARITHMETIC: a transcription of the chain, in double unless the reference says float, built with -ffp-contract=off.
+ *   errors and Jacobians: Thirdparty/g2o/g2o/types/types_six_dof_expmap.cpp:266-364 (e = obs - cam_project(T.map(Xw)); the stereo edge's
+ *     const float invz = 1.0f/z of :300 is a float); chi2 = e . (info e).
+ *   the robust kernel: Huber, Thirdparty/g2o/g2o/core/robust_kernel_impl.cpp:78-91, its deltas the FLOATS sqrt(5.991) and sqrt(7.815)
+ *     (src/Optimizer.cpp:278-279); robustInformation is rho[1] Omega only.
+ *   the quadratic form: Thirdparty/g2o/g2o/core/base_unary_edge.hpp:56-66 (b -= rho[1] A^T Omega e, H += A^T (rho[1] Omega) A).
+ *   the LM step: Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189 - lambda0 = 1e-5 max |H_jj| at iteration 0 of each optimize(),
+ *     the trial loop with computeScale() + 1e-3, alpha = 1 - (2 rho - 1)^3 clamped to [1/3, 2/3], _ni doubling, Terminate on 10 failed trials or
+ *     rho == 0, the (iniChi - currentChi) * 1e3 < iniChi counter with its limit of 3.  The outer loop is SparseOptimizer::optimize's
+ *     (Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:376-414): it stops at the first result that is not OK.
+ *   the update: SE3Quat::exp(dx) * estimate with the theta < 1e-5 branch and the quaternion normalisation (Thirdparty/g2o/g2o/types/se3quat.h:223-257,
+ *     :104-110, :280-285), the rotations through Eigen's quaternion formulas.
+ *   the solve: the 6x6 solve of Thirdparty/g2o/g2o/solvers/linear_solver_dense.h:65-113 as an LDL^T WITHOUT pivoting; a pivot that is not > 0 is
+ *     "not positive definite": a failed trial (tempChi = DBL_MAX) whose dx is the last solved one (zero at the start of an optimize()).
+ *   The sums over the edges are ONE fixed tree (a butterfly over each wave of 64 edges-in-thread-order, then the waves in order): no floating-point
+ *   atomics; a problem's result depends on its inputs alone, not on the run, on n_problems or on its index in the batch.  It is NOT bit-equal to
+ *   g2o: the tree is not Eigen's order, and sin, cos and pow are the device's.
+ * THE FOUR ROUNDS (:379-447), quirks kept.  Every round restarts from Tcw_in (:382: setEstimate(toSE3Quat(pFrame->mTcw)), src/Converter.cpp:38-51).
+ *   The edges flagged as outliers are left out (level 1) and re-tested each round on a freshly computed error at the round's estimate; an INLIER's
+ *   chi2() reads the error its last computeError left, which is the LAST TRIAL's pose - after a rejected last trial the rejected pose, not the
+ *   restored one.  The test is (float)chi2 > 5.991f, for a stereo edge > 7.815f.  The kernel comes off after round index 2.  The loop breaks after
+ *   a round when the TOTAL number of edges is below 10.  A round with no active edge leaves the estimate at the initial one (g2o's optimize
+ *   returns -1) and classifies all the same.
+ * OUTPUTS, per problem.  counts[4] = nInitialCorrespondences, nBad of the last round run, the return value (nInitialCorrespondences - nBad; 0
+ *   with fewer than 3 edges, :369-370), the rounds run.  With fewer than 3 edges Tcw_out = Tcw_in bit for bit, pose_out = its R and t widened, and the
+ *   flags are 0.  Otherwise Tcw_out = Converter::toCvMat of the estimate (src/Converter.cpp:53-57): the doubles rounded to float, last row 0 0 0 1; and
+ *   pose_out[12] = R row-major, t in double.  outlier[k] = mvbOutlier[k], 0 for a keypoint without an edge.  point_row_out[k] =
+ *   frame_point_row[k], or -1 where outlier[k]: the discard of src/Tracking.cpp:1086-1103 (TrackLocalMap's caller uses it only for stereo,
+ *   :1159-1160).
+ * All arrays are DEVICE pointers: frame_point_row and outlier n_problems x N, u_right N or NULL, Tcw_in and Tcw_out n_problems x 16, pose_out
+ * n_problems x 12 (8-byte aligned) or NULL, point_row_out n_problems x N or NULL, counts_dev n_problems x 4; `prm` and `table` are host structs (of
+ * the table, n_rows, Px, Py, Pz and the alignment of desc are looked at).  Defined for every device input: a row is range-checked before
+ * anything is read through it, and every loop is bounded (4 rounds x 10 iterations x 10 trials), so no input makes it spin.  Enqueued on the
+ * handle's stream behind the last extract, no host decision after the argument checks, launch shapes from N and n_problems alone, capturable once
+ * the scratch has its size (a call with the same or larger n_problems x N has run); the call does not synchronise.  One kernel:
+ * k_pose_optimize, a workgroup a problem.
+ * JSORB_ERR_INVALID: NULL prm or table; n_problems < 0 or n_rows < 0; NULL Px, Py or Pz with n_rows > 0; desc not 16-byte aligned; with
+ * n_problems > 0 a NULL Tcw_in, Tcw_out or counts_dev, and with N > 0 a NULL frame_point_row or outlier; pose_out not 8-byte aligned.
+ * JSORB_ERR_UNSUPPORTED: n_problems x N >= 2^31.  JSORB_ERR_STATE: no extract result for `image`.  Nothing is launched then. */
+typedef struct jsorb_pose_params {           /* pFrame->fx, fy, cx, cy, mbf, mvInvLevelSigma2 */
+    float fx, fy, cx, cy, bf;
+    float inv_level_sigma2[JSORB_MAX_LEVELS];
+} jsorb_pose_params;
+int jsorb_pose_optimization_async(jsorb_extractor *e, int image, const jsorb_pose_params *prm, const jsorb_map_point_table *table, int n_problems,
+                                  const int32_t *frame_point_row, const float *u_right, const float *Tcw_in, float *Tcw_out, double *pose_out,
+                                  uint8_t *outlier, int32_t *point_row_out, int32_t *counts_dev);
+/* Synchronous: the poses from the host (Tcw_host, n_problems x 16), then Tcw_out_host (n_problems x 16), pose_out_host (n_problems x 12, or NULL),
+ * outlier_host (n_problems x N) and counts_host (n_problems x 4) on the host; buffers of the handle hold them on the device.  frame_point_row,
+ * u_right and point_row_out (or NULL) stay DEVICE arrays.  The return value of src/Optimizer.cpp:455 is counts_host[4 p + 2]. */
+int jsorb_pose_optimization(jsorb_extractor *e, int image, const jsorb_pose_params *prm, const jsorb_map_point_table *table, int n_problems,
+                            const int32_t *frame_point_row, const float *u_right, const float *Tcw_host, float *Tcw_out_host,
+                            double *pose_out_host, uint8_t *outlier_host, int32_t *point_row_out, int32_t *counts_host);
+/* Diagnostics of the last call (waits for it), summed over its problems: n_outside_rows, monocular edges, stereo edges, LM iterations, trials,
+ * rejected trials, failed solves, rounds without an active edge.  They are diagnostics: at convergence rho is rounding noise, so the iteration and
+ * trial counts may differ between builds.  JSORB_ERR_STATE before the first call. */
+int jsorb_pose_optimization_stats(jsorb_extractor *e, int32_t stats[8]);
+/* The compile-time caps of the library in use: threads of a problem's workgroup (256) and edges a thread keeps in registers (4; the edges
+ * beyond threads x registers are read again every pass). */
+int jsorb_pose_optimization_build_caps(int *threads, int *edge_registers);
+/* F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cpp:107) between a matcher and the optimisation: frame_point_row[match_kp[i]] = point_row[i]
+ * wherever 0 <= match_kp[i] < N and point_row[i] >= 0; every other entry of frame_point_row stays.  The matchers give distinct match_kp; with a
+ * duplicate ONE of the writers wins, which one is not defined.  DEVICE arrays: point_row and match_kp n_points, frame_point_row N.  With it
+ * jsorb_local_map_points_async -> jsorb_search_local_points_async -> this -> jsorb_pose_optimization_async has no host hop.  Enqueued on
+ * hip_stream, does not synchronise.  JSORB_ERR_INVALID: n_points < 0, N < 0, or a NULL array that would be read or written. */
+int jsorb_apply_matches_async(void *hip_stream, int n_points, const int32_t *point_row, const int32_t *match_kp, int N, int32_t *frame_point_row);
+
 /* ---- the covisibility graph on the device: KeyFrame::UpdateConnections (src/KeyFrame.cpp:293-383), AddConnection / UpdateBestCovisibles
  * (:127-161), EraseConnection (:557-571) and the getters over them, on a keyframe matcher (its stream, its scratch; LocalMapping and LoopClosing
  * each own one; no extractor handle is involved) ----

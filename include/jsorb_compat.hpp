@@ -783,6 +783,16 @@ struct LocalMapPoints {
     int32_t counts[5] = {0, 0, 0, 0, 0};
     int capacity = 0;
 };
+// What Optimizer::PoseOptimization reads of the frame besides its keypoints (jsorb_pose_params, include/jsorb.h): pFrame->fx, fy, cx, cy, mbf and
+// mvInvLevelSigma2 (up to JSORB_MAX_LEVELS levels, the rest 0)
+struct PoseParams : jsorb_pose_params {
+    PoseParams(float fx_, float fy_, float cx_, float cy_, float mbf, const std::vector<float> &mvInvLevelSigma2)
+    {
+        if (mvInvLevelSigma2.size() > JSORB_MAX_LEVELS) throw std::runtime_error("jsorb::PoseParams: more than JSORB_MAX_LEVELS levels");
+        fx = fx_; fy = fy_; cx = cx_; cy = cy_; bf = mbf;
+        for (int l = 0; l < JSORB_MAX_LEVELS; l++) inv_level_sigma2[l] = (size_t)l < mvInvLevelSigma2.size() ? mvInvLevelSigma2[l] : 0.0f;
+    }
+};
 // The keyframes as the device arrays jsorb_local_keyframes reads (jsorb_keyframe_graph, include/jsorb.h): RAII over eleven device arrays of
 // max_keyframes slots, the caller's index for a KeyFrame* as for KeyframeDatabase.  The binding calls a setter where the reference changes the
 // map (INTEGRATION.md lists which event rewrites which array); each setter is one small upload.  Runs are handed out from the pools front to
@@ -1504,6 +1514,35 @@ inline int SearchLocalPoints(ORBExtractor &ex, const jsorb_search_params &params
 {
     return SearchLocalPoints(ex, params, pts.capacity, pts.u, pts.v, pts.invz, pts.predictedlevel, pts.viewCos, pts.isinfrustum, pts.descriptors, u_right_gpu,
                              pts.blocked.gpu_data(), match_kp);
+}
+
+// F.mvpMapPoints[bestIdx] = pMP (ORBmatcher.cpp:107) on the device, enqueued on the extractor's stream: frame_point_row_gpu[match_kp_gpu[i]] =
+// point_row_gpu[i] for the matches of a matcher whose match_kp stayed on the device (jsorb_search_local_points_async over pts: point_row_gpu =
+// pts.point_row_gpu).  frame_point_row_gpu: one row per keypoint of the frame, -1 = NULL.
+inline void ApplyMatches(ORBExtractor &ex, int n_points, const int32_t *point_row_gpu, const int32_t *match_kp_gpu, int32_t *frame_point_row_gpu)
+{
+    if (jsorb_apply_matches_async(jsorb_get_stream(ex.handle()), n_points, point_row_gpu, match_kp_gpu, jsorb_n_keypoints(ex.handle(), 0), frame_point_row_gpu) != JSORB_OK)
+        throw std::runtime_error("jsorb_apply_matches_async failed");
+}
+// Optimizer::PoseOptimization(&mCurrentFrame) (Optimizer.cpp:244-456; Tracking.cpp:937, :1077, :1140) on the device: frame_point_row_gpu is
+// mCurrentFrame.mvpMapPoints as table rows (-1 = NULL), u_right_gpu mvuRight on the device (nullptr: monocular), Tcw mTcw row-major - read, and
+// written as SetPose(pose) does.  outlier = mvbOutlier (one byte per keypoint).  point_row_out_gpu (or nullptr): the rows with the outliers' set to
+// -1, the discard of Tracking.cpp:1086-1103.  Returns the reference's int: nInitialCorrespondences - nBad, 0 with fewer than 3 correspondences.
+inline int PoseOptimization(ORBExtractor &ex, const jsorb::MapPointTable &table, const int32_t *frame_point_row_gpu, float Tcw[16],
+                            std::vector<unsigned char> &outlier, const jsorb::PoseParams &prm, const float *u_right_gpu = nullptr,
+                            int32_t *point_row_out_gpu = nullptr, int32_t counts[4] = nullptr)
+{
+    const int N = jsorb_n_keypoints(ex.handle(), 0);
+    outlier.assign(N > 0 ? N : 1, 0);
+    const jsorb_map_point_table t = table.view();
+    float out[16];
+    int32_t c[4] = {0, 0, 0, 0};
+    if (jsorb_pose_optimization(ex.handle(), 0, &prm, &t, 1, frame_point_row_gpu, u_right_gpu, Tcw, out, nullptr, outlier.data(), point_row_out_gpu, c) != JSORB_OK)
+        throw std::runtime_error(std::string("jsorb_pose_optimization: ") + jsorb_last_error(ex.handle()));
+    outlier.resize(N > 0 ? N : 0);
+    for (int i = 0; i < 16; i++) Tcw[i] = out[i];
+    if (counts) for (int i = 0; i < 4; i++) counts[i] = c[i];
+    return c[2];
 }
 
 // TrackWithMotionModel's matcher.SearchByProjection(mCurrentFrame, mLastFrame, th, bMono) and its retry at 2 th (Tracking.cpp:1045-1064,

@@ -677,6 +677,7 @@ void jsorb_destroy(jsorb_extractor *e)
     search_local_release(e);
     local_map_release(e);
     local_kf_release(e);
+    pose_release(e);
     search_last_release(e);
     search_kf_release(e);
     search_init_release(e);

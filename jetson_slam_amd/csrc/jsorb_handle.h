@@ -315,6 +315,14 @@ struct jsorb_extractor {
         bool done = false;
     } lk;
 
+    // ---- the pose optimisation (jsorb_pose.hip, jsorb_pose_optimization*): allocated on the first call, grown only ----
+    struct {
+        WordBuf edges;                     // n_problems x N: a problem's edges as keypoints in ascending order (PoseArgs::edge_kp)
+        int *stats = nullptr;              // PO_STATS words of the last call (device)
+        WordBuf io;                        // synchronous call: Tcw_in, Tcw_out (16 floats a problem each), pose (12 doubles), counts (4), outlier (N bytes)
+        bool done = false;
+    } po;
+
     // ---- bag of words (jsorb_bow.hip, jsorb_bow_transform_async / jsorb_search_by_bow*): allocated on first use, the keyframe parts grown only ----
     struct {
         int32_t *ids = nullptr;            // B x T word ids, then B x T node ids, then 2 statistics words (descriptors with a shallow leaf)
@@ -740,6 +748,9 @@ void local_map_release(jsorb_extractor *e);
 
 // ---- jsorb_localkf.hip ----
 void local_kf_release(jsorb_extractor *e);
+
+// ---- jsorb_pose.hip ----
+void pose_release(jsorb_extractor *e);
 
 // ---- jsorb_bow.hip ----
 void bow_after_extract(jsorb_extractor *e);

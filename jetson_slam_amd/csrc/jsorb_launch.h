@@ -376,6 +376,31 @@ int new_points_chunk();                          // the compile-time cap of k_ne
 void launch_new_points_gather(const NewPointsArgs &a, const NewPointsSlots &s, hipStream_t st);
 void launch_new_points_verdict(const NewPointsArgs &a, const NewPointsPoses &p, hipStream_t st);
 void launch_new_points_apply(const NewPointsArgs &a, hipStream_t st);      // ownership, compaction, the rows' writes, the KF2 entries, the counts
+// k_pose_optimize / k_apply_matches (k_pose.hip): Optimizer::PoseOptimization (Optimizer.cpp:244-456) for n_problems problems over one image, one
+// workgroup a problem for the whole four-round loop; and the F.mvpMapPoints[bestIdx] = pMP of the matchers' callers
+#define PO_STATS 8
+struct PoseArgs {
+    jsorb_pose_params prm;
+    float delta_mono, delta_stereo;              // the FLOATS sqrt(5.991), sqrt(7.815) (Optimizer.cpp:278-279)
+    const int32_t *soa;                          // keypoint SoA (6N): x, y, ., ., octave, .
+    const float *xy_un;                          // mvKeysUn as x_un[N] y_un[N] (NULL: the keypoints themselves)
+    int N, n_rows, n_problems;
+    const float *Px, *Py, *Pz;                   // the table's positions
+    const int32_t *frame_row;                    // n_problems x N
+    const float *u_right;                        // N or NULL
+    const float *Tcw_in;                         // n_problems x 16
+    float *Tcw_out;
+    double *pose_out;                            // n_problems x 12 or NULL
+    uint8_t *outlier;                            // n_problems x N: the edges' flags between the rounds, too
+    int32_t *row_out;                            // n_problems x N or NULL
+    int32_t *counts;                             // n_problems x 4
+    int32_t *edge_kp;                            // scratch, n_problems x N: a problem's edges as keypoints in ascending order, bit 31 = stereo
+    int *stats;                                  // PO_STATS words (cleared to 0), jsorb_pose_optimization_stats' order
+};
+int pose_threads();                              // the compile-time caps of k_pose.hip (jsorb_pose_optimization_build_caps)
+int pose_edge_regs();
+void launch_pose_optimize(const PoseArgs &a, hipStream_t s);
+void launch_apply_matches(int n_points, const int32_t *point_row, const int32_t *match_kp, int N, int32_t *frame_point_row, hipStream_t s);
 // k_loop_bow_match (k_loop.hip): ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) for several candidates KF2 of LoopClosing::ComputeSim3; the grouping
 // is launch_bow_group over a BowMatchArgs whose frame side is KF1, the resolver launch_tri_resolve over the same rows
 struct LoopBowArgs {

@@ -84,6 +84,8 @@ EXPORTS = [
     "jsorb_cull_keyframes_async", "jsorb_cull_keyframes", "jsorb_cull_keyframes_stats", "jsorb_cull_keyframes_build_caps",
     "jsorb_fuse_map_async", "jsorb_fuse_map", "jsorb_fuse_map_stats", "jsorb_fuse_map_build_caps",
     "jsorb_create_new_map_points_async", "jsorb_create_new_map_points", "jsorb_create_new_map_points_stats", "jsorb_create_new_map_points_build_caps",
+    "jsorb_pose_optimization_async", "jsorb_pose_optimization", "jsorb_pose_optimization_stats", "jsorb_pose_optimization_build_caps",
+    "jsorb_apply_matches_async",
 ]
 
 
@@ -297,6 +299,41 @@ def make_frustum_params(Rcw, tcw, Ow, camera, bounds, n_levels, log_scale_factor
 MAP_POINT_RECORD_DTYPE = np.dtype([("P", "<f4", 3), ("Pn", "<f4", 3), ("MaxDistance", "<f4"), ("invariance_maxDistance", "<f4"),
                                    ("invariance_minDistance", "<f4"), ("bad", "u1"), ("pad", "u1", 3)])
 MAP_POINT_FLOATS = ("Px", "Py", "Pz", "Pnx", "Pny", "Pnz", "MaxDistance", "invariance_maxDistance", "invariance_minDistance")
+
+
+class JsorbPoseParams(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf")] + [("inv_level_sigma2", C.c_float * 16)]
+
+
+def make_pose_params(camera, bf, inv_level_sigma2):
+    """jsorb_pose_params: camera = (fx, fy, cx, cy), bf = mbf, inv_level_sigma2 = mvInvLevelSigma2 (up to 16 floats, the rest 0)"""
+    v = np.asarray(inv_level_sigma2, np.float32).ravel()
+    if v.size > 16:
+        raise JsorbError("make_pose_params: at most 16 levels")
+    return JsorbPoseParams(*[float(x) for x in camera], float(bf), (C.c_float * 16)(*v.tolist()))
+
+
+POSE_COUNTS = ("n_initial", "n_bad", "n_inliers", "rounds")
+POSE_STATS = ("n_outside_rows", "n_mono", "n_stereo", "iterations", "trials", "rejected", "failed", "idle_rounds")
+
+
+def apply_matches(point_row, match_kp, frame_point_row, stream_ptr=None, wait=True):
+    """jsorb_apply_matches_async: frame_point_row[match_kp[i]] = point_row[i] wherever 0 <= match_kp[i] < N and point_row[i] >= 0, in place.  int32
+    device tensors: point_row and match_kp of the same length (a matcher's point rows and its match_kp), frame_point_row[N].  stream_ptr None:
+    the default stream, after the current torch stream has been waited for; wait: the call waits for its own work."""
+    import torch
+    n = int(match_kp.shape[0])
+    a = _i32_ptr("apply_matches: point_row", point_row, n, flat=True)
+    b = _i32_ptr("apply_matches: match_kp", match_kp, n, flat=True)
+    f = _i32_ptr("apply_matches: frame_point_row", frame_point_row, flat=True)
+    if stream_ptr is None:
+        torch.cuda.current_stream(frame_point_row.device).synchronize()
+    rc = load_library().jsorb_apply_matches_async(stream_ptr, n, a, b, int(frame_point_row.shape[0]), f)
+    if rc:
+        raise JsorbError("jsorb_apply_matches_async: error %d" % rc)
+    if wait:
+        torch.cuda.synchronize(frame_point_row.device)
+    return frame_point_row
 
 
 class MapPointTable:
@@ -1035,6 +1072,11 @@ def load_library(path=None):
                                             I, I, I, I, P, P, P, P, C.c_float, I, I, P, I] + [P] * 10),
         "jsorb_create_new_map_points_stats": (I, [P, P]),
         "jsorb_create_new_map_points_build_caps": (I, [C.POINTER(I)]),
+        "jsorb_pose_optimization_async": (I, [P, I, C.POINTER(JsorbPoseParams), C.POINTER(JsorbMapPointTable), I] + [P] * 8),
+        "jsorb_pose_optimization": (I, [P, I, C.POINTER(JsorbPoseParams), C.POINTER(JsorbMapPointTable), I] + [P] * 8),
+        "jsorb_pose_optimization_stats": (I, [P, P]),
+        "jsorb_pose_optimization_build_caps": (I, [C.POINTER(I)] * 2),
+        "jsorb_apply_matches_async": (I, [P, I, P, P, I, P]),
     }
     for name, (rt, at) in sig.items():
         fn = getattr(lib, name)
@@ -1925,6 +1967,11 @@ def vocab_train_build_caps():
     return _build_caps("vocab_train", 2)
 
 
+def pose_optimization_build_caps():
+    """jsorb_pose_optimization_build_caps of the loaded library: (threads of a problem's workgroup, edges a thread keeps in registers)"""
+    return _build_caps("pose_optimization", 2)
+
+
 def local_map_build_caps():
     """jsorb_local_map_build_caps of the loaded library: entries per chunk of k_local_map's compaction"""
     return _build_caps("local_map", 1)
@@ -2591,6 +2638,69 @@ class ORBExtractor:
         v = [C.c_int() for _ in range(6)]
         self._chk(self._lib.jsorb_local_map_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("n_entries", "n_null", "n_invalid_rows", "n_duplicates", "n_bad", "n_seen"), (x.value for x in v)))
+
+    # ---- the frame's pose: Optimizer::PoseOptimization (Optimizer.cpp:244-456) on the device ----
+    def pose_optimization(self, table, params, frame_point_row, Tcw, u_right=None, image=0, sync=False, out=None, wait=True, point_rows=True):
+        """jsorb_pose_optimization*: table a MapPointTable, params a JsorbPoseParams (make_pose_params), frame_point_row an int32 device tensor
+        [n_problems, N] (or [N]: one problem), u_right float32[N] device tensor or None (monocular).  Tcw: float32 [n_problems, 4, 4] (or [4, 4]) -
+        a device tensor, or with sync=True a host array.  Returns a dict of device tensors - Tcw_out float32[n_problems, 4, 4], pose
+        float64[n_problems, 12] (R row-major, t), outlier uint8[n_problems, N], point_row_out int32[n_problems, N] (point_rows=False: left out),
+        counts int32[n_problems, 4] (POSE_COUNTS).  out: the dict of an earlier call, written again (nothing is allocated).  sync=True: the
+        synchronous form; the dict holds Tcw_out, pose, outlier and counts as numpy arrays instead.  Otherwise the call waits for the current
+        torch stream before it starts and for its own work before it returns; wait=False: it only enqueues on the handle's stream."""
+        import torch
+        N = self.n_keypoints(image)
+        if N < 0:
+            raise JsorbError("pose_optimization: no extract result for image %d" % image)
+        dev = table.floats.device
+        rows = frame_point_row if frame_point_row.dim() == 2 else frame_point_row.reshape(1, -1)
+        n = int(rows.shape[0])
+        if int(rows.shape[1]) != N:
+            raise JsorbError("pose_optimization: frame_point_row must have %d columns" % N)
+        fp = _i32_ptr("pose_optimization: frame_point_row", rows, n * N) if n * N else None
+        ur = None
+        if u_right is not None:
+            if u_right.dtype != torch.float32 or not u_right.is_cuda or not u_right.is_contiguous() or u_right.numel() < N:
+                raise JsorbError("pose_optimization: u_right must be a contiguous float32 device tensor of at least %d entries" % N)
+            ur = u_right.data_ptr()
+        tb = table.struct()
+        n1 = max(n, 1)
+        if sync:
+            T = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1, 16))
+            if len(T) != n:
+                raise JsorbError("pose_optimization: one Tcw per problem")
+            To, po = np.zeros((n1, 16), np.float32), np.zeros((n1, 12), np.float64)
+            fl, cn = np.zeros((n1, max(N, 1)), np.uint8)[:, :N].copy(), np.zeros((n1, 4), np.int32)
+            ro = torch.empty((n1, max(N, 1)), dtype=torch.int32, device=dev) if point_rows else None
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self._lib.jsorb_pose_optimization(self._h, image, C.byref(params), C.byref(tb), n, fp, ur, T.ctypes.data, To.ctypes.data, po.ctypes.data,
+                                                        fl.ctypes.data, None if ro is None else ro.data_ptr(), cn.ctypes.data))
+            r = dict(Tcw_out=To[:n].reshape(n, 4, 4), pose=po[:n], outlier=fl[:n], counts=cn[:n])
+            if ro is not None:
+                r["point_row_out"] = ro.reshape(-1)[:n * N].reshape(n, N)
+            return r
+        if not torch.is_tensor(Tcw) or not Tcw.is_cuda or Tcw.dtype != torch.float32 or not Tcw.is_contiguous() or Tcw.numel() != 16 * n:
+            raise JsorbError("pose_optimization: Tcw must be a contiguous float32 device tensor of %d entries" % (16 * n))
+        if out is None:
+            out = dict(Tcw_out=torch.empty((n1, 4, 4), dtype=torch.float32, device=dev)[:n], pose=torch.empty((n1, 12), dtype=torch.float64, device=dev)[:n],
+                       outlier=torch.empty(n1 * max(N, 1), dtype=torch.uint8, device=dev)[:n * N].reshape(n, N),
+                       counts=torch.empty((n1, 4), dtype=torch.int32, device=dev)[:n])
+            if point_rows:
+                out["point_row_out"] = torch.empty(n1 * max(N, 1), dtype=torch.int32, device=dev)[:n * N].reshape(n, N)
+        if wait:
+            torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._lib.jsorb_pose_optimization_async(self._h, image, C.byref(params), C.byref(tb), n, fp, ur, Tcw.data_ptr(), out["Tcw_out"].data_ptr(),
+                                                          out["pose"].data_ptr(), out["outlier"].data_ptr(),
+                                                          out["point_row_out"].data_ptr() if "point_row_out" in out else None, out["counts"].data_ptr()))
+        if wait:
+            self.sync()
+        return out
+
+    def pose_optimization_stats(self):
+        """dict over POSE_STATS of the last pose_optimization, summed over its problems (diagnostics)"""
+        v = np.zeros(8, np.int32)
+        self._chk(self._lib.jsorb_pose_optimization_stats(self._h, v.ctypes.data))
+        return dict(zip(POSE_STATS, (int(x) for x in v)))
 
     # ---- the local keyframes: Tracking::UpdateLocalKeyFrames (Tracking.cpp:1844-1952) and the concatenation of their rows on the device ----
     def local_keyframes(self, graph, table, frame_point_row, kf_capacity, entry_capacity, state=None, sync=False, out=None, wait=True):
